@@ -7,17 +7,23 @@ fastRiccati = false).  The whole input stream is resident in HBM before the time
 (eqf_stream_upload); the timed region replays events by index through the C ABI.
 
     python bench.py                       # 1 GPU, 1 filter, N = 200  (BASELINE configs[1])
+    python bench.py --full                # the same headline figure + roofline, CPU baselines, parity prefix and the other legs below
     python bench.py --filters-per-gpu 64  # 64 independent filters batched on one GPU
     python bench.py --gpus 8              # starts 8 ranks ITSELF (one per GPU, RCCL rendezvous on 127.0.0.1), one JSON line from rank 0;
-                                          # BASELINE configs[3] (64 filters over the 8 GPUs) is its `batch64_strong` leg
+                                          # BASELINE configs[3] (64 filters over the 8 GPUs) is the `batch64_strong` leg of --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8   # same job
+
+A plain run sets up, warms up, times --steps steps, writes what the timed path computed if --dump-outputs DIR is given, and prints the
+line.  Everything else -- roofline and per-kernel figures, PMC traffic, the oracle-checked parity prefix, the CPU baselines, the legs
+steady_state / batch64_strong / batch8 / n1000 / tiled_cfg5 / churn -- runs only with --full (each can still be skipped there with its
+--no-* option).
 
 Multi-GPU: independent filters are sharded over ranks (no data-path collective); RCCL is used once to
 scatter the pre-generated input streams from rank 0 and once to gather the results.
 
 The JSON line's `value` is the WEAK-scaling figure (--filters-per-gpu filters on every GPU, default 1 = BASELINE configs[1]
 at N = 1).  BASELINE configs[3] / north_star's "64-instance batch" is a STRONG-scaling workload (64 filters in total, 64/G per
-GPU); it is measured in the same run as a second leg and reported under "batch64_strong" (--no-batch64 skips it).
+GPU); --full measures it in the same run as a second leg and reports it under "batch64_strong" (--no-batch64 skips it).
 """
 import argparse
 import json
@@ -50,6 +56,10 @@ def parse():
     ap.add_argument("--filters-per-gpu", type=int, default=1)
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64")
     ap.add_argument("--dense-propagate", action="store_true", help="Riccati step as dense F Sigma F^T on MFMA (BASELINE cfg 3)")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure: roofline and per-kernel figures, PMC "
+                    "traffic, parity prefix, CPU baselines and the other legs (the --no-* options below skip single ones of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what they computed (state estimate, bias, Sigma of "
+                    "this process's filters; pose and |Sigma|_F of all filters) as DIR/<name>.npy, float64, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-batch64", action="store_true", help="skip the strong-scaling leg (64 filters in total over the GPUs)")
     ap.add_argument("--batch64-steps", type=int, default=440)
@@ -367,6 +377,8 @@ def timed_job(args, dist, rank, world, device, N, B, steps, warmup, dense=False)
         fb.debug_option(kv.split("=")[0], int(kv.split("=")[1]))
     fb.stream_upload(imu, vst, ids, bear)
     warm, timed = events[:warmup], events[warmup:]
+    if len(timed) != steps:  # (`steps` and `ms_per_step` of the line must describe the timed region exactly)
+        raise RuntimeError("the input stream holds %d timed events, not the %d asked for" % (len(timed), steps))
     run_events(fb, warm)
     fb.synchronize()
     if dist is not None:
@@ -392,6 +404,41 @@ def timed_job(args, dist, rank, world, device, N, B, steps, warmup, dense=False)
         res[b, 7] = np.linalg.norm(fb.sigma(b))
     res = shard.gather_results(dist, rank, world, res, device="cuda" if dist is not None else None)
     return fb, timed, dt, res
+
+
+DUMP_BYTES = 64_000_000  # (64 MB, .npy headers included)
+
+
+def dump_outputs(path, fb, B, res):
+    """--dump-outputs: what a caller of the timed path reads back after its last step, one float64 .npy per array -- the state estimate,
+    bias and Sigma of this process's B filters, and `pose_sigma_norm` (x, q, |Sigma|_F of every filter of the job, gathered to rank 0).
+    Sigma goes out whole while everything fits in DUMP_BYTES; beyond that, as a fixed sample of its entries (seed 0, flat indices into
+    the (B, n, n) stack, sorted): `sigma_sample` and `sigma_sample_index`.  The inputs are seeded, so two builds run with the same
+    arguments can be compared file by file."""
+    os.makedirs(path, exist_ok=True)
+    est = [fb.state_estimate(b) for b in range(B)]
+    arrays = {
+        "position": np.stack([e["x"] for e in est]),
+        "attitude_q": np.stack([e["q"] for e in est]),
+        "velocity": np.stack([e["v"] for e in est]),
+        "landmarks": np.stack([e["p"] for e in est]),
+        "bias": np.stack([fb.bias(b) for b in range(B)]),
+        "pose_sigma_norm": np.asarray(res, dtype=np.float64),
+    }
+    n = 11 + 3 * fb.num_landmarks(0)
+    room = DUMP_BYTES - 128 * 10 - sum(a.nbytes for a in arrays.values())  # (128 bytes: one .npy header)
+    if B * n * n * 8 <= room:
+        arrays["sigma"] = np.stack([fb.sigma(b) for b in range(B)])
+    else:
+        idx = np.unique(np.random.default_rng(0).integers(0, B * n * n, size=room // 16))
+        vals = np.empty(len(idx))
+        for b in range(B):
+            sel = (idx >= b * n * n) & (idx < (b + 1) * n * n)
+            if sel.any():
+                vals[sel] = fb.sigma(b).ravel()[idx[sel] - b * n * n]
+        arrays["sigma_sample"], arrays["sigma_sample_index"] = vals, idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def churn_leg(device, seconds=3.0, pool=260, fixed=200):
@@ -741,6 +788,8 @@ def main():
         del pw
     fb, timed, dt, res = timed_job(args, dist, rank, world, device, N, B, args.steps, args.warmup, dense=args.dense_propagate)
     err = fb.device_error()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fb, B, res)  # (before anything else runs on this handle: the roofline pass replays the events)
     if args.pmc_child:
         fb.sigma(0)  # one k_sigma_export launch: known byte count, calibrates FETCH_SIZE
         return
@@ -789,7 +838,7 @@ def main():
     from eqf_vio_amd import binding as _binding
 
     line["build"] = _binding.build_info()  # which .so ran, and that it was built from the sources beside it
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         rl, rows, cover = roofline(fb, timed, N, B, args.precision)
         line["roofline"] = rl
         line["kernels"] = rows
@@ -815,7 +864,7 @@ def main():
 
     # ---- steady-state leg: the driver's default run times 20 steps (two frames, half a millisecond); the same workload over 10 s of
     # stream (2200 steps after 220 of warm-up) is what DESIGN / README quote, so it is measured in the same run
-    if not args.no_steady_state and args.steps < 2200 and not args.dense_propagate and N <= 400:
+    if args.full and not args.no_steady_state and args.steps < 2200 and not args.dense_propagate and N <= 400:
         fb3, timed3, dt3, _ = timed_job(args, dist, rank, world, device, N, B, 2200, 220)
         err3 = fb3.device_error()
         del fb3
@@ -826,7 +875,7 @@ def main():
         }
 
     # ---- strong-scaling leg: BASELINE configs[3], 64 filters IN TOTAL over the GPUs of the job (64 / world per GPU)
-    if not args.no_batch64 and 64 % world == 0 and not args.dense_propagate and N == 200:
+    if args.full and not args.no_batch64 and 64 % world == 0 and not args.dense_propagate and N == 200:
         Bs = 64 // world
         fb2, timed2, dt2, res2 = timed_job(args, dist, rank, world, device, 200, Bs, args.batch64_steps, 110)
         err2 = fb2.device_error()
@@ -854,7 +903,7 @@ def main():
 
     # ---- 8 filters per GPU: ONE GPU's share of BASELINE configs[3] on an 8-GPU node -- the figure the 0.9x strong-scaling target hangs on
     # (8 GPUs x this against 8 x the one-GPU batch of 64 above).  One GPU only: on several GPUs batch64_strong already runs 64 / world.
-    if not args.no_batch8 and world == 1 and not args.dense_propagate and N == 200 and B == 1 and args.precision == "f64":
+    if args.full and not args.no_batch8 and world == 1 and not args.dense_propagate and N == 200 and B == 1 and args.precision == "f64":
         fb8, timed8, dt8, _ = timed_job(args, dist, rank, world, device, 200, 8, 880, 110)
         err8 = fb8.device_error()
         leg8 = {"metric": "EqF propagate+update steps/sec, 8 filters of N=200 on one GPU (one GPU's share of the 64-filter batch on 8 GPUs)",
@@ -874,7 +923,7 @@ def main():
         line["batch8"] = leg8
 
     # ---- BASELINE configs[2]: one filter of N = 1000 (Sigma 3011 x 3011), the structured product path, with its own roofline
-    if not args.no_n1000 and world == 1 and not args.dense_propagate and N == 200 and B == 1 and args.precision == "f64":
+    if args.full and not args.no_n1000 and world == 1 and not args.dense_propagate and N == 200 and B == 1 and args.precision == "f64":
         fbk, timedk, dtk, _ = timed_job(args, dist, rank, world, device, 1000, 1, 220, 55)
         errk = fbk.device_error()
         legk = {"metric": "EqF propagate+update steps/sec at N=1000 landmarks (BASELINE configs[2]), structured product path, 1 GPU",
@@ -891,7 +940,7 @@ def main():
         line["n1000"] = legk
 
     # ---- BASELINE configs[4]: one N = 4000 filter partitioned over the ranks of the job
-    if not args.no_tiled and world in GRIDS and not args.dense_propagate and not args.pmc_child:
+    if args.full and not args.no_tiled and world in GRIDS and not args.dense_propagate and not args.pmc_child:
         # (a failure of this leg must not take the headline line with it: exceptions are reported in its place, and on several GPUs --
         # where a lost peer shows as a collective that never returns -- a watchdog prints the line without the leg and ends the rank)
         watchdog = None
@@ -918,13 +967,13 @@ def main():
                     print(json.dumps(line), flush=True)
                 os._exit(0)
 
-    if rank == 0 and not args.no_churn and N == 200 and B == 1 and not args.dense_propagate and args.precision == "f64":
+    if rank == 0 and args.full and not args.no_churn and N == 200 and B == 1 and not args.dense_propagate and args.precision == "f64":
         try:
             line["churn"] = churn_leg(device)
         except Exception as e:
             line["churn"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         rl = line.get("roofline")
         if rl is not None and not args.no_traffic:
             traffic, note = pmc_traffic(args, rl["kernel"])

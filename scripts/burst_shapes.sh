@@ -4,7 +4,7 @@
 for B in ${1:-4 8 12}; do
   for opt in "burst_lm=0 burst_rows=0 ring_ahead2=1" "burst_lm=16 burst_rows=2 ring_ahead2=0" "burst_lm=16 burst_rows=2 ring_ahead2=1" "burst_lm=8 burst_rows=2 ring_ahead2=0" "burst_lm=8 burst_rows=2 ring_ahead2=1" "burst_lm=4 burst_rows=2 ring_ahead2=1" "burst_lm=8 burst_rows=1 ring_ahead2=1" "burst_lm=8 burst_rows=4 ring_ahead2=1"; do
     args=""; for o in $opt; do args="$args --debug-option $o"; done
-    python bench.py --filters-per-gpu $B --steps 880 --warmup 110 --no-batch64 --no-cpu-baseline --no-traffic --no-parity --no-steady-state --no-batch8 --no-n1000 --no-tiled --no-churn $args 2>/dev/null | python -c "
+    python bench.py --full --filters-per-gpu $B --steps 880 --warmup 110 --no-batch64 --no-cpu-baseline --no-traffic --no-parity --no-steady-state --no-batch8 --no-n1000 --no-tiled --no-churn $args 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k={r['kernel']:r for r in d['kernels']}

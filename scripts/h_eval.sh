@@ -10,11 +10,11 @@ cd $ROOT
 ( python -m pytest tests/test_gpu_parity.py -x -q -k "resident or layouts or prep_roles or handoff or stream_parity or golden" 2>&1 | tail -4
   python -m pytest tests/test_gpu_configs.py -x -q -k "withheld or batch_of_16 or mid_size or cfg4" 2>&1 | tail -4
   for B in 1 2 4 8 16 64; do
-    env $EXTRA python bench.py --filters-per-gpu $B --steps 880 --warmup 110 --no-batch64 --no-cpu-baseline --no-traffic --no-parity --no-tiled --no-churn --no-steady-state --no-n1000 --no-batch8 2>/dev/null | python -c "
+    env $EXTRA python bench.py --full --filters-per-gpu $B --steps 880 --warmup 110 --no-batch64 --no-cpu-baseline --no-traffic --no-parity --no-tiled --no-churn --no-steady-state --no-n1000 --no-batch8 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('B=$B', round(d['value']), 'steps/s  err', d['device_error_flag'], 'cover', d['profile_coverage']['kernel_time_over_wall'], [(k['kernel'], k['avg_us']) for k in d['kernels'][:5]])"
   done
-  env $EXTRA python bench.py --landmarks 1000 --steps 220 --warmup 55 --no-batch64 --no-cpu-baseline --no-traffic --no-parity --no-tiled --no-churn --no-steady-state --no-n1000 --no-batch8 2>/dev/null | python -c "
+  env $EXTRA python bench.py --full --landmarks 1000 --steps 220 --warmup 55 --no-batch64 --no-cpu-baseline --no-traffic --no-parity --no-tiled --no-churn --no-steady-state --no-n1000 --no-batch8 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('N=1000', round(d['value']), 'steps/s  err', d['device_error_flag'], [(k['kernel'], k['avg_us']) for k in d['kernels'][:5]])"
   if [ -f build_variants/libeqf_stamps.so ]; then

@@ -13,7 +13,7 @@ NAME=$1; VALS=$2; CASES=${3:-"8:200"}
     [ "$B" -ge 64 ] && ST=440
     [ "$N" -ge 1000 ] && ST=220
     for V in $VALS; do
-      timeout 300 python $ROOT/bench.py --filters-per-gpu $B --landmarks $N --steps $ST --warmup $WU --debug-option $NAME=$V --no-batch64 --no-cpu-baseline --no-traffic --no-parity --no-tiled --no-churn --no-steady-state --no-n1000 --no-batch8 2>/dev/null | python -c "
+      timeout 300 python $ROOT/bench.py --full --filters-per-gpu $B --landmarks $N --steps $ST --warmup $WU --debug-option $NAME=$V --no-batch64 --no-cpu-baseline --no-traffic --no-parity --no-tiled --no-churn --no-steady-state --no-n1000 --no-batch8 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('B=$B N=$N $NAME=$V', round(d['value']), 'steps/s  err', d['device_error_flag'], [(k['kernel'], k['avg_us']) for k in d['kernels'][:5]])"
     done

@@ -13,7 +13,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--gpus", "1", "--steps", "220", "--warmup", "110", "--no-batch64", "--no-cpu-baseline", "--no-traffic", "--no-parity",
+ARGS = ["--gpus", "1", "--steps", "220", "--warmup", "110", "--full", "--no-batch64", "--no-cpu-baseline", "--no-traffic", "--no-parity",
         "--no-steady-state"]
 
 

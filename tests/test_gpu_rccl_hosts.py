@@ -108,16 +108,29 @@ def test_tiled_host_matches_the_oracle(oracle_lib):
     assert abs(fro / np.linalg.norm(fo.stateCovariance()) - 1) < 1e-8
 
 
-def test_bench_gpus_1_prints_one_line():
-    """`python bench.py --gpus 1`, the shape of the driver's command: one process, n_gpus 1, launcher named in the line."""
+def test_bench_gpus_1_prints_one_line(tmp_path):
+    """`python bench.py --gpus 1`, the shape of the driver's command: one process, n_gpus 1, launcher named in the line; a plain run
+    (no --full) times exactly --steps steps and nothing else, and --dump-outputs leaves what the timed steps computed."""
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
+    out = tmp_path / "outputs"
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "44", "--warmup", "22", "--no-batch64",
                           "--no-cpu-baseline", "--no-traffic", "--no-parity", "--no-steady-state", "--no-batch8", "--no-n1000", "--no-tiled",
-                          "--no-churn"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                          "--no-churn", "--dump-outputs", str(out)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stderr[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1
     line = json.loads(lines[0])
     assert line["n_gpus"] == 1 and line["launcher"] == "single process" and line["device_error_flag"] == 0
+    assert line["steps"] == 44 and line["config"]["events"]["imu"] + line["config"]["events"]["vision"] == 44
+    assert abs(line["value"] * line["ms_per_step"] / 1e3 - 1.0) < 1e-9  # (one filter: steps/s and ms per step describe the same window)
+    assert "roofline" not in line and "batch8" not in line  # (what --full adds)
+    files = sorted(p.name for p in out.iterdir())
+    assert files == sorted(n + ".npy" for n in ("position", "attitude_q", "velocity", "landmarks", "bias", "pose_sigma_norm", "sigma"))
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64_000_000
+    a = {p.stem: np.load(p) for p in out.iterdir()}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["sigma"].shape == (1, 611, 611) and a["landmarks"].shape == (1, 200, 3) and a["pose_sigma_norm"].shape == (1, 8)
+    assert np.linalg.norm(a["sigma"][0]) == line["sigma_fro_filter0"] == a["pose_sigma_norm"][0, 7]
+    assert np.array_equal(a["position"][0], a["pose_sigma_norm"][0, :3]) and np.array_equal(a["attitude_q"][0], a["pose_sigma_norm"][0, 3:7])
