@@ -59,8 +59,8 @@ EXPORTED_SYMBOLS = [
     "eqf_settings_default", "eqf_create", "eqf_destroy", "eqf_reset", "eqf_process_imu", "eqf_process_vision",
     "eqf_stream_upload", "eqf_stream_imu", "eqf_stream_vision", "eqf_synchronize", "eqf_get_time", "eqf_num_landmarks",
     "eqf_get_ids", "eqf_get_state_estimate", "eqf_get_origin", "eqf_get_group", "eqf_get_bias", "eqf_get_sigma",
-    "eqf_set_sigma", "eqf_set_state", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_profile_enable",
-    "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
+    "eqf_set_sigma", "eqf_set_state", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
+    "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
     "eqf_tiled_create", "eqf_tiled_destroy", "eqf_tiled_set_stream", "eqf_tiled_set_geometry", "eqf_tiled_propagate", "eqf_tiled_add_landmarks",
     "eqf_tiled_edit_landmarks", "eqf_tiled_propagate_burst", "eqf_tiled_stage_bearings", "eqf_tiled_pingpong",
     "eqf_tiled_update_prep", "eqf_tiled_update_finish", "eqf_tiled_synchronize", "eqf_tiled_num_landmarks", "eqf_tiled_get_time",
@@ -123,6 +123,8 @@ def lib():
             L.eqf_debug_launch_shape.argtypes = [vp, C.POINTER(C.c_int)]
         L.eqf_set_dense_propagate.argtypes = [vp, C.c_int]
         L.eqf_set_imu_burst.argtypes = [vp, C.c_int]
+        if hasattr(L, "eqf_set_option"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
+            L.eqf_set_option.argtypes = [vp, C.c_char_p, C.c_int]
         L.eqf_profile_enable.argtypes = [vp, C.c_int]
         L.eqf_profile_get.argtypes = [vp, C.c_int, C.POINTER(C.c_longlong), _dp]
         L.eqf_profile_class_name.argtypes = [C.c_int]
@@ -143,6 +145,11 @@ def lib():
             L.eqf_tile_downdate_i8.argtypes = [C.c_int, vpp, vpp, C.c_int, C.c_int, C.c_int, vpp, C.c_int, vpp, C.c_int, C.c_int, C.c_int, C.c_int, vpp, C.c_size_t]
         if hasattr(L, "eqf_tile_gemm_tn_i8"):
             L.eqf_tile_gemm_tn_i8.argtypes = [C.c_int, vpp, vpp, C.c_int, C.c_int, C.c_int, vpp, C.c_int, vpp, C.c_int, C.c_int, C.c_int] + [C.c_int] * 9 + [vpp, C.c_size_t]
+        if hasattr(L, "eqf_tile_syrk_i8"):
+            L.eqf_tile_syrk_i8_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+            L.eqf_tile_syrk_i8_workspace_bytes.restype = C.c_size_t
+            L.eqf_tile_syrk_i8.argtypes = [C.c_int, vpp, C.c_int, _ip, _ip, vpp, C.c_int, C.c_longlong, vpp, vpp, C.c_int, C.c_longlong, C.c_int,
+                                           vpp, C.c_size_t]
         L.eqf_stream_create_masked.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vpp)]
         L.eqf_stream_destroy.argtypes = [C.c_int, vpp]
         # the 2-D block-partitioned filter (BASELINE configs[4]); device buffers are plain pointers (torch tensors' data_ptr)
@@ -311,6 +318,12 @@ class FilterBatch:
         """IMU calls are queued and launched as bursts of up to `max_steps` steps (0: one launch per call); see
         include/eqf_vio_amd.h."""
         _check(lib().eqf_set_imu_burst(self._h, int(max_steps)), "eqf_set_imu_burst")
+
+    def set_option(self, name, value):
+        """Handle option by name (include/eqf_vio_amd.h: eqf_set_option): ``"downdate_slices"`` 0 (fp64, default) / 5 / 6 / 7 -- the
+        covariance downdate on the integer matrix pipe from that many 7-bit slices (6 holds Sigma within 1e-4 of fp64, 5 does not) --
+        or ``"res_tickets"`` 0 / 1 / 2."""
+        _check(lib().eqf_set_option(self._h, name.encode(), int(value)), "eqf_set_option")
 
     def synchronize(self):
         _check(lib().eqf_synchronize(self._h), "eqf_synchronize")

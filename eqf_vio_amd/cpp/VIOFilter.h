@@ -149,6 +149,10 @@ class VIOFilter {
         check(eqf_process_vision(handle_.get(), &measurement.stamp, &nb, ids_.data(), y_.data(), nb, &lastStatus_), "eqf_process_vision");
     }
 
+    // Handle option by name (include/eqf_vio_amd.h: eqf_set_option), e.g. setOption("downdate_slices", 6): the covariance downdate on the
+    // integer matrix pipe from six 7-bit slices per column of Y (off by default: fp64).
+    void setOption(const char* name, int value) { check(eqf_set_option(handle_.get(), name, value), "eqf_set_option"); }
+
     // VIOFilter.cpp:74-82: origin pose from the given attitude / position, zero origin velocity, camera offset replaced,
     // filter marked initialised (so the first IMU sample does no gravity alignment).
     void setAuxiliaryData(const AuxiliaryFilterData& auxiliaryData) {

@@ -21,6 +21,7 @@
 #include "eqf_chol64.hpp"
 #include "eqf_resident.hpp"
 #include "eqf_update.hpp"
+#include "eqf_i8dd.hpp"
 
 using namespace eqf;
 
@@ -191,6 +192,12 @@ struct eqf_filter {
     int *dReadyA = nullptr, *dReadyY = nullptr, *dResCounters = nullptr, *dStageFlags = nullptr;
     unsigned* dTicket = nullptr;  // k_chol_resident on a grid larger than the chip: arrival tickets, [B][32] (ResArgs::ticket); ticketBase = tickets drawn per filter by earlier launches
     unsigned ticketBase = 0;
+    // the covariance downdate on the integer matrix pipe (eqf_i8dd.hpp; eqf_set_option "downdate_slices"): slices (0 = fp64), and the
+    // workspace of the split -- slices for i8Slices, i8WsStride bytes per filter, and the columns' exponent words
+    int ddSlices = 0, i8Slices = 0;
+    signed char* dI8Ws = nullptr;
+    int* dI8Expo = nullptr;
+    long long i8WsStride = 0;
     int resTickets = 0;           // eqf_debug_option "res_tickets": 0 (default) the block index (rounds 3-5), 1 tickets on grids >= 6 x the resident slots, 2 on every grid larger than the chip (non-FOLD)
     double *dGammaPart = nullptr, *dG11Part = nullptr;
     ResRole* dRoles = nullptr;
@@ -857,6 +864,10 @@ int launchUpdateT(eqf_filter* f, const double* bearings, long long bearStride, c
     if (resESigma && f->eFromSigma && f->precision != EQF_PRECISION_F32) a.eFromSigma = 2;
     fold = fold && resident;
     if (fold) a.eFromSigma = 2;
+    // the downdate on the integer pipe (eqf_set_option "downdate_slices"): never inside the chain launches -- k_chol_resident runs without its
+    // downdate tiles, the per-column shapes without `embed` -- but as the tail launch below, for every launch shape
+    const int i8S = std::is_same<T, double>::value ? f->ddSlices : 0;
+    if (i8S && !resident) embed = false;
     // (round 5, measured and dropped: with the burst's operands in place, the landmark work as one LANE per landmark -- 128 per workgroup, the
     // stores from an LDS image -- instead of one wavefront: bit for bit the same and no faster.  Such a workgroup takes 21-31 us (33
     // uncoalesced loads per lane, then the stores) against 12.7 us for the 4-landmark ones, and a launch of 64 filters is three dispatch
@@ -921,7 +932,7 @@ int launchUpdateT(eqf_filter* f, const double* bearings, long long bearStride, c
             // waits for a higher block index)
             ra.nRoles = f->rolesCount;
             ra.errflag = f->errflag;
-            const int ddGrid = ra.ddNt * (ra.ddNt + 1) / 2;  // downdate tiles as workgroups of their own behind the roles
+            const int ddGrid = i8S ? 0 : ra.ddNt * (ra.ddNt + 1) / 2;  // downdate tiles as workgroups of their own behind the roles
             rc = profiled(f, EQF_PROF_CHOL_RESIDENT, [&] {
                 // (row heads with the pipelined panel loop only on a grid larger than the chip: see the kernel's PIPEH)
                 const bool pipeHeads = resPipeHeads;
@@ -997,9 +1008,20 @@ int launchUpdateT(eqf_filter* f, const double* bearings, long long bearStride, c
             }
             if (rc) return rc;
         }
-        tailLaunch = !embed;
+        tailLaunch = !embed || i8S;
     }
-    if (tailLaunch) {
+    if (tailLaunch && i8S) {
+        // split + symmetric product on the integer pipe; the innovation lift rides along in the split launch unless k_chol_resident's roles
+        // ran it (they do whenever the resident kernel runs: `embed`)
+        I8DdArgs ia{};
+        ia.Y = a.YO; ia.ldY = a.ldY; ia.strideY = a.strideY;
+        ia.Sin = static_cast<const double*>(a.Sin); ia.Sout = static_cast<double*>(a.Sout); ia.ld = a.ld; ia.sigmaStride = a.sigmaStride;
+        ia.g = a.g; ia.dims = nullptr; ia.pad = a.pad; ia.skipCol = 11;
+        ia.ws = f->dI8Ws; ia.wsStride = f->i8WsStride; ia.expo = f->dI8Expo; ia.expoStride = i8ddExpoWords(kLm0 + 3 * f->cap);
+        ia.B = B; ia.nt = (nv + 63) / 64;
+        rc = profiled(f, EQF_PROF_DOWNDATE, [&] { launchI8DdS(i8S, ia, resident ? nullptr : &a, (nv + 31) / 32, f->stream); });
+        if (rc) return rc;
+    } else if (tailLaunch) {
         // the last workgroup of the launch runs the (independent) innovation-lift / group-update part
         rc = profiled(f, EQF_PROF_DOWNDATE, [&] {
             if (small) hipLaunchKernelGGL((k_downdate<T, 32>), dim3(ddTiles + 1, B), dim3(256), (downdateLdsBytes<T, 32>()), f->stream, a, nt32, 1);
@@ -1559,7 +1581,7 @@ void freeAll(eqf_filter* f) {
              (void*)f->ZO, (void*)f->dbgDelta, (void*)f->dbgGamma, (void*)f->dbgGammaTot, (void*)f->red, (void*)f->errflag, (void*)f->dMap,
              (void*)f->dPerm, (void*)f->dChord, (void*)f->dDepth2, (void*)f->dDepthSel, (void*)f->dScratch, (void*)f->dMeas,
              (void*)f->dOut, (void*)f->dRing, (void*)f->sImu, (void*)f->sVis, (void*)f->sBear, f->dF, f->dG, f->dBn, f->dBlk, (void*)f->dBlkCommon, f->dColRec, f->dRowRec, (void*)f->dSteps, (void*)f->dFlags, (void*)f->dReadyA, (void*)f->dReadyY, (void*)f->dResCounters, (void*)f->dTicket, (void*)f->dStageFlags, (void*)f->dPrepFlags, (void*)f->dBuildFlags, (void*)f->dGammaPart,
-             (void*)f->dG11Part, (void*)f->dRoles})
+             (void*)f->dG11Part, (void*)f->dRoles, (void*)f->dI8Ws, (void*)f->dI8Expo})
         hipFree(p);
     if (f->hGate) hipHostFree(f->hGate);
     if (f->dMask) hipFree(f->dMask);
@@ -2374,6 +2396,102 @@ int eqf_debug_option(eqf_filter* f, const char* name, int value) {
         return EQF_OK;
     }
     return EQF_ERR_INVALID;
+}
+
+int eqf_set_option(eqf_filter* f, const char* name, int value) {
+    if (!f || !name) return EQF_ERR_INVALID;
+    if (!std::strcmp(name, "downdate_slices")) {
+        if (value != 0 && (value < 5 || value > 7)) return EQF_ERR_INVALID;
+        if (value && f->precision == EQF_PRECISION_F32) return EQF_ERR_UNSUPPORTED;
+        GATE(f);
+        if (value > f->i8Slices) {
+            // workspace from the capacity: the slices of every filter's Y (mp x nv at most) and one exponent word per column
+            const int nvCap = kLm0 + 3 * f->cap, mpCap = roundUp(sDim(f->cap), kSB);
+            if (!i8ddExact(mpCap, value)) return EQF_ERR_CAPACITY;  // (int32 accumulation would no longer be exact: capacity > ~37 000)
+            HIPC(hipStreamSynchronize(f->stream));
+            hipFree(f->dI8Ws);
+            hipFree(f->dI8Expo);
+            f->dI8Ws = nullptr;
+            f->dI8Expo = nullptr;
+            f->i8Slices = 0;
+            f->ddSlices = 0;
+            const long long stride = i8ddSliceBytes(nvCap, mpCap, value);
+            if (hipMalloc(&f->dI8Ws, size_t(stride) * f->B) != hipSuccess ||
+                hipMalloc(&f->dI8Expo, sizeof(int) * size_t(i8ddExpoWords(nvCap)) * f->B) != hipSuccess) {
+                (void)hipGetLastError();  // (a failed allocation must not fail the next update through the sticky last error)
+                hipFree(f->dI8Ws);
+                hipFree(f->dI8Expo);
+                f->dI8Ws = nullptr;
+                f->dI8Expo = nullptr;
+                return EQF_ERR_HIP;
+            }
+            f->i8WsStride = stride;
+            f->i8Slices = value;
+        }
+        f->ddSlices = value;
+        return EQF_OK;
+    }
+    if (!std::strcmp(name, "res_tickets")) {
+        if (value < 0 || value > 2) return EQF_ERR_INVALID;
+        GATE(f);
+        f->resTickets = value;
+        return EQF_OK;
+    }
+    return EQF_ERR_INVALID;
+}
+
+int eqf_tile_syrk_i8(int device, void* stream, int batch, const int* nv, const int* mp, const double* Y, int ldY, long long strideY,
+    const double* Sin, double* Sout, int ld, long long sigmaStride, int slices, void* workspace, size_t workspace_bytes) {
+    if (batch < 1 || !nv || !mp || !Y || !Sin || !Sout || !workspace || slices < 5 || slices > 7 || Sin == Sout) return EQF_ERR_INVALID;
+    int nvMax = 1, mpMax = 32;
+    for (int b = 0; b < batch; ++b) {
+        if (nv[b] < 1 || mp[b] < 0 || mp[b] % 32 || nv[b] > ld || nv[b] > ldY) return EQF_ERR_INVALID;
+        nvMax = std::max(nvMax, nv[b]);
+        mpMax = std::max(mpMax, mp[b]);
+    }
+    if (!i8ddExact(mpMax, slices)) return EQF_ERR_INVALID;
+    if ((long long)ld * nvMax > sigmaStride && batch > 1) return EQF_ERR_INVALID;
+    if ((long long)ldY * mpMax > strideY && batch > 1) return EQF_ERR_INVALID;
+    if (workspace_bytes < eqf_tile_syrk_i8_workspace_bytes(batch, nvMax, mpMax, slices)) return EQF_ERR_INVALID;
+    int prev = 0;
+    HIPC(hipGetDevice(&prev));
+    HIPC(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // layout of the workspace: the dims [batch][2], the exponent words, the slices (1 KB aligned)
+    const long long stride = i8ddSliceBytes(nvMax, mpMax, slices);
+    const int expoWords = i8ddExpoWords(nvMax);
+    char* ws = static_cast<char*>(workspace);
+    int* dDims = reinterpret_cast<int*>(ws);
+    int* dExpo = dDims + roundUp(2 * batch, 256);
+    signed char* dSl = reinterpret_cast<signed char*>(ws + roundUp(int(sizeof(int)) * (roundUp(2 * batch, 256) + expoWords * batch), 1024));
+    std::vector<int> hd(2 * batch);
+    for (int b = 0; b < batch; ++b) {
+        hd[2 * b] = nv[b];
+        hd[2 * b + 1] = mp[b];
+    }
+    HIPC(hipStreamSynchronize(st));  // (the workspace may still be in use by an earlier call on this stream)
+    HIPC(hipMemcpy(dDims, hd.data(), sizeof(int) * 2 * batch, hipMemcpyHostToDevice));
+    I8DdArgs ia{};
+    ia.Y = Y; ia.ldY = ldY; ia.strideY = strideY;
+    ia.Sin = Sin; ia.Sout = Sout; ia.ld = ld; ia.sigmaStride = sigmaStride;
+    ia.g = nullptr; ia.dims = dDims; ia.pad = 32; ia.skipCol = -1;
+    ia.ws = dSl; ia.wsStride = stride; ia.expo = dExpo; ia.expoStride = expoWords;
+    ia.B = batch; ia.nt = (nvMax + 63) / 64;
+    launchI8DdS(slices, ia, nullptr, (nvMax + 31) / 32, st);
+    const hipError_t e = hipGetLastError();
+    (void)hipSetDevice(prev);
+    if (e != hipSuccess) {
+        std::fprintf(stderr, "eqf_vio_amd: eqf_tile_syrk_i8: %s\n", hipGetErrorString(e));
+        return EQF_ERR_HIP;
+    }
+    return EQF_OK;
+}
+
+size_t eqf_tile_syrk_i8_workspace_bytes(int batch, int max_nv, int max_mp, int slices) {
+    if (batch < 1 || max_nv < 1 || max_mp < 0 || slices < 5 || slices > 7) return 0;
+    max_mp = std::max(roundUp(max_mp, 32), 32);
+    const long long head = roundUp(int(sizeof(int)) * (roundUp(2 * batch, 256) + i8ddExpoWords(max_nv) * batch), 1024);
+    return size_t(head + i8ddSliceBytes(max_nv, max_mp, slices) * batch);
 }
 
 int eqf_set_imu_burst(eqf_filter* f, int max_steps) {

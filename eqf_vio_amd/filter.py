@@ -133,6 +133,11 @@ class VIOFilter:
     def reset(self):
         self._fb.reset()
 
+    def set_option(self, name, value):
+        """Handle option by name (include/eqf_vio_amd.h: eqf_set_option), e.g. ``set_option("downdate_slices", 6)``: the covariance downdate
+        on the integer matrix pipe (off by default)."""
+        self._fb.set_option(name, value)
+
     @property
     def batch(self):
         return self._fb

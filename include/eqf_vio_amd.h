@@ -175,6 +175,19 @@ int eqf_device_error(eqf_filter* f);
  * is called (getters, eqf_synchronize, ...): the deferral is invisible apart from timing.  max_steps = 0 launches
  * every call at once through the single-step kernel (k_propagate); default 15 (environment: EQF_IMU_BURST). */
 int eqf_set_imu_burst(eqf_filter* f, int max_steps);
+/* Handle options by name.  EQF_ERR_INVALID (no effect) for a NULL handle or name, an unknown name or a value out of range.
+ *   "downdate_slices" 0 (default) | 5 | 6 | 7: the covariance downdate Sigma - Y^T Y of every vision update (VIOFilter.cpp:297) on the
+ *       INTEGER matrix pipe: Y's columns are scaled by powers of two and cut into that many 7-bit slices, multiplied with exact int32
+ *       accumulation and recombined in fp64 (csrc/eqf_i8dd.hpp).  Sigma stays fp64 and exactly symmetric.  Six slices keep Sigma within
+ *       1e-4 of the fp64 downdate on the bench streams; FIVE DO NOT and are there for measurement; seven come within
+ *       ~1e-8.  A NaN / Inf in Y makes the rows and columns of Sigma it touches non-finite, as in fp64.  Takes effect at the next vision
+ *       update, per call and in stream mode alike; 0 returns to the fp64 downdate (bit for bit the default).  The first non-zero value
+ *       allocates the slices' workspace from capacity and batch (about capacity^2 * 6 * slices bytes per filter): EQF_ERR_HIP if that fails
+ *       (the option stays as it was).  EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle.
+ *   "res_tickets" 0 (default) | 1 | 2: arrival tickets for the workgroups of the one-launch factorisation on grids larger than the chip (1:
+ *       grids of at least six times the resident slots, 2: all of them) -- for a device or driver that might not start workgroups in the
+ *       order of their index (see eqf_device_error); the result is bit for bit the same. */
+int eqf_set_option(eqf_filter* f, const char* name, int value);
 
 /* Propagate backend: 0 = block-structured HBM-bound kernel (default, product path),
  * 1 = dense F Sigma F^T on MFMA (what the reference executes; BASELINE cfg 3 cross-check). */

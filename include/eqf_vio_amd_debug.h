@@ -135,6 +135,15 @@ int eqf_tile_downdate_i8(int device, void* stream, double* C, int ldc, int m, in
 int eqf_tile_gemm_tn_i8(int device, void* stream, double* C, int ldc, int m, int n, const double* A, int lda, const double* B, int ldb, int k,
     int slices, int mask_rb, int mask_cb, int rblk0, int Pr, int pr, int cblk0, int Pc, int pc, int mask_cols, void* workspace,
     size_t workspace_bytes);
+/* eqf_tile_syrk_i8: the kernels behind eqf_set_option "downdate_slices" (csrc/eqf_i8dd.hpp) on caller-owned device buffers, batched: for
+ *   b < batch, Sout_b = Sin_b - Y_b^T Y_b over the leading nv[b] x nv[b] of Sigma (ld, sigmaStride doubles between the filters) and the leading
+ *   mp[b] rows x nv[b] columns of Y (ldY, strideY), with `slices` (5, 6 or 7) 7-bit slices per column and exact int32 accumulation.  mp[b] is
+ *   a multiple of 32; mp[b] == 0 copies Sin_b.  The upper triangle is formed, the lower one written from the same values (exactly
+ *   symmetric).  A column of Y with a NaN / Inf makes its row and column of Sout NaN.  nv / mp are host arrays; the call synchronises the
+ *   stream before it reuses the workspace (at least eqf_tile_syrk_i8_workspace_bytes(batch, max nv, max mp, slices) bytes). */
+size_t eqf_tile_syrk_i8_workspace_bytes(int batch, int max_nv, int max_mp, int slices);
+int eqf_tile_syrk_i8(int device, void* stream, int batch, const int* nv, const int* mp, const double* Y, int ldY, long long strideY,
+    const double* Sin, double* Sout, int ld, long long sigmaStride, int slices, void* workspace, size_t workspace_bytes);
 int eqf_tile_potrf(int device, void* stream, double* A, int ld, int n, double* drec, int* info);
 int eqf_tile_trsm(int device, void* stream, const double* A, int ld, int n, const double* drec, double* B, int ldb, int m, int right);
 
