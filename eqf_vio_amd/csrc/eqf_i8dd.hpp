@@ -5,8 +5,9 @@
 // The same construction as the partitioned filter's eqf_tile_downdate_i8 (eqf_tile.hpp): every column of Y is scaled by a power of two and cut
 // into S signed 7-bit slices (|q| <= 64), the slice pairs (ta, tb) with ta + tb < S are multiplied on v_mfma_i32_32x32x32_i8 with EXACT int32
 // accumulation (mp * S * 64^2 < 2^31: the host checks it against the handle's capacity) and the S accumulators of an element (one per ta + tb)
-// are recombined in fp64.  Lost is only what the slices do not hold: the bits of an entry below 2^-(6 + 7 (S - 1)) of its column's largest
-// entry, and the dropped slice pairs ta + tb >= S.  Six slices keep Sigma within 1e-4 of the fp64 downdate on the bench streams; FIVE do NOT
+// are recombined in fp64.  Lost are the rounding of every entry to the slices (at most 2^-7S of its column's power of two per entry) and the
+// dropped slice pairs ta + tb >= S (up to (S - 1) 2^-7S per product term): the rigorous bound and a bit-exact numpy model of these kernels
+// are in tests/i8_emulator.py.  Entries are scaled by ldexp(x, -e) each, not times 2^-e (which overflows below 2^-1024).  Six slices keep Sigma within 1e-4 of the fp64 downdate on the bench streams; FIVE do NOT
 // (1.4e-4 .. 9e-4 on the partitioned filter) and are accepted for measurement only; seven reach ~1e-8.
 //
 // Two launches, batched over the filters of a handle (each filter its own nv = kLm0 + 3 N rows / columns of Sigma and mp rows of Y, the rows
@@ -113,14 +114,15 @@ __global__ __launch_bounds__(256) void k_i8dd_split(I8DdArgs a, UpdArgs u, int w
     const int c = ct * 32 + (l & 31);
     const int es = a.expo[(long long)b * a.expoStride + c];  // (written by this workgroup: the barrier above orders it)
     const bool live = c < nv && c != a.skipCol && es > kI8ddNonFinite;
-    const double sc = live ? ldexp(1.0, -(es - 2048)) : 0.0;
+    const int e = live ? es - 2048 : 0;
     int4* out = reinterpret_cast<int4*>(a.ws + (long long)b * a.wsStride);
     for (int kc = tid >> 6; kc < nKc; kc += 4) {
         const int k0 = kc * 32 + (l >> 5) * 16;
         signed char q[S][16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            double r = live ? Y[(long long)(k0 + j) * a.ldY + c] * sc : 0.0;  // |r| < 1, exact (power-of-two scale)
+            // |r| < 1, correctly rounded (exact unless it underflows); per entry, not times 2^-e: that factor overflows when e < -1023
+            double r = live ? ldexp(Y[(long long)(k0 + j) * a.ldY + c], -e) : 0.0;
             double w = 64.0, wi = 0.015625;                                    // 2^6, then 2^13, 2^20, ...
 #pragma unroll
             for (int t = 0; t < S; ++t) {

@@ -588,41 +588,55 @@ __global__ __launch_bounds__(256) void k_tile_trsm(const double* A, int ld, int 
 // The downdate's product on the INTEGER matrix pipe (round 6; opt-in, eqf_tf_set_option "downdate_slices"): C -= A^T B for A (k x m), B (k x n)
 // row-major (VIOFilter.cpp:297 as Sigma - Y^T Y), with every column of A and B scaled by a power of two and cut into S signed 7-bit slices
 // (int8, |q| <= 64): the S (S + 1) / 2 slice pairs (ta, tb) with ta + tb < S are multiplied on v_mfma_i32_32x32x32_i8 -- int32 accumulation is
-// EXACT (k * S * 64^2 < 2^31 for k <= 70 000) -- and the S accumulators of an element (one per ta + tb) are recombined in fp64.  What is lost
-// is only what the slices do not hold: the bits of an entry below 2^-(6 + 7 (S - 1)) of its column's largest entry (S = 5: 34 bits, 6: 41, 7:
-// 48).  Sigma itself stays fp64 in memory, and unlike an fp32 product nothing is lost in the accumulation -- the two things DESIGN.md section
-// 2 measured fp32 to fail on.  What the filter needs was measured on the bench stream with this truncation put into the fp64 restatement
+// EXACT (k * S * 64^2 < 2^31 for k <= 70 000) -- and the S accumulators of an element (one per ta + tb) are recombined in fp64.  Two things
+// are lost: the rounding of every entry to the slices (at most 2^-7S of its column's power of two 2^e, so up to 2 x 2^-7S per product term),
+// and the slice pairs ta + tb >= S that are not multiplied (up to (S - 1) x 2^-7S per term); with the S - 1 roundings of the recombination
+// |error_ij| <= k 2^(e_i + e_j) ((2 + (S - 1)) 2^-7S + ...) -- the rigorous bound is derived in tests/i8_emulator.py, the kernels' numpy
+// model, which they equal bit for bit (tests/test_gpu_i8_exact.py).  Random data stay well inside it; inputs whose digits all have the same
+// sign come close (an older "k ca cb 2^-(5 + 7 (S - 1))" bound is exceeded by 1.5x there).  Sigma itself stays fp64 in memory, and unlike an
+// fp32 product nothing is lost in the accumulation -- the two things DESIGN.md section 2 measured fp32 to fail on.  What the filter needs was measured on the bench stream with this truncation put into the fp64 restatement
 // (scripts/slice_precision_study.py, profiles/r06_slice_precision_study*.txt) and with this kernel in the filter (profiles/r06_i8_downdate_error.txt):
 // the truncation alone would allow S = 5 (5e-6), but the slice pairs the product drops (ta + tb >= S: products of the LOWER slices, of the
 // truncation's size) add up coherently over Y's correlated columns -- S = 5: 1.4e-4 .. 9e-4, misses; S = 6: 2e-6 .. 6e-5; S = 7: 1e-8 .. 8e-8.
-//   k_i8_colexp   per column the exponent of its largest |entry| (frexp), as an atomicMax over row slabs (expo zeroed by k_i8_zero; stored + 2048)
+//   k_i8_colexp   per column the exponent of its largest |entry| (frexp), as an atomicMax over row slabs (expo zeroed by k_i8_zero; stored + 2048);
+//                 a column holding a NaN / Inf gets kI8NonFinite, which wins the atomicMax: it is cut as zeros and the epilogue writes NaN
+//                 into its whole row / column of C (what fp64 gives: x NaN and Inf x 0 are NaN; never finite garbage)
 //   k_i8_split<S> the slices in MFMA FRAGMENT order: for a 32-column tile ct, a 32-row chunk kc and slice t one 1 KB block whose lane l holds
 //                 column ct * 32 + (l & 31), rows kc * 32 + 16 (l >> 5) .. + 16  -- the operand layout of v_mfma_i32_32x32x32_i8; block index
-//                 ((ct * nKc + kc) * S + t).  Rows past k and columns past m are zero.
+//                 ((ct * nKc + kc) * S + t).  Rows past k and columns past m are zero.  Entries are scaled by ldexp(x, -e) each (a factor
+//                 2^-e would overflow for a column whose largest entry is below 2^-1024; both are correctly rounded, so results are the same
+//                 wherever the factor exists).
 //   k_i8_gemm<S>  512 threads = 8 waves as 4 x 2, workgroup tile 128 (rows of C) x 64, a wave owns ONE 32 x 32 MFMA tile with S accumulators
 //                 (two waves per SIMD); a chunk's 4 S + 2 S fragment blocks go global -> LDS directly (global_load_lds_dwordx4: the global
 //                 layout IS the LDS image), three LDS buffers (chunk kc + 2 in flight while kc is multiplied), one raw s_barrier per chunk
 //                 behind a counted vmcnt.  mk.rb > 0: the first maskCols columns of C are masked as in k_tile_gemm_tn (GemmMask: tiles entirely
 //                 below the block diagonal are skipped -- the downdate's symmetric local matrix, which k_tile_mirror completes, and the
-//                 factorisations' upper block rows); columns from maskCols on (right-hand sides) are always formed.  Epilogue: C[i][j] += alpha 2^(eA[i] + eB[j]) sum_d acc_d 2^-(12 + 7 d).
+//                 factorisations' upper block rows); columns from maskCols on (right-hand sides) are always formed.  Epilogue: C[i][j] += alpha 2^(eA[i] + eB[j]) sum_d acc_d 2^-(12 + 7 d)
+//                 (nothing for an all-zero column, NaN for a flagged one).
 // Measured (scripts/micro/i8_split_gemm.hip, profiles/r06_i8_split_gemm_v2.txt): S = 5: 84 - 108 fp64-equivalent TFLOP/s at the downdate's
 // shapes (1.3 - 1.6 POPS of int8) against 51 - 57 for k_tile_gemm_tn in the same run.
 typedef int i8v4 __attribute__((ext_vector_type(4)));
 typedef int i8v16 __attribute__((ext_vector_type(16)));
 constexpr int kI8Bits = 7;
+constexpr int kI8NonFinite = 4096;  // exponent word of a column holding a NaN / Inf: above every frexp exponent + 2048 (<= 3072)
 
 __global__ __launch_bounds__(256) void k_i8_colexp(const double* X, int K, int M, int ld, int* expo) {
     const int c = blockIdx.x * 64 + (threadIdx.x & 63), kq = threadIdx.x >> 6;
     const int k0 = blockIdx.y * 512, k1 = min(k0 + 512, K);
     double mx = 0.0;
     if (c < M)
-        for (int k = k0 + kq; k < k1; k += 4) mx = fmax(mx, fabs(X[(long long)k * ld + c]));
+        for (int k = k0 + kq; k < k1; k += 4) {
+            const double x = X[(long long)k * ld + c];
+            mx = fmax(mx, isfinite(x) ? fabs(x) : INFINITY);  // (fmax drops a NaN: a non-finite entry counts as +Inf)
+        }
     __shared__ double sm[4][64];
     sm[kq][threadIdx.x & 63] = mx;
     __syncthreads();
     if (kq == 0 && c < M) {
         mx = fmax(fmax(sm[0][threadIdx.x], sm[1][threadIdx.x]), fmax(sm[2][threadIdx.x], sm[3][threadIdx.x]));
-        if (mx > 0.0) {
+        if (mx == INFINITY) {
+            atomicMax(expo + c, kI8NonFinite);  // (wins over every row slab's exponent)
+        } else if (mx > 0.0) {
             int e = 0;
             frexp(mx, &e);  // mx = f 2^e, f in [0.5, 1): |x| 2^-e < 1
             atomicMax(expo + c, e + 2048);
@@ -641,12 +655,14 @@ __global__ __launch_bounds__(256) void k_i8_split(const double* X, int K, int M,
     if (kc >= nKc) return;
     const int c = ct * 32 + (l & 31), k0 = kc * 32 + (l >> 5) * 16;
     const int es = c < M ? expo[c] : 0;
-    const double sc = (c < M && es > 0) ? ldexp(1.0, -(es - 2048)) : 0.0;
+    const bool live = c < M && es > 0 && es != kI8NonFinite;  // (a column with a NaN / Inf is cut as zeros: the epilogue writes NaN for it)
+    const int e = live ? es - 2048 : 0;
     signed char q[S][16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         const int k = k0 + j;
-        double r = (c < M && k < K) ? X[(long long)k * ld + c] * sc : 0.0;  // |r| < 1, exact (power-of-two scale)
+        // |r| < 1, correctly rounded (exact unless it underflows); per entry, not times 2^-e: that factor overflows when e < -1023
+        double r = (live && k < K) ? ldexp(X[(long long)k * ld + c], -e) : 0.0;
         double w = 64.0, wi = 0.015625;                                    // 2^6, then 2^13, 2^20, ...
 #pragma unroll
         for (int t = 0; t < S; ++t) {
@@ -744,10 +760,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int d = S - 1; d >= 0; --d) v += ldexp((double)acc[d][r], -(12 + kI8Bits * d));  // smallest terms first
             const int ei = eA[i];
-            if (ei > 0 && eB[j] > 0) {  // (a column that is all zero has no exponent and contributes nothing)
-                double* dst = C + (long long)i * ldc + j;
-                *dst += alpha * ldexp(v, ei - 2048 + ej);
-            }
+            double* dst = C + (long long)i * ldc + j;
+            if (ei == kI8NonFinite || eB[j] == kI8NonFinite) *dst = __builtin_nan("");  // (as fp64: x NaN / Inf poisons the element)
+            else if (ei > 0 && eB[j] > 0) *dst += alpha * ldexp(v, ei - 2048 + ej);  // (an all-zero column has no exponent: nothing)
         }
     }
 }

@@ -120,8 +120,10 @@ int eqf_tile_downdate(int device, void* stream, double* C, int ldc, int m, int n
     int k);
 /* eqf_tile_downdate_i8 (round 6): C (m x n, ldc) -= A^T B as eqf_tile_downdate, but on the INTEGER matrix pipe: every column of A and B is scaled
  *   by a power of two and cut into `slices` (5, 6 or 7) signed 7-bit pieces, the slice pairs are multiplied on v_mfma_i32_32x32x32_i8 with exact
- *   int32 accumulation and recombined in fp64 (csrc/eqf_tile.hpp).  The only error is the truncation of an entry below 2^-(6 + 7 (slices - 1)) of
- *   its column's largest entry; k <= 70 000.  mask_rb > 0 (m == n): C is a symmetric local matrix in blocks of mask_rb, tiles entirely below the
+ *   int32 accumulation and recombined in fp64 (csrc/eqf_tile.hpp).  The error is the rounding of every entry to its slices plus the slice pairs
+ *   (ta, tb) with ta + tb >= slices that are not multiplied: |error_ij| <= about k 2^(e_i + e_j) (slices + 1) 2^-(7 slices), 2^e_i the power
+ *   of two above column i's largest |entry| (the rigorous form: tests/i8_emulator.py); k <= 70 000.  A column of A or B holding a NaN / Inf
+ *   makes its row / column of C NaN, as in fp64.  mask_rb > 0 (m == n): C is a symmetric local matrix in blocks of mask_rb, tiles entirely below the
  *   block diagonal are skipped (eqf_tile_mirror completes them).  workspace: caller-owned device memory of at least
  *   eqf_tile_i8_workspace_bytes(m, n, k, slices, A == B) bytes (the slices of both operands, once if they are the same matrix). */
 size_t eqf_tile_i8_workspace_bytes(int m, int n, int k, int slices, int same_operand);

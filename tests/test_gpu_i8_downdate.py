@@ -343,8 +343,9 @@ def _syrk(torch, dev, Y, Sin, nv, mp, S):
 
 def test_kernels_against_numpy():
     """eqf_tile_syrk_i8 over batched shapes -- ragged nv / mp, filters of different sizes in one batch, a filter that is only copied, an
-    all-zero column, NaN / Inf entries -- against numpy within the truncation bound of the slices (tests/test_gpu_tiled.py), exact symmetry,
-    nothing written outside each filter's nv x nv."""
+    all-zero column, NaN / Inf entries -- against numpy within the statistical bound of tests/test_gpu_tiled.py (random data stay inside it;
+    the construction's rigorous bound is larger, tests/i8_emulator.py; bit for bit: tests/test_gpu_i8_exact.py), exact symmetry, nothing
+    written outside each filter's nv x nv."""
     import torch
 
     dev = torch.device("cuda", 0)

@@ -19,9 +19,10 @@ def _t(dev):
 
 def test_tile_downdate_on_the_integer_pipe_against_numpy():
     """C -= A^T B from 7-bit slices of the operands' columns on v_mfma_i32_32x32x32_i8 with exact int32 accumulation (round 6,
-    eqf_tile_downdate_i8): against numpy, with the error bound the construction gives -- every entry of an operand is truncated below
-    2^-(6 + 7 (S - 1)) of its column's largest entry, so |error_ij| <= k (ca_i cb_j) 2^-(5 + 7 (S - 1)) up to second order, ca / cb the columns'
-    largest entries -- on ragged sizes around the 128 x 64 x 32 tiling, views with leading dimensions, columns of very different scales, an
+    eqf_tile_downdate_i8): against numpy within k (ca_i cb_j) 2^-(5 + 7 (S - 1)), ca / cb the columns' largest entries.  That bound is
+    STATISTICAL, not what the construction guarantees: the rounding to slices (up to 2 x 2^-7S per term) and the dropped slice pairs
+    ta + tb >= S (up to (S - 1) x 2^-7S) exceed it on inputs whose errors share a sign (tests/test_i8_emulator.py); random data stay inside.
+    The bit-exact check against the kernels' model is tests/test_gpu_i8_exact.py.  On ragged sizes around the 128 x 64 x 32 tiling, views with leading dimensions, columns of very different scales, an
     all-zero column, the same matrix on both sides, and the block-upper mask."""
     import torch
 
@@ -65,8 +66,8 @@ def test_tile_downdate_on_the_integer_pipe_against_numpy():
 def test_tile_gemm_tn_on_the_integer_pipe_behind_the_block_mask():
     """eqf_tile_gemm_tn_i8 (round 6, what "chain_slices" runs for a block row's trailing products): C -= A^T B from slices, behind
     eqf_tile_gemm_tn's block mask over the first mask_cols columns (the matrix part) with the columns behind them (right-hand sides) always
-    formed; A as a column range of B (cut once: offsets that are a multiple of 32) and as a matrix of its own; the same error bound as the
-    downdate's product.  Below the staircase an element is untouched or the whole product, never garbage."""
+    formed; A as a column range of B (cut once: offsets that are a multiple of 32) and as a matrix of its own; the same statistical error
+    bound as the downdate's product (see there; bit for bit: tests/test_gpu_i8_exact.py).  Below the staircase an element is untouched or the whole product, never garbage."""
     import torch
 
     from eqf_vio_amd import tiled
