@@ -21,7 +21,7 @@
 #include "eqf_chol64.hpp"
 #include "eqf_resident.hpp"
 #include "eqf_update.hpp"
-#include "eqf_i8dd.hpp"
+#include "eqf_i8.hpp"
 
 using namespace eqf;
 
@@ -45,6 +45,17 @@ struct ProfSample {
     int key;  // launch shape within the class (chain step index, burst length, ...): launches of one key do identical work
     float ms;
 };
+
+// the downdate on the integer pipe (eqf_i8.hpp).  u != nullptr: the innovation lift rides along in the split launch (the per-column launch
+// shapes; k_chol_resident ran it in its roles)
+void launchI8Dd(int slices, const I8DdArgs& a, const UpdArgs* u, int nCt, hipStream_t st) {
+    UpdArgs uu{};
+    if (u) uu = *u;
+    i8WithSlices(slices, [&](auto s) {
+        hipLaunchKernelGGL((k_i8dd_split<s>), dim3(nCt + (u ? 1 : 0), a.B), dim3(256), 0, st, a, uu, u ? 1 : 0);
+        hipLaunchKernelGGL((k_i8dd_syrk<s>), dim3(a.nt * (a.nt + 1) / 2 * a.B), dim3(256), kI8ddLdsBytes, st, a);
+    });
+}
 }  // namespace
 
 // Ring of pinned int buffers for the small host->device uploads of the landmark bookkeeping (permutation, compaction map,
@@ -192,7 +203,7 @@ struct eqf_filter {
     int *dReadyA = nullptr, *dReadyY = nullptr, *dResCounters = nullptr, *dStageFlags = nullptr;
     unsigned* dTicket = nullptr;  // k_chol_resident on a grid larger than the chip: arrival tickets, [B][32] (ResArgs::ticket); ticketBase = tickets drawn per filter by earlier launches
     unsigned ticketBase = 0;
-    // the covariance downdate on the integer matrix pipe (eqf_i8dd.hpp; eqf_set_option "downdate_slices"): slices (0 = fp64), and the
+    // the covariance downdate on the integer matrix pipe (eqf_i8.hpp; eqf_set_option "downdate_slices"): slices (0 = fp64), and the
     // workspace of the split -- slices for i8Slices, i8WsStride bytes per filter, and the columns' exponent words
     int ddSlices = 0, i8Slices = 0;
     signed char* dI8Ws = nullptr;
@@ -1019,7 +1030,7 @@ int launchUpdateT(eqf_filter* f, const double* bearings, long long bearStride, c
         ia.g = a.g; ia.dims = nullptr; ia.pad = a.pad; ia.skipCol = 11;
         ia.ws = f->dI8Ws; ia.wsStride = f->i8WsStride; ia.expo = f->dI8Expo; ia.expoStride = i8ddExpoWords(kLm0 + 3 * f->cap);
         ia.B = B; ia.nt = (nv + 63) / 64;
-        rc = profiled(f, EQF_PROF_DOWNDATE, [&] { launchI8DdS(i8S, ia, resident ? nullptr : &a, (nv + 31) / 32, f->stream); });
+        rc = profiled(f, EQF_PROF_DOWNDATE, [&] { launchI8Dd(i8S, ia, resident ? nullptr : &a, (nv + 31) / 32, f->stream); });
         if (rc) return rc;
     } else if (tailLaunch) {
         // the last workgroup of the launch runs the (independent) innovation-lift / group-update part
@@ -2407,7 +2418,7 @@ int eqf_set_option(eqf_filter* f, const char* name, int value) {
         if (value > f->i8Slices) {
             // workspace from the capacity: the slices of every filter's Y (mp x nv at most) and one exponent word per column
             const int nvCap = kLm0 + 3 * f->cap, mpCap = roundUp(sDim(f->cap), kSB);
-            if (!i8ddExact(mpCap, value)) return EQF_ERR_CAPACITY;  // (int32 accumulation would no longer be exact: capacity > ~37 000)
+            if (!i8Exact(mpCap, value)) return EQF_ERR_CAPACITY;  // (int32 accumulation would no longer be exact: capacity > ~37 000)
             HIPC(hipStreamSynchronize(f->stream));
             hipFree(f->dI8Ws);
             hipFree(f->dI8Expo);
@@ -2415,7 +2426,7 @@ int eqf_set_option(eqf_filter* f, const char* name, int value) {
             f->dI8Expo = nullptr;
             f->i8Slices = 0;
             f->ddSlices = 0;
-            const long long stride = i8ddSliceBytes(nvCap, mpCap, value);
+            const long long stride = i8SliceBytes(mpCap, nvCap, value);
             if (hipMalloc(&f->dI8Ws, size_t(stride) * f->B) != hipSuccess ||
                 hipMalloc(&f->dI8Expo, sizeof(int) * size_t(i8ddExpoWords(nvCap)) * f->B) != hipSuccess) {
                 (void)hipGetLastError();  // (a failed allocation must not fail the next update through the sticky last error)
@@ -2449,16 +2460,15 @@ int eqf_tile_syrk_i8(int device, void* stream, int batch, const int* nv, const i
         nvMax = std::max(nvMax, nv[b]);
         mpMax = std::max(mpMax, mp[b]);
     }
-    if (!i8ddExact(mpMax, slices)) return EQF_ERR_INVALID;
+    if (!i8Exact(mpMax, slices)) return EQF_ERR_INVALID;
     if ((long long)ld * nvMax > sigmaStride && batch > 1) return EQF_ERR_INVALID;
     if ((long long)ldY * mpMax > strideY && batch > 1) return EQF_ERR_INVALID;
     if (workspace_bytes < eqf_tile_syrk_i8_workspace_bytes(batch, nvMax, mpMax, slices)) return EQF_ERR_INVALID;
-    int prev = 0;
-    HIPC(hipGetDevice(&prev));
-    HIPC(hipSetDevice(device));
+    DeviceScope ds(device);
+    if (!ds.ok) return EQF_ERR_HIP;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // layout of the workspace: the dims [batch][2], the exponent words, the slices (1 KB aligned)
-    const long long stride = i8ddSliceBytes(nvMax, mpMax, slices);
+    const long long stride = i8SliceBytes(mpMax, nvMax, slices);
     const int expoWords = i8ddExpoWords(nvMax);
     char* ws = static_cast<char*>(workspace);
     int* dDims = reinterpret_cast<int*>(ws);
@@ -2477,13 +2487,8 @@ int eqf_tile_syrk_i8(int device, void* stream, int batch, const int* nv, const i
     ia.g = nullptr; ia.dims = dDims; ia.pad = 32; ia.skipCol = -1;
     ia.ws = dSl; ia.wsStride = stride; ia.expo = dExpo; ia.expoStride = expoWords;
     ia.B = batch; ia.nt = (nvMax + 63) / 64;
-    launchI8DdS(slices, ia, nullptr, (nvMax + 31) / 32, st);
-    const hipError_t e = hipGetLastError();
-    (void)hipSetDevice(prev);
-    if (e != hipSuccess) {
-        std::fprintf(stderr, "eqf_vio_amd: eqf_tile_syrk_i8: %s\n", hipGetErrorString(e));
-        return EQF_ERR_HIP;
-    }
+    launchI8Dd(slices, ia, nullptr, (nvMax + 31) / 32, st);
+    HIPC(hipGetLastError());
     return EQF_OK;
 }
 
@@ -2491,7 +2496,7 @@ size_t eqf_tile_syrk_i8_workspace_bytes(int batch, int max_nv, int max_mp, int s
     if (batch < 1 || max_nv < 1 || max_mp < 0 || slices < 5 || slices > 7) return 0;
     max_mp = std::max(roundUp(max_mp, 32), 32);
     const long long head = roundUp(int(sizeof(int)) * (roundUp(2 * batch, 256) + i8ddExpoWords(max_nv) * batch), 1024);
-    return size_t(head + i8ddSliceBytes(max_nv, max_mp, slices) * batch);
+    return size_t(head + i8SliceBytes(max_mp, max_nv, slices) * batch);
 }
 
 int eqf_set_imu_burst(eqf_filter* f, int max_steps) {

@@ -1,4 +1,5 @@
-// Device-resident filter state of the MI355X EqF path, shared by the kernels and the C ABI host code.
+// Device-resident filter state of the MI355X EqF path, shared by the kernels and the C ABI host code; also the small types several kernel
+// headers and host translation units share (GemmMask, DeviceScope).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -60,6 +61,28 @@ struct ImuRec {
 struct LmPtrs {
     double* p0;  // [3][cap]
     double* Q;   // [5][cap]: qw qx qy qz a
+};
+
+// Block mask of the partitioned filter's products (k_tile_gemm_tn, k_i8_gemm): row r of C belongs to global block (rblk0 + r / rb) * Pr + pr,
+// column c to (cblk0 + c / cb) * Pc + pc.
+struct GemmMask {
+    int rb, cb;          // rows / columns per block (0 = no mask)
+    int rblk0, Pr, pr;   // local row block index of C's first row, process grid rows, this rank's grid row
+    int cblk0, Pc, pc;
+};
+
+// Host: the caller's (torch's) current device is restored when an entry point returns
+struct DeviceScope {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceScope(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceScope() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) hipSetDevice(prev);
+    }
 };
 
 }  // namespace eqf

@@ -17,6 +17,7 @@
 #include "../../include/eqf_vio_amd_debug.h"  // (the public header + the test / measurement hooks this library also exports)
 #include "eqf_tile.hpp"
 #include "eqf_tiled.hpp"
+#include "eqf_i8.hpp"
 
 using namespace eqf;
 
@@ -30,19 +31,6 @@ using namespace eqf;
     } while (0)
 
 namespace {
-// the caller's (torch's) current device is restored when an entry point returns
-struct DeviceScope {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) hipSetDevice(prev);
-    }
-};
 // > 64 KB of dynamic LDS needs the function attribute once per device
 int tileAttributes(int device) {
     static std::mutex mu;
@@ -886,7 +874,7 @@ int eqf_tile_downdate(int device, void* stream, double* C, int ldc, int m, int n
     return eqf_tile_gemm_tn(device, stream, C, ldc, m, n, A, lda, B, ldb, k, -1.0, 0, 0, 0, 1, 0, 0, 1, 0);
 }
 
-// ---- products on the integer matrix pipe (csrc/eqf_tile.hpp: k_i8_colexp / k_i8_split / k_i8_gemm): the downdate, the factorisations' trailing updates
+// ---- products on the integer matrix pipe (csrc/eqf_i8.hpp: k_i8_colexp / k_i8_split / k_i8_gemm): the downdate, the factorisations' trailing updates
 extern "C++" {
 namespace {
 // aOff >= 0: A is the columns [aOff, aOff + m) of B (aOff a multiple of 32): one split serves both sides, A's tiles are B's from tile aOff / 32 on
@@ -900,8 +888,8 @@ I8Plan i8Plan(int m, int n, int k, int slices, int aOff) {
     p.np = (n + 63) / 64 * 64;     // columns of C: 64 per workgroup
     p.ntB = aOff >= 0 ? std::max(p.np, aOff + p.mp) : p.np;  // columns of B that are cut (past n: zero)
     p.nKc = (k + 31) / 32;
-    p.sliceA = aOff >= 0 ? 0 : (size_t)(p.mp / 32) * p.nKc * slices * 1024;
-    p.sliceB = (size_t)(p.ntB / 32) * p.nKc * slices * 1024;
+    p.sliceA = aOff >= 0 ? 0 : (size_t)i8SliceBytes(k, p.mp, slices);
+    p.sliceB = (size_t)i8SliceBytes(k, p.ntB, slices);
     p.offB = p.sliceA;
     p.offEA = p.sliceA + p.sliceB;
     p.offEB = p.offEA + (aOff >= 0 ? 0 : sizeof(int) * (size_t)p.mp);
@@ -913,7 +901,7 @@ int i8Product(hipStream_t st, double* C, int ldc, int m, int n, const double* A,
     int maskCols, int aOff, char* ws, const I8Plan& p) {
     signed char* sB = reinterpret_cast<signed char*>(ws + p.offB);
     int* eB = reinterpret_cast<int*>(ws + p.offEB);
-    signed char* sA = aOff >= 0 ? sB + (size_t)(aOff / 32) * p.nKc * S * 1024 : reinterpret_cast<signed char*>(ws);
+    signed char* sA = aOff >= 0 ? sB + i8SliceBytes(k, aOff, S) : reinterpret_cast<signed char*>(ws);
     int* eA = aOff >= 0 ? eB + aOff : reinterpret_cast<int*>(ws + p.offEA);
     const int nExp = (int)((p.total - p.offEA) / sizeof(int));  // (a kernel, not hipMemsetAsync: 32 of these per update on CU-masked streams)
     hipLaunchKernelGGL(k_i8_zero, dim3((nExp + 255) / 256), dim3(256), 0, st, reinterpret_cast<int*>(ws + p.offEA), nExp);
@@ -939,7 +927,7 @@ size_t eqf_tile_i8_workspace_bytes(int m, int n, int k, int slices, int same_ope
 int eqf_tile_gemm_tn_i8(int device, void* stream, double* C, int ldc, int m, int n, const double* A, int lda, const double* B, int ldb, int k,
     int slices, int mask_rb, int mask_cb, int rblk0, int Pr, int pr, int cblk0, int Pc, int pc, int mask_cols, void* workspace,
     size_t workspace_bytes) {
-    if (!C || !A || !B || !workspace || m < 1 || n < 1 || k < 1 || k > 70000 || ldc < n || lda < m || ldb < n) return EQF_ERR_INVALID;
+    if (!C || !A || !B || !workspace || m < 1 || n < 1 || k < 1 || k > kI8MaxK || ldc < n || lda < m || ldb < n) return EQF_ERR_INVALID;
     if (slices < 5 || slices > 7) return EQF_ERR_INVALID;
     if (mask_rb < 0 || mask_cb < 0 || (mask_rb > 0) != (mask_cb > 0) || (mask_rb > 0 && (Pr < 1 || Pc < 1 || mask_cols < 0 || mask_cols > n)))
         return EQF_ERR_INVALID;
@@ -956,9 +944,7 @@ int eqf_tile_gemm_tn_i8(int device, void* stream, double* C, int ldc, int m, int
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     const GemmMask mk{mask_rb, mask_cb, rblk0, Pr, pr, cblk0, Pc, pc};
-    if (slices == 5) return i8Product<5>(st, C, ldc, m, n, A, lda, B, ldb, k, mk, mask_cols, aOff, ws, p);
-    if (slices == 6) return i8Product<6>(st, C, ldc, m, n, A, lda, B, ldb, k, mk, mask_cols, aOff, ws, p);
-    return i8Product<7>(st, C, ldc, m, n, A, lda, B, ldb, k, mk, mask_cols, aOff, ws, p);
+    return i8WithSlices(slices, [&](auto s) { return i8Product<s>(st, C, ldc, m, n, A, lda, B, ldb, k, mk, mask_cols, aOff, ws, p); });
 }
 
 int eqf_tile_downdate_i8(int device, void* stream, double* C, int ldc, int m, int n, const double* A, int lda, const double* B, int ldb, int k,

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/eqf_vio_amd_debug.h"  // (the public header + the test / measurement hooks this library also exports)
+#include "eqf_device.hpp"  // (DeviceScope)
 
 #define HIPC(expr)                                                                              \
     do {                                                                                        \
@@ -45,6 +46,7 @@
     } while (0)
 
 extern "C" __attribute__((visibility("hidden"))) int eqf_tiled_bearings_consumed(eqf_tiled* t, void* stream);  // csrc/eqf_tiled.hip
+using eqf::DeviceScope;
 
 namespace {
 constexpr int kNarrowS = 18;  // (C Sigma)_Ib (11) | delta | V (6)
@@ -144,17 +146,13 @@ struct eqf_tf {
     // options
     int lookahead = 1, overlapChains = 1, burst = 1, checkEvery = 1, framesSinceCheck = 0, profiling = 0, graphs = 0;
     // "downdate_slices" (round 6): 0 = the downdate Sigma - Y^T Y on the fp64 matrix cores (default, parity grade); 5 / 6 / 7 = on the INTEGER
-    // matrix pipe from that many 7-bit slices of Y's columns, exact accumulation (eqf_tile_downdate_i8): 34 / 41 / 48 bits of every entry
-    // relative to its column's largest -- Sigma within 1e-4 of the fp64 path from SIX slices on: measured 2e-6 .. 6e-5 at N = 200 .. 4000, five
-    // miss it (1.4e-4 .. 9e-4: profiles/r06_i8_downdate_error.txt, r06_slice_precision_study_2s_with_pairs.txt)
+    // matrix pipe from that many 7-bit slices of Y's columns (eqf_tile_downdate_i8; construction, error bound and accuracy: eqf_i8.hpp)
     int ddSlices = 0;
     void* i8Work = nullptr;
     size_t i8WorkBytes = 0;
     // "chain_slices" (round 6): the same for the trailing products of the two factorisations (every block row's U_k^T U_k and U_k^T Y_k; the
-    // diagonal blocks' look-ahead products, the solves and the factors stay fp64).  A factorisation forgives more than the downdate -- the
-    // products are subtracted from S and Sigma_e, not from Sigma, and K = Sigma C^T S^-1 averages the error over 2 N rows: FIVE slices keep Sigma
-    // to 1e-8 and the pose to 3e-9 of the fp64 path over the bench stream (scripts/slice_precision_study_chain.py,
-    // profiles/r06_slice_precision_study_chain.txt).  One workspace per factorisation (they run next to each other).
+    // diagonal blocks' look-ahead products, the solves and the factors stay fp64; eqf_tile_gemm_tn_i8, accuracy: eqf_i8.hpp).  One workspace
+    // per factorisation (they run next to each other).
     int trsmLeaf = 0;  // > 0: block-row solves split recursively down to this many 64-row blocks (0: one split); see trsmLeft
     // "downdate_early" (round 6; percent, with overlapping chains and the fp64 downdate): the downdate Sigma -= Y^T Y is a sum over the S-chain's
     // block rows, and block row k's share Y_k^T Y_k can be subtracted as soon as that block row is solved.  The S-chain's stream carries the
@@ -222,18 +220,6 @@ struct CurStream {  // (the Python reference's `with be.main():` / `with side():
     hipStream_t prev;
     CurStream(eqf_tf* f_, hipStream_t s) : f(f_), prev(f_->cur) { f->cur = s; }
     ~CurStream() { f->cur = prev; }
-};
-struct DeviceScope {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) hipSetDevice(prev);
-    }
 };
 
 int dalloc(eqf_tf* f, double** p, size_t count, bool zero) {

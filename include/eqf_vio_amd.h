@@ -178,7 +178,7 @@ int eqf_set_imu_burst(eqf_filter* f, int max_steps);
 /* Handle options by name.  EQF_ERR_INVALID (no effect) for a NULL handle or name, an unknown name or a value out of range.
  *   "downdate_slices" 0 (default) | 5 | 6 | 7: the covariance downdate Sigma - Y^T Y of every vision update (VIOFilter.cpp:297) on the
  *       INTEGER matrix pipe: Y's columns are scaled by powers of two and cut into that many 7-bit slices, multiplied with exact int32
- *       accumulation and recombined in fp64 (csrc/eqf_i8dd.hpp).  Sigma stays fp64 and exactly symmetric.  Six slices keep Sigma within
+ *       accumulation and recombined in fp64 (csrc/eqf_i8.hpp).  Sigma stays fp64 and exactly symmetric.  Six slices keep Sigma within
  *       1e-4 of the fp64 downdate on the bench streams; FIVE DO NOT and are there for measurement; seven come within
  *       ~1e-8.  A NaN / Inf in Y makes the rows and columns of Sigma it touches non-finite, as in fp64.  Takes effect at the next vision
  *       update, per call and in stream mode alike; 0 returns to the fp64 downdate (bit for bit the default).  The first non-zero value
@@ -305,7 +305,7 @@ int eqf_tiled_set_state(eqf_tiled* t, int N, const double* pose_q, const double*
  * Options (eqf_tf_set_option): "lookahead" (1), "overlap_chains" (1 on one rank, 0 on a grid: the interleaved chains are not validated over RCCL on a node; EQF_TILED_OVERLAP_CHAINS), "burst" (1: IMU calls queued and sent as
  * bursts), "check_every" (1), "downdate_slices" (0: the covariance downdate Sigma - Y^T Y on the fp64 matrix cores, parity grade; 5 / 6 / 7: on the INTEGER matrix pipe from
  * that many 7-bit slices of Y's columns with exact accumulation -- Sigma within 1e-4 of the fp64 path from 6 slices on (measured 2e-6 at N = 200 .. 6e-5 at N = 4000), two thirds of the downdate's time;
- * round 6, csrc/eqf_tile.hpp), "chain_slices" (0: the two factorisations' trailing products on the fp64 matrix cores; 5 / 6 / 7: on the integer pipe in the same
+ * round 6, csrc/eqf_i8.hpp), "chain_slices" (0: the two factorisations' trailing products on the fp64 matrix cores; 5 / 6 / 7: on the integer pipe in the same
  * way -- they forgive more than the downdate: five slices keep Sigma to 1e-8 and the pose to 3e-9 of the fp64 path on the bench stream), "downdate_early" (50: with the chains side by side and the fp64 downdate, the shares Y_k^T Y_k of this percentage of the S-chain's block rows are subtracted on the
  * E-chain's stream as soon as each block row is solved, the rest in one product behind the S-chain; 0: the whole downdate behind the S-chain, as until round 6),
  * "trsm_leaf" (0: a block row's triangular solve is split once into two solves and a product; > 0: recursively, down to this many 64-row blocks -- measured slower at N = 4000),

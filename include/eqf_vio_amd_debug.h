@@ -120,9 +120,7 @@ int eqf_tile_downdate(int device, void* stream, double* C, int ldc, int m, int n
     int k);
 /* eqf_tile_downdate_i8 (round 6): C (m x n, ldc) -= A^T B as eqf_tile_downdate, but on the INTEGER matrix pipe: every column of A and B is scaled
  *   by a power of two and cut into `slices` (5, 6 or 7) signed 7-bit pieces, the slice pairs are multiplied on v_mfma_i32_32x32x32_i8 with exact
- *   int32 accumulation and recombined in fp64 (csrc/eqf_tile.hpp).  The error is the rounding of every entry to its slices plus the slice pairs
- *   (ta, tb) with ta + tb >= slices that are not multiplied: |error_ij| <= about k 2^(e_i + e_j) (slices + 1) 2^-(7 slices), 2^e_i the power
- *   of two above column i's largest |entry| (the rigorous form: tests/i8_emulator.py); k <= 70 000.  A column of A or B holding a NaN / Inf
+ *   int32 accumulation and recombined in fp64; k <= 70 000 (csrc/eqf_i8.hpp: construction, error bound, accuracy).  A column of A or B holding a NaN / Inf
  *   makes its row / column of C NaN, as in fp64.  mask_rb > 0 (m == n): C is a symmetric local matrix in blocks of mask_rb, tiles entirely below the
  *   block diagonal are skipped (eqf_tile_mirror completes them).  workspace: caller-owned device memory of at least
  *   eqf_tile_i8_workspace_bytes(m, n, k, slices, A == B) bytes (the slices of both operands, once if they are the same matrix). */
@@ -137,7 +135,7 @@ int eqf_tile_downdate_i8(int device, void* stream, double* C, int ldc, int m, in
 int eqf_tile_gemm_tn_i8(int device, void* stream, double* C, int ldc, int m, int n, const double* A, int lda, const double* B, int ldb, int k,
     int slices, int mask_rb, int mask_cb, int rblk0, int Pr, int pr, int cblk0, int Pc, int pc, int mask_cols, void* workspace,
     size_t workspace_bytes);
-/* eqf_tile_syrk_i8: the kernels behind eqf_set_option "downdate_slices" (csrc/eqf_i8dd.hpp) on caller-owned device buffers, batched: for
+/* eqf_tile_syrk_i8: the kernels behind eqf_set_option "downdate_slices" (csrc/eqf_i8.hpp) on caller-owned device buffers, batched: for
  *   b < batch, Sout_b = Sin_b - Y_b^T Y_b over the leading nv[b] x nv[b] of Sigma (ld, sigmaStride doubles between the filters) and the leading
  *   mp[b] rows x nv[b] columns of Y (ldY, strideY), with `slices` (5, 6 or 7) 7-bit slices per column and exact int32 accumulation.  mp[b] is
  *   a multiple of 32; mp[b] == 0 copies Sin_b.  The upper triangle is formed, the lower one written from the same values (exactly

@@ -1,4 +1,4 @@
-"""A/B of the covariance downdate on the integer matrix pipe (eqf_set_option "downdate_slices", csrc/eqf_i8dd.hpp) against the fp64 downdate,
+"""A/B of the covariance downdate on the integer matrix pipe (eqf_set_option "downdate_slices", csrc/eqf_i8.hpp) against the fp64 downdate,
 in ONE process, stream mode, the two legs alternating round by round: 1, 8 and 64 filters of N = 200, one filter of N = 1000 and of N = 4000.
 Per leg: steps/s (IMU + vision events per second over the timed rounds, best round) and the update's kernel time per vision frame from the
 handle's profile (EQF_PROF_CHOL_RESIDENT + EQF_PROF_DOWNDATE, the event-bracket times of eqf_profile_get; one profiled round of its own).

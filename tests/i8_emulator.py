@@ -1,9 +1,9 @@
 """Test helper: a numpy model of the int8-slice products, operation for operation (CPU only; like tiled_double.py for the tile kernels).
 
-Three entry points share one construction (csrc/eqf_tile.hpp: k_i8_colexp / k_i8_split / k_i8_gemm behind eqf_tile_downdate_i8 and
-eqf_tile_gemm_tn_i8; csrc/eqf_i8dd.hpp: k_i8dd_split / k_i8dd_syrk behind eqf_tile_syrk_i8 and the handles' "downdate_slices"):
+Three entry points share one construction (csrc/eqf_i8.hpp: k_i8_colexp / k_i8_split / k_i8_gemm behind eqf_tile_downdate_i8 and
+eqf_tile_gemm_tn_i8; k_i8dd_split / k_i8dd_syrk behind eqf_tile_syrk_i8 and the handles' "downdate_slices"):
 
-  1. exponent word per column: 0 = all zero, a flag = holds a NaN / Inf (TILE_NONFINITE, SYRK_NONFINITE), else frexp(max |entry|) + 2048;
+  1. exponent word per column: 0 = all zero, NONFINITE = holds a NaN / Inf, else frexp(max |entry|) + 2048;
   2. every entry scaled to r = ldexp(x, -e) (|r| < 1, correctly rounded) and cut into S signed slices, q_t = rint(r 2^(6 + 7 t)) (ties to
      even, |q_t| <= 64), r -= q_t 2^-(6 + 7 t) (exact);
   3. per d = ta + tb < S the exact integer accumulator acc_d = sum over k and over the pairs (ta, tb) of q_ta q_tb;
@@ -33,27 +33,26 @@ from fractions import Fraction
 import numpy as np
 
 BITS = 7
-TILE_NONFINITE = 4096  # k_i8_colexp's flag word (eqf_tile.hpp kI8NonFinite): above every exponent + 2048, it wins the atomicMax
-SYRK_NONFINITE = 1     # k_i8dd_split's flag word (eqf_i8dd.hpp kI8ddNonFinite)
+NONFINITE = 4096  # the exponent word of a column holding a NaN / Inf (eqf_i8.hpp kI8NonFinite): above every exponent + 2048
 
 
-def exponent_words(X, flag, skip_col=-1):
-    """Exponent word of every column of X (k x n): 0 all zero, `flag` holds a NaN / Inf, else frexp's exponent of the largest |entry| +
+def exponent_words(X, skip_col=-1):
+    """Exponent word of every column of X (k x n): 0 all zero, NONFINITE holds a NaN / Inf, else frexp's exponent of the largest |entry| +
     2048.  skip_col: a column that is not part of the operand (the handles' z column of Y): word 0."""
     X = np.asarray(X, dtype=np.float64)
     fin = np.isfinite(X)
     mx = np.where(fin, np.abs(X), 0.0).max(axis=0, initial=0.0)
     e = np.frexp(mx)[1].astype(np.int64)
-    w = np.where(~fin.all(axis=0), flag, np.where(mx > 0, e + 2048, 0)).astype(np.int64)
+    w = np.where(~fin.all(axis=0), NONFINITE, np.where(mx > 0, e + 2048, 0)).astype(np.int64)
     if skip_col >= 0 and skip_col < w.size:
         w[skip_col] = 0
     return w
 
 
-def slices(X, words, S, flag):
-    """The S slices of X's columns as float64 integers, shape (S, k, n); columns with word 0 or `flag` are all zero."""
+def slices(X, words, S):
+    """The S slices of X's columns as float64 integers, shape (S, k, n); columns with word 0 or NONFINITE are all zero."""
     X = np.asarray(X, dtype=np.float64)
-    live = (words > 0) & (words != flag)
+    live = (words > 0) & (words != NONFINITE)
     e = np.where(live, words - 2048, 0)
     r = np.ldexp(np.where(live[None, :], X, 0.0), -e[None, :])  # correctly rounded: exact unless it underflows
     out = np.empty((S,) + X.shape)
@@ -89,13 +88,13 @@ class Product:
     """The int8-slice product A^T B (A k x m, B k x n) up to the epilogue: exponent words eA / eB, accumulators acc, recombined v and
     the product term P = ldexp(v, e_i + e_j) (0 where a column is zero, NaN where one is flagged)."""
 
-    def __init__(self, A, B, S, flag, skip_col=-1):
-        self.S, self.flag = S, flag
-        self.eA = exponent_words(A, flag, skip_col)
-        self.eB = exponent_words(B, flag, skip_col)
-        self.acc = accumulators(slices(A, self.eA, S, flag), slices(B, self.eB, S, flag))
+    def __init__(self, A, B, S, skip_col=-1):
+        self.S = S
+        self.eA = exponent_words(A, skip_col)
+        self.eB = exponent_words(B, skip_col)
+        self.acc = accumulators(slices(A, self.eA, S), slices(B, self.eB, S))
         self.v = recombine(self.acc)
-        bad = (self.eA == flag)[:, None] | (self.eB == flag)[None, :]
+        bad = (self.eA == NONFINITE)[:, None] | (self.eB == NONFINITE)[None, :]
         zero = (self.eA == 0)[:, None] | (self.eB == 0)[None, :]
         live = ~bad & ~zero
         ee = np.where(live, (self.eA - 2048)[:, None] + (self.eB - 2048)[None, :], 0)
@@ -132,7 +131,7 @@ def tile_gemm(C, A, B, S, alpha=-1.0, mask=None, mask_cols=0):
     of all-zero columns are untouched; a flagged row / column is NaN.  (A as a column range of B cut once gives the same result: the
     exponent words and slices of a column do not depend on which operand it was cut with.)"""
     C = np.array(C, dtype=np.float64)
-    p = Product(A, B, S, TILE_NONFINITE)
+    p = Product(A, B, S)
     keep = ~tile_skipped(C.shape[0], C.shape[1], mask, mask_cols)
     upd = keep & p.live
     C[upd] = C[upd] + alpha * p.P[upd]
@@ -146,7 +145,7 @@ def syrk(Sin, Y, S, skip_col=-1):
     Sin = np.asarray(Sin, dtype=np.float64)
     if Y.shape[0] == 0:
         return Sin.copy()
-    p = Product(Y, Y, S, SYRK_NONFINITE, skip_col)
+    p = Product(Y, Y, S, skip_col)
     out = Sin - p.P
     low = np.tril_indices(out.shape[0], -1)
     out[low] = out.T[low]  # (assigned, not added: -0.0 keeps its sign)

@@ -1,4 +1,4 @@
-"""The covariance downdate of the single-GPU / batched handles on the integer matrix pipe (eqf_set_option "downdate_slices", csrc/eqf_i8dd.hpp):
+"""The covariance downdate of the single-GPU / batched handles on the integer matrix pipe (eqf_set_option "downdate_slices", csrc/eqf_i8.hpp):
 Y's columns cut into 7-bit slices, v_mfma_i32_32x32x32_i8 with exact int32 accumulation, fp64 recombination.  "Against fp64" is a second
 handle on the same stream with the option off -- the fp64 path itself is pinned to the oracle by the rest of the suite.  The kernels alone
 are checked against numpy through eqf_tile_syrk_i8 (include/eqf_vio_amd_debug.h)."""

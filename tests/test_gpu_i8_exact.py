@@ -1,6 +1,6 @@
 """The int8-slice products on the MI355X BIT FOR BIT against their numpy model (tests/i8_emulator.py): eqf_tile_downdate_i8 and
-eqf_tile_gemm_tn_i8 (the partitioned filter's "downdate_slices" / "chain_slices", csrc/eqf_tile.hpp) and eqf_tile_syrk_i8 (the handles'
-"downdate_slices", csrc/eqf_i8dd.hpp), five to seven slices.  An error bound cannot see a kernel bug smaller than the slicing error itself
+eqf_tile_gemm_tn_i8 (the partitioned filter's "downdate_slices" / "chain_slices", csrc/eqf_i8.hpp) and eqf_tile_syrk_i8 (the handles'
+"downdate_slices", the same header), five to seven slices.  An error bound cannot see a kernel bug smaller than the slicing error itself
 (a truncating splitter, one lost half-chunk of the lowest slice pair); equality with the emulator can.  Ragged shapes around the 32-row
 chunks and the 128 x 64 / 64 x 64 tiles, views with leading dimensions and sentinels around them, the block mask, A as a column range of B,
 column maxima at powers of two and at 2^e (1 - 2^-53), exact ties, subnormal and near-overflow columns, zero and -0.0 columns, NaN / Inf,
@@ -227,7 +227,7 @@ def test_tile_product_at_the_k_limit():
     B = E.all63(k, n, e=-2)
     B[:, 5] *= -1.0
     C0 = rng.standard_normal((m, n + 2))
-    p = E.Product(A, B, S, E.TILE_NONFINITE)
+    p = E.Product(A, B, S)
     assert p.max_acc >= 0.9 * 2 ** 31
     Ad, Bd, Cd = (torch.from_numpy(x).to(dev) for x in (A, B, C0))
     assert _tile(Cd[:, 1: 1 + n], Ad, Bd, S) == 0
@@ -342,7 +342,7 @@ def test_syrk_at_the_mp_limit(S):
     Y = E.all63(mp + 32, nv + 3, e=1)
     Y[:, 4] *= -1.0
     Y[:, 9] = E.all63(mp + 32, 1, e=-20)[:, 0]
-    assert E.Product(Y[:mp, :nv], Y[:mp, :nv], S, E.SYRK_NONFINITE).max_acc >= 0.9 * 2 ** 31
+    assert E.Product(Y[:mp, :nv], Y[:mp, :nv], S).max_acc >= 0.9 * 2 ** 31
     rng = np.random.default_rng(S)
     Sin = rng.standard_normal((1, nv, nv + 1))
     Yd, Sd = torch.from_numpy(Y[None]).to(dev), torch.from_numpy(Sin).to(dev)

@@ -1,6 +1,6 @@
 """The numpy model of the int8-slice products (tests/i8_emulator.py) on the CPU: against the exact product within its rigorous bound, the
 suite's older bound shown to be statistical only, and the integer accumulators at the two exactness limits (eqf_tile_gemm_tn_i8's
-k <= 70 000, eqf_tile_syrk_i8's i8ddExact) -- what tests/test_gpu_i8_exact.py drives the kernels to, bit for bit."""
+k <= 70 000, eqf_tile_syrk_i8's i8Exact) -- what tests/test_gpu_i8_exact.py drives the kernels to, bit for bit."""
 import numpy as np
 import pytest
 
@@ -10,13 +10,13 @@ K_MAX_TILE = 70000  # eqf_tile_gemm_tn_i8 / eqf_tile_downdate_i8 reject k > 70 0
 
 
 def mp_limit(S):
-    """The largest multiple of 32 that eqf_i8dd.hpp's i8ddExact accepts: mp S 64^2 < 2^31."""
+    """The largest multiple of 32 that eqf_i8.hpp's i8Exact accepts: mp S 64^2 < 2^31."""
     mp = (2 ** 31 - 1) // (S * 4096)
     return mp // 32 * 32
 
 
 def _exact_ratio(A, B, S):
-    p = E.Product(A, B, S, E.TILE_NONFINITE)
+    p = E.Product(A, B, S)
     return E.max_error_ratio(p, E.exact_product(A, B), S, A.shape[0]), p
 
 
@@ -52,7 +52,7 @@ def test_all63_exceeds_the_old_bound(S, over):
     compare bit for bit with the emulator rather than with a bound."""
     k = 64
     A, B = E.all63(k, 2), E.all63(k, 2)
-    p = E.Product(A, B, S, E.TILE_NONFINITE)
+    p = E.Product(A, B, S)
     exact = E.exact_product(A, B)
     err = np.array([[abs(float(p.P[i, j] - float(exact[i, j]))) for j in range(2)] for i in range(2)])
     ratio = float((err / E.old_bound(A, B, S)).max())
@@ -64,9 +64,9 @@ def test_the_model_is_the_documented_arithmetic():
     """Small hand-checked cases: ties to even in every slice, the q0 = 64 column maximum 2^e (1 - 2^-53), an exact power of two, the flag
     words, zero / -0.0 columns, the syrk mirror and copy."""
     x = 1.0 - 2.0 ** -53
-    w = E.exponent_words(np.array([[x, 0.0, -0.0, 4.0, np.nan], [0.5, 0.0, 0.0, -1.0, 1.0]]), E.TILE_NONFINITE)
-    assert list(w) == [2048, 0, 0, 2048 + 3, E.TILE_NONFINITE]
-    q = E.slices(np.array([[x], [2.5 / 64], [3.5 / 64], [-2.5 / 64], [1.5 * 2.0 ** -13]]), np.array([2048]), 3, E.TILE_NONFINITE)
+    w = E.exponent_words(np.array([[x, 0.0, -0.0, 4.0, np.nan], [0.5, 0.0, 0.0, -1.0, 1.0]]))
+    assert list(w) == [2048, 0, 0, 2048 + 3, E.NONFINITE]
+    q = E.slices(np.array([[x], [2.5 / 64], [3.5 / 64], [-2.5 / 64], [1.5 * 2.0 ** -13]]), np.array([2048]), 3)
     assert q[0, 0, 0] == 64 and q[1, 0, 0] == 0                              # q0 = 64, the rest exact
     assert q[0, 1, 0] == 2 and q[0, 2, 0] == 4 and q[0, 3, 0] == -2         # ties to even
     assert q[1, 1, 0] == 64 and q[1, 3, 0] == -64                            # (their remainders, exact)
@@ -110,12 +110,12 @@ def test_accumulators_at_the_exactness_limits():
     k = K_MAX_TILE
     acc = k * 7 * 63 * 63
     assert 0.9 * 2 ** 31 <= acc < 2 ** 31
-    p = E.Product(E.all63(k, 2), E.all63(k, 2), 7, E.TILE_NONFINITE)
+    p = E.Product(E.all63(k, 2), E.all63(k, 2), 7)
     assert p.max_acc == acc
     for S in (5, 6, 7):
         mp = mp_limit(S)
         assert mp * S * 4096 < 2 ** 31 <= (mp + 32) * S * 4096
         acc = mp * S * 63 * 63
         assert 0.9 * 2 ** 31 <= acc < 2 ** 31, S
-        p = E.Product(E.all63(mp, 1), E.all63(mp, 1), S, E.SYRK_NONFINITE)
+        p = E.Product(E.all63(mp, 1), E.all63(mp, 1), S)
         assert p.max_acc == acc, S
