@@ -51,6 +51,12 @@ class Settings(C.Structure):
     ]
 
 
+class InnovationStats(C.Structure):
+    """eqf_innovation_stats (include/eqf_vio_amd.h)."""
+
+    _fields_ = [("nis", C.c_double), ("logdet_S", C.c_double), ("loglik", C.c_double), ("dof", C.c_int), ("valid", C.c_int)]
+
+
 _lib = None
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -59,6 +65,7 @@ EXPORTED_SYMBOLS = [
     "eqf_settings_default", "eqf_create", "eqf_destroy", "eqf_reset", "eqf_process_imu", "eqf_process_vision",
     "eqf_stream_upload", "eqf_stream_imu", "eqf_stream_vision", "eqf_synchronize", "eqf_get_time", "eqf_num_landmarks",
     "eqf_get_ids", "eqf_get_state_estimate", "eqf_get_origin", "eqf_get_group", "eqf_get_bias", "eqf_get_sigma",
+    "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats",
     "eqf_set_sigma", "eqf_set_state", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
     "eqf_tiled_create", "eqf_tiled_destroy", "eqf_tiled_set_stream", "eqf_tiled_set_geometry", "eqf_tiled_propagate", "eqf_tiled_add_landmarks",
@@ -112,6 +119,12 @@ def lib():
         L.eqf_get_bias.argtypes = [vp, C.c_int, _dp]
         L.eqf_get_sigma.argtypes = [vp, C.c_int, _dp, C.c_int]
         L.eqf_set_sigma.argtypes = [vp, C.c_int, _dp, C.c_int]
+        if hasattr(L, "eqf_get_sigma_local"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
+            L.eqf_get_sigma_local.argtypes = [vp, C.c_int, _dp, C.c_int]
+            L.eqf_get_marginals.argtypes = [vp, C.c_int, C.c_int, _dp, _dp]
+            L.eqf_get_local_jacobian.argtypes = [vp, C.c_int, _dp, _dp, _dp]
+            L.eqf_debug_sigma_local_all.argtypes = [vp]
+            L.eqf_get_innovation_stats.argtypes = [vp, C.c_int, C.POINTER(InnovationStats), _dp]
         L.eqf_get_last_update.argtypes = [vp, C.c_int, _dp, _dp, _dp]
         L.eqf_set_state.argtypes = [vp, C.c_int, C.c_int, _ip] + [_dp] * 11 + [C.c_int, C.c_double, _dp, _dp, C.c_double, C.c_int]
         L.eqf_get_integrator.argtypes = [vp, C.c_int, _dp, _dp, _dp, _ip]
@@ -322,7 +335,7 @@ class FilterBatch:
     def set_option(self, name, value):
         """Handle option by name (include/eqf_vio_amd.h: eqf_set_option): ``"downdate_slices"`` 0 (fp64, default) / 5 / 6 / 7 -- the
         covariance downdate on the integer matrix pipe from that many 7-bit slices (6 holds Sigma within 1e-4 of fp64, 5 does not) --
-        or ``"res_tickets"`` 0 / 1 / 2."""
+        ``"res_tickets"`` 0 / 1 / 2, or ``"innovation_stats"`` 0 / 1 (innovation_stats())."""
         _check(lib().eqf_set_option(self._h, name.encode(), int(value)), "eqf_set_option")
 
     def synchronize(self):
@@ -374,6 +387,39 @@ class FilterBatch:
         out = np.zeros((n, n))
         _check(lib().eqf_get_sigma(self._h, b, _p(out), n), "eqf_get_sigma")
         return out
+
+    def sigma_local(self, b=0):
+        """Sigma in the coordinates of the estimate, J Sigma J^T (include/eqf_vio_amd.h: eqf_get_sigma_local); layout of sigma()."""
+        n = 11 + 3 * self.num_landmarks(b)
+        out = np.zeros((n, n))
+        _check(lib().eqf_get_sigma_local(self._h, b, _p(out), n), "eqf_get_sigma_local")
+        return out
+
+    def marginals(self, b=0, local=True):
+        """The 11 x 11 base block and the N diagonal 3 x 3 landmark blocks of sigma_local() (local) or sigma(), O(N)."""
+        N = self.num_landmarks(b)
+        base, lm = np.zeros((11, 11)), np.zeros((max(N, 1), 3, 3))
+        _check(lib().eqf_get_marginals(self._h, b, int(bool(local)), _p(base), _p(lm)), "eqf_get_marginals")
+        return dict(base=base, lm=lm[:N])
+
+    def local_jacobian(self, b=0):
+        """The blocks of J (origin chart -> estimate chart) as the device built them: G (2,2), RAt (3,3), lm (N,3,3)."""
+        N = self.num_landmarks(b)
+        G, RAt, lm = np.zeros((2, 2)), np.zeros((3, 3)), np.zeros((max(N, 1), 3, 3))
+        _check(lib().eqf_get_local_jacobian(self._h, b, _p(G), _p(RAt), _p(lm)), "eqf_get_local_jacobian")
+        return dict(G=G, RAt=RAt, lm=lm[:N])
+
+    def innovation_stats(self, b=0):
+        """Statistics of filter b's most recent vision update (set_option("innovation_stats", 1) first): dict with nis, logdet_S, loglik,
+        dof, valid and nis_lm (N,); include/eqf_vio_amd.h: eqf_get_innovation_stats."""
+        N = self.num_landmarks(b)
+        st, lm = InnovationStats(), np.zeros(max(N, 1))
+        _check(lib().eqf_get_innovation_stats(self._h, b, C.byref(st), _p(lm)), "eqf_get_innovation_stats")
+        return dict(nis=st.nis, logdet_S=st.logdet_S, loglik=st.loglik, dof=st.dof, valid=bool(st.valid), nis_lm=lm[:N] if st.valid else np.zeros(0))
+
+    def debug_sigma_local_all(self):
+        """k_sigma_local for every filter of the handle in one launch, nothing copied (include/eqf_vio_amd_debug.h)."""
+        _check(lib().eqf_debug_sigma_local_all(self._h), "eqf_debug_sigma_local_all")
 
     def set_sigma(self, S, b=0):
         S = np.ascontiguousarray(S, dtype=np.float64)

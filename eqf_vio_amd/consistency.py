@@ -1,0 +1,167 @@
+"""Filter consistency on the host (pure numpy): what turns the covariance in the coordinates of the estimate
+(FilterBatch.sigma_local / marginals, include/eqf_vio_amd.h: eqf_get_sigma_local) into a number for a Monte-Carlo batch.
+
+Sigma is the covariance of eps = chart_xi0(phi_{X^-1}(xi)): coordinates around the ORIGIN xi0 (VIOFilter.cpp:306-309, "TODO: propagate to
+local tangent space").  The error one can measure against a ground truth is eps_loc = chart_xiHat(xi), xiHat = phi_X(xi0) the estimate;
+to first order eps_loc = J eps with the block-diagonal J of local_jacobian_blocks, and Sigma_loc = J Sigma J^T.
+
+  local_jacobian_blocks(origin, group)   the J blocks (the device builds the same ones: FilterBatch.local_jacobian)
+  local_error(estimate, truth, ...)      eps_loc for gravity direction, velocity and landmarks, plus the bias difference
+  nees_marginal(marginals, error)        navigation-state NEES (11 or 5 dof) and per-landmark NEES (3 dof), O(N)
+
+`origin`, `group`, `estimate` are the dicts of FilterBatch.origin() / group() / state_estimate(): quaternions (w, x, y, z), Eigen semantics.
+"""
+import numpy as np
+
+E3 = np.array([0.0, 0.0, 1.0])
+
+
+# ---- quaternions / sphere charts with the reference's formulas (libs/core SO3.cpp, VIOState.cpp:199-251)
+def quat_to_matrix(q):
+    """Eigen toRotationMatrix (SO3.cpp:94)."""
+    w, x, y, z = q
+    tx, ty, tz = 2 * x, 2 * y, 2 * z
+    twx, twy, twz = tx * w, ty * w, tz * w
+    txx, txy, txz = tx * x, ty * x, tz * x
+    tyy, tyz, tzz = ty * y, tz * y, tz * z
+    return np.array([[1 - (tyy + tzz), txy - twz, txz + twy], [txy + twz, 1 - (txx + tzz), tyz - twx], [txz - twy, tyz + twx, 1 - (txx + tyy)]])
+
+
+def _quat_from_matrix(m):
+    """Eigen matrix -> quaternion (SO3.cpp:100)."""
+    t = m[0, 0] + m[1, 1] + m[2, 2]
+    q = np.zeros(4)
+    if t > 0:
+        t = np.sqrt(t + 1.0)
+        q[0] = 0.5 * t
+        t = 0.5 / t
+        q[1], q[2], q[3] = (m[2, 1] - m[1, 2]) * t, (m[0, 2] - m[2, 0]) * t, (m[1, 0] - m[0, 1]) * t
+        return q
+    i = 0
+    if m[1, 1] > m[0, 0]:
+        i = 1
+    if m[2, 2] > m[i, i]:
+        i = 2
+    j, k = (i + 1) % 3, (i + 2) % 3
+    t = np.sqrt(m[i, i] - m[j, j] - m[k, k] + 1.0)
+    q[1 + i] = 0.5 * t
+    t = 0.5 / t
+    q[0] = (m[k, j] - m[j, k]) * t
+    q[1 + j] = (m[j, i] + m[i, j]) * t
+    q[1 + k] = (m[k, i] + m[i, k]) * t
+    return q
+
+
+def _quat_inverse(q):
+    q = np.asarray(q, dtype=float)
+    return np.array([q[0], -q[1], -q[2], -q[3]]) / float(q @ q)
+
+
+def _quat_rotate(q, v):
+    """Eigen _transformVector (SO3.cpp:66)."""
+    u = np.asarray(q[1:4], dtype=float)
+    uv = np.cross(u, v)
+    uv = uv + uv
+    return v + q[0] * uv + np.cross(u, uv)
+
+
+def _skew(v):
+    return np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+
+
+def _sphere_rot(pole):
+    """SO3FromVectors(-pole, e3) as the quaternion the reference stores (VIOState.cpp:231, SO3.cpp:155-167)."""
+    o = -np.asarray(pole, dtype=float)
+    o = o / np.linalg.norm(o)
+    v = np.cross(o, E3)
+    c = float(o @ E3)
+    if abs(1 + c) <= 1e-8:
+        raise ValueError("the gravity chart is singular: its pole is e3 (SO3.cpp:160)")
+    vx = _skew(v)
+    return _quat_from_matrix(np.eye(3) + (vx + 1.0 / (1.0 + c) * vx @ vx))
+
+
+def stereo_sphere_chart(eta, pole):
+    """VIOState.cpp:230-234."""
+    r = _quat_rotate(_sphere_rot(pole), np.asarray(eta, dtype=float))
+    return (r - E3)[0:2] / (1 - r[2])
+
+
+def stereo_sphere_chart_diff(eta, pole):
+    """VIOState.cpp:242-246, 2 x 3."""
+    q = _sphere_rot(pole)
+    r = _quat_rotate(q, np.asarray(eta, dtype=float))
+    D = np.eye(3)[0:2, :] @ (np.eye(3) * (1 - r[2]) + np.outer(r - E3, E3))
+    return (1 - r[2]) ** -2.0 * D @ quat_to_matrix(q)
+
+
+def stereo_sphere_chart_inv_diff_at_zero(pole):
+    """VIOState.cpp:248-251 at y = 0, 3 x 2."""
+    D = np.zeros((3, 2))
+    D[0, 0] = D[1, 1] = 2.0
+    return quat_to_matrix(_quat_inverse(_sphere_rot(pole))) @ D
+
+
+def gravity_dir(pose_q):
+    """R^T e3 (VIOState.cpp:90)."""
+    return _quat_rotate(_quat_inverse(pose_q), E3)
+
+
+# ---- the three functions
+def local_jacobian_blocks(origin, group):
+    """Blocks of J = d chart_xiHat(phi_X(chart_xi0^-1(eps))) / d eps at eps = 0, in Sigma's index map:
+    [0,6) bias I (not returned); [6,8) G (2,2); [8,11) RAt (3,3) = R_A^T; landmark i lm[i] (3,3) = a_i^-1 R(q_i)^T."""
+    Aq = np.asarray(group["Aq"], dtype=float)
+    RAt = quat_to_matrix(_quat_inverse(Aq))
+    eta0 = gravity_dir(origin["q"])
+    etaHat = _quat_rotate(_quat_inverse(Aq), eta0)
+    G = stereo_sphere_chart_diff(etaHat, etaHat) @ RAt @ stereo_sphere_chart_inv_diff_at_zero(eta0)
+    Qq = np.asarray(group["Qq"], dtype=float).reshape(-1, 4)
+    Qa = np.asarray(group["Qa"], dtype=float).reshape(-1)
+    lm = np.zeros((len(Qa), 3, 3))
+    for i in range(len(Qa)):
+        lm[i] = quat_to_matrix(Qq[i]).T / Qa[i]
+    return dict(G=G, RAt=RAt, lm=lm)
+
+
+def jacobian_matrix(blocks):
+    """The dense (11 + 3N) x (11 + 3N) J of the blocks (tests, small N)."""
+    N = len(blocks["lm"])
+    J = np.zeros((11 + 3 * N, 11 + 3 * N))
+    J[0:6, 0:6] = np.eye(6)
+    J[6:8, 6:8] = blocks["G"]
+    J[8:11, 8:11] = blocks["RAt"]
+    for i in range(N):
+        J[11 + 3 * i : 14 + 3 * i, 11 + 3 * i : 14 + 3 * i] = blocks["lm"][i]
+    return J
+
+
+def local_error(estimate, truth, bias=None, true_bias=None):
+    """eps_loc = chart_xiHat(xi_true): dict with `gravity` (2,), `velocity` (3,), `lm` (N,3) and `bias` (6,), all "truth minus estimate"
+    like every chart coordinate here (the bias difference is zero if no bias is given).
+    estimate / truth: dicts with q (pose attitude), v (body velocity), p (N,3) body-frame landmarks."""
+    etaHat = gravity_dir(estimate["q"])
+    eta = gravity_dir(truth["q"])
+    b = np.zeros(6)
+    if bias is not None and true_bias is not None:
+        b = np.asarray(true_bias, dtype=float) - np.asarray(bias, dtype=float)
+    return dict(
+        bias=b,
+        gravity=stereo_sphere_chart(eta, etaHat),
+        velocity=np.asarray(truth["v"], dtype=float) - np.asarray(estimate["v"], dtype=float),
+        lm=np.asarray(truth["p"], dtype=float).reshape(-1, 3) - np.asarray(estimate["p"], dtype=float).reshape(-1, 3),
+    )
+
+
+def nees_marginal(marginals, error, with_bias=True):
+    """Normalised estimation error squared from the marginals of Sigma_loc (FilterBatch.marginals(local=True): base (11,11), lm (N,3,3)):
+    `nav` = e^T P^-1 e over the navigation state -- 11 dof with the bias, 5 (gravity direction + velocity) without -- and `lm` (N,), 3 dof each."""
+    base = np.asarray(marginals["base"], dtype=float)
+    e = np.concatenate([error["bias"], error["gravity"], error["velocity"]])
+    if not with_bias:
+        base, e = base[6:, 6:], e[6:]
+    nav = float(e @ np.linalg.solve(base, e))
+    P = np.asarray(marginals["lm"], dtype=float).reshape(-1, 3, 3)
+    el = np.asarray(error["lm"], dtype=float).reshape(-1, 3)
+    lm = np.array([el[i] @ np.linalg.solve(P[i], el[i]) for i in range(len(el))])
+    return dict(nav=nav, nav_dof=len(e), lm=lm, lm_dof=3)

@@ -234,6 +234,28 @@ class VIOFilter {
         check(eqf_get_sigma(handle_.get(), 0, S.data.data(), S.n), "eqf_get_sigma");
         return S;
     }
+    // The covariance in the coordinates of the ESTIMATE, J Sigma J^T (eqf_get_sigma_local): stateCovariance() -- like the reference's,
+    // VIOFilter.cpp:306-309 "TODO: propagate to local tangent space" -- is in the chart around the origin xi0.
+    MatrixXd stateCovarianceLocal() const {
+        MatrixXd S;
+        S.n = 11 + 3 * eqf_num_landmarks(handle_.get(), 0);
+        S.data.resize(size_t(S.n) * S.n);
+        check(eqf_get_sigma_local(handle_.get(), 0, S.data.data(), S.n), "eqf_get_sigma_local");
+        return S;
+    }
+    // Innovation statistics of the most recent vision update (setOption("innovation_stats", 1) first; eqf_get_innovation_stats):
+    // NIS, log det S, log-likelihood, degrees of freedom and the per-landmark NIS in the state's landmark order.
+    struct InnovationStats : eqf_innovation_stats {
+        std::vector<double> nis_lm;
+    };
+    InnovationStats innovationStats() const {
+        InnovationStats st;
+        const int N = eqf_num_landmarks(handle_.get(), 0);
+        st.nis_lm.assign(size_t(N > 0 ? N : 1), 0.0);
+        check(eqf_get_innovation_stats(handle_.get(), 0, &st, st.nis_lm.data()), "eqf_get_innovation_stats");
+        st.nis_lm.resize(st.valid ? size_t(N) : 0);
+        return st;
+    }
     int lastStatus() const { return lastStatus_; }  // EQF_SKIPPED_* where the reference returns early
     eqf_filter* handle() const { return handle_.get(); }
 

@@ -1,11 +1,14 @@
 // Minimal C++ caller of the facade, shaped like the reference's offline runner (eqf_vio/src/main.cpp:111-170):
 // events are interleaved by "imu.stamp < meas.stamp", the state is read after every vision call.
-// Usage: eqf_example <N landmarks> <frames> [aux | level | init]  -- runs a small synthetic sequence and prints the final
+// Usage: eqf_example <N landmarks> <frames> [aux | level | init | local]  -- runs a small synthetic sequence and prints the final
 // pose and |Sigma|_F.  With "aux" the filter starts from AuxiliaryFilterData + setInertialPoints (VIOFilter.cpp:51-58,
 // 74-118) instead of the gravity alignment at the first IMU sample; with "init" from an explicit initialiseFromIMUData
 // call (VIOFilter.cpp:133-144; same result as the lazy one).  With "level" the vehicle rests level: the reference's gravity
 // chart is then singular and its first Riccati step throws std::domain_error (SO3.cpp:160-161) -- here the device raises
 // its sticky flag and the facade throws the same exception; the example reports it and exits with status 3.
+// With "local" the innovation statistics are switched on and, after the last frame, two more lines follow with every value as a
+// hexadecimal float (bit-exact): "innovation" nis logdet_S loglik dof nis_lm[N], and "sigma_local" n and the n x n covariance in the
+// coordinates of the estimate (VIOFilter::stateCovarianceLocal).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +29,7 @@ int main(int argc, char** argv) {
     const bool aux = argc > 3 && std::string(argv[3]) == "aux";
     const bool level = argc > 3 && std::string(argv[3]) == "level";
     const bool init = argc > 3 && std::string(argv[3]) == "init";
+    const bool local = argc > 3 && std::string(argv[3]) == "local";
     std::vector<Vector3d> lm(N);
     for (int i = 0; i < N; ++i) lm[i] = {2 * std::sin(1.3 * i), 2 * std::cos(0.7 * i), 5 + std::sin(0.37 * i)};
     AuxiliaryFilterData ad;
@@ -56,6 +60,7 @@ int main(int argc, char** argv) {
     imu.accel = {GRAVITY_CONSTANT, 0, 0};
     if (level) imu.accel = {0, 0, GRAVITY_CONSTANT};
     if (init) filter.initialiseFromIMUData(imu);
+    if (local) filter.setOption("innovation_stats", 1);
     int k = 0;
     try {
     for (int f = 0; f < frames; ++f) {
@@ -81,6 +86,15 @@ int main(int argc, char** argv) {
             std::printf("t=%.4f N=%zu pos=(%.6f %.6f %.6f) q=(%.6f %.6f %.6f %.6f) |Sigma|_F=%.6e\n", filter.getTime(),
                 est.bodyLandmarks.size(), est.pose.x[0], est.pose.x[1], est.pose.x[2], est.pose.R.w, est.pose.R.x, est.pose.R.y,
                 est.pose.R.z, std::sqrt(fro));
+            if (local) {
+                const VIOFilter::InnovationStats is = filter.innovationStats();
+                std::printf("innovation %a %a %a %d", is.nis, is.logdet_S, is.loglik, is.valid ? is.dof : -1);
+                for (double v : is.nis_lm) std::printf(" %a", v);
+                const MatrixXd Sl = filter.stateCovarianceLocal();
+                std::printf("\nsigma_local %d", Sl.n);
+                for (double v : Sl.data) std::printf(" %a", v);
+                std::printf("\n");
+            }
         }
     }
     } catch (const std::domain_error& e) {

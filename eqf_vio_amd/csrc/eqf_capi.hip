@@ -22,6 +22,8 @@
 #include "eqf_resident.hpp"
 #include "eqf_update.hpp"
 #include "eqf_i8.hpp"
+#include "eqf_local.hpp"
+#include "eqf_innov.hpp"
 
 using namespace eqf;
 
@@ -209,6 +211,13 @@ struct eqf_filter {
     signed char* dI8Ws = nullptr;
     int* dI8Expo = nullptr;
     long long i8WsStride = 0;
+    // covariance in the coordinates of the estimate (eqf_local.hpp): the J blocks [B][kJacHead + 9 cap] and an image of Sigma's size, both
+    // allocated by the first getter that needs them
+    double *dJac = nullptr, *dSigmaLoc = nullptr;
+    // innovation statistics of every update (eqf_innov.hpp; eqf_set_option "innovation_stats"): the tail launch k_innov_stats and its
+    // records [B][kInnovHead + cap], allocated when the option is first switched on
+    int innovStats = 0;
+    double* dInnov = nullptr;
     int resTickets = 0;           // eqf_debug_option "res_tickets": 0 (default) the block index (rounds 3-5), 1 tickets on grids >= 6 x the resident slots, 2 on every grid larger than the chip (non-FOLD)
     double *dGammaPart = nullptr, *dG11Part = nullptr;
     ResRole* dRoles = nullptr;
@@ -1040,6 +1049,14 @@ int launchUpdateT(eqf_filter* f, const double* bearings, long long bearStride, c
         });
         if (rc) return rc;
     }
+    if (f->innovStats && std::is_same<T, double>::value) {
+        // (a tail launch of its own, only with the option on: the update's other launches are what they are without it)
+        InnovArgs na{};
+        na.g = a.g; na.YO = f->YO; na.ldY = f->ldY; na.strideY = f->strideY; na.SL = f->SL; na.strideDS = f->strideDS;
+        na.delta = f->dbgDelta; na.lmc = f->lmc; na.Sin = static_cast<const double*>(a.Sin); na.ld = f->ld; na.cap = f->cap;
+        na.sigmaStride = f->sigmaStride; na.measurementVariance = f->prm.measurementVariance; na.out = f->dInnov;
+        hipLaunchKernelGGL(k_innov_stats, dim3(B), dim3(256), 0, f->stream, na);
+    }
     HIPC(hipGetLastError());
     f->pS ^= 1;
     return EQF_OK;
@@ -1130,6 +1147,9 @@ int visionCore(eqf_filter* f, const std::vector<const int*>& measIds, const std:
     // their measurement entries -- the gate is not evaluated again
     const int B = f->B, cap = f->cap;
     // (per-call API: the bearings are still in pinned host memory -- whoever enqueues the first consumer enqueues their copy)
+    // innovation statistics: every filter's record starts the vision call with valid = 0; k_innov_stats sets it for the filters whose
+    // update runs (a redo of a gated frame only concerns the filters it flags: the others keep what the first pass left)
+    if (f->innovStats && !gated) HIPC(hipMemsetAsync(f->dInnov, 0, sizeof(double) * (size_t)(kInnovHead + cap) * B, f->stream));
     auto flushMeas = [&]() -> int {
         if (!f->measPending) return EQF_OK;
         f->measPending = false;
@@ -1592,7 +1612,7 @@ void freeAll(eqf_filter* f) {
              (void*)f->ZO, (void*)f->dbgDelta, (void*)f->dbgGamma, (void*)f->dbgGammaTot, (void*)f->red, (void*)f->errflag, (void*)f->dMap,
              (void*)f->dPerm, (void*)f->dChord, (void*)f->dDepth2, (void*)f->dDepthSel, (void*)f->dScratch, (void*)f->dMeas,
              (void*)f->dOut, (void*)f->dRing, (void*)f->sImu, (void*)f->sVis, (void*)f->sBear, f->dF, f->dG, f->dBn, f->dBlk, (void*)f->dBlkCommon, f->dColRec, f->dRowRec, (void*)f->dSteps, (void*)f->dFlags, (void*)f->dReadyA, (void*)f->dReadyY, (void*)f->dResCounters, (void*)f->dTicket, (void*)f->dStageFlags, (void*)f->dPrepFlags, (void*)f->dBuildFlags, (void*)f->dGammaPart,
-             (void*)f->dG11Part, (void*)f->dRoles, (void*)f->dI8Ws, (void*)f->dI8Expo})
+             (void*)f->dG11Part, (void*)f->dRoles, (void*)f->dI8Ws, (void*)f->dI8Expo, (void*)f->dJac, (void*)f->dSigmaLoc, (void*)f->dInnov})
         hipFree(p);
     if (f->hGate) hipHostFree(f->hGate);
     if (f->dMask) hipFree(f->dMask);
@@ -1866,6 +1886,8 @@ int eqf_reset(eqf_filter* f) {
     GATE(f);
     HIPC(hipSetDevice(f->device));
     HIPC(hipStreamSynchronize(f->stream));
+    // (no vision call has been made on the fresh state: the innovation statistics of the old one are not valid any more)
+    if (f->dInnov) HIPC(hipMemsetAsync(f->dInnov, 0, sizeof(double) * (size_t)(kInnovHead + f->cap) * f->B, f->stream));
     return initState(f);
 }
 
@@ -2175,6 +2197,106 @@ int eqf_get_sigma(eqf_filter* f, int b, double* dst, int ld) {
     return EQF_OK;
 }
 
+// The J blocks of filters [b0, b0 + count) (k_local_jacobian) behind whatever the stream holds; with sigmaToo the image of Sigma in the
+// coordinates of the estimate as well (k_sigma_local).  The buffers are allocated on first use: a failed allocation is EQF_ERR_HIP and
+// leaves the handle as it was.
+static int launchLocal(eqf_filter* f, int b0, int count, bool sigmaToo) {
+    if (!f->dJac) {
+        if (hipMalloc(reinterpret_cast<void**>(&f->dJac), sizeof(double) * size_t(jacStride(f->cap)) * f->B) != hipSuccess) {
+            (void)hipGetLastError();
+            f->dJac = nullptr;
+            return EQF_ERR_HIP;
+        }
+    }
+    if (sigmaToo && !f->dSigmaLoc) {
+        if (hipMalloc(reinterpret_cast<void**>(&f->dSigmaLoc), sizeof(double) * size_t(f->sigmaStride) * f->B) != hipSuccess) {
+            (void)hipGetLastError();
+            f->dSigmaLoc = nullptr;
+            return EQF_ERR_HIP;
+        }
+    }
+    int nMax = 0;
+    for (int b = b0; b < b0 + count; ++b) nMax = std::max(nMax, int(f->ids[b].size()));
+    LocalArgs a{};
+    a.g = f->g[f->pG]; a.Q = f->Q[f->pG]; a.cap = f->cap; a.b0 = b0; a.jac = f->dJac;
+    a.Sin = static_cast<const double*>(f->Sigma[f->pS]); a.Sout = f->dSigmaLoc; a.ld = f->ld; a.sigmaStride = f->sigmaStride;
+    const int strips = std::max(1, (nMax + 255) / 256);
+    hipLaunchKernelGGL(k_local_jacobian, dim3(strips, count), dim3(256), 0, f->stream, a);
+    if (sigmaToo)
+        hipLaunchKernelGGL(k_sigma_local, dim3(strips, std::max(1, (nMax + kLocalRows - 1) / kLocalRows), count), dim3(256), 0, f->stream, a);
+    HIPC(hipGetLastError());
+    return EQF_OK;
+}
+static LocalArgs localArgs(eqf_filter* f, int b) {
+    LocalArgs a{};
+    a.g = f->g[f->pG]; a.Q = f->Q[f->pG]; a.cap = f->cap; a.b0 = b; a.jac = f->dJac;
+    a.Sin = static_cast<const double*>(f->Sigma[f->pS]); a.Sout = f->dSigmaLoc; a.ld = f->ld; a.sigmaStride = f->sigmaStride;
+    return a;
+}
+
+int eqf_get_sigma_local(eqf_filter* f, int b, double* dst, int ld) {
+    if (!f || b < 0 || b >= f->B || !dst) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);
+    const int n = kBase + 3 * int(f->ids[b].size());
+    if (ld < n) return EQF_ERR_INVALID;
+    int rc = launchLocal(f, b, 1, true);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_sigma_export<double>, dim3((n + 255) / 256, n), dim3(256), 0, f->stream, f->dSigmaLoc + (long long)b * f->sigmaStride,
+        f->ld, n, f->dOut, n);
+    HIPC(hipMemcpyAsync(f->hOut, f->dOut, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost, f->stream));
+    double head[kJacHead];
+    HIPC(hipMemcpyAsync(head, f->dJac + (long long)b * jacStride(f->cap), sizeof(head), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipStreamSynchronize(f->stream));
+    if (head[13] != 0.0) return EQF_ERR_NUMERIC;
+    for (int r = 0; r < n; ++r) std::copy(f->hOut + (size_t)r * n, f->hOut + (size_t)(r + 1) * n, dst + (size_t)r * ld);
+    return EQF_OK;
+}
+
+int eqf_get_marginals(eqf_filter* f, int b, int local, double* base, double* lm) {
+    if (!f || b < 0 || b >= f->B || !base || (local != 0 && local != 1)) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);
+    const int N = int(f->ids[b].size());
+    if (N > 0 && !lm) return EQF_ERR_INVALID;
+    int rc = launchLocal(f, b, 1, false);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_marginals, dim3(std::max(1, (N + 255) / 256)), dim3(256), 0, f->stream, localArgs(f, b), local, f->dOut);
+    HIPC(hipMemcpyAsync(f->hOut, f->dOut, sizeof(double) * (121 + (size_t)9 * N), hipMemcpyDeviceToHost, f->stream));
+    double head[kJacHead];
+    HIPC(hipMemcpyAsync(head, f->dJac + (long long)b * jacStride(f->cap), sizeof(head), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipStreamSynchronize(f->stream));
+    if (local && head[13] != 0.0) return EQF_ERR_NUMERIC;
+    std::copy(f->hOut, f->hOut + 121, base);
+    if (N > 0) std::copy(f->hOut + 121, f->hOut + 121 + (size_t)9 * N, lm);
+    return EQF_OK;
+}
+
+int eqf_get_local_jacobian(eqf_filter* f, int b, double* G, double* RAt, double* lmJ) {
+    if (!f || b < 0 || b >= f->B || !G || !RAt) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);
+    const int N = int(f->ids[b].size());
+    if (N > 0 && !lmJ) return EQF_ERR_INVALID;
+    int rc = launchLocal(f, b, 1, false);
+    if (rc) return rc;
+    HIPC(hipMemcpyAsync(f->hOut, f->dJac + (long long)b * jacStride(f->cap), sizeof(double) * (kJacHead + (size_t)9 * N), hipMemcpyDeviceToHost,
+        f->stream));
+    HIPC(hipStreamSynchronize(f->stream));
+    if (f->hOut[13] != 0.0) return EQF_ERR_NUMERIC;
+    std::copy(f->hOut, f->hOut + 4, G);
+    std::copy(f->hOut + 4, f->hOut + 13, RAt);
+    if (N > 0) std::copy(f->hOut + kJacHead, f->hOut + kJacHead + (size_t)9 * N, lmJ);
+    return EQF_OK;
+}
+
+int eqf_debug_sigma_local_all(eqf_filter* f) {
+    if (!f) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);
+    return launchLocal(f, 0, f->B, true);
+}
+
 int eqf_set_sigma(eqf_filter* f, int b, const double* src, int ld) {
     if (!f || b < 0 || b >= f->B || !src) return EQF_ERR_INVALID;
     GATE(f);
@@ -2448,7 +2570,43 @@ int eqf_set_option(eqf_filter* f, const char* name, int value) {
         f->resTickets = value;
         return EQF_OK;
     }
+    if (!std::strcmp(name, "innovation_stats")) {
+        if (value != 0 && value != 1) return EQF_ERR_INVALID;
+        if (value && f->precision == EQF_PRECISION_F32) return EQF_ERR_UNSUPPORTED;
+        GATE(f);
+        if (value && !f->dInnov) {
+            if (hipMalloc(reinterpret_cast<void**>(&f->dInnov), sizeof(double) * (size_t)(kInnovHead + f->cap) * f->B) != hipSuccess) {
+                (void)hipGetLastError();
+                f->dInnov = nullptr;
+                return EQF_ERR_HIP;
+            }
+        }
+        // (switching the option, either way, forgets the last update's statistics)
+        if (f->dInnov) HIPC(hipMemsetAsync(f->dInnov, 0, sizeof(double) * (size_t)(kInnovHead + f->cap) * f->B, f->stream));
+        f->innovStats = value;
+        return EQF_OK;
+    }
     return EQF_ERR_INVALID;
+}
+
+int eqf_get_innovation_stats(eqf_filter* f, int b, eqf_innovation_stats* out, double* nis_lm) {
+    if (!f || b < 0 || b >= f->B || !out) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);
+    HIPC(hipStreamSynchronize(f->stream));
+    std::memset(out, 0, sizeof(*out));
+    if (!f->innovStats || !f->dInnov) return EQF_OK;
+    const int N = int(f->ids[b].size());
+    std::vector<double> tmp(kInnovHead + (size_t)N);
+    HIPC(hipMemcpy(tmp.data(), f->dInnov + (size_t)b * (kInnovHead + f->cap), sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
+    if (tmp[4] == 0.0) return EQF_OK;
+    out->nis = tmp[0];
+    out->logdet_S = tmp[1];
+    out->loglik = tmp[3];
+    out->dof = int(tmp[2]);
+    out->valid = 1;
+    if (nis_lm) std::copy(tmp.begin() + kInnovHead, tmp.end(), nis_lm);
+    return EQF_OK;
 }
 
 int eqf_tile_syrk_i8(int device, void* stream, int batch, const int* nv, const int* mp, const double* Y, int ldY, long long strideY,

@@ -130,6 +130,16 @@ class VIOFilter:
     def stateCovariance(self):
         return self._fb.sigma(0)
 
+    def stateCovarianceLocal(self):
+        """The covariance in the coordinates of the ESTIMATE, J Sigma J^T (include/eqf_vio_amd.h: eqf_get_sigma_local); stateCovariance()
+        -- like the reference's, VIOFilter.cpp:306-309 "TODO: propagate to local tangent space" -- is in the chart around the origin."""
+        return self._fb.sigma_local(0)
+
+    def innovationStats(self):
+        """NIS, log det S, log-likelihood, dof and per-landmark NIS of the most recent vision update (set_option("innovation_stats", 1)
+        first); include/eqf_vio_amd.h: eqf_get_innovation_stats."""
+        return self._fb.innovation_stats(0)
+
     def reset(self):
         self._fb.reset()
 

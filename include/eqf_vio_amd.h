@@ -125,6 +125,26 @@ int eqf_get_bias(eqf_filter* f, int b, double* bias6);
 /* VIOFilter::stateCovariance (VIOFilter.cpp:306-309): n x n, n = 11 + 3N, row-major with leading
  * dimension ld >= n, in the reference's index map. */
 int eqf_get_sigma(eqf_filter* f, int b, double* dst, int ld);
+/* The same covariance in the coordinates of the ESTIMATE.  eqf_get_sigma -- like VIOFilter::stateCovariance, VIOFilter.cpp:306-309, whose
+ * own comment reads "TODO: propagate to local tangent space" -- returns Sigma in the chart around the origin xi0: the covariance of
+ * eps = chart_xi0(phi_{X^-1}(xi)).  The error a caller can measure against eqf_get_state_estimate is eps_loc = chart_xiHat(xi), xiHat =
+ * phi_X(xi0); to first order eps_loc = J eps with a block-diagonal J (the group action with X fixed acts component by component):
+ *   [0,6) bias I;  [6,8) gravity direction G = stereoSphereChartDiff(etaHat, etaHat) R_A^T stereoSphereChartInvDiff(0, eta0) (2 x 2),
+ *   eta0 = R_P0^T e3, etaHat = R_A^T eta0;  [8,11) velocity R_A^T;  landmark i: a_i^-1 R(q_i)^T (the differential of Q_i^-1 p),
+ * and Sigma_loc = J Sigma J^T, formed on the device in one pass over Sigma (csrc/eqf_local.hpp); Sigma itself is only read.  Layout and
+ * index map of eqf_get_sigma.  The first call allocates a device buffer of Sigma's size (EQF_ERR_HIP if that fails; nothing else is
+ * affected).  All three getters below flush queued IMU calls and synchronise like every getter; EQF_ERR_INVALID for bad arguments (b, a
+ * NULL output, ld < n), EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle, EQF_ERR_NUMERIC (not sticky) while the gravity chart of xiHat
+ * or xi0 is singular (SO3.cpp:160: a level identity pose, i.e. a filter that has not been initialised).  A filter without landmarks
+ * answers with the base part only. */
+int eqf_get_sigma_local(eqf_filter* f, int b, double* dst, int ld);
+/* The marginals a consumer normally wants, without the n^2 pass and the n^2 copy: base (11 x 11, row-major) and the N diagonal 3 x 3
+ * blocks lm[N][3][3], in the origin's coordinates (local = 0: blocks of eqf_get_sigma) or the estimate's (local = 1: blocks of
+ * eqf_get_sigma_local, bit for bit).  O(N) work and traffic.  lm may be NULL for a filter without landmarks. */
+int eqf_get_marginals(eqf_filter* f, int b, int local, double* base, double* lm);
+/* The blocks of J as the device built them: G[2][2], RAt[3][3] = R_A^T, lmJ[N][3][3] = a_i^-1 R(q_i)^T -- what a caller needs to map
+ * vectors of its own between the two charts. */
+int eqf_get_local_jacobian(eqf_filter* f, int b, double* G, double* RAt, double* lmJ);
 /* Test hook: overwrite Sigma (same layout as eqf_get_sigma). */
 int eqf_set_sigma(eqf_filter* f, int b, const double* src, int ld);
 /* Checkpoint / resume (full precision; the reference's only dump is the lossy, write-only operator<<,
@@ -186,8 +206,29 @@ int eqf_set_imu_burst(eqf_filter* f, int max_steps);
  *       (the option stays as it was).  EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle.
  *   "res_tickets" 0 (default) | 1 | 2: arrival tickets for the workgroups of the one-launch factorisation on grids larger than the chip (1:
  *       grids of at least six times the resident slots, 2: all of them) -- for a device or driver that might not start workgroups in the
- *       order of their index (see eqf_device_error); the result is bit for bit the same. */
+ *       order of their index (see eqf_device_error); the result is bit for bit the same.
+ *   "innovation_stats" 0 (default) | 1: every vision update that actually runs also leaves its innovation statistics (eqf_get_innovation_stats,
+ *       below): one small launch behind the update's own (csrc/eqf_innov.hpp).  With 0 the launches and every output bit of an update are
+ *       what they are without the option.  EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle; EQF_ERR_HIP (option unchanged) if the
+ *       records cannot be allocated.  Switching the option forgets the statistics of the last update. */
 int eqf_set_option(eqf_filter* f, const char* name, int value);
+/* What the update's factorisation S = C Sigma C^T + R = L L^T and z = L^-1 delta (VIOFilter.cpp:276-280 forms S.inverse() instead) say about
+ * the most recent vision update of filter b -- the numbers a filter is tuned by, which need the PRE-update Sigma that no getter can reach:
+ *   nis = delta^T S^-1 delta = z^T z;  logdet_S = 2 sum_k log L_kk;  dof = 2 N of that update;
+ *   loglik = -(nis + logdet_S + dof log 2 pi) / 2, the measurement log-likelihood;
+ *   nis_lm[i] = delta_i^T (S_ii)^-1 delta_i with the 2 x 2 diagonal block of S (2 degrees of freedom; what a chi-square gate or an outlier
+ *   report needs), in the state's landmark order; nis_lm [N] may be NULL.
+ * valid = 0 (and every other field 0) when that filter's last vision call was skipped (EQF_SKIPPED_*), was gated down to nothing, or
+ * the option "innovation_stats" was off.  fp64 in every build, also with "downdate_slices" on, and bit for bit the same under every launch
+ * shape of the factorisation and from run to run (one fixed summation order).  Flushes and synchronises like every getter. */
+typedef struct eqf_innovation_stats {
+    double nis;
+    double logdet_S;
+    double loglik;
+    int dof;
+    int valid;
+} eqf_innovation_stats;
+int eqf_get_innovation_stats(eqf_filter* f, int b, eqf_innovation_stats* out, double* nis_lm);
 
 /* Propagate backend: 0 = block-structured HBM-bound kernel (default, product path),
  * 1 = dense F Sigma F^T on MFMA (what the reference executes; BASELINE cfg 3 cross-check). */

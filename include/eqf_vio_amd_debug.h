@@ -50,6 +50,10 @@ int eqf_debug_option(eqf_filter* f, const char* name, int value);
  * of C Sigma and S (the update's prep work does not read Sigma then), [4] builder workgroups per filter, [5] block-kernel workgroups per
  * filter, [6] steps in the burst, [7] reserved.  Does not touch the device or flush anything. */
 int eqf_debug_launch_shape(eqf_filter* f, int* shape8);
+/* Measurement hook: k_local_jacobian + k_sigma_local (csrc/eqf_local.hpp) for EVERY filter of the handle in one batched launch, into the
+ * handle's device buffer; nothing is copied to the host and nothing waits (eqf_synchronize does).  eqf_get_sigma_local launches the same
+ * kernels for one filter. */
+int eqf_debug_sigma_local_all(eqf_filter* f);
 
 /* Per-kernel-class timing with HIP events on the handle's stream (bench.py roofline leg).
  * eqf_profile_get: for class c in [0, EQF_PROF_CLASSES) -> launches and total milliseconds.  The total is, per launch shape

@@ -1,0 +1,165 @@
+"""Measurements behind DESIGN.md section 4.5c (estimate-frame covariance, innovation statistics).  Every leg needs the GPU.
+
+  kernels B N      a workload for `rocprofv3 --kernel-trace --stats -- python scripts/consistency_bench.py kernels B N`: k_sigma_local (batched
+                   over the handle's B filters, eqf_debug_sigma_local_all) next to k_riccati_stream (single-step split propagate,
+                   EQF_SPLIT_PROPAGATE=1 + imu burst 0) on the same Sigma, 30 launches each.  Algorithmic bytes of either: 2 n^2 * 8 * B,
+                   n = 12 + 3 N (read Sigma once, write it once).
+  wall N           wall time of marginals() / sigma_local() / sigma() through the binding.
+  ab B N MODE      stream-mode timing, MODE = off | on ("innovation_stats"); EQF_VIO_AMD_LIB selects another build of the library (the
+                   parent commit's, for off-against-parent).  Prints one JSON line: events/s (IMU + vision calls), us per vision frame.
+  frames N F MODE  F vision frames in stream mode and nothing else (for a kernel-trace table of what an update launches).
+  summarize DIR    kernel-trace stats CSVs under DIR -> the table of the `kernels` legs (achieved bytes/s, ratio).
+"""
+import csv
+import glob
+import json
+import os
+import sys
+import time
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _filled(B, N, frames=3, burst=None, stats=None, duration=None):
+    from eqf_vio_amd import binding, synth
+
+    st = synth.make_stream(N, duration=duration or (0.05 * frames + 0.06))
+    fg = binding.FilterBatch(synth.template_settings_dict(), capacity=N, batch=B)
+    if burst is not None:
+        fg.set_imu_burst(burst)
+    if stats is not None:
+        fg.set_option("innovation_stats", stats)
+    fg.stream_upload(st.imu, st.vision_stamps, st.ids, st.bearings)
+    return fg, st
+
+
+def kernels(B, N):
+    os.environ["EQF_SPLIT_PROPAGATE"] = "1"
+    fg, st = _filled(B, N, frames=3, burst=0)
+    ev = list(st.events())
+    seen = 0
+    for i, (kind, k) in enumerate(ev):
+        (fg.stream_imu if kind == "imu" else fg.stream_vision)(k)
+        seen += kind == "vision"
+        if seen == 3:
+            break
+    fg.synchronize()
+    assert fg.num_landmarks(0) == N and fg.device_error() == 0
+    t = float(fg.get_time()[0])
+    for j in range(30):
+        t += 0.005
+        fg.process_imu(t, [0.01, 0.02, -0.01], [9.7, 0.3, 0.2])  # one Riccati step: k_build_blocks + k_riccati_stream
+        fg.debug_sigma_local_all()                               # k_local_jacobian + k_sigma_local over all B filters
+    fg.synchronize()
+    assert fg.device_error() == 0
+    print(f"kernels B={B} N={N}: done")
+
+
+def wall(N):
+    fg, st = _filled(1, N, frames=2)
+    for kind, k in st.events():
+        (fg.stream_imu if kind == "imu" else fg.stream_vision)(k)
+    fg.synchronize()
+    out = {}
+    for name, fn in (("marginals(local=True)", lambda: fg.marginals(0, local=True)), ("sigma_local()", lambda: fg.sigma_local(0)),
+                     ("sigma()", lambda: fg.sigma(0))):
+        fn()  # (first call: allocations)
+        ts = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        out[name] = min(ts) * 1e3
+    n = 11 + 3 * N
+    print(f"wall N={N}: " + ", ".join(f"{k} {v:.2f} ms" for k, v in out.items()) +
+          f"  (bytes to the host: {(121 + 9 * N) * 8 / 1e3:.0f} KB against {n * n * 8 / 1e6:.0f} MB)")
+
+
+def ab(B, N, mode, reps=3):
+    dur = 2.2 if N <= 200 else 0.6
+    fg, st = _filled(B, N, duration=dur, stats=None)
+    if mode == "on":
+        fg.set_option("innovation_stats", 1)
+    elif mode != "off":
+        raise SystemExit("MODE is off or on")
+    ev = list(st.events())
+    nvis = sum(1 for kind, _ in ev if kind == "vision")
+    warm = [i for i, (kind, _) in enumerate(ev) if kind == "vision"][max(1, nvis // 5)] + 1
+    best = None
+    for _ in range(reps):
+        fg.reset()
+        for kind, k in ev[:warm]:
+            (fg.stream_imu if kind == "imu" else fg.stream_vision)(k)
+        fg.synchronize()
+        t0 = time.perf_counter()
+        for kind, k in ev[warm:]:
+            (fg.stream_imu if kind == "imu" else fg.stream_vision)(k)
+        fg.synchronize()
+        dt = time.perf_counter() - t0
+        best = dt if best is None else min(best, dt)
+    assert fg.device_error() == 0
+    nev = len(ev) - warm
+    nfr = sum(1 for kind, _ in ev[warm:] if kind == "vision")
+    print(json.dumps(dict(B=B, N=N, mode=mode, lib=os.environ.get("EQF_VIO_AMD_LIB", "this tree"), events_per_s=round(nev * B / best, 1),
+                          us_per_frame=round(best / nfr * 1e6, 2), frames=nfr)))
+
+
+def frames(N, F, mode):
+    fg, st = _filled(1, N, frames=F)
+    if mode == "on":
+        fg.set_option("innovation_stats", 1)
+    seen = 0
+    for kind, k in st.events():
+        (fg.stream_imu if kind == "imu" else fg.stream_vision)(k)
+        seen += kind == "vision"
+        if seen == F:
+            break
+    fg.synchronize()
+    assert fg.device_error() == 0
+    print(f"frames N={N} F={seen} mode={mode}: done")
+
+
+def summarize(d):
+    rows = []
+    for path in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)):
+        tag = os.path.relpath(path, d).split(os.sep)[0]  # kernels_B_N
+        try:
+            _, B, N = tag.split("_")
+            B, N = int(B), int(N)
+        except ValueError:
+            continue
+        avg = {}
+        for r in csv.DictReader(open(path)):
+            name = r.get("Name") or r.get("KernelName") or ""
+            for key in ("k_sigma_local", "k_riccati_stream", "k_local_jacobian", "k_build_blocks"):
+                if key in name:
+                    avg[key] = (float(r["AverageNs"]) / 1e3, float(r["MinNs"]) / 1e3, int(r["Calls"]))
+        rows.append((B, N, avg))
+    print("B x N      bytes (2 n^2 8 B)   k_sigma_local avg / min us   TB/s (avg)   k_riccati_stream avg / min us   TB/s (avg)   sigma_local / riccati time")
+    for B, N, avg in rows:
+        n = 12 + 3 * N
+        by = 2.0 * n * n * 8 * B
+        if "k_sigma_local" not in avg or "k_riccati_stream" not in avg:
+            print(B, N, "incomplete", avg)
+            continue
+        a, r = avg["k_sigma_local"], avg["k_riccati_stream"]
+        print(f"{B:3d} x {N:<5d} {by / 1e6:10.1f} MB   {a[0]:10.1f} / {a[1]:8.1f}   {by / a[0] / 1e6:6.2f}   {r[0]:10.1f} / {r[1]:8.1f}   {by / r[0] / 1e6:6.2f}   {a[0] / r[0]:.2f}"
+              f"   (k_local_jacobian {avg.get('k_local_jacobian', (0, 0, 0))[0]:.1f} us)")
+
+
+if __name__ == "__main__":
+    cmd = sys.argv[1]
+    if cmd == "kernels":
+        kernels(int(sys.argv[2]), int(sys.argv[3]))
+    elif cmd == "wall":
+        wall(int(sys.argv[2]))
+    elif cmd == "ab":
+        ab(int(sys.argv[2]), int(sys.argv[3]), sys.argv[4])
+    elif cmd == "frames":
+        frames(int(sys.argv[2]), int(sys.argv[3]), sys.argv[4])
+    elif cmd == "summarize":
+        summarize(sys.argv[2])
+    else:
+        raise SystemExit(__doc__)
