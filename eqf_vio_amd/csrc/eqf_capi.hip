@@ -141,10 +141,8 @@ struct eqf_filter {
     void *dF = nullptr, *dG = nullptr, *dBn = nullptr;  // dense backend: F, G = F Sigma, Bn (n x 6)
     void* dBlk = nullptr;          // split propagate path: per-landmark records [B][cap][kBlkRec] (T)
     CommonLds* dBlkCommon = nullptr;
-    int streamPropagate = 1;       // split path: landmark blocks by k_riccati_stream ([no switch since round 5]: by the tile kernel)
     int splitPropagate = -1;       // -1 heuristic, 0 never, 1 always (EQF_SPLIT_PROPAGATE)
-    int cholEmbed = 1;             // [no switch since round 5]: downdate + innovation lift as a launch of their own
-    bool ldsAttrSet[2] = {false, false};  // hipFuncAttributeMaxDynamicSharedMemorySize applied on this handle's device
+    bool ldsAttrSet = false;       // hipFuncAttributeMaxDynamicSharedMemorySize applied on this handle's device (allowUpdateLds)
     // speculative outlier gate: the frame whose gate answer the host has not looked at yet
     struct {
         bool pending = false;
@@ -172,7 +170,7 @@ struct eqf_filter {
     int burstMax = kBurstMax;      // EQF_IMU_BURST / eqf_set_imu_burst
     int burstRows = 0;             // block kernel: row landmarks per wavefront, 0 = by launch size (EQF_BURST_ROWS = 1 | 2 | 4)
     int ringAhead2 = 0;            // block kernel with two row landmarks per wave: constants requested two steps ahead -- measured 1.5-2.7 us SLOWER per burst at 4..12 filters (profiles/r06_burst_shapes.txt), kept behind eqf_debug_option "ring_ahead2"
-    int burstLm = 0;               // builder: landmarks per workgroup, 0 = by launch size ([no switch since round 5])
+    int burstLm = 0;               // builder: landmarks per workgroup, 0 = by launch size (eqf_debug_option "burst_lm")
     struct {
         int kind = 0;              // 0 nothing pending, 1 records k0 .. k0+cnt-1 of the uploaded stream, 2 inline records (one filter)
         int k0 = 0, cnt = 0;
@@ -181,25 +179,18 @@ struct eqf_filter {
     void *dColRec = nullptr, *dRowRec = nullptr;  // per step and landmark records of k_burst_build
     BurstStep* dSteps = nullptr;
     int cholSplit = -1;            // -1 heuristic, 0 fused chain launches, 1 panel + update launches (EQF_CHOL_SPLIT)
-    int cholTail = 1;              // split chain: update launches also solve the next block column ([no switch since round 5]: panel + update launches)
     int* dFlags = nullptr;         // [B][2][flagStride]: epoch flags of the in-launch hand-off of the diagonal-factor records
     int flagStride = 0;
     int updateEpoch = 0;           // one per launchUpdate
     // k_chol_resident (one launch per update while the grid fits the chip): EQF_CHOL_RESIDENT = 0 switches it off
     int cholResident = 1;
-    int resOversub = -1;           // [no switch since round 5]: roles per CU up to which the resident kernel is used on a grid larger than the chip; -1 = no limit
-    int resStaged = 1;             // row heads consume D[R-1] stage by stage ([no switch since round 5]: whole record after its last pivot)
     int resFoldPrep = 1;           // co-resident grid: the prep work as roles of the SAME launch (EQF_RES_FOLD_PREP = 0: k_update_prep64 launched first)
     int* dPrepFlags = nullptr;     // [B][nPrepCap]
     int nPrepCap = 0;
     int burstFused = 1;            // latency case: builder and block workgroups of a burst in ONE launch (EQF_BURST_FUSED = 0: two launches)
     int* dBuildFlags = nullptr;    // [B][nBuildCap]: steps each builder workgroup has published, + 32 * burstEpoch
     int nBuildCap = 0, burstEpoch = 0;
-    bool rolesFold = false;
     int residentPerCU = -1;        // hipOccupancyMaxActiveBlocksPerMultiprocessor of k_chol_resident on this device (lazily queried)
-    int eFromSigma = 1;            // split chain: block column 0 of the E-chain read straight from Sigma ([no switch since round 5]: copied by prep)
-    int cholOrder = -1;            // order of the workgroup classes in an update launch, -1 = by launch size ([no switch since round 5])
-    int cholStreams = 0;           // stream workgroups per filter of an update launch, 0 = by launch size ([no switch since round 5])
     int numCUs = 0;
     int nbCap = 0, wtCap = 0;
     int *dReadyA = nullptr, *dReadyY = nullptr, *dResCounters = nullptr, *dStageFlags = nullptr;
@@ -221,13 +212,8 @@ struct eqf_filter {
     int resTickets = 0;           // eqf_debug_option "res_tickets": 0 (default) the block index (rounds 3-5), 1 tickets on grids >= 6 x the resident slots, 2 on every grid larger than the chip (non-FOLD)
     double *dGammaPart = nullptr, *dG11Part = nullptr;
     ResRole* dRoles = nullptr;
-    int resPipeHeads = -1;         // [no switch since round 5]: row heads with the pipelined panel loop (1), without (0), by grid size (-1)
-    int prepOcc2 = -1;             // [no switch since round 5]: the prep launch built for two workgroups per CU (1), one (0), by launch size (-1)
-    int burstOcc2 = -1;            // [no switch since round 5]: the 16-landmark builder built for two workgroups per CU (1), one (0), by launch size (-1)
-    int resOcc2 = -1;              // [no switch since round 5]: k_chol_resident built for two workgroups per CU (1), one (0), by grid size (-1)
     int rolesN = -1, rolesCount = 0;  // chain shape (nbS, nbE, wtS) the role table was built for
     int rolesFront = 0;               // roles in front of the prep roles (buildRoles' `front`)
-    int resFoldFront = 1;             // EQF_RES_FOLD_FRONT: dependency groups of the E-chain in front of the prep roles of a batch
     int dropRole[4] = {-1, 0, 0, 0};  // eqf_debug_drop_role: (kind, role, R, C) of the role whose workgroup leaves without publishing anything
     // profiling
     bool prof = false;
@@ -426,8 +412,7 @@ int launchPropagate(eqf_filter* f, const ImuRec* devRecs, const ImuRec& inl, con
     a.isImu = isImu ? 1 : 0;
     a.doRiccati = doRiccati ? 1 : 0;
     a.prm = f->prm;
-    // tiles + base-block workgroup + scalar-state workgroup + NT row-tail + NT column-tail workgroups (see k_propagate)
-    const dim3 grid(a.NT * a.NT + 2 + 2 * a.NT, f->B), block(256);
+    const dim3 block(256);
     int rc = EQF_OK;
     if (f->densePropagate && doRiccati) {
         // dense backend: F and Bn from the same linearisation blocks, then two MFMA GEMMs; k_propagate below only
@@ -464,23 +449,21 @@ int launchPropagate(eqf_filter* f, const ImuRec* devRecs, const ImuRec& inl, con
         if (split) {
             const dim3 bgrid((std::max(1, maxN(f)) + 63) / 64 + 1, f->B);  // landmark workgroups + the scalar-state workgroup
             // builder (blocks + G rows + group step + scalar state), then everything of Sigma by the lean streaming kernel
-            // ([no switch since round 5]: by the tile kernel instead -- kept as a cross-check)
             const int nmx = std::max(1, maxN(f));
             const dim3 sgrid((nmx + 255) / 256, (nmx + kStreamRows - 1) / kStreamRows, f->B);
             if (f->precision == EQF_PRECISION_F32) {
                 hipLaunchKernelGGL(k_build_blocks<float>, bgrid, dim3(128), 0, f->stream, a);
-                if (f->streamPropagate) hipLaunchKernelGGL(k_riccati_stream<float>, sgrid, block, 0, f->stream, a);
-                else hipLaunchKernelGGL((k_propagate<float, true>), grid, block, 0, f->stream, a);
+                hipLaunchKernelGGL(k_riccati_stream<float>, sgrid, block, 0, f->stream, a);
             } else {
                 hipLaunchKernelGGL(k_build_blocks<double>, bgrid, dim3(128), 0, f->stream, a);
-                if (f->streamPropagate) hipLaunchKernelGGL(k_riccati_stream<double>, sgrid, block, 0, f->stream, a);
-                else hipLaunchKernelGGL((k_propagate<double, true>), grid, block, 0, f->stream, a);
+                hipLaunchKernelGGL(k_riccati_stream<double>, sgrid, block, 0, f->stream, a);
             }
         } else {
-            // fused kernel: ... + one workgroup per 64 landmarks (group step)
+            // fused kernel: tiles + base-block workgroup + scalar-state workgroup + NT row-tail + NT column-tail workgroups (see k_propagate)
+            // + one workgroup per 64 landmarks (group step)
             const dim3 fgrid(a.NT * a.NT + 2 + 2 * a.NT + (std::max(1, maxN(f)) + 63) / 64, f->B);
-            if (f->precision == EQF_PRECISION_F32) hipLaunchKernelGGL((k_propagate<float, false>), fgrid, block, 0, f->stream, a);
-            else hipLaunchKernelGGL((k_propagate<double, false>), fgrid, block, 0, f->stream, a);
+            if (f->precision == EQF_PRECISION_F32) hipLaunchKernelGGL(k_propagate<float>, fgrid, block, 0, f->stream, a);
+            else hipLaunchKernelGGL(k_propagate<double>, fgrid, block, 0, f->stream, a);
         }
     });
     if (rc) return rc;
@@ -543,7 +526,7 @@ int launchBurst(eqf_filter* f, int K, const ImuRec* devRecs, long long recStride
     const dim3 bgrid(std::max(1, (nmx + lm - 1) / lm), f->B);
     // (round 5: the 4-landmark builder built for two workgroups per CU so that 8 filters keep its short ticks -- 400 workgroups on 512 slots --
     // measured: 70.9 against 71.0 us per burst, nothing; not kept)
-    const bool occ2 = f->burstOcc2 >= 0 ? f->burstOcc2 != 0 : (lm == 16 && (long long)bgrid.x * bgrid.y > cus);
+    const bool occ2 = lm == 16 && (long long)bgrid.x * bgrid.y > cus;
     // rows per wavefront of the block kernel: one while the launch cannot fill the chip anyway (latency), four once the
     // column constants of a lane are worth sharing between several of its blocks.  (Two rows: 286 VGPRs, one wave per SIMD
     // like four rows but half their reuse -- measured slower than both at every size, N = 200 x 2..64 filters, N = 400..4000.)
@@ -731,14 +714,281 @@ int buildRoles(eqf_filter* f, int Nmax, bool fold, int front = 0) {
     return EQF_OK;
 }
 
-// (the FOLD build only exists for fp64: the fp32 mode keeps the prep launch)
-template <typename T>
-void launchFold(dim3 rg, hipStream_t st, const ResArgs& ra, bool pipeHeads, bool occ2) {
-    if constexpr (std::is_same<T, double>::value) {
-        if (pipeHeads && occ2) hipLaunchKernelGGL((k_chol_resident<double, true, true, true>), rg, dim3(256), kLdsRes2Bytes, st, ra);
-        else if (pipeHeads) hipLaunchKernelGGL((k_chol_resident<double, true, false, true>), rg, dim3(256), sizeof(Step64Lds), st, ra);
-        else hipLaunchKernelGGL((k_chol_resident<double, false, false, true>), rg, dim3(256), sizeof(Step64Lds), st, ra);
+// ---- The launch shape of one update: decided once, from the handle and the largest landmark count of the batch, before anything is
+// launched (the prep launch already needs to know whether anybody reads EA's block column 0).  The launches below only read it.
+struct UpdateShape {
+    int nbS, nbE, wtS, nv;  // 64-wide block columns of the S- and of the E-chain, right-hand-side column tiles of the S-chain; rows of Sigma in use
+    // prep work (a launch of its own, or roles of k_chol_resident: `fold`): landmark wavefronts per workgroup, padded row length of their LDS
+    // image, landmark workgroups, workgroups of the E-chain's operand, LDS bytes of a landmark workgroup, the launch built for two workgroups per CU
+    int wpb, nvPad, lmBlocks, eBlocks;
+    size_t prepLds;
+    bool occ2Prep;          // (B >= 4 and more workgroups than CUs)
+    bool embed;             // downdate + innovation lift ride in the chain launches
+    bool splitChain;        // per-column launches: panel launch + update launches that also solve the next block column (else fused launches)
+    bool resident;          // one launch for both chains (k_chol_resident); else one launch per block column
+    bool residentFits;      // ... and its whole grid is co-resident
+    bool fold;              // ... with the prep work as roles of the same launch
+    int front;              // ... and this many dependency groups of the E-chain in front of the prep roles (buildRoles)
+    bool pipeHeads, occ2;   // builds of k_chol_resident: row heads with the pipelined panel loop, two workgroups per CU
+    int eFromSigma;         // UpdArgs::eFromSigma
+    bool small;             // downdate: 32 x 32 tiles (4x the workgroups) instead of 64 x 64
+    int ddNt, ddTiles;      // ... tiles per edge, tiles
+    int i8Slices;           // ... on the integer pipe with this many slices (0: fp64)
+    bool tailLaunch, tailLift;  // ... as a launch of its own behind the chains; the innovation lift rides in it
+};
+
+int updateShape(eqf_filter* f, int Nmax, UpdateShape& s) {
+    const int B = f->B;
+    const bool f64 = f->precision != EQF_PRECISION_F32;
+    // Factorisation kernels: k_chol_step64 / k_chol_resident (64-wide block columns, register-chained MFMA panel solves).  (The 32-wide
+    // family of round 1 -- k_chol_step<INVERSE>, k_update_reduce, a separate prep launch -- was dominated at every size measured and has
+    // been removed in round 3; the cross-checks of a factorisation are now the other launch shapes of the same mathematics -- resident
+    // vs per-column launches bitwise, fused vs split chain to rounding -- and the fp64 oracle of the tests.)
+    s.nbS = roundUp(sDim(Nmax), kSB) / kSB, s.nbE = roundUp(eDim(Nmax), kSB) / kSB, s.wtS = roundUp(yCols(Nmax), kSB) / kSB;
+    s.nv = kLm0 + 3 * Nmax;
+    const int mp = roundUp(sDim(Nmax), kSB), nep = roundUp(eDim(Nmax), kSB);
+    s.nvPad = roundUp(std::min(s.nv, kLm0 + 3 * kPrepLmChunk), 16);
+    const size_t perWave = size_t(2) * s.nvPad * sizeof(double);
+    s.wpb = int(std::min<size_t>(4, (150 * 1024) / perWave));
+    if (s.wpb < 1) return EQF_ERR_CAPACITY;
+    s.lmBlocks = (mp / 2 + s.wpb - 1) / s.wpb, s.eBlocks = nep / kNB;
+    s.prepLds = perWave * s.wpb;
+    s.occ2Prep = B >= 4 && (long long)(s.lmBlocks + s.eBlocks + 2) * B > f->numCUs;
+    // The reductions ride along in the rhs workgroups; the downdate and the innovation lift ride along too when every filter's S-chain
+    // is shorter than its E-chain (always, except for a handful of landmarks)
+    bool eLonger = s.nbS < s.nbE;
+    for (int b = 0; b < B && eLonger; ++b) {
+        const int Nb = int(f->ids[b].size());
+        if (Nb > 0 && roundUp(sDim(Nb), kSB) >= roundUp(eDim(Nb), kSB)) eLonger = false;
     }
+    // Per-column launches: fused launches (each tile solves its own panel blocks) while a launch is bound by the serial diagonal chain;
+    // panel + update launches (every panel block solved once, 2 workgroups per CU) once it is bound by throughput
+    // (measured on the 256-CU part: 1500 workgroups = six per CU -- N = 200 from 8 filters on, N >= ~600)
+    const int nblk64 = s.nbS * s.nbS + s.wtS * s.nbS + s.nbE * s.nbE + s.nbE;
+    s.splitChain = f->cholSplit >= 0 ? f->cholSplit != 0 : (long long)nblk64 * B >= 6LL * std::max(f->numCUs, 1);
+    // ONE launch for the whole factorisation part, k_chol_resident.  While its grid fits the chip every workgroup is resident (one small
+    // filter, the latency case).  Beyond co-residency the grid is interleaved (filter index fastest: all filters advance together, group
+    // by group), the role table's block order keeps the roles deadlock-free and nothing waits for later workgroups.  Its workgroups mostly
+    // wait for hand-offs, so the chip carries several per CU without slowing the chains down; the downdate tiles are workgroups of their
+    // own at the end of the grid.  History of the switch-over (round 3, steps/s, per-column launches -> this): first up to 10 roles per CU
+    // (2 .. 16 filters of N = 200: 89 -> 107 k, 132 -> 202 k, 226 -> 298 k, 340 -> 373 k), then ONE filter up to ~26 roles per CU, whose
+    // per-column launches sit on the latency floor of the diagonal workgroup (N = 600: 11.7 k -> 19.7 k, N = 1000: 5.2 k -> 6.3 k), and
+    // finally: since the build for two workgroups per CU (k_chol_resident's OCC2, late in round 3) the resident kernel wins at EVERY size
+    // measured -- 24 / 32 / 64 / 96 filters of N = 200: 386 -> 447 k, 410 -> 479 k, 453 -> 509 k, 478 -> 507 k steps/s; one filter of
+    // N = 1500 / 2000 / 3000 / 4000: 2.23 -> 2.85 k, 1053 -> 1335, 344 -> 406, 151 -> 174 -- so it runs whenever its buffers exist and
+    // the E-chain is the longer one, on a grid of any size; the per-column launches remain for EQF_CHOL_RESIDENT=0 / EQF_CHOL_SPLIT=1 and
+    // for filters whose chains are equally long (a handful of landmarks).
+    s.resident = eLonger && f->cholResident && f->cholSplit <= 0 && f->dReadyA;
+    // the downdate on the integer pipe (eqf_set_option "downdate_slices"): never inside the chain launches -- k_chol_resident runs without its
+    // downdate tiles, the per-column shapes without `embed` -- but as the tail launch, for every launch shape
+    s.i8Slices = f64 ? f->ddSlices : 0;
+    s.embed = eLonger && (s.resident || !s.i8Slices);
+    // co-residency of the whole grid by the occupancy calculation (one workgroup per CU with the 119 KB LDS image), not by
+    // the CU count alone: the in-kernel downdate waits for workgroups with HIGHER block indices while holding its CU
+    if (s.resident && f->residentPerCU < 0) {
+        int nblk = 0;
+        const void* fn = f64 ? reinterpret_cast<const void*>(&k_chol_resident<double>) : reinterpret_cast<const void*>(&k_chol_resident<float>);
+        HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, fn, 256, sizeof(Step64Lds)));
+        f->residentPerCU = std::max(nblk, 0);
+    }
+    auto chainRoles = [](int nb, int wt) { return (nb - 1) + (nb - 1) * (nb - 2) / 2 + wt * nb; };
+    const int rolesAll = chainRoles(s.nbS, s.wtS) + chainRoles(s.nbE, 1);
+    s.residentFits = s.resident && (long long)rolesAll * B <= (long long)f->residentPerCU * f->numCUs;
+    // A co-resident grid (one small filter: the latency case): the prep work -- residuals, C Sigma, S, the lift rows, the chains' first
+    // diagonal blocks -- runs as roles of the SAME launch (ResArgs::nPrep, role F0).  The E-chain's diagonal-factor chain, the critical
+    // path of the update, needs nothing of it (Sigma_e is Sigma[6:, 6:]: its tiles are read straight from Sigma) and starts at t = 0
+    // instead of behind a 12 us launch and a dispatch gap; the S-chain and the right-hand sides wait for the prep roles' flags.
+    // (the FOLD build only exists for fp64: the fp32 mode keeps the prep launch)
+    const bool foldable = s.resident && f64 && f->cholResident < 2 && s.nbE > 1 && f->dPrepFlags && s.lmBlocks + s.eBlocks <= f->nPrepCap;
+    const bool foldFits = foldable && f->resFoldPrep && s.residentFits && s.prepLds <= sizeof(Step64Lds);
+    // Round 5: the same on a grid LARGER than the chip (the PIPEH / OCC2 builds with the prep roles in front; filter index fastest, so the
+    // prep workgroups of all filters are dispatched first and wait for nobody).  Measured at N = 200 (profiles/r05_fold_batch.txt, steps/s,
+    // prep launch -> prep roles): 2 filters 113.7 k -> 118.6 k; 4: 210.2 -> 210.7 k; 8: 316 -> 321 k (the update launch grows by what the
+    // prep launch took: 166 -> 195 us -- the prep workgroups fill the chip first and the E-chains start behind them all the same); 16:
+    // 436 -> 419 k; 64: 500 -> 465 k.  With the E-chain's first dependency group IN FRONT of the prep roles (buildRoles' `front`;
+    // profiles/r05_fold_front.txt): 4 filters 212 -> 219.6 k, 8 and 16 unchanged -- there the path prep -> S-chain ->
+    // right-hand sides -> downdate is as long as the E-chain's, and the prep work is on it wherever it runs.  So: while prep roles + chain
+    // roles together are at most four per CU (2 .. 4 filters of N = 200) -- round 6, behind the 8-landmark burst builder and this round's
+    // other launches (profiles/r06_fold_batch.txt, best of three, prep launch -> prep roles): 5 filters 234.0 -> 246.0 k, 6: 270.6 -> 283.7 k,
+    // 8: 340.4 -> 338.5 k, 10: 362.4 -> 357.0 k, 12: 397.5 -> 390.4 k -- so now up to SIX per CU (2 .. 6 filters of N = 200);
+    // EQF_RES_FOLD_PREP=3 forces it on every batch (the bitwise test does), = 2 keeps it to co-resident grids.
+    const bool foldBatch = foldable && (f->resFoldPrep == 1 || f->resFoldPrep == 3) && !s.residentFits && s.prepLds <= (size_t)kLdsRes2Bytes &&
+                           (f->resFoldPrep == 3 || (long long)(s.lmBlocks + s.eBlocks + rolesAll) * B <= 6LL * f->numCUs);
+    s.fold = foldFits || foldBatch, s.front = foldBatch ? 1 : 0;
+    // the builds of the kernel: row heads with the pipelined panel loop on grids larger than the chip (PIPEH), two workgroups per CU when
+    // the grid is many times the chip (OCC2)
+    s.pipeHeads = s.resident && !s.residentFits;
+    // (roles per CU by buildRoles' table: the chains' roles, and the two first diagonal blocks when the prep work is folded in)
+    const double perCU = double(rolesAll + (s.fold ? 2 : 0)) * B / std::max(f->numCUs, 1);
+    // (round 4, measured at N = 200: two per CU wins from 5 filters on -- 5 / 6 / 7 filters 217 -> 227 k, 242 -> 255 k, 270 -> 280 k steps/s -- and
+    // loses below: 4 filters 210 -> 195 k; one filter of N = 400, three roles per CU, 33.5 -> 32.5 k)
+    s.occ2 = s.pipeHeads && (perCU > 6.0 || (B >= 5 && perCU > 2.4));
+    // 2: k_chol_resident reads the E-chain's tiles straight from Sigma, no copy in the prep work -- the FOLD builds, and the OCC2 build from
+    // eSigmaMinPerCU roles per CU on; 1: the split chain reads block column 0 of the E-chain there (fp64 only, both)
+    const bool eSigma = s.occ2 && perCU > f->eSigmaMinPerCU && f64;
+    s.eFromSigma = (s.fold || eSigma) ? 2 : ((!s.resident && s.splitChain && f64) ? 1 : 0);
+    // downdate tiling: 64x64 tiles when they fill the chip, 32x32 tiles (4x the workgroups) for a single small filter.  Inside
+    // k_chol_resident: 64 x 64 -- a tile costs the same 14 dependent chunk fetches whatever its size, and there are enough finished
+    // workgroups to take one each -- except in the FOLD build without PIPEH (co-resident grids: 32 x 32 tiles, see the kernel)
+    const int nt64 = (s.nv + 63) / 64, nt32 = (s.nv + 31) / 32;
+    s.small = (long long)nt64 * (nt64 + 1) / 2 * B < 2LL * std::max(f->numCUs, 1);
+    s.ddNt = (s.resident ? s.fold && !s.pipeHeads : s.small) ? nt32 : nt64;
+    s.ddTiles = s.ddNt * (s.ddNt + 1) / 2;
+    s.tailLaunch = !s.embed || s.i8Slices;
+    s.tailLift = !s.resident;  // (k_chol_resident's roles run the lift whenever that kernel runs)
+    return EQF_OK;
+}
+
+// Dynamic LDS beyond 64 KB has to be allowed function by function (and device by device: remembered per handle, not per process).  The
+// table lists exactly the instantiations that the launches below it name.
+int allowUpdateLds(eqf_filter* f) {
+    if (f->ldsAttrSet) return EQF_OK;
+#ifdef EQF_F64_STAMPS
+    const int prepLds = 158 * 1024;  // (the instrumented build keeps factor64's stamps in 1 KB of static LDS)
+#else
+    const int prepLds = 160 * 1024;
+#endif
+    const int fullLds = int(sizeof(Step64Lds));
+    auto fn = [](auto* kernel) { return reinterpret_cast<const void*>(kernel); };
+    const struct { const void* fn; int bytes; } table[] = {
+        {fn(&k_update_prep64<float, false>), prepLds},
+        {fn(&k_update_prep64<double, false>), prepLds},
+        {fn(&k_update_prep64<float, true>), prepLds},
+        {fn(&k_update_prep64<double, true>), prepLds},
+        {fn(&k_chol_resident<float, false>), fullLds},
+        {fn(&k_chol_resident<double, false>), fullLds},
+        {fn(&k_chol_resident<float, true>), fullLds},
+        {fn(&k_chol_resident<double, true>), fullLds},
+        {fn(&k_chol_resident<float, true, true>), kLdsRes2Bytes},
+        {fn(&k_chol_resident<double, true, true>), kLdsRes2Bytes},
+        {fn(&k_chol_resident<double, false, false, true>), fullLds},
+        {fn(&k_chol_resident<double, true, false, true>), fullLds},
+        {fn(&k_chol_resident<double, true, true, true>), kLdsRes2Bytes},
+        {fn(&k_chol_resident<float, true, false, false, true>), fullLds},
+        {fn(&k_chol_resident<double, true, false, false, true>), fullLds},
+        {fn(&k_chol_resident<float, true, true, false, true>), kLdsRes2Bytes},
+        {fn(&k_chol_resident<double, true, true, false, true>), kLdsRes2Bytes},
+        {fn(&k_chol_step64<float, 0>), fullLds},
+        {fn(&k_chol_step64<double, 0>), fullLds},
+        {fn(&k_chol_step64<float, 1>), fullLds},
+        {fn(&k_chol_step64<double, 1>), fullLds},
+        {fn(&k_chol_step64<float, 3>), kLdsTailBytes},
+        {fn(&k_chol_step64<double, 3>), kLdsTailBytes},
+    };
+    for (const auto& e : table) HIPC(hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, e.bytes));
+    f->ldsAttrSet = true;
+    return EQF_OK;
+}
+
+// ONE launch for both chains: the roles of the table buildRoles left, the prep roles in front of them with `fold`, the downdate tiles
+// behind them unless the downdate runs on the integer pipe
+template <typename T>
+int launchChainsResident(eqf_filter* f, const UpdateShape& s, const ChainArgs& cS, const ChainArgs& cE, const UpdArgs& a) {
+    ResArgs ra{};
+    ra.c0 = cS; ra.c1 = cE; ra.a = a;
+    ra.roles = f->dRoles;
+    ra.readyA = f->dReadyA; ra.readyY = f->dReadyY; ra.counters = f->dResCounters;
+    ra.gammaPart = f->dGammaPart; ra.g11Part = f->dG11Part;
+    ra.nbCap = f->nbCap; ra.wtCap = f->wtCap;
+    ra.stageFlags = f->dStageFlags;  // (row heads consume D[R-1] stage by stage)
+    ra.eFromSigma = s.eFromSigma == 2 ? 1 : 0;
+    if (s.fold) {
+        ra.waitD0 = 3;
+        ra.nPrep = s.lmBlocks + s.eBlocks;
+        ra.nFront = f->rolesFront;
+        ra.lmBlocks = s.lmBlocks;
+        ra.prepWpb = s.wpb;
+        ra.prepNvPad = s.nvPad;
+        ra.prepFlags = f->dPrepFlags;
+        ra.nPrepCap = f->nPrepCap;
+    }
+    ra.ddNt = s.ddNt;
+    // (the downdate tiles are workgroups of their own behind the roles, also when the whole grid is co-resident: nothing in the kernel
+    // waits for a higher block index; a grid larger than what is co-resident must not wait for later workgroups while holding CUs)
+    ra.nDdTiles = s.i8Slices ? 0 : s.ddTiles;
+    ra.nRoles = f->rolesCount;
+    ra.errflag = f->errflag;
+    const int perFilter = ra.nPrep + f->rolesCount + ra.nDdTiles;
+    ra.rolesPerRow = std::min(perFilter, 32768);
+    const dim3 rg(f->B * ra.rolesPerRow, (perFilter + ra.rolesPerRow - 1) / ra.rolesPerRow);
+    // Arrival tickets (ResArgs::ticket, the TICKET build): eqf_debug_option "res_tickets" 0 (default) = never, 2 = on every grid larger
+    // than the chip that has its prep launch in front (not the FOLD build of 2 - 4 filters), 1 = where they cost least -- grids of at
+    // least six times the resident slots (16+ filters of N = 200, N >= ~700), whose workgroups are dispatched long before they are needed;
+    // on lightly oversubscribed grids a role is dispatched just in time and the ticket's round trip (~2 us) lands on the critical
+    // path at every dependency hop: +12.8 / +7.4 / +14.6 / +3.2 / +8.6 us per update at 2 / 4 / 6 / 8 / 12 filters, +1.1 % at 64, +0.7 %
+    // at N = 1000 in one binary (profiles/r06_tickets_ab.txt), 2.3 % against round 5's library on the same box.  OFF by default: the
+    // block index with the time-outs as its guard, as in rounds 3 - 5 -- the guarantee is there for whoever wants to pay for it.
+    const long long slots = (long long)std::max(f->numCUs, 1) * (s.occ2 ? 2 : 1);
+    const bool tickets = f->resTickets == 2 || (f->resTickets == 1 && (long long)rg.x * rg.y >= 6 * slots);
+    const bool ticketBuild = s.pipeHeads && !s.fold && tickets && f->dTicket;
+    return profiled(f, EQF_PROF_CHOL_RESIDENT, [&] {
+        if (ticketBuild) {  // (every workgroup of the launch draws exactly one ticket, padding workgroups included)
+            ra.ticket = f->dTicket;
+            ra.ticketBase = f->ticketBase;
+            f->ticketBase += ra.rolesPerRow * rg.y;  // (per filter)
+        }
+        const dim3 wg(256);
+        const size_t fullLds = sizeof(Step64Lds);
+        if (s.fold) {
+            if constexpr (std::is_same<T, double>::value) {  // (the FOLD build only exists for fp64: updateShape)
+                if (s.occ2) hipLaunchKernelGGL((k_chol_resident<double, true, true, true>), rg, wg, kLdsRes2Bytes, f->stream, ra);
+                else if (s.pipeHeads) hipLaunchKernelGGL((k_chol_resident<double, true, false, true>), rg, wg, fullLds, f->stream, ra);
+                else hipLaunchKernelGGL((k_chol_resident<double, false, false, true>), rg, wg, fullLds, f->stream, ra);
+            }
+        } else if (ticketBuild && s.occ2) hipLaunchKernelGGL((k_chol_resident<T, true, true, false, true>), rg, wg, kLdsRes2Bytes, f->stream, ra);
+        else if (ticketBuild) hipLaunchKernelGGL((k_chol_resident<T, true, false, false, true>), rg, wg, fullLds, f->stream, ra);
+        else if (s.occ2) hipLaunchKernelGGL((k_chol_resident<T, true, true>), rg, wg, kLdsRes2Bytes, f->stream, ra);
+        else if (s.pipeHeads) hipLaunchKernelGGL((k_chol_resident<T, true>), rg, wg, fullLds, f->stream, ra);
+        else hipLaunchKernelGGL((k_chol_resident<T, false>), rg, wg, fullLds, f->stream, ra);
+    });
+}
+
+// One launch per block column, split chain: the panel launch of column 0, then update launches that also solve column k+1
+// (k_chol_step64<T, 3>); the S-chain's right-hand sides are complete after launch nbS - 2, the downdate joins launch nbS - 1 (`embed`:
+// nbS < nbE, so there is one)
+template <typename T>
+int launchChainsSplit(eqf_filter* f, const UpdateShape& s, const ChainArgs& cS, const ChainArgs& cE, const UpdArgs& a) {
+    const int B = f->B;
+    int rc = profiled(f, EQF_PROF_CHOL_STEP, [&] {
+        const int grid = chainBlocks64(s.nbS, s.wtS, 0, 1) + chainBlocks64(s.nbE, 1, 0, 1);
+        hipLaunchKernelGGL((k_chol_step64<T, 1>), dim3(grid, B), dim3(256), sizeof(Step64Lds), f->stream, cS, cE, a, 0, 0, 0, s.embed ? 1 : 0,
+            f->errflag);
+    }, 1000);
+    if (rc) return rc;
+    // (A downdate with 128 x 128 tiles -- half the Y traffic per flop -- as a launch of its own was tried here and measured
+    // SLOWER: 788 vs 516 us for 64 filters, 48 vs 29.5 ms at N = 4000; 352 registers leave one wave per SIMD.  The 64-wide
+    // tiles are not bandwidth-bound: they run at half the fp64 MFMA peak in executed flops.)
+    for (int k = 0; k + 1 < std::max(s.nbS, s.nbE); ++k) {
+        const int dd = (s.embed && k == s.nbS - 1) ? s.ddTiles : 0;
+        // workgroups per filter: 2 diagonal + the tails of block column k+1 + nStream streams over the pure updates
+        // (about two per CU over the whole launch; four for ONE large filter: N = 4000 150 -> 154 steps/s) + the downdate tiles; see step3Counts
+        int tS, uS, tE, uE;
+        step3Counts(s.nbS, s.wtS, k, &tS, &uS);
+        step3Counts(s.nbE, 1, k, &tE, &uE);
+        const int nStream = std::min(uS + uE, std::max(1, ((B == 1 ? 4 : 2) * f->numCUs + B - 1) / B));
+        rc = profiled(f, dd ? EQF_PROF_CHOL_DD : EQF_PROF_CHOL_STEP, [&] {
+            // (the last argument, tailsLast = 1: the streams are dispatched before the tails, which only wait)
+            hipLaunchKernelGGL((k_chol_step64<T, 3>), dim3(2 + tS + tE + nStream + dd, B), dim3(256), kLdsTailBytes, f->stream, cS, cE, a, k,
+                dd ? s.ddNt : 0, s.small ? 1 : 0, s.embed ? 1 : 0, f->errflag, nStream, 1);
+        }, k);
+        if (rc) return rc;
+    }
+    return EQF_OK;
+}
+
+// One launch per block column, fused: every tile workgroup solves the two panel blocks it needs itself; the downdate joins launch nbS
+template <typename T>
+int launchChainsFused(eqf_filter* f, const UpdateShape& s, const ChainArgs& cS, const ChainArgs& cE, const UpdArgs& a) {
+    for (int k = 0; k < std::max(s.nbS, s.nbE); ++k) {
+        const int dd = (s.embed && k == s.nbS) ? s.ddTiles : 0;
+        const int rc = profiled(f, dd ? EQF_PROF_CHOL_DD : EQF_PROF_CHOL_STEP, [&] {
+            const int grid = chainBlocks64(s.nbS, s.wtS, k, 0) + chainBlocks64(s.nbE, 1, k, 0);
+            hipLaunchKernelGGL((k_chol_step64<T, 0>), dim3(grid + dd, f->B), dim3(256), sizeof(Step64Lds), f->stream, cS, cE, a, k, dd ? s.ddNt : 0,
+                s.small ? 1 : 0, s.embed ? 1 : 0, f->errflag);
+        }, k);
+        if (rc) return rc;
+    }
+    return EQF_OK;
 }
 
 template <typename T>
@@ -746,309 +996,55 @@ int launchUpdateT(eqf_filter* f, const double* bearings, long long bearStride, c
     UpdArgs a = makeUpdArgs(f, bearings, bearStride, perm);
     f->csValid = false;  // (consumed)
     const int B = f->B;
-    // Factorisation kernels: k_chol_step64 / k_chol_resident (64-wide block columns, register-chained MFMA panel solves).  (The 32-wide
-    // family of round 1 -- k_chol_step<INVERSE>, k_update_reduce, a separate prep launch -- was dominated at every size measured and has
-    // been removed in round 3; the cross-checks of a factorisation are now the other launch shapes of the same mathematics -- resident
-    // vs per-column launches bitwise, fused vs split chain to rounding -- and the fp64 oracle of the tests.)
-    const int nb64S = roundUp(sDim(Nmax), kSB) / kSB, nb64E = roundUp(eDim(Nmax), kSB) / kSB;
-    const int wt64 = roundUp(yCols(Nmax), kSB) / kSB;
-    const int nblk64 = nb64S * nb64S + wt64 * nb64S + nb64E * nb64E + nb64E;
-    a.pad = kSB;
-    const int mp = roundUp(sDim(Nmax), a.pad), nep = roundUp(eDim(Nmax), a.pad);
-    const int nv = kLm0 + 3 * Nmax;
-    // prep
-    const int nvPad = roundUp(std::min(nv, kLm0 + 3 * kPrepLmChunk), 16);
-    const size_t perWave = size_t(2) * nvPad * sizeof(double);
-    int wpb = int(std::min<size_t>(4, (150 * 1024) / perWave));
-    if (wpb < 1) return EQF_ERR_CAPACITY;
-    const int lmBlocks = (mp / 2 + wpb - 1) / wpb, eBlocks = nep / kNB;
-    const size_t lds = perWave * wpb;
-    // (function attributes are per device: remembered per handle, not per process)
-    bool& attrSet = f->ldsAttrSet[0];
-    bool& attrSet64 = f->ldsAttrSet[1];
-    if (!attrSet) {
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_step64<float, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, int(sizeof(Step64Lds))));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_step64<double, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, int(sizeof(Step64Lds))));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_step64<float, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, int(sizeof(Step64Lds))));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_step64<double, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, int(sizeof(Step64Lds))));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_resident<float>), hipFuncAttributeMaxDynamicSharedMemorySize, int(sizeof(Step64Lds))));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_resident<double>), hipFuncAttributeMaxDynamicSharedMemorySize, int(sizeof(Step64Lds))));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_resident<double, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(sizeof(Step64Lds))));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_resident<double, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(sizeof(Step64Lds))));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_resident<double, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsRes2Bytes));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_resident<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(sizeof(Step64Lds))));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_resident<double, true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(sizeof(Step64Lds))));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_resident<float, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsRes2Bytes));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_resident<double, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsRes2Bytes));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_resident<float, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(sizeof(Step64Lds))));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_resident<double, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(sizeof(Step64Lds))));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_resident<float, true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsRes2Bytes));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_resident<double, true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsRes2Bytes));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_step64<float, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTailBytes));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chol_step64<double, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTailBytes));
-        attrSet = true;
-    }
-    // chains
+    UpdateShape s{};
+    int rc = allowUpdateLds(f);
+    if (!rc) rc = updateShape(f, Nmax, s);
+    if (!rc && s.resident) rc = buildRoles(f, Nmax, s.fold, s.front);
+    if (rc) return rc;
+    a.pad = kSB; a.eFromSigma = s.eFromSigma;
     ChainArgs cS{}, cE{};
     cS.g = a.g; cS.A = f->SA; cS.D = f->SL; cS.W = f->YW; cS.WO = f->YO;
     cS.ldA = f->ldS; cS.ldW = f->ldY; cS.strideA = f->strideS; cS.strideD = f->strideDS; cS.strideW = f->strideY;
-    cS.kind = 0;
+    cS.kind = 0; cS.nbMax = s.nbS; cS.wtMax = s.wtS;
     cE.g = a.g; cE.A = f->EA; cE.D = f->EL; cE.W = f->ZW; cE.WO = f->ZO;
     cE.ldA = f->ldE; cE.ldW = f->ldZ; cE.strideA = f->strideE; cE.strideD = f->strideDE; cE.strideW = f->strideZ;
-    cE.kind = 1;
+    cE.kind = 1; cE.nbMax = s.nbE; cE.wtMax = 1;
     f->updateEpoch = f->updateEpoch == 0x7fffffff ? 1 : f->updateEpoch + 1;
     cS.flags = f->dFlags; cS.strideF = 2 * f->flagStride; cS.epoch = f->updateEpoch;
     cE.flags = f->dFlags + f->flagStride; cE.strideF = 2 * f->flagStride; cE.epoch = f->updateEpoch;
-    if (!attrSet64) {
-#ifdef EQF_F64_STAMPS
-        const int prepLdsMax = 158 * 1024;  // (the instrumented build keeps factor64's stamps in 1 KB of static LDS)
-#else
-        const int prepLdsMax = 160 * 1024;
-#endif
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_prep64<float, false>), hipFuncAttributeMaxDynamicSharedMemorySize, prepLdsMax));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_prep64<double, false>), hipFuncAttributeMaxDynamicSharedMemorySize, prepLdsMax));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_prep64<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, prepLdsMax));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_prep64<double, true>), hipFuncAttributeMaxDynamicSharedMemorySize, prepLdsMax));
-        attrSet64 = true;
-    }
-    // ---- which shape the factorisation launches will have (decided here: the prep launch needs to know whether anybody reads EA's
-    // block column 0)
-    bool embed = nb64S < nb64E;
-    for (int b = 0; b < B && embed; ++b) {
-        const int Nb = int(f->ids[b].size());
-        if (Nb > 0 && roundUp(sDim(Nb), kSB) >= roundUp(eDim(Nb), kSB)) embed = false;
-    }
-    if (!f->cholEmbed) embed = false;
-    // (measured on the 256-CU part: 1500 workgroups = six per CU -- N = 200 from 8 filters on, N >= ~600)
-    const bool splitChain = f->cholSplit >= 0 ? f->cholSplit != 0 : (long long)nblk64 * B >= 6LL * std::max(f->numCUs, 1);
-    bool resident = false, residentFits = false, resPipeHeads = false, resOcc2 = false, resESigma = false;
-    int rc = EQF_OK;
-    bool fold = false;
-    if (embed && f->cholResident && f->cholSplit <= 0 && f->dReadyA) {
-        // co-residency of the whole grid by the occupancy calculation (one workgroup per CU with the 119 KB LDS image), not by
-        // the CU count alone: the in-kernel downdate waits for workgroups with HIGHER block indices while holding its CU
-        if (f->residentPerCU < 0) {
-            int nblk = 0;
-            HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, reinterpret_cast<const void*>(&k_chol_resident<T>), 256, sizeof(Step64Lds)));
-            f->residentPerCU = std::max(nblk, 0);
-        }
-        auto chainRoles = [](int nb, int wt) { return (nb - 1) + (nb - 1) * (nb - 2) / 2 + wt * nb; };
-        const int rolesAll = chainRoles(nb64S, wt64) + chainRoles(nb64E, 1);
-        residentFits = (long long)rolesAll * B <= (long long)f->residentPerCU * f->numCUs;
-        // A co-resident grid (one small filter: the latency case): the prep work -- residuals, C Sigma, S, the lift rows, the chains' first
-        // diagonal blocks -- runs as roles of the SAME launch (ResArgs::nPrep, role F0).  The E-chain's diagonal-factor chain, the critical
-        // path of the update, needs nothing of it (Sigma_e is Sigma[6:, 6:]: its tiles are read straight from Sigma) and starts at t = 0
-        // instead of behind a 12 us launch and a dispatch gap; the S-chain and the right-hand sides wait for the prep roles' flags.
-        fold = f->resFoldPrep && residentFits && std::is_same<T, double>::value && f->cholResident < 2 && f->resPipeHeads <= 0 && f->resOcc2 <= 0 &&
-               nb64E > 1 && f->dPrepFlags && lmBlocks + eBlocks <= f->nPrepCap && lds <= sizeof(Step64Lds);
-        // Round 5: the same on a grid LARGER than the chip (the PIPEH / OCC2 builds with the prep roles in front; filter index fastest, so the
-        // prep workgroups of all filters are dispatched first and wait for nobody).  Measured at N = 200 (profiles/r05_fold_batch.txt, steps/s,
-        // prep launch -> prep roles): 2 filters 113.7 k -> 118.6 k; 4: 210.2 -> 210.7 k; 8: 316 -> 321 k (the update launch grows by what the
-        // prep launch took: 166 -> 195 us -- the prep workgroups fill the chip first and the E-chains start behind them all the same); 16:
-        // 436 -> 419 k; 64: 500 -> 465 k.  With the E-chain's first dependency group IN FRONT of the prep roles (buildRoles' `front`,
-        // EQF_RES_FOLD_FRONT; profiles/r05_fold_front.txt): 4 filters 212 -> 219.6 k, 8 and 16 unchanged -- there the path prep -> S-chain ->
-        // right-hand sides -> downdate is as long as the E-chain's, and the prep work is on it wherever it runs.  So: while prep roles + chain
-        // roles together are at most four per CU (2 .. 4 filters of N = 200) -- round 6, behind the 8-landmark burst builder and this round's
-        // other launches (profiles/r06_fold_batch.txt, best of three, prep launch -> prep roles): 5 filters 234.0 -> 246.0 k, 6: 270.6 -> 283.7 k,
-        // 8: 340.4 -> 338.5 k, 10: 362.4 -> 357.0 k, 12: 397.5 -> 390.4 k -- so now up to SIX per CU (2 .. 6 filters of N = 200);
-        // EQF_RES_FOLD_PREP=3 forces it on every batch (the bitwise test does), = 2 keeps it to co-resident grids.
-        const bool foldBatch = (f->resFoldPrep == 1 || f->resFoldPrep == 3) && !residentFits && std::is_same<T, double>::value && f->cholResident < 2 &&
-                               nb64E > 1 && f->dPrepFlags && lmBlocks + eBlocks <= f->nPrepCap && lds <= (size_t)kLdsRes2Bytes &&
-                               (f->resFoldPrep == 3 || (long long)(lmBlocks + eBlocks + rolesAll) * B <= 6LL * f->numCUs);
-        fold = fold || foldBatch;
-        rc = buildRoles(f, Nmax, fold, foldBatch ? f->resFoldFront : 0);
-        if (rc) return rc;
-        // Beyond co-residency the grid is interleaved (filter index fastest: all filters advance together, group by group) and nothing
-        // waits for later workgroups.  Its workgroups mostly wait for hand-offs, so the chip carries several per CU without slowing the
-        // chains down; the downdate tiles are workgroups of their own at the end of the grid.  History of the switch-over (round 3, steps/s,
-        // per-column launches -> this): first up to 10 roles per CU (2 .. 16 filters of N = 200: 89 -> 107 k, 132 -> 202 k, 226 -> 298 k,
-        // 340 -> 373 k), then ONE filter up to ~26 roles per CU, whose per-column launches sit on the latency floor of the diagonal workgroup
-        // (N = 600: 11.7 k -> 19.7 k, N = 1000: 5.2 k -> 6.3 k), and finally:
-        // Since the build for two workgroups per CU (k_chol_resident's OCC2, late in round 3) the resident kernel wins at EVERY size measured
-        // -- 24 / 32 / 64 / 96 filters of N = 200: 386 -> 447 k, 410 -> 479 k, 453 -> 509 k, 478 -> 507 k steps/s; one filter of N = 1500 / 2000 /
-        // 3000 / 4000: 2.23 -> 2.85 k, 1053 -> 1335, 344 -> 406, 151 -> 174 -- so the default is "whenever its buffers exist"; the per-column
-        // launches remain for EQF_CHOL_RESIDENT=0 / [no switch since round 5] and for filters whose chains are equally long (a handful of landmarks).
-        const long long oversub = f->resOversub >= 0 ? f->resOversub : 1000000;
-        resident = f->cholResident >= 2 || residentFits || (long long)f->rolesCount * B <= oversub * f->numCUs;
-        // the builds of the kernel: row heads with the pipelined panel loop on grids larger than the chip (PIPEH), two workgroups per CU when
-        // the grid is many times the chip (OCC2)
-        resPipeHeads = f->resPipeHeads >= 0 ? f->resPipeHeads != 0 : !residentFits;
-        const double perCU = double(f->rolesCount) * B / std::max(f->numCUs, 1);
-        // (round 4, measured at N = 200: two per CU wins from 5 filters on -- 5 / 6 / 7 filters 217 -> 227 k, 242 -> 255 k, 270 -> 280 k steps/s -- and
-        // loses below: 4 filters 210 -> 195 k; one filter of N = 400, three roles per CU, 33.5 -> 32.5 k)
-        resOcc2 = resident && (f->resOcc2 >= 0 ? f->resOcc2 != 0 : (resPipeHeads && (perCU > 6.0 || (B >= 5 && perCU > 2.4))));
-        resESigma = resOcc2 && resPipeHeads && perCU > f->eSigmaMinPerCU;
-    }
-    a.eFromSigma = (!resident && splitChain && f->cholTail && f->eFromSigma && f->precision != EQF_PRECISION_F32) ? 1 : 0;
-    // (the OCC2 build reads the E-chain's tiles straight from Sigma: no copy in the prep launch; [no switch since round 5]: copied)
-    if (resESigma && f->eFromSigma && f->precision != EQF_PRECISION_F32) a.eFromSigma = 2;
-    fold = fold && resident;
-    if (fold) a.eFromSigma = 2;
-    // the downdate on the integer pipe (eqf_set_option "downdate_slices"): never inside the chain launches -- k_chol_resident runs without its
-    // downdate tiles, the per-column shapes without `embed` -- but as the tail launch below, for every launch shape
-    const int i8S = std::is_same<T, double>::value ? f->ddSlices : 0;
-    if (i8S && !resident) embed = false;
     // (round 5, measured and dropped: with the burst's operands in place, the landmark work as one LANE per landmark -- 128 per workgroup, the
     // stores from an LDS image -- instead of one wavefront: bit for bit the same and no faster.  Such a workgroup takes 21-31 us (33
     // uncoalesced loads per lane, then the stores) against 12.7 us for the 4-landmark ones, and a launch of 64 filters is three dispatch
     // rounds each as long as its longest workgroup: 63 -> 65 us; N = 1000 18 -> 82 us (one workgroup wrote all the padding rows).
     // profiles/r05_prep_stamps.txt)
-    if (!fold) rc = profiled(f, EQF_PROF_UPDATE_PREP, [&] {
+    if (!s.fold) rc = profiled(f, EQF_PROF_UPDATE_PREP, [&] {
         // the landmark waves + E-chain operand + two more workgroups per filter that factor the first diagonal block of each chain
         // straight from Sigma (one launch: measured never slower than a separate factor launch, 4..64 filters)
-        const bool occ2 = f->prepOcc2 >= 0 ? f->prepOcc2 != 0 : (B >= 4 && (long long)(lmBlocks + eBlocks + 2) * B > f->numCUs);
-        if (occ2)
-            hipLaunchKernelGGL((k_update_prep64<T, true>), dim3(lmBlocks + eBlocks + 2, B), dim3(256), std::max(lds, (size_t)kLdsFactorBytes), f->stream, a,
-                cS, cE, lmBlocks, eBlocks, wpb, nvPad);
-        else
-            hipLaunchKernelGGL((k_update_prep64<T, false>), dim3(lmBlocks + eBlocks + 2, B), dim3(256), std::max(lds, (size_t)kLdsFactorBytes), f->stream, a,
-                cS, cE, lmBlocks, eBlocks, wpb, nvPad);
+        const dim3 grid(s.lmBlocks + s.eBlocks + 2, B);
+        const size_t lds = std::max(s.prepLds, (size_t)kLdsFactorBytes);
+        if (s.occ2Prep) hipLaunchKernelGGL((k_update_prep64<T, true>), grid, dim3(256), lds, f->stream, a, cS, cE, s.lmBlocks, s.eBlocks, s.wpb, s.nvPad);
+        else hipLaunchKernelGGL((k_update_prep64<T, false>), grid, dim3(256), lds, f->stream, a, cS, cE, s.lmBlocks, s.eBlocks, s.wpb, s.nvPad);
     });
     if (rc) return rc;
-    // downdate tiling: 64x64 tiles when they fill the chip, 32x32 tiles (4x the workgroups) for a single small filter
-    const int nt64 = (nv + 63) / 64, nt32 = (nv + 31) / 32;
-    const bool small = (long long)nt64 * (nt64 + 1) / 2 * B < 2LL * std::max(f->numCUs, 1);
-    const int ddNt = small ? nt32 : nt64, ddTiles = ddNt * (ddNt + 1) / 2;
-    bool tailLaunch = true;  // downdate / finish as a launch of their own after the chains
-    {
-        cS.nbMax = nb64S; cS.wtMax = wt64;
-        cE.nbMax = nb64E; cE.wtMax = 1;
-        const int steps = std::max(nb64S, nb64E);
-        // The reductions ride along in the rhs workgroups; the downdate and the innovation lift ride along too when
-        // every filter's S-chain is shorter than its E-chain (always, except for a handful of landmarks): `embed`, above.
-        // Fused launches (each tile solves its own panel blocks) while a launch is bound by the serial diagonal chain;
-        // panel + update launches (every panel block solved once, 2 workgroups per CU) once it is bound by throughput:
-        // `splitChain`, above.
-        auto blocks = [&](int k, int phase) {
-            return chainBlocks64(cS.nbMax, cS.wtMax, k, phase) + chainBlocks64(cE.nbMax, cE.wtMax, k, phase);
-        };
-        // ONE launch for the whole factorisation part while its grid fits the chip (every workgroup resident: one small
-        // filter, the latency case); the role table's block order keeps the ROLES deadlock-free even when it does not, and the
-        // downdate -- the one wait for later workgroups -- then runs as a launch of its own: `resident` / `residentFits`, above.
-        if (resident) {
-            ResArgs ra{};
-            ra.c0 = cS; ra.c1 = cE; ra.a = a;
-            ra.roles = f->dRoles;
-            ra.readyA = f->dReadyA; ra.readyY = f->dReadyY; ra.counters = f->dResCounters;
-            ra.gammaPart = f->dGammaPart; ra.g11Part = f->dG11Part;
-            ra.nbCap = f->nbCap; ra.wtCap = f->wtCap;
-            ra.stageFlags = f->resStaged ? f->dStageFlags : nullptr;
-            ra.eFromSigma = a.eFromSigma == 2 ? 1 : 0;
-            if (fold) {
-                ra.waitD0 = 3;
-                ra.nPrep = lmBlocks + eBlocks;
-                ra.nFront = f->rolesFront;
-                ra.lmBlocks = lmBlocks;
-                ra.prepWpb = wpb;
-                ra.prepNvPad = nvPad;
-                ra.prepFlags = f->dPrepFlags;
-                ra.nPrepCap = f->nPrepCap;
-            }
-            // 64 x 64 downdate tiles: a tile costs the same 14 dependent chunk fetches whatever its size, and there are enough
-            // finished workgroups to take one each
-            // (a grid larger than what is co-resident must not wait for later workgroups while holding CUs: no-wait mode, see the kernel)
-            ra.ddNt = (fold && !resPipeHeads) ? nt32 : nt64;  // (the FOLD build without PIPEH -- co-resident grids: 32 x 32 tiles, see the kernel)
-            // (the downdate tiles are workgroups of their own behind the roles, also when the whole grid is co-resident: nothing in the kernel
-            // waits for a higher block index)
-            ra.nRoles = f->rolesCount;
-            ra.errflag = f->errflag;
-            const int ddGrid = i8S ? 0 : ra.ddNt * (ra.ddNt + 1) / 2;  // downdate tiles as workgroups of their own behind the roles
-            rc = profiled(f, EQF_PROF_CHOL_RESIDENT, [&] {
-                // (row heads with the pipelined panel loop only on a grid larger than the chip: see the kernel's PIPEH)
-                const bool pipeHeads = resPipeHeads;
-                // (two workgroups per CU when the grid is many times the chip: see the kernel's OCC2)
-                const bool occ2 = resOcc2;
-                ra.nDdTiles = ddGrid;
-                const int perFilter = ra.nPrep + f->rolesCount + ddGrid;
-                ra.rolesPerRow = std::min(perFilter, 32768);
-                const dim3 rg(B * ra.rolesPerRow, (perFilter + ra.rolesPerRow - 1) / ra.rolesPerRow);
-                // Arrival tickets (ResArgs::ticket, the TICKET build): eqf_debug_option "res_tickets" 0 (default) = never, 2 = on every grid larger
-                // than the chip that has its prep launch in front (not the FOLD build of 2 - 4 filters), 1 = where they cost least -- grids of at
-                // least six times the resident slots (16+ filters of N = 200, N >= ~700), whose workgroups are dispatched long before they are needed;
-                // on lightly oversubscribed grids a role is dispatched just in time and the ticket's round trip (~2 us) lands on the critical
-                // path at every dependency hop: +12.8 / +7.4 / +14.6 / +3.2 / +8.6 us per update at 2 / 4 / 6 / 8 / 12 filters, +1.1 % at 64, +0.7 %
-                // at N = 1000 in one binary (profiles/r06_tickets_ab.txt), 2.3 % against round 5's library on the same box.  OFF by default: the
-                // block index with the time-outs as its guard, as in rounds 3 - 5 -- the guarantee is there for whoever wants to pay for it.
-                const long long slots = (long long)std::max(f->numCUs, 1) * (occ2 ? 2 : 1);
-                const bool tickets = f->resTickets == 2 || (f->resTickets == 1 && (long long)rg.x * rg.y >= 6 * slots);
-                const bool ticketBuild = pipeHeads && !fold && tickets && f->dTicket;
-                if (ticketBuild) {  // (every workgroup of the launch draws exactly one ticket, padding workgroups included)
-                    ra.ticket = f->dTicket;
-                    ra.ticketBase = f->ticketBase;
-                    f->ticketBase += ra.rolesPerRow * rg.y;  // (per filter)
-                }
-                if (ticketBuild && occ2) hipLaunchKernelGGL((k_chol_resident<T, true, true, false, true>), rg, dim3(256), kLdsRes2Bytes, f->stream, ra);
-                else if (ticketBuild) hipLaunchKernelGGL((k_chol_resident<T, true, false, false, true>), rg, dim3(256), sizeof(Step64Lds), f->stream, ra);
-                else if (fold && pipeHeads) launchFold<T>(rg, f->stream, ra, true, occ2);
-                else if (pipeHeads && occ2) hipLaunchKernelGGL((k_chol_resident<T, true, true>), rg, dim3(256), kLdsRes2Bytes, f->stream, ra);
-                else if (pipeHeads) hipLaunchKernelGGL((k_chol_resident<T, true>), rg, dim3(256), sizeof(Step64Lds), f->stream, ra);
-                else if (fold) launchFold<T>(rg, f->stream, ra, false, false);
-                else hipLaunchKernelGGL((k_chol_resident<T, false>), rg, dim3(256), sizeof(Step64Lds), f->stream, ra);
-            });
-            if (rc) return rc;
-        } else if (splitChain && f->cholTail) {
-            // one launch per block column: the panel launch of column 0, then update launches that also solve column k+1
-            // (k_chol_step64<T, 3>); the S-chain's right-hand sides are complete after launch nb64S - 2, the downdate joins
-            // launch nb64S - 1 (or runs on its own below when there is none)
-            rc = profiled(f, EQF_PROF_CHOL_STEP, [&] {
-                hipLaunchKernelGGL((k_chol_step64<T, 1>), dim3(blocks(0, 1), B), dim3(256), sizeof(Step64Lds), f->stream, cS, cE, a, 0, 0, 0,
-                    embed ? 1 : 0, f->errflag);
-            }, 1000);
-            if (rc) return rc;
-            // (A downdate with 128 x 128 tiles -- half the Y traffic per flop -- as a launch of its own was tried here and measured
-            // SLOWER: 788 vs 516 us for 64 filters, 48 vs 29.5 ms at N = 4000; 352 registers leave one wave per SIMD.  The 64-wide
-            // tiles are not bandwidth-bound: they run at half the fp64 MFMA peak in executed flops.)
-            bool ddDone = false;
-            for (int k = 0; k + 1 < steps; ++k) {
-                const int dd = (embed && k == nb64S - 1) ? ddTiles : 0;
-                if (dd) ddDone = true;
-                // workgroups per filter: 2 diagonal + the tails of block column k+1 + nStream streams over the pure updates
-                // (about two per CU over the whole launch; four for ONE large filter: N = 4000 150 -> 154 steps/s) + the downdate tiles; see step3Counts
-                int tS, uS, tE, uE;
-                step3Counts(cS.nbMax, cS.wtMax, k, &tS, &uS);
-                step3Counts(cE.nbMax, cE.wtMax, k, &tE, &uE);
-                const int nStream = f->cholStreams > 0 ? std::min(f->cholStreams, std::max(uS + uE, 1))
-                                                       : std::min(uS + uE, std::max(1, ((B == 1 ? 4 : 2) * f->numCUs + B - 1) / B));
-                const int tailsLast = f->cholOrder >= 0 ? f->cholOrder : 1;
-                rc = profiled(f, dd ? EQF_PROF_CHOL_DD : EQF_PROF_CHOL_STEP, [&] {
-                    hipLaunchKernelGGL((k_chol_step64<T, 3>), dim3(2 + tS + tE + nStream + dd, B), dim3(256), kLdsTailBytes, f->stream, cS, cE, a,
-                        k, dd ? ddNt : 0, small ? 1 : 0, embed ? 1 : 0, f->errflag, nStream, tailsLast);
-                }, k);
-                if (rc) return rc;
-            }
-            if (embed && !ddDone) embed = false;  // (cannot happen while nb64S < nb64E: kept for safety -> tail launch below)
-        } else
-        for (int k = 0; k < steps; ++k) {
-            {
-                const int dd = (embed && k == nb64S) ? ddTiles : 0;
-                rc = profiled(f, dd ? EQF_PROF_CHOL_DD : EQF_PROF_CHOL_STEP, [&] {
-                    hipLaunchKernelGGL((k_chol_step64<T, 0>), dim3(blocks(k, 0) + dd, B), dim3(256), sizeof(Step64Lds), f->stream, cS, cE, a, k,
-                        dd ? ddNt : 0, small ? 1 : 0, embed ? 1 : 0, f->errflag);
-                }, k);
-            }
-            if (rc) return rc;
-        }
-        tailLaunch = !embed || i8S;
-    }
-    if (tailLaunch && i8S) {
-        // split + symmetric product on the integer pipe; the innovation lift rides along in the split launch unless k_chol_resident's roles
-        // ran it (they do whenever the resident kernel runs: `embed`)
+    rc = s.resident ? launchChainsResident<T>(f, s, cS, cE, a) : s.splitChain ? launchChainsSplit<T>(f, s, cS, cE, a) : launchChainsFused<T>(f, s, cS, cE, a);
+    if (rc) return rc;
+    if (s.tailLaunch && s.i8Slices) {
+        // split + symmetric product on the integer pipe; the innovation lift rides along in the split launch (`tailLift`)
         I8DdArgs ia{};
         ia.Y = a.YO; ia.ldY = a.ldY; ia.strideY = a.strideY;
         ia.Sin = static_cast<const double*>(a.Sin); ia.Sout = static_cast<double*>(a.Sout); ia.ld = a.ld; ia.sigmaStride = a.sigmaStride;
         ia.g = a.g; ia.dims = nullptr; ia.pad = a.pad; ia.skipCol = 11;
         ia.ws = f->dI8Ws; ia.wsStride = f->i8WsStride; ia.expo = f->dI8Expo; ia.expoStride = i8ddExpoWords(kLm0 + 3 * f->cap);
-        ia.B = B; ia.nt = (nv + 63) / 64;
-        rc = profiled(f, EQF_PROF_DOWNDATE, [&] { launchI8Dd(i8S, ia, resident ? nullptr : &a, (nv + 31) / 32, f->stream); });
-        if (rc) return rc;
-    } else if (tailLaunch) {
+        ia.B = B; ia.nt = (s.nv + 63) / 64;
+        rc = profiled(f, EQF_PROF_DOWNDATE, [&] { launchI8Dd(s.i8Slices, ia, s.tailLift ? &a : nullptr, (s.nv + 31) / 32, f->stream); });
+    } else if (s.tailLaunch) {
         // the last workgroup of the launch runs the (independent) innovation-lift / group-update part
         rc = profiled(f, EQF_PROF_DOWNDATE, [&] {
-            if (small) hipLaunchKernelGGL((k_downdate<T, 32>), dim3(ddTiles + 1, B), dim3(256), (downdateLdsBytes<T, 32>()), f->stream, a, nt32, 1);
-            else hipLaunchKernelGGL((k_downdate<T, 64>), dim3(ddTiles + 1, B), dim3(256), (downdateLdsBytes<T, 64>()), f->stream, a, nt64, 1);
+            if (s.small) hipLaunchKernelGGL((k_downdate<T, 32>), dim3(s.ddTiles + 1, B), dim3(256), (downdateLdsBytes<T, 32>()), f->stream, a, s.ddNt, 1);
+            else hipLaunchKernelGGL((k_downdate<T, 64>), dim3(s.ddTiles + 1, B), dim3(256), (downdateLdsBytes<T, 64>()), f->stream, a, s.ddNt, 1);
         });
-        if (rc) return rc;
     }
+    if (rc) return rc;
     if (f->innovStats && std::is_same<T, double>::value) {
         // (a tail launch of its own, only with the option on: the update's other launches are what they are without it)
         InnovArgs na{};

@@ -120,8 +120,7 @@ EQF_DI void chainDims64(const ChainArgs& ch, int N, int* nb, int* wt) {
 // of the matrix -- block rows / columns K+1.. -- so late launches do not spawn thousands of workgroups that exit at once.
 //   phase 0 (fused):  rem x rem A tiles (lower triangle used) + wt x (rem + 1) rhs tiles (column K solves, K+1.. update)
 //   phase 1 (panel):  rem A blocks (R, K)                    + wt rhs tiles (column K)
-//   phase 2 (update): rem x rem A tiles                      + wt x rem rhs tiles
-//   phase 3 (update + solve of block column K+1 in the same launch): as phase 2
+//   phase 3 (update + solve of block column K+1 in the same launch): rem x rem A tiles + wt x rem rhs tiles
 __host__ __device__ inline int chainBlocks64(int nbMax, int wtMax, int K, int phase) {
     const int rem = nbMax - K - 1;
     if (rem < 0) return 0;
@@ -680,10 +679,10 @@ inline __global__ __launch_bounds__(256) void k_factor_first64(ChainArgs c0, Cha
 //
 // PHASE 0: fused launch (above): every tile workgroup solves the two panel blocks it needs itself -- right when a launch
 //          is bound by the serial diagonal chain (one / a few small filters).
-// PHASE 1 + PHASE 2: the split chain for throughput (many tiles per launch): a panel launch solves every block of column
-//          K ONCE, in place (A_RK <- L_RK, Y_K -> WO), an update launch then only multiplies: no redundant solves
-//          (2.25x fewer MFMAs per tile) and the 77 KB LDS layout lets two workgroups share a CU.
-// PHASE 3: an update launch that ALSO solves block column K+1 (the next panel launch folded in: one launch per block column
+// PHASE 1: the panel launch that opens the split chain for throughput (many tiles per launch): it solves every block of
+//          column 0 ONCE, in place (A_R0 <- L_R0, Y_0 -> WO); the launches behind it only multiply by solved panel blocks: no
+//          redundant solves (2.25x fewer MFMAs per tile) and an LDS layout that lets two workgroups share a CU.
+// PHASE 3: an update launch that ALSO solves block column K+1 (a panel launch folded in: one launch per block column
 //          instead of two).  The workgroups of column K+1 keep their freshly updated tile in registers, wait INSIDE the
 //          launch for the diagonal workgroup to publish D[K+1] (eqf_handoff.hpp: write-through record + epoch flag, 2.6 us
 //          for the 40 KB record), then solve in place.  Only those (nb - K - 2 + wt) workgroups per chain wait, and the
@@ -886,7 +885,7 @@ struct CholWgStamp {
 };
 #endif
 template <typename T, int PHASE>
-__global__ __launch_bounds__(256, (PHASE == 2 || PHASE == 3) ? 2 : 1) void k_chol_step64(ChainArgs c0, ChainArgs c1, UpdArgs a, int K, int ddNt, int ddSmall,
+__global__ __launch_bounds__(256, PHASE == 3 ? 2 : 1) void k_chol_step64(ChainArgs c0, ChainArgs c1, UpdArgs a, int K, int ddNt, int ddSmall,
     int embedFinish, int* errflag, int nStream = 0, int tailsLast = 0) {
 #ifdef EQF_CHOL_WG_STAMPS
     CholWgStamp wgStamp(K);
@@ -1025,8 +1024,8 @@ __global__ __launch_bounds__(256, (PHASE == 2 || PHASE == 3) ? 2 : 1) void k_cho
     const int ldA = ch.ldA, ldW = ch.ldW;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 
-    constexpr bool UPD = PHASE == 2 || PHASE == 3;  // update launches of the split chain: panel blocks arrive solved
-    const Lds64 s = PHASE == 3 ? ldsTail(smem64) : (PHASE == 2 ? ldsUpdate(smem64) : ldsFull(smem64));
+    constexpr bool UPD = PHASE == 3;  // update launches of the split chain: panel blocks arrive solved
+    const Lds64 s = PHASE == 3 ? ldsTail(smem64) : ldsFull(smem64);
     int bad = 0;
 #ifdef EQF_CHOL_WG_STAMPS
     if (threadIdx.x == 0 && blockIdx.y == 0 && K < 16 && blockIdx.x < 256) {

@@ -268,16 +268,16 @@ EQF_DI void stepGlobal(const Glob& G, Glob* out, const ImuRec& r, const Args& a,
     }
 }
 
-// PRE = false: fused kernel (single small filter: one launch per step, scalar chain on waves 0..2).
-// PRE = true : streaming kernel of the split path; the blocks, the group step and the scalar state were produced by
-//              k_build_blocks, so this instantiation carries no fp64 scalar chain (few registers, high occupancy).
+// The fused kernel (single small filter: one launch per step, scalar chain on waves 0..2).  The split path for throughput-bound sizes is
+// k_build_blocks (the blocks, the group step and the scalar state) followed by k_riccati_stream, below: no fp64 scalar chain in the
+// streaming kernel (few registers, high occupancy).
 #ifdef EQF_PROP_STAMPS
 __device__ long long g_propStamps[4][8];
 #define EQF_PSTAMP(i) do { if ((tid & 63) == 0 && (blockIdx.x == a.NT * a.NT || blockIdx.x == a.NT + 1)) g_propStamps[(blockIdx.x == a.NT + 1 ? 2 : 0) + ((tid >> 6) == 2 ? 1 : 0)][i] = __builtin_readcyclecounter(); } while (0)
 #else
 #define EQF_PSTAMP(i) do { } while (0)
 #endif
-template <typename T, bool PRE>
+template <typename T>
 __global__ __launch_bounds__(256) void k_propagate(PropArgs a) {
     const int tid = threadIdx.x;
     EQF_PSTAMP(0);
@@ -285,10 +285,10 @@ __global__ __launch_bounds__(256) void k_propagate(PropArgs a) {
     const bool isExtra = (int)blockIdx.x == a.NT * a.NT;  // the base-block workgroup
     // Workgroups after the tiles carry no tile (index relative to NT^2):
     //   0              the 11 x 11 base block
-    //   1              the scalar state (X.A, X.w, ZOH bookkeeping)                      [fused kernel only]
+    //   1              the scalar state (X.A, X.w, ZOH bookkeeping)
     //   2 .. 2+NT-1    "row tails":    Sigma'_Ib of one landmark group (they run that group's linearisation chain, no tile math)
     //   2+NT .. 2+2NT-1 "column tails": Sigma'_bJ of one landmark group
-    //   2+2NT ..       the group step Q_i <- Q_i lift_i of 64 landmarks each              [fused kernel only]
+    //   2+2NT ..       the group step Q_i <- Q_i lift_i of 64 landmarks each
     // Measured per-workgroup durations (N = 200, cycles): tiles 15.5 k; with the tails inside the tiles of the last tile
     // row / column that corner tile took 21.4 k, one workgroup doing both tails of a group 19.6 k, base block + scalar
     // state in one workgroup 18.4 k, the landmark group step inside the diagonal tiles held their barrier up by 3 k.
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256) void k_propagate(PropArgs a) {
     const bool isColTail = rel >= 2 + a.NT && rel < 2 + 2 * a.NT;
     const bool isTail = isRowTail || isColTail;
     const int tailG = isRowTail ? rel - 2 : rel - 2 - a.NT;
-    const bool isLmWg = !PRE && rel >= 2 + 2 * a.NT;
+    const bool isLmWg = rel >= 2 + 2 * a.NT;
     const int ti = isTail ? tailG : (rel >= 0 ? 0 : blockIdx.x / a.NT);
     const int tj = isTail ? tailG : (rel >= 0 ? 0 : blockIdx.x % a.NT);
     const int cap = a.cap, ld = a.ld;
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(256) void k_propagate(PropArgs a) {
         }
         return;
     }
-    if (!PRE && wv == 1 && riccati && ln < 32 && !isExtra && !isState) {
+    if (wv == 1 && riccati && ln < 32 && !isExtra && !isState) {
         // ---- wave 1: the Lw blocks of the tile's landmarks -- they need nothing of the linearisation but T, so they are
         // built beside wave 0's chain instead of at its end
         const int i = (ln < 16) ? I0 + ln : J0 + ln - 16;
@@ -417,7 +417,7 @@ __global__ __launch_bounds__(256) void k_propagate(PropArgs a) {
     }
     if (isState) {
         // ---- scalar state.  Word-parallel copy in -> out, then one lane patches the changed fields
-        if (!PRE && wv == 0) {
+        if (wv == 0) {
             static_assert(sizeof(Glob) % 8 == 0 && sizeof(Glob) / 8 <= 64, "Glob copy is one word per lane");
             const double* src = reinterpret_cast<const double*>(&G);
             double* dst = reinterpret_cast<double*>(a.gout + b);
@@ -432,19 +432,6 @@ __global__ __launch_bounds__(256) void k_propagate(PropArgs a) {
         }
         return;
     }
-    if (PRE) {
-        if (riccati && tid < 32 && !isExtra) {
-            const int i = (tid < 16) ? I0 + tid : J0 + tid - 16;
-            const T* bp = static_cast<const T*>(a.blk) + ((long long)b * cap + i) * kBlkRec;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                sD[tid][k] = (i < N) ? bp[k] : (T)0;
-                sLw[tid][k] = (i < N) ? bp[9 + k] : (T)0;
-                sLv[tid][k] = (i < N) ? bp[18 + k] : (T)0;
-            }
-        }
-        if (riccati && tid == 32) sC = a.blkCommon[b];
-    } else {
     if (wv == 0 && riccati) {
         // ---- wave 0: common quantities of the linearisation + this tile's per-landmark blocks
         StepCommon c;
@@ -478,7 +465,6 @@ __global__ __launch_bounds__(256) void k_propagate(PropArgs a) {
                 sC.RA[k] = c.RA.a[k];
             }
         }
-    }
     }
     if (!riccati && a.sigmaExternal && step && a.doRiccati) {
         if (bad && a.errflag) atomicOr(a.errflag, 1);
