@@ -57,6 +57,12 @@ class InnovationStats(C.Structure):
     _fields_ = [("nis", C.c_double), ("logdet_S", C.c_double), ("loglik", C.c_double), ("dof", C.c_int), ("valid", C.c_int)]
 
 
+class SigmaStats(C.Structure):
+    """eqf_sigma_stats (include/eqf_vio_amd.h)."""
+
+    _fields_ = [("logdet", C.c_double), ("min_pivot", C.c_double), ("dof", C.c_int), ("info", C.c_int)]
+
+
 _lib = None
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -65,7 +71,7 @@ EXPORTED_SYMBOLS = [
     "eqf_settings_default", "eqf_create", "eqf_destroy", "eqf_reset", "eqf_process_imu", "eqf_process_vision",
     "eqf_stream_upload", "eqf_stream_imu", "eqf_stream_vision", "eqf_synchronize", "eqf_get_time", "eqf_num_landmarks",
     "eqf_get_ids", "eqf_get_state_estimate", "eqf_get_origin", "eqf_get_group", "eqf_get_bias", "eqf_get_sigma",
-    "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats",
+    "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
     "eqf_set_sigma", "eqf_set_state", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
     "eqf_tiled_create", "eqf_tiled_destroy", "eqf_tiled_set_stream", "eqf_tiled_set_geometry", "eqf_tiled_propagate", "eqf_tiled_add_landmarks",
@@ -125,6 +131,8 @@ def lib():
             L.eqf_get_local_jacobian.argtypes = [vp, C.c_int, _dp, _dp, _dp]
             L.eqf_debug_sigma_local_all.argtypes = [vp]
             L.eqf_get_innovation_stats.argtypes = [vp, C.c_int, C.POINTER(InnovationStats), _dp]
+        if hasattr(L, "eqf_get_nees"):
+            L.eqf_get_nees.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, C.POINTER(SigmaStats)]
         L.eqf_get_last_update.argtypes = [vp, C.c_int, _dp, _dp, _dp]
         L.eqf_set_state.argtypes = [vp, C.c_int, C.c_int, _ip] + [_dp] * 11 + [C.c_int, C.c_double, _dp, _dp, C.c_double, C.c_int]
         L.eqf_get_integrator.argtypes = [vp, C.c_int, _dp, _dp, _dp, _ip]
@@ -416,6 +424,31 @@ class FilterBatch:
         st, lm = InnovationStats(), np.zeros(max(N, 1))
         _check(lib().eqf_get_innovation_stats(self._h, b, C.byref(st), _p(lm)), "eqf_get_innovation_stats")
         return dict(nis=st.nis, logdet_S=st.logdet_S, loglik=st.loglik, dof=st.dof, valid=bool(st.valid), nis_lm=lm[:N] if st.valid else np.zeros(0))
+
+    def nees(self, err=None, local=True, first=0):
+        """Joint NEES e^T A^-1 e, log det A and the definiteness of A for EVERY filter of the handle in one call, A the trailing principal
+        submatrix from reference index `first` (0 | 6 | 11) of sigma_local() (local) or sigma(), factored on the device
+        (include/eqf_vio_amd.h: eqf_get_nees).  err: array (B, nrhs, n_max) or a list of per-filter arrays (nrhs, n_b) in the reference's
+        index map, nrhs <= 16; None: the statistics only.  Returns a dict with nees (B, nrhs), logdet, min_pivot, dof, info (B,)."""
+        B = self.B
+        nrhs, lde, E = 0, 0, None
+        if err is not None:
+            if isinstance(err, np.ndarray) and err.ndim == 3:
+                E = np.ascontiguousarray(err, dtype=np.float64)
+                assert E.shape[0] == B
+            else:
+                rows = [np.atleast_2d(np.asarray(e, dtype=np.float64)) for e in err]
+                assert len(rows) == B and all(r.shape[0] == rows[0].shape[0] for r in rows)
+                E = np.zeros((B, rows[0].shape[0], max(max(r.shape[1] for r in rows), 1)))
+                for b, r in enumerate(rows):
+                    E[b, :, : r.shape[1]] = r
+            nrhs, lde = int(E.shape[1]), int(E.shape[2])
+        out = np.zeros((B, max(nrhs, 1)))
+        st = (SigmaStats * B)()
+        _check(lib().eqf_get_nees(self._h, int(bool(local)), int(first), nrhs, _p(E) if nrhs else None, lde, _p(out) if nrhs else None, st),
+               "eqf_get_nees")
+        return dict(nees=out[:, :nrhs], logdet=np.array([s.logdet for s in st]), min_pivot=np.array([s.min_pivot for s in st]),
+                    dof=np.array([s.dof for s in st], dtype=np.int32), info=np.array([s.info for s in st], dtype=np.int32))
 
     def debug_sigma_local_all(self):
         """k_sigma_local for every filter of the handle in one launch, nothing copied (include/eqf_vio_amd_debug.h)."""

@@ -8,6 +8,9 @@ to first order eps_loc = J eps with the block-diagonal J of local_jacobian_block
   local_jacobian_blocks(origin, group)   the J blocks (the device builds the same ones: FilterBatch.local_jacobian)
   local_error(estimate, truth, ...)      eps_loc for gravity direction, velocity and landmarks, plus the bias difference
   nees_marginal(marginals, error)        navigation-state NEES (11 or 5 dof) and per-landmark NEES (3 dof), O(N)
+  error_vector(error)                    local_error's dict flattened into Sigma's index map
+  nees_joint(Sigma, e, first)            the joint NEES e^T A^-1 e, log det A and the smallest pivot over the whole state or a trailing part of
+                                         it -- the host counterpart of FilterBatch.nees (include/eqf_vio_amd.h: eqf_get_nees)
 
 `origin`, `group`, `estimate` are the dicts of FilterBatch.origin() / group() / state_estimate(): quaternions (w, x, y, z), Eigen semantics.
 """
@@ -165,3 +168,30 @@ def nees_marginal(marginals, error, with_bias=True):
     el = np.asarray(error["lm"], dtype=float).reshape(-1, 3)
     lm = np.array([el[i] @ np.linalg.solve(P[i], el[i]) for i in range(len(el))])
     return dict(nav=nav, nav_dof=len(e), lm=lm, lm_dof=3)
+
+
+def error_vector(error, with_bias=True):
+    """local_error's dict as one vector in the reference's index map: [0,6) bias, [6,8) gravity direction, [8,11) velocity, then the
+    landmarks (11 + 3N,); without the bias the first six entries are zero (use first=6 with nees_joint / FilterBatch.nees)."""
+    b = np.asarray(error["bias"], dtype=float) if with_bias else np.zeros(6)
+    return np.concatenate([b, error["gravity"], error["velocity"], np.asarray(error["lm"], dtype=float).reshape(-1)])
+
+
+def nees_joint(Sigma, e, first=0):
+    """Joint NEES over the trailing principal submatrix A = Sigma[first:, first:] (first = 0 whole state, 6 without the bias, 11 landmarks
+    only): numpy Cholesky A = L L^T of the LOWER triangle, z = L^-1 e.  e: (n,) or (nrhs, n) in Sigma's index map (entries below `first`
+    are ignored).  Returns dict(nees (scalar or (nrhs,)), logdet = 2 sum log L_kk, min_pivot = min L_kk^2, dof); an empty A gives
+    nees 0, logdet 0, min_pivot inf.  Raises numpy.linalg.LinAlgError if A is not positive definite."""
+    S = np.asarray(Sigma, dtype=float)
+    A = np.tril(S[first:, first:])
+    A = A + np.tril(A, -1).T
+    ev = np.asarray(e, dtype=float)
+    E = np.atleast_2d(ev)[:, first:]
+    if A.shape[0] == 0:
+        nees, logdet, mp = np.zeros(E.shape[0]), 0.0, np.inf
+    else:
+        L = np.linalg.cholesky(A)
+        d = np.diag(L)
+        z = np.linalg.solve(L, E.T)
+        nees, logdet, mp = np.sum(z * z, axis=0), 2.0 * float(np.sum(np.log(d))), float(np.min(d * d))
+    return dict(nees=float(nees[0]) if ev.ndim == 1 else nees, logdet=logdet, min_pivot=mp, dof=A.shape[0])

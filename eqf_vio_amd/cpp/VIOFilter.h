@@ -256,6 +256,23 @@ class VIOFilter {
         st.nis_lm.resize(st.valid ? size_t(N) : 0);
         return st;
     }
+    // Joint NEES err^T A^-1 err with log det A, the smallest pivot and the definiteness word (eqf_get_nees): A = the covariance in the
+    // coordinates of the estimate (local) or of the origin, from reference index `first` (0 whole state | 6 without the bias | 11 landmarks
+    // only) on; err has 11 + 3 N entries in Sigma's index map (those below `first` are ignored).  A matrix that is not positive definite is
+    // reported in `info`, not thrown.
+    struct StateNEES : eqf_sigma_stats {
+        double nees = 0.0;
+    };
+    template <typename Vec>
+    StateNEES stateNEES(const Vec& err, bool local = true, int first = 0) const {
+        StateNEES st;
+        const int n = 11 + 3 * eqf_num_landmarks(handle_.get(), 0);
+        if (int(err.size()) < n) throw std::invalid_argument("stateNEES: err needs 11 + 3 N entries");
+        std::vector<double> e(size_t(n), 0.0);
+        for (int i = 0; i < n; ++i) e[i] = err[i];
+        check(eqf_get_nees(handle_.get(), local ? 1 : 0, first, 1, e.data(), n, &st.nees, &st), "eqf_get_nees");
+        return st;
+    }
     int lastStatus() const { return lastStatus_; }  // EQF_SKIPPED_* where the reference returns early
     eqf_filter* handle() const { return handle_.get(); }
 

@@ -1,6 +1,6 @@
 // Minimal C++ caller of the facade, shaped like the reference's offline runner (eqf_vio/src/main.cpp:111-170):
 // events are interleaved by "imu.stamp < meas.stamp", the state is read after every vision call.
-// Usage: eqf_example <N landmarks> <frames> [aux | level | init | local]  -- runs a small synthetic sequence and prints the final
+// Usage: eqf_example <N landmarks> <frames> [aux | level | init | local | nees]  -- runs a small synthetic sequence and prints the final
 // pose and |Sigma|_F.  With "aux" the filter starts from AuxiliaryFilterData + setInertialPoints (VIOFilter.cpp:51-58,
 // 74-118) instead of the gravity alignment at the first IMU sample; with "init" from an explicit initialiseFromIMUData
 // call (VIOFilter.cpp:133-144; same result as the lazy one).  With "level" the vehicle rests level: the reference's gravity
@@ -9,6 +9,8 @@
 // With "local" the innovation statistics are switched on and, after the last frame, two more lines follow with every value as a
 // hexadecimal float (bit-exact): "innovation" nis logdet_S loglik dof nis_lm[N], and "sigma_local" n and the n x n covariance in the
 // coordinates of the estimate (VIOFilter::stateCovarianceLocal).
+// With "nees", after the last frame, one line per (local, first) in {1, 0} x {0, 6, 11} of VIOFilter::stateNEES for the error vector
+// e_i = 0.01 sin(0.9 i + 0.3): "nees" local first dof info, then nees logdet min_pivot as hexadecimal floats.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -30,6 +32,7 @@ int main(int argc, char** argv) {
     const bool level = argc > 3 && std::string(argv[3]) == "level";
     const bool init = argc > 3 && std::string(argv[3]) == "init";
     const bool local = argc > 3 && std::string(argv[3]) == "local";
+    const bool nees = argc > 3 && std::string(argv[3]) == "nees";
     std::vector<Vector3d> lm(N);
     for (int i = 0; i < N; ++i) lm[i] = {2 * std::sin(1.3 * i), 2 * std::cos(0.7 * i), 5 + std::sin(0.37 * i)};
     AuxiliaryFilterData ad;
@@ -94,6 +97,15 @@ int main(int argc, char** argv) {
                 std::printf("\nsigma_local %d", Sl.n);
                 for (double v : Sl.data) std::printf(" %a", v);
                 std::printf("\n");
+            }
+            if (nees) {
+                std::vector<double> e(size_t(S.n));
+                for (int i = 0; i < S.n; ++i) e[i] = 0.01 * std::sin(0.9 * i + 0.3);
+                for (int loc = 1; loc >= 0; --loc)
+                    for (int first : {0, 6, 11}) {
+                        const VIOFilter::StateNEES r = filter.stateNEES(e, loc != 0, first);
+                        std::printf("nees %d %d %d %d %a %a %a\n", loc, first, r.dof, r.info, r.nees, r.logdet, r.min_pivot);
+                    }
             }
         }
     }

@@ -24,6 +24,7 @@
 #include "eqf_i8.hpp"
 #include "eqf_local.hpp"
 #include "eqf_innov.hpp"
+#include "eqf_nees.hpp"
 
 using namespace eqf;
 
@@ -205,6 +206,11 @@ struct eqf_filter {
     // covariance in the coordinates of the estimate (eqf_local.hpp): the J blocks [B][kJacHead + 9 cap] and an image of Sigma's size, both
     // allocated by the first getter that needs them
     double *dJac = nullptr, *dSigmaLoc = nullptr;
+    // joint NEES / log det (eqf_nees.hpp; eqf_get_nees), allocated by its first call: error vectors -> z [B][kNeesRhs][ld], the record of
+    // the current diagonal block [B][kDRec], the results [B][kNeesHead + kNeesRhs], and the pivot words [B]
+    double *dNeesE = nullptr, *dNeesD = nullptr, *dNeesOut = nullptr;
+    int* dNeesBad = nullptr;
+    bool neesLdsSet = false;
     // innovation statistics of every update (eqf_innov.hpp; eqf_set_option "innovation_stats"): the tail launch k_innov_stats and its
     // records [B][kInnovHead + cap], allocated when the option is first switched on
     int innovStats = 0;
@@ -1608,7 +1614,8 @@ void freeAll(eqf_filter* f) {
              (void*)f->ZO, (void*)f->dbgDelta, (void*)f->dbgGamma, (void*)f->dbgGammaTot, (void*)f->red, (void*)f->errflag, (void*)f->dMap,
              (void*)f->dPerm, (void*)f->dChord, (void*)f->dDepth2, (void*)f->dDepthSel, (void*)f->dScratch, (void*)f->dMeas,
              (void*)f->dOut, (void*)f->dRing, (void*)f->sImu, (void*)f->sVis, (void*)f->sBear, f->dF, f->dG, f->dBn, f->dBlk, (void*)f->dBlkCommon, f->dColRec, f->dRowRec, (void*)f->dSteps, (void*)f->dFlags, (void*)f->dReadyA, (void*)f->dReadyY, (void*)f->dResCounters, (void*)f->dTicket, (void*)f->dStageFlags, (void*)f->dPrepFlags, (void*)f->dBuildFlags, (void*)f->dGammaPart,
-             (void*)f->dG11Part, (void*)f->dRoles, (void*)f->dI8Ws, (void*)f->dI8Expo, (void*)f->dJac, (void*)f->dSigmaLoc, (void*)f->dInnov})
+             (void*)f->dG11Part, (void*)f->dRoles, (void*)f->dI8Ws, (void*)f->dI8Expo, (void*)f->dJac, (void*)f->dSigmaLoc, (void*)f->dInnov,
+             (void*)f->dNeesE, (void*)f->dNeesD, (void*)f->dNeesOut, (void*)f->dNeesBad})
         hipFree(p);
     if (f->hGate) hipHostFree(f->hGate);
     if (f->dMask) hipFree(f->dMask);
@@ -2602,6 +2609,99 @@ int eqf_get_innovation_stats(eqf_filter* f, int b, eqf_innovation_stats* out, do
     out->dof = int(tmp[2]);
     out->valid = 1;
     if (nis_lm) std::copy(tmp.begin() + kInnovHead, tmp.end(), nis_lm);
+    return EQF_OK;
+}
+
+// One device allocation of eqf_get_nees's buffers; a failure frees what this call got and leaves the handle as it was.
+static int neesAlloc(eqf_filter* f) {
+    if (f->dNeesE && f->dSigmaLoc) return EQF_OK;
+    void *e = nullptr, *d = nullptr, *o = nullptr, *w = nullptr, *s = nullptr;
+    bool ok = true;
+    if (!f->dNeesE) {
+        ok = hipMalloc(&e, sizeof(double) * size_t(kNeesRhs) * f->ld * f->B) == hipSuccess &&
+             hipMalloc(&d, sizeof(double) * size_t(kDRec) * f->B) == hipSuccess &&
+             hipMalloc(&o, sizeof(double) * size_t(kNeesHead + kNeesRhs) * f->B) == hipSuccess &&
+             hipMalloc(&w, sizeof(int) * size_t(f->B)) == hipSuccess;
+    }
+    if (ok && !f->dSigmaLoc) ok = hipMalloc(&s, sizeof(double) * size_t(f->sigmaStride) * f->B) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        for (void* p : {e, d, o, w, s})
+            if (p) hipFree(p);
+        return EQF_ERR_HIP;
+    }
+    if (e) {
+        f->dNeesE = static_cast<double*>(e);
+        f->dNeesD = static_cast<double*>(d);
+        f->dNeesOut = static_cast<double*>(o);
+        f->dNeesBad = static_cast<int*>(w);
+    }
+    if (s) f->dSigmaLoc = static_cast<double*>(s);
+    return EQF_OK;
+}
+
+int eqf_get_nees(eqf_filter* f, int local, int first, int nrhs, const double* err, int lde, double* nees, eqf_sigma_stats* stats) {
+    if (!f || !stats || (local != 0 && local != 1) || (first != 0 && first != 6 && first != kBase) || nrhs < 0 || nrhs > kNeesRhs)
+        return EQF_ERR_INVALID;
+    if (nrhs > 0 && (!err || !nees)) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);  // (a pending outlier gate may still change the landmark counts: settle them before they are looked at)
+    const int B = f->B, nMax = maxN(f);
+    if (nrhs > 0 && lde < kBase + 3 * nMax) return EQF_ERR_INVALID;
+    int rc = neesAlloc(f);
+    if (rc) return rc;
+    if (!f->neesLdsSet) {  // (dynamic LDS beyond 64 KB: see allowUpdateLds)
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nees_panel), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesPanelLdsBytes));
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nees_trail), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesTrailLdsBytes));
+        f->neesLdsSet = true;
+    }
+    const int off = first == kBase ? kLm0 : first;
+    const int mMax = kLm0 + 3 * nMax - off, nb = (mMax + kSB - 1) / kSB, ldE = std::max(mMax, 1);
+    // the image that is factored in place: Sigma_loc (k_sigma_local) or a copy of Sigma
+    if (local) {
+        rc = launchLocal(f, 0, B, true);
+        if (rc) return rc;
+    } else {
+        HIPC(hipMemcpyAsync(f->dSigmaLoc, f->Sigma[f->pS], sizeof(double) * size_t(f->sigmaStride) * B, hipMemcpyDeviceToDevice, f->stream));
+    }
+    // the error vectors in the submatrix' own (padded) index map: entry i of the reference -> column (i < 11 ? i : i + 1) - off
+    std::vector<double> hE;
+    if (nrhs > 0) {
+        hE.assign(size_t(B) * nrhs * ldE, 0.0);
+        for (int b = 0; b < B; ++b) {
+            const int n = kBase + 3 * int(f->ids[b].size());
+            for (int k = 0; k < nrhs; ++k) {
+                const double* src = err + (size_t(b) * nrhs + k) * lde;
+                double* dst = hE.data() + (size_t(b) * nrhs + k) * ldE;
+                for (int i = first; i < n; ++i) dst[(i < kBase ? i : i + 1) - off] = src[i];
+            }
+        }
+        HIPC(hipMemcpyAsync(f->dNeesE, hE.data(), sizeof(double) * hE.size(), hipMemcpyHostToDevice, f->stream));
+    }
+    NeesArgs a{};
+    a.g = f->g[f->pG]; a.A = f->dSigmaLoc; a.ld = f->ld; a.strideA = f->sigmaStride; a.E = f->dNeesE; a.ldE = ldE; a.D = f->dNeesD;
+    a.bad = f->dNeesBad; a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.off = off; a.nrhs = nrhs; a.out = f->dNeesOut;
+    const int rhsWg = nrhs > 0 ? 1 : 0;
+    hipLaunchKernelGGL(k_nees_diag, dim3(1, B), dim3(256), kLdsFactorBytes, f->stream, a, 0);  // (also for an empty submatrix: the pivot word)
+    for (int K = 0; K < nb; ++K) {
+        const int t = nb - K - 1;
+        if (K > 0) hipLaunchKernelGGL(k_nees_diag, dim3(1, B), dim3(256), kLdsFactorBytes, f->stream, a, K);
+        if (t + rhsWg > 0) hipLaunchKernelGGL(k_nees_panel, dim3(t + rhsWg, B), dim3(256), kNeesPanelLdsBytes, f->stream, a, K, t);
+        if (t > 0) hipLaunchKernelGGL(k_nees_trail, dim3(t * (t + 1) / 2 + rhsWg * t, B), dim3(256), kNeesTrailLdsBytes, f->stream, a, K, t);
+    }
+    hipLaunchKernelGGL(k_nees_tail, dim3(B), dim3(256), 0, f->stream, a);
+    HIPC(hipGetLastError());
+    std::vector<double> hO(size_t(B) * (kNeesHead + kNeesRhs));
+    HIPC(hipMemcpyAsync(hO.data(), f->dNeesOut, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipStreamSynchronize(f->stream));
+    for (int b = 0; b < B; ++b) {
+        const double* o = hO.data() + size_t(b) * (kNeesHead + kNeesRhs);
+        stats[b].logdet = o[0];
+        stats[b].min_pivot = o[1];
+        stats[b].dof = int(o[2]);
+        stats[b].info = int(o[3]);
+        for (int k = 0; k < nrhs; ++k) nees[size_t(b) * nrhs + k] = o[kNeesHead + k];
+    }
     return EQF_OK;
 }
 

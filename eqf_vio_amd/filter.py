@@ -140,6 +140,13 @@ class VIOFilter:
         first); include/eqf_vio_amd.h: eqf_get_innovation_stats."""
         return self._fb.innovation_stats(0)
 
+    def stateNEES(self, err, local=True, first=0):
+        """Joint NEES err^T A^-1 err, log det A, smallest pivot, dof and the definiteness word `info` of the covariance from reference index
+        `first` on, in the coordinates of the estimate (local) or of the origin; include/eqf_vio_amd.h: eqf_get_nees."""
+        r = self._fb.nees([np.asarray(err, dtype=float).reshape(1, -1)], local=local, first=first)
+        return dict(nees=float(r["nees"][0, 0]), logdet=float(r["logdet"][0]), min_pivot=float(r["min_pivot"][0]), dof=int(r["dof"][0]),
+                    info=int(r["info"][0]))
+
     def reset(self):
         self._fb.reset()
 

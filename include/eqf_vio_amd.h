@@ -229,6 +229,31 @@ typedef struct eqf_innovation_stats {
     int valid;
 } eqf_innovation_stats;
 int eqf_get_innovation_stats(eqf_filter* f, int b, eqf_innovation_stats* out, double* nis_lm);
+/* The joint NEES e^T A^-1 e, log det A and the definiteness of the covariance, for EVERY filter of the handle in one call, from a batched
+ * Cholesky factorisation A = L L^T with the forward solve z = L^-1 e on the device (csrc/eqf_nees.hpp) -- the marginals of
+ * eqf_get_marginals ignore every landmark-landmark and landmark-base correlation, and the host route is eqf_get_sigma_local for every filter
+ * plus a factorisation of order 11 + 3 N each.
+ *   local = 0: A is taken from Sigma as eqf_get_sigma returns it; local = 1: from Sigma_loc as eqf_get_sigma_local returns it.
+ *   first = 0 | 6 | 11: the trailing principal submatrix from that reference index is factored -- the whole state, the state without the
+ *       bias (the EqF part), the landmarks only.  These are block boundaries of J, so both charts are defined for all three.
+ *   err[(b * nrhs + k) * lde + i] is entry i (reference index map) of error vector k of filter b; entries below `first` are ignored;
+ *       lde >= 11 + 3 N_b for every b.  0 <= nrhs <= 16; with nrhs = 0 err and nees may be NULL and only stats is produced.
+ *   nees [batch][nrhs], stats [batch].  Only the lower triangle (row >= column) of A is read.
+ * Flushes queued IMU calls and synchronises like every getter; Sigma, the state and the ping-pong indices are only read (the factor
+ * overwrites the scratch image of eqf_get_sigma_local).  EQF_ERR_INVALID for bad arguments, before any effect; EQF_ERR_UNSUPPORTED on an
+ * EQF_PRECISION_F32 handle; EQF_ERR_HIP if the buffers, allocated by the first call, cannot be had (the handle stays as it was).  Trouble of
+ * ONE filter goes into stats[b].info, the call returns EQF_OK and eqf_device_error is not touched.  A filter without landmarks answers for
+ * its base part; with first = 11 its dof, nees and logdet are 0 (min_pivot: +inf).  Bit for bit the same from run to run and for a filter
+ * alone in a handle or anywhere in a batch (no atomics, one fixed summation order). */
+typedef struct eqf_sigma_stats {
+    double logdet;     /* log det of the factored matrix = 2 sum log L_kk                          */
+    double min_pivot;  /* smallest L_kk^2                                                          */
+    int dof;           /* 11 + 3 N_b - first                                                       */
+    int info;          /* 0 ok; 1 a pivot was not positive (logdet, min_pivot, nees are NaN);      */
+                       /* -1 local = 1 and the gravity chart of this filter is singular (the same) */
+} eqf_sigma_stats;
+int eqf_get_nees(eqf_filter* f, int local, int first, int nrhs, const double* err, int lde, double* nees /* [batch][nrhs] */,
+    eqf_sigma_stats* stats /* [batch] */);
 
 /* Propagate backend: 0 = block-structured HBM-bound kernel (default, product path),
  * 1 = dense F Sigma F^T on MFMA (what the reference executes; BASELINE cfg 3 cross-check). */

@@ -8,6 +8,12 @@
   ab B N MODE      stream-mode timing, MODE = off | on ("innovation_stats"); EQF_VIO_AMD_LIB selects another build of the library (the
                    parent commit's, for off-against-parent).  Prints one JSON line: events/s (IMU + vision calls), us per vision frame.
   frames N F MODE  F vision frames in stream mode and nothing else (for a kernel-trace table of what an update launches).
+  nees B N         the joint NEES of every filter of a handle, two routes in one process on the same states after three frames, nrhs = 1:
+                   (a) FilterBatch.nees (one call, ends in a synchronise), (b) the host route it replaces, sigma_local(b) for every b +
+                   consistency.nees_joint.  Both warmed up, alternated over 20 repetitions; prints one JSON line with medians, min / max.
+  neeskern B N     a workload for `rocprofv3 --kernel-trace --stats -- python scripts/consistency_bench.py neeskern B N`: ten nees calls.
+  neessum DIR      kernel-trace stats CSVs under DIR/neeskern_B_N -> summed time of the k_nees_* kernels per call against B n^3 / 3 flops at
+                   the fp64 matrix peak (78.6 Tflop/s).
   summarize DIR    kernel-trace stats CSVs under DIR -> the table of the `kernels` legs (achieved bytes/s, ratio).
 """
 import csv
@@ -121,6 +127,83 @@ def frames(N, F, mode):
     print(f"frames N={N} F={seen} mode={mode}: done")
 
 
+def _nees_setup(B, N):
+    import numpy as np
+
+    fg, st = _filled(B, N, frames=3)
+    seen = 0
+    for kind, k in st.events():
+        (fg.stream_imu if kind == "imu" else fg.stream_vision)(k)
+        seen += kind == "vision"
+        if seen == 3:
+            break
+    fg.synchronize()
+    assert fg.num_landmarks(0) == N and fg.device_error() == 0
+    rng = np.random.default_rng(1)
+    E = 1e-2 * rng.standard_normal((B, 1, 11 + 3 * N))
+    return fg, E
+
+
+def nees(B, N, reps=20):
+    import numpy as np
+    from eqf_vio_amd import consistency
+
+    fg, E = _nees_setup(B, N)
+
+    def device():
+        return fg.nees(E, local=True, first=0)["nees"][:, 0]
+
+    def host():
+        return np.array([consistency.nees_joint(fg.sigma_local(b), E[b, 0])["nees"] for b in range(B)])
+
+    a, h = device(), host()  # (first calls: allocations)
+    rel = float(np.max(np.abs(a - h) / h))
+    device(), host()
+    ta, th = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        device()
+        t1 = time.perf_counter()
+        host()
+        t2 = time.perf_counter()
+        ta.append((t1 - t0) * 1e3)
+        th.append((t2 - t1) * 1e3)
+    q = lambda v: dict(median_ms=round(float(np.median(v)), 3), min_ms=round(min(v), 3), max_ms=round(max(v), 3))
+    print(json.dumps(dict(B=B, N=N, reps=reps, device=q(ta), host=q(th), speedup_of_medians=round(float(np.median(th) / np.median(ta)), 1),
+                          device_vs_host_rel=rel)))
+
+
+def neeskern(B, N):
+    fg, E = _nees_setup(B, N)
+    for _ in range(10):
+        fg.nees(E, local=True, first=0)
+    print(f"neeskern B={B} N={N}: done")
+
+
+def neessum(d):
+    for path in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)):
+        tag = [t for t in os.path.relpath(path, d).split(os.sep) if t.startswith("neeskern_")]
+        if not tag:
+            continue
+        _, B, N = tag[0].split("_")
+        B, N = int(B), int(N)
+        tot, calls, parts = 0.0, 0, []
+        for r in csv.DictReader(open(path)):
+            name = r.get("Name") or r.get("KernelName") or ""
+            if "k_nees_" in name:
+                tot += float(r["TotalDurationNs"])
+                parts.append(f"{name.split('(')[0].split('::')[-1]} {float(r['TotalDurationNs']) / 1e3:.0f} us / {r['Calls']}")
+                if "k_nees_tail" in name:
+                    calls = int(r["Calls"])
+        if not calls:
+            continue
+        n = 11 + 3 * N
+        us = tot / calls / 1e3
+        fl = B * n ** 3 / 3.0
+        print(f"{B:3d} x {N:<5d} k_nees_* {us:10.1f} us per call, {fl / 1e9:8.2f} Gflop -> {fl / us / 1e6:7.2f} Tflop/s = {100 * fl / us / 1e6 / 78.6:5.2f} % of 78.6"
+              f"   [{'; '.join(parts)}]")
+
+
 def summarize(d):
     rows = []
     for path in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)):
@@ -159,6 +242,12 @@ if __name__ == "__main__":
         ab(int(sys.argv[2]), int(sys.argv[3]), sys.argv[4])
     elif cmd == "frames":
         frames(int(sys.argv[2]), int(sys.argv[3]), sys.argv[4])
+    elif cmd == "nees":
+        nees(int(sys.argv[2]), int(sys.argv[3]))
+    elif cmd == "neeskern":
+        neeskern(int(sys.argv[2]), int(sys.argv[3]))
+    elif cmd == "neessum":
+        neessum(sys.argv[2])
     elif cmd == "summarize":
         summarize(sys.argv[2])
     else:
