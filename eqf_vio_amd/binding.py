@@ -72,7 +72,7 @@ EXPORTED_SYMBOLS = [
     "eqf_stream_upload", "eqf_stream_imu", "eqf_stream_vision", "eqf_synchronize", "eqf_get_time", "eqf_num_landmarks",
     "eqf_get_ids", "eqf_get_state_estimate", "eqf_get_origin", "eqf_get_group", "eqf_get_bias", "eqf_get_sigma",
     "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
-    "eqf_set_sigma", "eqf_set_state", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
+    "eqf_set_sigma", "eqf_set_state", "eqf_copy_filters", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
     "eqf_tiled_create", "eqf_tiled_destroy", "eqf_tiled_set_stream", "eqf_tiled_set_geometry", "eqf_tiled_propagate", "eqf_tiled_add_landmarks",
     "eqf_tiled_edit_landmarks", "eqf_tiled_propagate_burst", "eqf_tiled_stage_bearings", "eqf_tiled_pingpong",
@@ -136,6 +136,8 @@ def lib():
         L.eqf_get_last_update.argtypes = [vp, C.c_int, _dp, _dp, _dp]
         L.eqf_set_state.argtypes = [vp, C.c_int, C.c_int, _ip] + [_dp] * 11 + [C.c_int, C.c_double, _dp, _dp, C.c_double, C.c_int]
         L.eqf_get_integrator.argtypes = [vp, C.c_int, _dp, _dp, _dp, _ip]
+        if hasattr(L, "eqf_copy_filters"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
+            L.eqf_copy_filters.argtypes = [vp, vp, C.c_int, _ip, _ip]
         L.eqf_debug_get_blocks.argtypes = [vp, C.c_int, _dp, _dp, _dp]
         L.eqf_device_error.argtypes = [vp]
         L.eqf_debug_drop_role.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -490,6 +492,27 @@ class FilterBatch:
                                 float(st["accumulatedTime"]), int(st["initialised"])),
             "eqf_set_state",
         )
+
+    def copy_filters(self, src, dst_idx, src_idx):
+        """Filter dst_idx[k] of this handle becomes what filter src_idx[k] of `src` (another FilterBatch, or this one) was before the call,
+        on the device (include/eqf_vio_amd.h: eqf_copy_filters).  The state is copied, settings and capacity stay this handle's; filters that
+        are not named are untouched.  dst_idx must not repeat, src_idx may (fan-out)."""
+        di = np.ascontiguousarray(np.atleast_1d(dst_idx), dtype=np.int32)
+        si = np.ascontiguousarray(np.atleast_1d(src_idx), dtype=np.int32)
+        if di.ndim != 1 or di.shape != si.shape:
+            raise ValueError("dst_idx and src_idx must be one-dimensional and of one length")
+        n = len(di)
+        if n == 0:  # (an empty numpy array may have no address: the C ABI wants two arrays also for n = 0)
+            di = si = np.zeros(1, dtype=np.int32)
+        _check(lib().eqf_copy_filters(self._h, src._h, n, di.ctypes.data_as(_ip), si.ctypes.data_as(_ip)), "eqf_copy_filters")
+
+    def resample(self, parents):
+        """In place: filter b continues from what filter parents[b] was before the call (consistency.systematic_resample gives parents
+        from the log-likelihoods of innovation_stats())."""
+        parents = np.ascontiguousarray(parents, dtype=np.int32)
+        if parents.shape != (self.B,):
+            raise ValueError(f"parents must have shape ({self.B},)")
+        self.copy_filters(self, np.arange(self.B, dtype=np.int32), parents)
 
     def set_camera_offset(self, q, x):
         q, x = np.ascontiguousarray(q, dtype=np.float64), np.ascontiguousarray(x, dtype=np.float64)

@@ -11,6 +11,7 @@ to first order eps_loc = J eps with the block-diagonal J of local_jacobian_block
   error_vector(error)                    local_error's dict flattened into Sigma's index map
   nees_joint(Sigma, e, first)            the joint NEES e^T A^-1 e, log det A and the smallest pivot over the whole state or a trailing part of
                                          it -- the host counterpart of FilterBatch.nees (include/eqf_vio_amd.h: eqf_get_nees)
+  systematic_resample(loglik, u)         log-likelihoods (FilterBatch.innovation_stats) -> parents for FilterBatch.resample
 
 `origin`, `group`, `estimate` are the dicts of FilterBatch.origin() / group() / state_estimate(): quaternions (w, x, y, z), Eigen semantics.
 """
@@ -195,3 +196,28 @@ def nees_joint(Sigma, e, first=0):
         z = np.linalg.solve(L, E.T)
         nees, logdet, mp = np.sum(z * z, axis=0), 2.0 * float(np.sum(np.log(d))), float(np.min(d * d))
     return dict(nees=float(nees[0]) if ev.ndim == 1 else nees, logdet=logdet, min_pivot=mp, dof=A.shape[0])
+
+
+def systematic_resample(loglik, u):
+    """Systematic resampling of a batch of B filters by weight: parents (B,) int32 for FilterBatch.resample, filter b continues from
+    parents[b].  Weights are exp(loglik - max) normalised; a log-likelihood of -inf or NaN (an update that did not run, a filter that
+    diverged) gets weight 0.  The B points (u + b) / B, u in [0, 1), are looked up in the cumulative weights: deterministic for a given u,
+    parents ascending, and filter i is drawn floor(B w_i) or ceil(B w_i) times.  Raises ValueError if no weight is positive or u is out
+    of range."""
+    ll = np.asarray(loglik, dtype=float).reshape(-1)
+    B = len(ll)
+    if not 0.0 <= float(u) < 1.0:
+        raise ValueError("u must lie in [0, 1)")
+    ok = ~np.isnan(ll) & (ll > -np.inf)
+    if B == 0 or not ok.any():
+        raise ValueError("no filter with a finite log-likelihood")
+    if np.isposinf(ll[ok]).any():
+        raise ValueError("a log-likelihood of +inf")
+    w = np.zeros(B)
+    w[ok] = np.exp(ll[ok] - ll[ok].max())
+    c = np.cumsum(w)
+    pts = (float(u) + np.arange(B)) / B * c[-1]
+    # (side="right": a point on a boundary belongs to the next filter, so a filter of weight 0 is never drawn -- also not at u = 0)
+    parents = np.searchsorted(c, pts, side="right")
+    last = int(np.flatnonzero(w > 0)[-1])
+    return np.minimum(parents, last).astype(np.int32)

@@ -273,6 +273,13 @@ class VIOFilter {
         check(eqf_get_nees(handle_.get(), local ? 1 : 0, first, 1, e.data(), n, &st.nees, &st), "eqf_get_nees");
         return st;
     }
+    // This filter continues from the state of `other` (fork, or snapshot and roll back), copied on the device (eqf_copy_filters): landmarks,
+    // origin, group element, bias, covariance, time and integrator.  Settings, camera offset and capacity stay this filter's own; throws
+    // std::runtime_error if `other` tracks more landmarks than this filter's capacity or differs in precision or device.
+    void copyStateFrom(const VIOFilter& other) {
+        const int zero = 0;
+        check(eqf_copy_filters(handle_.get(), other.handle_.get(), 1, &zero, &zero), "eqf_copy_filters");
+    }
     int lastStatus() const { return lastStatus_; }  // EQF_SKIPPED_* where the reference returns early
     eqf_filter* handle() const { return handle_.get(); }
 

@@ -1,6 +1,6 @@
 // Minimal C++ caller of the facade, shaped like the reference's offline runner (eqf_vio/src/main.cpp:111-170):
 // events are interleaved by "imu.stamp < meas.stamp", the state is read after every vision call.
-// Usage: eqf_example <N landmarks> <frames> [aux | level | init | local | nees]  -- runs a small synthetic sequence and prints the final
+// Usage: eqf_example <N landmarks> <frames> [aux | level | init | local | nees | clone]  -- runs a small synthetic sequence and prints the final
 // pose and |Sigma|_F.  With "aux" the filter starts from AuxiliaryFilterData + setInertialPoints (VIOFilter.cpp:51-58,
 // 74-118) instead of the gravity alignment at the first IMU sample; with "init" from an explicit initialiseFromIMUData
 // call (VIOFilter.cpp:133-144; same result as the lazy one).  With "level" the vehicle rests level: the reference's gravity
@@ -11,9 +11,13 @@
 // coordinates of the estimate (VIOFilter::stateCovarianceLocal).
 // With "nees", after the last frame, one line per (local, first) in {1, 0} x {0, 6, 11} of VIOFilter::stateNEES for the error vector
 // e_i = 0.01 sin(0.9 i + 0.3): "nees" local first dof info, then nees logdet min_pivot as hexadecimal floats.
+// With "clone", after frames / 2 frames a second VIOFilter with twice the measurement variance is forked off the first
+// (VIOFilter::copyStateFrom) and both run on; after the last frame one line each, "clone_a" for the first and "clone_b" for the fork: N,
+// then pose q (4), pose x (3), velocity (3) and the n x n covariance as hexadecimal floats.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <string>
 
 #include "VIOFilter.h"
@@ -33,6 +37,16 @@ int main(int argc, char** argv) {
     const bool init = argc > 3 && std::string(argv[3]) == "init";
     const bool local = argc > 3 && std::string(argv[3]) == "local";
     const bool nees = argc > 3 && std::string(argv[3]) == "nees";
+    const bool clone = argc > 3 && std::string(argv[3]) == "clone";
+    std::unique_ptr<VIOFilter> fork;
+    auto printState = [](const char* tag, const VIOFilter& flt) {
+        const VIOState e = flt.stateEstimate();
+        const MatrixXd S = flt.stateCovariance();
+        std::printf("%s %zu %a %a %a %a %a %a %a %a %a %a", tag, e.bodyLandmarks.size(), e.pose.R.w, e.pose.R.x, e.pose.R.y, e.pose.R.z,
+            e.pose.x[0], e.pose.x[1], e.pose.x[2], e.velocity[0], e.velocity[1], e.velocity[2]);
+        for (double v : S.data) std::printf(" %a", v);
+        std::printf("\n");
+    };
     std::vector<Vector3d> lm(N);
     for (int i = 0; i < N; ++i) lm[i] = {2 * std::sin(1.3 * i), 2 * std::cos(0.7 * i), 5 + std::sin(0.37 * i)};
     AuxiliaryFilterData ad;
@@ -72,6 +86,7 @@ int main(int argc, char** argv) {
         for (; 0.005 * k < meas.stamp; ++k) {  // main.cpp:113
             imu.stamp = 0.005 * k;
             filter.processIMUData(imu);
+            if (fork) fork->processIMUData(imu);
         }
         meas.numberOfBearings = N;
         meas.bearings.resize(N);
@@ -81,7 +96,14 @@ int main(int argc, char** argv) {
             meas.bearings[i].id = aux ? 100 + 2 * i : i;
         }
         filter.processVisionData(meas);
+        if (fork) fork->processVisionData(meas);
         const VIOState est = filter.stateEstimate();
+        if (clone && f + 1 == frames / 2) {
+            VIOFilter::Settings s2 = s;
+            s2.measurementVariance = 2 * s.measurementVariance;
+            fork = std::make_unique<VIOFilter>(s2, N);
+            fork->copyStateFrom(filter);
+        }
         if (f == frames - 1) {
             const MatrixXd S = filter.stateCovariance();
             double fro = 0;
@@ -97,6 +119,10 @@ int main(int argc, char** argv) {
                 std::printf("\nsigma_local %d", Sl.n);
                 for (double v : Sl.data) std::printf(" %a", v);
                 std::printf("\n");
+            }
+            if (clone) {
+                printState("clone_a", filter);
+                if (fork) printState("clone_b", *fork);
             }
             if (nees) {
                 std::vector<double> e(size_t(S.n));

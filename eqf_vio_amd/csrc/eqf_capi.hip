@@ -25,6 +25,7 @@
 #include "eqf_local.hpp"
 #include "eqf_innov.hpp"
 #include "eqf_nees.hpp"
+#include "eqf_clone.hpp"
 
 using namespace eqf;
 
@@ -211,6 +212,13 @@ struct eqf_filter {
     double *dNeesE = nullptr, *dNeesD = nullptr, *dNeesOut = nullptr;
     int* dNeesBad = nullptr;
     bool neesLdsSet = false;
+    // eqf_copy_filters (eqf_clone.hpp): the pair table (pinned image + device copy, grown on demand), the small-state staging image of the
+    // in-place case (allocated on first need) and two events -- evCloneSrc orders a copy behind this handle's work when it is the source,
+    // evCloneDone marks the end of the last copy INTO this handle (its pair table may be reused, the source may go on)
+    ClonePair *hClonePairs = nullptr, *dClonePairs = nullptr;
+    int clonePairsCap = 0;
+    char* dCloneSmall = nullptr;
+    hipEvent_t evCloneSrc = nullptr, evCloneDone = nullptr;
     // innovation statistics of every update (eqf_innov.hpp; eqf_set_option "innovation_stats"): the tail launch k_innov_stats and its
     // records [B][kInnovHead + cap], allocated when the option is first switched on
     int innovStats = 0;
@@ -1632,6 +1640,11 @@ void freeAll(eqf_filter* f) {
     for (auto& e : f->evRing)
         if (e) hipEventDestroy(e);
     if (f->evMeas) hipEventDestroy(f->evMeas);
+    hipFree(f->dClonePairs);
+    hipFree(f->dCloneSmall);
+    if (f->hClonePairs) hipHostFree(f->hClonePairs);
+    if (f->evCloneSrc) hipEventDestroy(f->evCloneSrc);
+    if (f->evCloneDone) hipEventDestroy(f->evCloneDone);
     for (auto e : f->evPool) hipEventDestroy(e);
     for (auto& p : f->profPairs) {
         hipEventDestroy(p.a);
@@ -2403,6 +2416,167 @@ int eqf_set_state(eqf_filter* f, int b, int N, const int* ids, const double* pos
             if (f->dEditBar) HIPC(hipMemset(f->dEditBar, 0, sizeof(int) * 4 * f->B));
         }
     }
+    return EQF_OK;
+}
+
+// The small state of a handle as eqf_clone.hpp's kernels see it (current parity of Glob and Q).
+static CloneSide cloneSide(eqf_filter* f) {
+    CloneSide s{};
+    s.g = f->g[f->pG]; s.p0 = f->p0; s.Q = f->Q[f->pG];
+    s.delta = f->dbgDelta; s.gamma = f->dbgGamma; s.gammaTot = f->dbgGammaTot;
+    s.innov = (f->innovStats && f->dInnov) ? f->dInnov : nullptr;
+    s.cap = f->cap;
+    return s;
+}
+// ... and of the staging image of the in-place case: one allocation, carved in the handle's own layout
+static size_t cloneSmallBytes(const eqf_filter* f) {
+    const size_t cap = f->cap;
+    return (sizeof(Glob) + sizeof(double) * (3 * cap + 5 * cap + 2 * cap + (kLm0 + 3 * cap) + (9 + 3 * cap) + (kInnovHead + cap))) * f->B;
+}
+static CloneSide cloneStageSide(eqf_filter* f) {
+    const size_t cap = f->cap, B = f->B;
+    CloneSide s{};
+    char* p = f->dCloneSmall;
+    s.g = reinterpret_cast<Glob*>(p); p += sizeof(Glob) * B;
+    s.p0 = reinterpret_cast<double*>(p); p += sizeof(double) * 3 * cap * B;
+    s.Q = reinterpret_cast<double*>(p); p += sizeof(double) * 5 * cap * B;
+    s.delta = reinterpret_cast<double*>(p); p += sizeof(double) * 2 * cap * B;
+    s.gamma = reinterpret_cast<double*>(p); p += sizeof(double) * (kLm0 + 3 * cap) * B;
+    s.gammaTot = reinterpret_cast<double*>(p); p += sizeof(double) * (9 + 3 * cap) * B;
+    s.innov = (f->innovStats && f->dInnov) ? reinterpret_cast<double*>(p) : nullptr;
+    s.cap = f->cap;
+    return s;
+}
+// the launches of a pair table (nPairs > 0) on `st`: covariance and small state; into a handle (ma.restore) also what k_restore_constants does
+static void launchClone(eqf_filter* dst, hipStream_t st, const CloneSigmaArgs& sa, const CloneSmallArgs& ma, int nMaxN) {
+    const int n = kLm0 + 3 * nMaxN, kV = dst->precision == EQF_PRECISION_F32 ? 4 : 2;
+    const dim3 grid((n + 256 * kV - 1) / (256 * kV), (n + kCloneRows - 1) / kCloneRows, std::min(sa.nPairs, 65535));
+    if (dst->precision == EQF_PRECISION_F32) hipLaunchKernelGGL(k_clone_sigma<float>, grid, dim3(256), 0, st, sa);
+    else hipLaunchKernelGGL(k_clone_sigma<double>, grid, dim3(256), 0, st, sa);
+    const int np = std::min(ma.nPairs, 65535);
+    hipLaunchKernelGGL(k_clone_small, dim3(std::max(1, (dst->cap + 255) / 256), np), dim3(256), 0, st, ma);
+    if (ma.restore)
+        hipLaunchKernelGGL(k_clone_restore, dim3(std::max(1, (nMaxN + 127) / 128), np), dim3(128), 0, st, dst->g[dst->pG], dst->p0, dst->lmc, dst->cap,
+            dst->errflag, ma.pairs, ma.nPairs);
+}
+
+int eqf_copy_filters(eqf_filter* dst, eqf_filter* src, int n, const int* dst_idx, const int* src_idx) {
+    if (!dst || !src || !dst_idx || !src_idx || n < 0) return EQF_ERR_INVALID;
+    {
+        std::vector<char> named(dst->B, 0);
+        for (int k = 0; k < n; ++k) {
+            if (dst_idx[k] < 0 || dst_idx[k] >= dst->B || src_idx[k] < 0 || src_idx[k] >= src->B) return EQF_ERR_INVALID;
+            if (named[dst_idx[k]]) return EQF_ERR_INVALID;
+            named[dst_idx[k]] = 1;
+        }
+    }
+    if (dst->precision != src->precision || dst->device != src->device) return EQF_ERR_UNSUPPORTED;
+    if (n == 0) return EQF_OK;
+    GATE(dst);
+    if (src != dst) GATE(src);
+    const bool inPlace = dst == src;
+    // the pairs that move something; in place, a source that is also somebody's destination is read from the staging image
+    std::vector<ClonePair> pairs, stagePairs;
+    std::vector<char> isDst(inPlace ? dst->B : 0, 0);
+    for (int k = 0; k < n; ++k) {
+        if (inPlace && dst_idx[k] == src_idx[k]) continue;
+        if (int(src->ids[src_idx[k]].size()) > dst->cap) return EQF_ERR_CAPACITY;
+        if (inPlace) isDst[dst_idx[k]] = 1;
+    }
+    int nMaxN = 0;
+    for (int k = 0; k < n; ++k) {
+        if (inPlace && dst_idx[k] == src_idx[k]) continue;
+        const int s = src_idx[k], N = int(src->ids[s].size());
+        const int staged = inPlace && isDst[s] ? 1 : 0;
+        if (staged == 1 && isDst[s] == 1) {
+            stagePairs.push_back(ClonePair{s, s, N, 0});
+            isDst[s] = 2;  // (staged once, however many pairs read it)
+        }
+        pairs.push_back(ClonePair{dst_idx[k], s, N, staged});
+        nMaxN = std::max(nMaxN, N);
+    }
+    if (pairs.empty()) return EQF_OK;
+    // everything that can fail is had before anything is written
+    const int nTab = int(pairs.size() + stagePairs.size());
+    if (!dst->evCloneDone) {
+        if (hipEventCreateWithFlags(&dst->evCloneDone, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); dst->evCloneDone = nullptr; return EQF_ERR_HIP; }
+    }
+    if (!src->evCloneSrc) {
+        if (hipEventCreateWithFlags(&src->evCloneSrc, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); src->evCloneSrc = nullptr; return EQF_ERR_HIP; }
+    }
+    HIPC(hipEventSynchronize(dst->evCloneDone));  // (the previous copy into this handle has read its pair table)
+    if (nTab > dst->clonePairsCap) {
+        ClonePair *h = nullptr, *d = nullptr;
+        if (hipHostMalloc(reinterpret_cast<void**>(&h), sizeof(ClonePair) * nTab, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&d), sizeof(ClonePair) * nTab) != hipSuccess) {
+            (void)hipGetLastError();
+            if (h) hipHostFree(h);
+            return EQF_ERR_HIP;
+        }
+        if (dst->hClonePairs) hipHostFree(dst->hClonePairs);
+        hipFree(dst->dClonePairs);
+        dst->hClonePairs = h;
+        dst->dClonePairs = d;
+        dst->clonePairsCap = nTab;
+    }
+    if (!stagePairs.empty()) {
+        if (!dst->dSigmaLoc && hipMalloc(reinterpret_cast<void**>(&dst->dSigmaLoc), sizeof(double) * size_t(dst->sigmaStride) * dst->B) != hipSuccess) {
+            (void)hipGetLastError();
+            dst->dSigmaLoc = nullptr;
+            return EQF_ERR_HIP;
+        }
+        if (!dst->dCloneSmall && hipMalloc(reinterpret_cast<void**>(&dst->dCloneSmall), cloneSmallBytes(dst)) != hipSuccess) {
+            (void)hipGetLastError();
+            dst->dCloneSmall = nullptr;
+            return EQF_ERR_HIP;
+        }
+    }
+    hipStream_t st = dst->stream;
+    if (!inPlace) {  // the copy sees what the source has enqueued
+        HIPC(hipEventRecord(src->evCloneSrc, src->stream));
+        HIPC(hipStreamWaitEvent(st, src->evCloneSrc, 0));
+    }
+    std::copy(pairs.begin(), pairs.end(), dst->hClonePairs);
+    std::copy(stagePairs.begin(), stagePairs.end(), dst->hClonePairs + pairs.size());
+    HIPC(hipMemcpyAsync(dst->dClonePairs, dst->hClonePairs, sizeof(ClonePair) * nTab, hipMemcpyHostToDevice, st));
+    CloneSigmaArgs sa{};
+    sa.src = src->Sigma[src->pS]; sa.stage = dst->dSigmaLoc; sa.dst = dst->Sigma[dst->pS];
+    sa.ldSrc = src->ld; sa.ldDst = dst->ld; sa.strideSrc = src->sigmaStride; sa.strideDst = dst->sigmaStride;
+    sa.pairs = dst->dClonePairs; sa.nPairs = int(pairs.size());
+    CloneSmallArgs ma{};
+    ma.src = cloneSide(src); ma.dst = cloneSide(dst); ma.restore = 1;
+    ma.pairs = dst->dClonePairs; ma.nPairs = int(pairs.size());
+    if (!stagePairs.empty()) {
+        int nStageN = 0;
+        for (auto& p : stagePairs) nStageN = std::max(nStageN, p.N);
+        CloneSigmaArgs ss = sa;
+        ss.dst = dst->dSigmaLoc;
+        ss.pairs = dst->dClonePairs + pairs.size(); ss.nPairs = int(stagePairs.size());
+        CloneSmallArgs ms = ma;
+        ms.dst = cloneStageSide(dst); ms.restore = 0;
+        ms.pairs = ss.pairs; ms.nPairs = ss.nPairs;
+        ma.stage = ms.dst;
+        launchClone(dst, st, ss, ms, nStageN);
+    }
+    launchClone(dst, st, sa, ma, nMaxN);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(dst->evCloneDone, st));
+    if (!inPlace) HIPC(hipStreamWaitEvent(src->stream, dst->evCloneDone, 0));  // (the source's later work flips its buffers: not before the copy has read them)
+    // host mirrors (read first: in place a destination may be a source); the caches that describe the device's landmark sets start over
+    std::vector<std::vector<int>> ids(pairs.size());
+    std::vector<double> t(pairs.size());
+    std::vector<char> ini(pairs.size()), dini(pairs.size());
+    for (size_t k = 0; k < pairs.size(); ++k) {
+        const int s = pairs[k].src;
+        ids[k] = src->ids[s]; t[k] = src->curTime[s]; ini[k] = src->init[s]; dini[k] = src->devInit[s];
+    }
+    for (size_t k = 0; k < pairs.size(); ++k) {
+        const int d = pairs[k].dst;
+        dst->ids[d] = std::move(ids[k]); dst->curTime[d] = t[k]; dst->init[d] = ini[k]; dst->devInit[d] = dini[k];
+    }
+    dst->csValid = false;
+    dst->permOnDevice.clear();
+    dst->editOnDevice.clear();
     return EQF_OK;
 }
 

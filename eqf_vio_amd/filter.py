@@ -147,6 +147,11 @@ class VIOFilter:
         return dict(nees=float(r["nees"][0, 0]), logdet=float(r["logdet"][0]), min_pivot=float(r["min_pivot"][0]), dof=int(r["dof"][0]),
                     info=int(r["info"][0]))
 
+    def copyStateFrom(self, other):
+        """This filter continues from the state of `other` (fork, or snapshot and roll back), copied on the device
+        (include/eqf_vio_amd.h: eqf_copy_filters).  Settings, camera offset and capacity stay this filter's own."""
+        self._fb.copy_filters(other._fb, [0], [0])
+
     def reset(self):
         self._fb.reset()
 

@@ -156,6 +156,20 @@ int eqf_set_state(eqf_filter* f, int b, int N, const int* ids, const double* pos
     const double* velocity, const double* p0, const double* A_q, const double* A_x, const double* w, const double* Q_q,
     const double* Q_a, const double* bias6, const double* sigma, int ld, double currentTime, const double* currentVelocity6,
     const double* accumulatedVelocity6, double accumulatedTime, int initialised);
+/* Copy, fork and resample on the device (csrc/eqf_clone.hpp): for k in [0, n), filter dst_idx[k] of dst becomes what filter src_idx[k] of src was
+ * BEFORE the call -- a gather, also with dst == src (swaps, cycles, shifts and fan-out come out right; an identity pair moves nothing).  A
+ * copied filter cannot be told from its source through this header: every getter answers bit for bit the same (eqf_get_innovation_stats when
+ * the option is on in both handles, otherwise valid = 0), and every later call gives the bits it gives on a handle restored through
+ * eqf_set_state from the source's getters.  The STATE is copied; capacity, batch size and settings (noise variances, camera offset) stay
+ * dst's.  Filters of dst that are not named are untouched, src is only read.  A fixed number of launches whatever n; Sigma moves once, at
+ * the extent (12 + 3 N)^2 of each source, never over the host.  Both handles first settle what they have deferred (speculative gate, queued
+ * IMU calls).  The call enqueues and returns; the two streams are ordered with EVENTS, both ways: the copy waits for what src has enqueued,
+ * and src's later work waits for the copy.  Before any effect: EQF_ERR_INVALID (NULL handle or array, n < 0, an index out of range, a
+ * dst_idx named twice; src_idx may repeat; n = 0 is EQF_OK), EQF_ERR_UNSUPPORTED (the handles differ in precision or device; F32 -> F32 is
+ * supported), EQF_ERR_CAPACITY (a source has more landmarks than dst's capacity), EQF_ERR_HIP (the staging images of the in-place case,
+ * allocated on first need, cannot be had).  The sticky error flag of either handle is neither copied nor cleared, and a copy does not
+ * count as a restore towards the recovery from bit 128 (eqf_device_error). */
+int eqf_copy_filters(eqf_filter* dst, eqf_filter* src, int n, const int* dst_idx, const int* src_idx);
 /* xi0.cameraOffset = T_IC for the whole batch (VIOFilter::setAuxiliaryData, VIOFilter.cpp:74-82, overwrites the value
  * taken from the settings at construction, :68).  q must be a unit quaternion (w,x,y,z). */
 int eqf_set_camera_offset(eqf_filter* f, const double* q, const double* x);

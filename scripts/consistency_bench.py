@@ -15,6 +15,13 @@
   neessum DIR      kernel-trace stats CSVs under DIR/neeskern_B_N -> summed time of the k_nees_* kernels per call against B n^3 / 3 flops at
                    the fp64 matrix peak (78.6 Tflop/s).
   summarize DIR    kernel-trace stats CSVs under DIR -> the table of the `kernels` legs (achieved bytes/s, ratio).
+  copy B N         DESIGN.md section 4.5d: FilterBatch.copy_filters (ends in a synchronise of both handles here) against the host route it
+                   replaces, dump_state + restore_state for every filter, on the same states after three frames; once for a whole-handle copy
+                   into a second handle and once for an in-place fan-out (every filter continues from filter 0).  Both warmed up, alternated
+                   over 20 repetitions; prints one JSON line per case with medians, min / max and the ratio.
+  copykern B N     a workload for `rocprofv3 --kernel-trace --stats -- python scripts/consistency_bench.py copykern B N`: k_clone_sigma (a
+                   whole-handle copy into a second handle) next to k_sigma_local (eqf_debug_sigma_local_all) on the same Sigma, 30 each.
+  copysum DIR      kernel-trace stats CSVs under DIR/copykern_B_N -> k_clone_sigma against k_sigma_local (both 2 n^2 * 8 * B bytes).
 """
 import csv
 import glob
@@ -204,6 +211,109 @@ def neessum(d):
               f"   [{'; '.join(parts)}]")
 
 
+def _copy_setup(B, N):
+    fg, st = _filled(B, N, frames=3)
+    seen = 0
+    for kind, k in st.events():
+        (fg.stream_imu if kind == "imu" else fg.stream_vision)(k)
+        seen += kind == "vision"
+        if seen == 3:
+            break
+    fg.synchronize()
+    assert fg.num_landmarks(0) == N and fg.device_error() == 0
+    from eqf_vio_amd import binding, synth
+
+    other = binding.FilterBatch(synth.template_settings_dict(), capacity=N, batch=B)
+    return fg, other
+
+
+def copy(B, N, reps=20):
+    import numpy as np
+
+    fg, other = _copy_setup(B, N)
+    idx = np.arange(B, dtype=np.int32)
+    zero = np.zeros(B, dtype=np.int32)
+
+    def dev_across():
+        other.copy_filters(fg, idx, idx)
+        other.synchronize()
+        fg.synchronize()
+
+    def host_across():
+        for b in range(B):
+            other.restore_state(fg.dump_state(b), b)
+
+    def dev_fan():
+        other.copy_filters(other, idx, zero)
+        other.synchronize()
+
+    def host_fan():
+        snap = other.dump_state(0)
+        for b in range(1, B):
+            other.restore_state(snap, b)
+
+    for name, dev, host in (("across", dev_across, host_across), ("fanout", dev_fan, host_fan)):
+        if name == "fanout" and B == 1:
+            # (one filter: an in-place fan-out is the identity and moves nothing; the snapshot / roll-back pair across handles is the row above)
+            print(json.dumps(dict(case=name, B=B, N=N, note="identity: nothing moves")))
+            continue
+        dev(), host(), dev(), host()  # (first calls: allocations)
+        td, th = [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            dev()
+            t1 = time.perf_counter()
+            host()
+            t2 = time.perf_counter()
+            td.append((t1 - t0) * 1e3)
+            th.append((t2 - t1) * 1e3)
+        q = lambda v: dict(median_ms=round(float(np.median(v)), 3), min_ms=round(min(v), 3), max_ms=round(max(v), 3))
+        same = all(np.array_equal(other.sigma(b), fg.sigma(0 if name == "fanout" else b)) for b in {0, B - 1})
+        print(json.dumps(dict(case=name, B=B, N=N, reps=reps, device=q(td), host=q(th),
+                              speedup_of_medians=round(float(np.median(th) / np.median(td)), 1),
+                              device_slower_than_fastest_host=bool(max(td) >= min(th)), sigma_equal=bool(same))), flush=True)
+    assert fg.device_error() == 0 and other.device_error() == 0
+
+
+def copykern(B, N):
+    import numpy as np
+
+    fg, other = _copy_setup(B, N)
+    idx = np.arange(B, dtype=np.int32)
+    for _ in range(30):
+        fg.debug_sigma_local_all()
+        other.copy_filters(fg, idx, idx)
+    fg.synchronize()
+    other.synchronize()
+    assert fg.device_error() == 0 and other.device_error() == 0
+    print(f"copykern B={B} N={N}: done")
+
+
+def copysum(d):
+    print("B x N      bytes (2 n^2 8 B)   k_clone_sigma avg / min / max us   TB/s (avg)   k_sigma_local avg / min / max us   TB/s (avg)   clone / local (avg)")
+    for path in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)):
+        tag = [t for t in os.path.relpath(path, d).split(os.sep) if t.startswith("copykern_")]
+        if not tag:
+            continue
+        _, B, N = tag[0].split("_")
+        B, N = int(B), int(N)
+        got = {}
+        for r in csv.DictReader(open(path)):
+            name = r.get("Name") or r.get("KernelName") or ""
+            for key in ("k_clone_sigma", "k_sigma_local", "k_clone_small", "k_clone_restore"):
+                if key in name:
+                    got[key] = (float(r["AverageNs"]) / 1e3, float(r["MinNs"]) / 1e3, float(r["MaxNs"]) / 1e3, int(r["Calls"]))
+        if "k_clone_sigma" not in got or "k_sigma_local" not in got:
+            print(B, N, "incomplete", got)
+            continue
+        n = 12 + 3 * N
+        by = 2.0 * n * n * 8 * B
+        c, l = got["k_clone_sigma"], got["k_sigma_local"]
+        print(f"{B:3d} x {N:<5d} {by / 1e6:10.1f} MB   {c[0]:9.1f} / {c[1]:8.1f} / {c[2]:8.1f}   {by / c[0] / 1e6:6.2f}   {l[0]:9.1f} / {l[1]:8.1f} / {l[2]:8.1f}   "
+              f"{by / l[0] / 1e6:6.2f}   {c[0] / l[0]:.2f}   (k_clone_small {got.get('k_clone_small', (0,))[0]:.1f} us, k_clone_restore "
+              f"{got.get('k_clone_restore', (0,))[0]:.1f} us; {c[3]} / {l[3]} calls)")
+
+
 def summarize(d):
     rows = []
     for path in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)):
@@ -248,6 +358,12 @@ if __name__ == "__main__":
         neeskern(int(sys.argv[2]), int(sys.argv[3]))
     elif cmd == "neessum":
         neessum(sys.argv[2])
+    elif cmd == "copy":
+        copy(int(sys.argv[2]), int(sys.argv[3]))
+    elif cmd == "copykern":
+        copykern(int(sys.argv[2]), int(sys.argv[3]))
+    elif cmd == "copysum":
+        copysum(sys.argv[2])
     elif cmd == "summarize":
         summarize(sys.argv[2])
     else:
