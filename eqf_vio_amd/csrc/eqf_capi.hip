@@ -26,6 +26,7 @@
 #include "eqf_innov.hpp"
 #include "eqf_nees.hpp"
 #include "eqf_clone.hpp"
+#include "eqf_frame.hpp"
 
 using namespace eqf;
 
@@ -1077,8 +1078,16 @@ int launchUpdate(eqf_filter* f, const double* bearings, long long bearStride, co
                                              : launchUpdateT<double>(f, bearings, bearStride, perm, Nmax);
 }
 
-// Batch-wide compaction with host keep-lists keep[b] = old indices that survive (ascending).
-int compact(eqf_filter* f, const std::vector<std::vector<int>>& keep) {
+// launch(T{}) with T = the handle's Sigma type, for a kernel whose two instantiations take the same arguments (the style of i8WithSlices)
+template <typename F>
+void withSigmaType(const eqf_filter* f, F&& launch) {
+    if (f->precision == EQF_PRECISION_F32) launch(float{});
+    else launch(double{});
+}
+
+// Batch-wide compaction with host keep-lists keep[b] = old indices that survive (ascending); once the launch is in the stream the host's
+// id lists follow.
+int compactIds(eqf_filter* f, const frame::Lists& keep) {
     const int B = f->B, cap = f->cap;
     f->csValid = false;
     int* h = nullptr;
@@ -1095,24 +1104,22 @@ int compact(eqf_filter* f, const std::vector<std::vector<int>>& keep) {
     HIPC(hipEventRecord(f->stMap.ev[slot], f->stream));
     const int nvn = kLm0 + 3 * nmax;
     int rc = profiled(f, EQF_PROF_CHURN, [&] {
-        const dim3 grid((nvn + 255) / 256, nvn, B);
-        if (f->precision == EQF_PRECISION_F32)
-            hipLaunchKernelGGL(k_compact<float>, grid, dim3(256), 0, f->stream, f->g[f->pG], f->dMap, f->dNewN, cap,
-                static_cast<const float*>(f->Sigma[f->pS]), static_cast<float*>(f->Sigma[f->pS ^ 1]), f->sigmaStride, f->ld, f->p0, f->Q[f->pG], f->lmc,
+        withSigmaType(f, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(k_compact<T>, dim3((nvn + 255) / 256, nvn, B), dim3(256), 0, f->stream, f->g[f->pG], f->dMap, f->dNewN, cap,
+                static_cast<const T*>(f->Sigma[f->pS]), static_cast<T*>(f->Sigma[f->pS ^ 1]), f->sigmaStride, f->ld, f->p0, f->Q[f->pG], f->lmc,
                 f->dScratch);
-        else
-            hipLaunchKernelGGL(k_compact<double>, grid, dim3(256), 0, f->stream, f->g[f->pG], f->dMap, f->dNewN, cap,
-                static_cast<const double*>(f->Sigma[f->pS]), static_cast<double*>(f->Sigma[f->pS ^ 1]), f->sigmaStride, f->ld, f->p0, f->Q[f->pG], f->lmc,
-                f->dScratch);
+        });
     });
     if (rc) return rc;
     HIPC(hipGetLastError());
     f->pS ^= 1;
+    frame::applyKeep(f->ids, keep);
     return EQF_OK;
 }
 
 // perm[b][i] = index into the measurement of state landmark i (or -1)
-int uploadPerm(eqf_filter* f, const std::vector<std::vector<int>>& perm) {
+int uploadPerm(eqf_filter* f, const frame::Lists& perm) {
     const int B = f->B, cap = f->cap;
     // A landmark that was removed as an outlier and comes back is appended at the END of the state: from then on the state's order differs
     // from the measurement's on every frame, with the SAME permutation as long as the set does not change.  Each copy is a blit launch on
@@ -1149,303 +1156,178 @@ int probe(eqf_filter* f, const double* bearings, long long bearStride, bool with
     return EQF_OK;
 }
 
-// processVisionData after integrateUpToTime: bookkeeping + update.  measIds[b] ascending ids of filter b,
-// device bearings at bearings + b*bearStride.  active[b] = integration succeeded && initialised.
-int visionCore(eqf_filter* f, const std::vector<const int*>& measIds, const std::vector<int>& nb, const double* bearings,
-    long long bearStride, const std::vector<char>& active, int* status, const std::vector<std::vector<char>>* gated = nullptr) {
-    // gated (resolveGate's redo of a frame whose speculative gate tripped): the outliers are known and already removed, (*gated)[b][k] marks
-    // their measurement entries -- the gate is not evaluated again
+// (per-call API: the bearings are still in pinned host memory -- whoever enqueues the first consumer enqueues their copy, with `extra` more
+// bytes behind them: k_edit's image)
+int flushMeas(eqf_filter* f, size_t extra = 0) {
+    if (!f->measPending) return EQF_OK;
+    f->measPending = false;
+    HIPC(hipMemcpyAsync(f->dMeas, f->hMeas, sizeof(double) * 3 * f->cap * f->B + extra, hipMemcpyHostToDevice, f->stream));
+    HIPC(hipEventRecord(f->evMeas, f->stream));
+    return EQF_OK;
+}
+
+// before a launch that raises hGate: a redo's k_set_update_ok may still have to read the flags of the frame before
+int awaitMaskAndClearFlags(eqf_filter* f) {
+    if (f->maskPending) {
+        HIPC(hipEventSynchronize(f->evMask));
+        f->maskPending = false;
+    }
+    std::fill(f->hGate, f->hGate + f->B, 0);
+    return EQF_OK;
+}
+
+// ... and behind it: the frame whose gate answer resolveGate() will look at (the route's own fields are the caller's to fill in)
+int armGate(eqf_filter* f, bool onDevice, const frame::Meas& m, const double* bearings, long long bearStride) {
+    HIPC(hipEventRecord(f->evGate, f->stream));
+    f->gate.pending = true;
+    f->gate.onDevice = onDevice;
+    f->gate.active = m.active;
+    f->gate.bearings = bearings;
+    f->gate.bearStride = bearStride;
+    return EQF_OK;
+}
+
+// resolveGate's redo: the update of the filters hGate marks runs after all
+int launchSetUpdateOk(eqf_filter* f) {
+    hipLaunchKernelGGL(k_set_update_ok, dim3((f->B + 63) / 64), dim3(64), 0, f->stream, f->g[f->pG], f->hGateDev, f->B);
+    HIPC(hipEventRecord(f->evMask, f->stream));
+    f->maskPending = true;
+    return EQF_OK;
+}
+
+// (k_median_depth reads N from the device state, which still holds the old counts: nmx = the largest of them)
+int launchMedianDepth(eqf_filter* f, int nmx) {
+    return profiled(f, EQF_PROF_CHURN, [&] {
+        hipLaunchKernelGGL(k_median_depth, dim3((nmx + 255) / 256, f->B), dim3(256), 0, f->stream, f->g[f->pG], f->dDepth2, f->cap, f->dDepthSel);
+    });
+}
+
+// nNew landmarks behind the nOld of filter b; the bearing of the j-th is entry permDev[nOld + j] of the filter's measurement (null: nOld + j)
+int launchAppend(eqf_filter* f, int b, int nOld, int nNew, const double* depthSel, const double* bearings, const int* permDev) {
+    f->csValid = false;
+    const long long work = (long long)3 * nNew * (kLm0 + 3 * (nOld + nNew)) * 2;
+    const int blocks = int(std::min<long long>(1024, (work + 255) / 256));
+    int rc = profiled(f, EQF_PROF_CHURN, [&] {
+        withSigmaType(f, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(k_append<T>, dim3(std::max(1, blocks)), dim3(256), 0, f->stream, f->g[f->pG], b, nOld, nNew, depthSel, (const double*)nullptr,
+                f->set.initialSceneDepth, f->set.initialPointVariance, f->cap, bearings, permDev, f->p0,
+                f->Q[f->pG], f->lmc, f->errflag, static_cast<T*>(f->Sigma[f->pS]), f->sigmaStride, f->ld);
+        });
+    });
+    if (rc) return rc;
+    HIPC(hipGetLastError());
+    return EQF_OK;
+}
+
+// The whole landmark bookkeeping of the frame in one launch (k_edit, eqf_churn.hpp; round 5) -- the host's keep list, the outlier gate
+// evaluated AND acted upon on the device, the new landmarks -- with one upload, and no frame is ever redone.
+int visionOneLaunch(eqf_filter* f, const frame::Meas& m, const double* bearings, long long bearStride, int* status, const frame::Lists& keep,
+    bool anyLost, bool gateArmed) {
     const int B = f->B, cap = f->cap;
-    // (per-call API: the bearings are still in pinned host memory -- whoever enqueues the first consumer enqueues their copy)
-    // innovation statistics: every filter's record starts the vision call with valid = 0; k_innov_stats sets it for the filters whose
-    // update runs (a redo of a gated frame only concerns the filters it flags: the others keep what the first pass left)
-    if (f->innovStats && !gated) HIPC(hipMemsetAsync(f->dInnov, 0, sizeof(double) * (size_t)(kInnovHead + cap) * B, f->stream));
-    auto flushMeas = [&]() -> int {
-        if (!f->measPending) return EQF_OK;
-        f->measPending = false;
-        HIPC(hipMemcpyAsync(f->dMeas, f->hMeas, sizeof(double) * 3 * cap * B, hipMemcpyHostToDevice, f->stream));
-        HIPC(hipEventRecord(f->evMeas, f->stream));
-        return EQF_OK;
-    };
-    // ---- removeOldLandmarks (VIOFilter.cpp:393-419): state ids absent from the measurement
-    bool anyLost = false;
-    std::vector<std::vector<int>> keep(B);
+    // (per-call API: the image rides behind the bearings, one copy for both; stream API: a staging ring of its own)
+    const bool withMeas = f->measPending;
+    int* h = withMeas ? reinterpret_cast<int*>(f->hMeas + (size_t)3 * cap * B) : nullptr;
+    int slot = 0;
+    int rc = withMeas ? EQF_OK : stageAcquire(f->stEdit, &h, &slot);
+    if (rc) return rc;
+    // (the new id lists and the "no bearings left" verdicts are committed to the handle only once k_edit is in the stream: an error on
+    // the way there -- capacity, a failed copy, a failed launch -- leaves the host's lists describing what the device still holds)
+    frame::EditPlan plan;
+    if (!frame::editImage(f->ids, keep, m, gateArmed, cap, h, plan)) return EQF_ERR_CAPACITY;  // (cannot happen: every entry point checks nb <= capacity)
+    // (a fixed set behind an armed gate: the same image every frame, nothing to upload)
+    const size_t nInts = (size_t)2 * B * cap + 4 * B;
+    const int* devImage = f->dEdit;
+    if (withMeas) {
+        rc = flushMeas(f, sizeof(int) * nInts);
+        if (rc) return rc;
+        devImage = reinterpret_cast<const int*>(f->dMeas + (size_t)3 * cap * B);
+    } else if (f->editOnDevice.size() != nInts || !std::equal(h, h + nInts, f->editOnDevice.begin())) {
+        f->editOnDevice.clear();
+        HIPC(hipMemcpyAsync(f->dEdit, h, sizeof(int) * nInts, hipMemcpyHostToDevice, f->stream));
+        HIPC(hipEventRecord(f->stEdit.ev[slot], f->stream));
+        f->editOnDevice.assign(h, h + nInts);
+    }
+    if (gateArmed) rc = awaitMaskAndClearFlags(f);
+    if (rc) return rc;
+    EditArgs ea{};
+    ea.g = f->g[f->pG];
+    ea.in = devImage;
+    ea.permOut = f->dPerm;
+    ea.B = B; ea.cap = cap;
+    ea.bearings = bearings; ea.bearStride = bearStride;
+    ea.gateThr = f->set.outlierThreshold;
+    ea.gateFlag = gateArmed ? f->hGateDev : nullptr;
+    ea.chordOut = gateArmed ? f->hChordDev : nullptr;
+    ea.depthDefault = f->set.initialSceneDepth; ea.pointVar = f->set.initialPointVariance;
+    ea.p0 = f->p0; ea.Q = f->Q[f->pG]; ea.lmc = f->lmc;
+    ea.errflag = f->errflag;
+    ea.Scur = f->Sigma[f->pS]; ea.Soth = f->Sigma[f->pS ^ 1];
+    ea.sigmaStride = f->sigmaStride; ea.ld = f->ld;
+    ea.hostFlip = anyLost ? 1 : 0;
+    ea.bar = f->dEditBar;
+    // (co-resident when an outliers-only compaction may have to wait for its workgroups; a frame whose Sigma the host knows to move
+    // anyway waits for nobody: a workgroup per four rows)
+    const int coRes = std::max(1, std::min(64, std::max(f->numCUs, 1) / B));
+    const int G = (anyLost || !gateArmed) ? std::max(coRes, std::min(1024, (kLm0 + 3 * plan.Nmax + 3) / 4)) : coRes;  // (no gate: nothing can trip)
+    rc = profiled(f, EQF_PROF_CHURN, [&] {
+        withSigmaType(f, [&](auto t) { hipLaunchKernelGGL(k_edit<decltype(t)>, dim3(G, B), dim3(256), 0, f->stream, ea); });
+    });
+    if (rc) return rc;
+    HIPC(hipGetLastError());
+    f->ids = std::move(plan.newIds);
+    if (status)
+        for (int b : plan.skipped) status[b] = EQF_SKIPPED_NO_BEARINGS;
+    if (anyLost) f->pS ^= 1;
+    f->csValid = false;
+    f->permOnDevice.clear();  // (dPerm now holds what k_edit made of the upload)
+    if (gateArmed) {
+        rc = armGate(f, true, m, bearings, bearStride);
+        if (rc) return rc;
+        f->gate.nKept = plan.nKept;
+    }
+    if (!plan.anyWork) return EQF_OK;
+    return launchUpdate(f, bearings, bearStride, f->dPerm, plan.Nmax);
+}
+
+// Speculative gate: the probe decides on the device, the frame's new landmarks and the update are enqueued without waiting for the
+// answer, and a frame that did have an outlier is redone the slow way by resolveGate() the next time the host touches the handle
+// (which first takes the frame's new landmarks out again: the reference removes the outliers BEFORE it initialises new landmarks
+// at the median depth, VIOFilter.cpp:429-443 then :345-391).
+int gateSpeculatively(eqf_filter* f, const frame::Meas& m, const double* bearings, long long bearStride, const frame::Lists& perm) {
+    const int B = f->B;
+    // the permutation the update will use -- the frame's new landmarks appended in measurement order -- is uploaded once, now: the
+    // probe reads its first N entries
+    frame::Lists permFull = perm;
+    for (int b = 0; b < B; ++b)
+        if (m.active[b]) frame::forUnmatched(perm[b].data(), int(perm[b].size()), m.n[b], nullptr, [&](int k) { permFull[b].push_back(k); });
+    const bool identityPerm = frame::isIdentity(permFull);
+    int rc = identityPerm ? EQF_OK : uploadPerm(f, permFull);
+    if (!rc) rc = awaitMaskAndClearFlags(f);  // (a redo's k_set_update_ok reads hGate)
+    if (!rc) rc = probe(f, bearings, bearStride, !identityPerm, false, true);
+    if (!rc) rc = armGate(f, false, m, bearings, bearStride);
+    if (rc) return rc;
+    f->gate.ids.assign(B, {});
+    f->gate.nOld.assign(B, 0);
     for (int b = 0; b < B; ++b) {
-        auto& sid = f->ids[b];
-        keep[b].resize(sid.size());
-        for (size_t i = 0; i < sid.size(); ++i) keep[b][i] = int(i);
-        if (!active[b]) continue;
-        std::vector<int> kept;
-        for (size_t i = 0; i < sid.size(); ++i)
-            if (std::binary_search(measIds[b], measIds[b] + nb[b], sid[i])) kept.push_back(int(i));
-        if (kept.size() != sid.size()) {
-            anyLost = true;
-            keep[b] = kept;
-        }
+        f->gate.ids[b].assign(m.ids[b], m.ids[b] + m.n[b]);
+        f->gate.nOld[b] = int(f->ids[b].size());
     }
-    // ---- round 5: the whole landmark bookkeeping of the frame in one launch (k_edit, eqf_churn.hpp) -- the host's keep list, the outlier
-    // gate evaluated AND acted upon on the device, the new landmarks -- with one upload, and no frame is ever redone.  Not for a redo
-    // itself, filters beyond kEditMax landmarks, a gate whose previous answer is still pending or switched to the synchronous mode, and
-    // -- gate armed -- filters so small that losing a landmark could make their two chains equally long (the update's launch shape is
-    // chosen from the host's count).
-    {
-        const bool gateArmed = !gated && f->set.outlierThreshold < 2.0 && maxN(f) > 0;
-        bool ok = f->deviceEdit && !gated && f->dEdit && (!gateArmed || (f->gateSpeculative && !f->gate.pending));
-        bool anyFresh = false;
-        for (int b = 0; b < B && ok; ++b) {
-            if (int(f->ids[b].size()) > kEditMax) ok = false;
-            if (!active[b]) continue;
-            if (gateArmed && nb[b] < kEditSafeN) ok = false;  // (kept + new landmarks = the measurement's entries)
-            if (nb[b] > int(keep[b].size())) anyFresh = true;  // (every kept id is in the measurement)
-        }
-        if (ok && (anyLost || anyFresh || gateArmed)) {
-            // (per-call API: the image rides behind the bearings, one copy for both; stream API: a staging ring of its own)
-            const bool withMeas = f->measPending;
-            int* h = nullptr;
-            int slot = 0;
-            int rc = EQF_OK;
-            if (withMeas) h = reinterpret_cast<int*>(f->hMeas + (size_t)3 * cap * B);
-            else rc = stageAcquire(f->stEdit, &h, &slot);
-            if (rc) return rc;
-            std::vector<int> nKept(B, 0);
-            // (the new id lists and the "no bearings left" verdicts are committed to the handle only once k_edit is in the stream: an error on
-            // the way there -- capacity, a failed copy, a failed launch -- leaves the host's lists describing what the device still holds)
-            std::vector<std::vector<int>> newIds(B);
-            std::vector<int> skipped;
-            bool anyWork = false;
-            int Nmax = 0;
-            for (int b = 0; b < B; ++b) {
-                int* hm = h + (size_t)b * cap;
-                int* hp = h + (size_t)(B + b) * cap;
-                int* hc = h + (size_t)2 * B * cap + 4 * b;
-                const int nK = int(keep[b].size());
-                nKept[b] = nK;
-                std::copy(keep[b].begin(), keep[b].end(), hm);
-                std::fill(hm + nK, hm + cap, -1);
-                std::vector<int> nid;
-                for (int o : keep[b]) nid.push_back(f->ids[b][o]);
-                int nNew = 0;
-                std::fill(hp, hp + cap, -1);
-                if (active[b]) {
-                    std::vector<char> used(nb[b], 0);
-                    for (int j = 0; j < nK; ++j) {
-                        const int k = int(std::lower_bound(measIds[b], measIds[b] + nb[b], nid[j]) - measIds[b]);
-                        hp[j] = k;
-                        used[k] = 1;
-                    }
-                    if (nK + (nb[b] - nK) > cap) return EQF_ERR_CAPACITY;  // (cannot happen: every entry point checks nb <= capacity)
-                    for (int k = 0; k < nb[b]; ++k)
-                        if (!used[k]) {
-                            hp[nK + nNew++] = k;
-                            nid.push_back(measIds[b][k]);
-                        }
-                }
-                hc[0] = nK; hc[1] = nNew; hc[2] = (gateArmed && active[b]) ? 1 : 0; hc[3] = 0;
-                const bool empty = nid.empty();
-                const int nNow = int(nid.size());
-                newIds[b] = std::move(nid);
-                if (!active[b]) continue;
-                if (empty) {
-                    skipped.push_back(b);
-                    continue;
-                }
-                anyWork = true;
-                Nmax = std::max(Nmax, nNow);
-            }
-            // (a fixed set behind an armed gate: the same image every frame, nothing to upload)
-            const size_t nInts = (size_t)2 * B * cap + 4 * B;
-            const int* devImage = f->dEdit;
-            if (withMeas) {
-                f->measPending = false;
-                HIPC(hipMemcpyAsync(f->dMeas, f->hMeas, sizeof(double) * 3 * cap * B + sizeof(int) * nInts, hipMemcpyHostToDevice, f->stream));
-                HIPC(hipEventRecord(f->evMeas, f->stream));
-                devImage = reinterpret_cast<const int*>(f->dMeas + (size_t)3 * cap * B);
-            } else if (f->editOnDevice.size() != nInts || !std::equal(h, h + nInts, f->editOnDevice.begin())) {
-                f->editOnDevice.clear();
-                HIPC(hipMemcpyAsync(f->dEdit, h, sizeof(int) * nInts, hipMemcpyHostToDevice, f->stream));
-                HIPC(hipEventRecord(f->stEdit.ev[slot], f->stream));
-                f->editOnDevice.assign(h, h + nInts);
-            }
-            if (gateArmed) {
-                if (f->maskPending) {
-                    HIPC(hipEventSynchronize(f->evMask));
-                    f->maskPending = false;
-                }
-                std::fill(f->hGate, f->hGate + B, 0);
-            }
-            EditArgs ea{};
-            ea.g = f->g[f->pG];
-            ea.in = devImage;
-            ea.permOut = f->dPerm;
-            ea.B = B; ea.cap = cap;
-            ea.bearings = bearings; ea.bearStride = bearStride;
-            ea.gateThr = f->set.outlierThreshold;
-            ea.gateFlag = gateArmed ? f->hGateDev : nullptr;
-            ea.chordOut = gateArmed ? f->hChordDev : nullptr;
-            ea.depthDefault = f->set.initialSceneDepth; ea.pointVar = f->set.initialPointVariance;
-            ea.p0 = f->p0; ea.Q = f->Q[f->pG]; ea.lmc = f->lmc;
-            ea.errflag = f->errflag;
-            ea.Scur = f->Sigma[f->pS]; ea.Soth = f->Sigma[f->pS ^ 1];
-            ea.sigmaStride = f->sigmaStride; ea.ld = f->ld;
-            ea.hostFlip = anyLost ? 1 : 0;
-            ea.bar = f->dEditBar;
-            // (co-resident when an outliers-only compaction may have to wait for its workgroups; a frame whose Sigma the host knows to move
-            // anyway waits for nobody: a workgroup per four rows)
-            const int coRes = std::max(1, std::min(64, std::max(f->numCUs, 1) / B));
-            const int G = (anyLost || !gateArmed) ? std::max(coRes, std::min(1024, (kLm0 + 3 * Nmax + 3) / 4)) : coRes;  // (no gate: nothing can trip)
-            rc = profiled(f, EQF_PROF_CHURN, [&] {
-                if (f->precision == EQF_PRECISION_F32) hipLaunchKernelGGL(k_edit<float>, dim3(G, B), dim3(256), 0, f->stream, ea);
-                else hipLaunchKernelGGL(k_edit<double>, dim3(G, B), dim3(256), 0, f->stream, ea);
-            });
-            if (rc) return rc;
-            HIPC(hipGetLastError());
-            for (int b = 0; b < B; ++b) f->ids[b] = std::move(newIds[b]);
-            if (status)
-                for (int b : skipped) status[b] = EQF_SKIPPED_NO_BEARINGS;
-            if (anyLost) f->pS ^= 1;
-            f->csValid = false;
-            f->permOnDevice.clear();  // (dPerm now holds what k_edit made of the upload)
-            if (gateArmed) {
-                HIPC(hipEventRecord(f->evGate, f->stream));
-                f->gate.pending = true;
-                f->gate.onDevice = true;
-                f->gate.nKept = nKept;
-                f->gate.active = active;
-                f->gate.bearings = bearings;
-                f->gate.bearStride = bearStride;
-            }
-            if (!anyWork) return EQF_OK;
-            return launchUpdate(f, bearings, bearStride, f->dPerm, Nmax);
-        }
-    }
-    {
-        int rc = flushMeas();
-        if (rc) return rc;
-    }
-    if (anyLost) {
-        int rc = compact(f, keep);
-        if (rc) return rc;
-        for (int b = 0; b < B; ++b) {
-            std::vector<int> nid;
-            for (int o : keep[b]) nid.push_back(f->ids[b][o]);
-            f->ids[b] = nid;
-        }
-    }
-    // ---- matchMeasurementsToState (:211-230): perm[b][i] = measurement index of state landmark i
-    std::vector<std::vector<int>> perm(B);
-    auto buildPerm = [&]() {
-        for (int b = 0; b < B; ++b) {
-            perm[b].assign(f->ids[b].size(), -1);
-            if (!active[b]) continue;
-            for (size_t i = 0; i < f->ids[b].size(); ++i) {
-                const int* it = std::lower_bound(measIds[b], measIds[b] + nb[b], f->ids[b][i]);
-                perm[b][i] = int(it - measIds[b]);
-            }
-        }
-    };
-    buildPerm();
-    // ---- removeOutliers (:429-443).  A chord between unit vectors never exceeds 2.
-    std::vector<std::vector<char>> dropped(B);  // measurement indices erased together with their landmark
-    for (int b = 0; b < B; ++b) dropped[b].assign(nb[b], 0);
-    if (gated) dropped = *gated;
-    const bool gateOn = !gated && f->set.outlierThreshold < 2.0 && maxN(f) > 0;
-    // Speculative gate: the probe decides on the device, the frame's new landmarks and the update are enqueued without waiting for the
-    // answer, and a frame that did have an outlier is redone the slow way by resolveGate() the next time the host touches the handle
-    // (which first takes the frame's new landmarks out again: the reference removes the outliers BEFORE it initialises new landmarks
-    // at the median depth, VIOFilter.cpp:429-443 then :345-391).
-    bool speculate = gateOn && f->gateSpeculative && !f->gate.pending;  // (lost landmarks are already compacted away)
-    bool depthFresh = false;  // dDepth2 holds the squared depths of the CURRENT landmark set
-    if (speculate) {
-        // the permutation the update will use -- the frame's new landmarks appended in measurement order -- is uploaded once, now: the
-        // probe reads its first N entries
-        std::vector<std::vector<int>> permFull = perm;
-        for (int b = 0; b < B; ++b) {
-            if (!active[b]) continue;
-            std::vector<char> used(nb[b], 0);
-            for (int k : perm[b]) used[k] = 1;
-            for (int k = 0; k < nb[b]; ++k)
-                if (!used[k]) permFull[b].push_back(k);
-        }
-        bool identityPerm = true;
-        for (int b = 0; b < B && identityPerm; ++b)
-            for (size_t i = 0; i < permFull[b].size(); ++i)
-                if (permFull[b][i] != int(i)) {
-                    identityPerm = false;
-                    break;
-                }
-        int rc = identityPerm ? EQF_OK : uploadPerm(f, permFull);
-        if (rc) return rc;
-        if (f->maskPending) {  // (a redo's k_set_update_ok reads hGate)
-            HIPC(hipEventSynchronize(f->evMask));
-            f->maskPending = false;
-        }
-        std::fill(f->hGate, f->hGate + B, 0);
-        rc = probe(f, bearings, bearStride, !identityPerm, false, true);
-        if (rc) return rc;
-        depthFresh = true;
-        HIPC(hipEventRecord(f->evGate, f->stream));
-        f->gate.pending = true;
-        f->gate.onDevice = false;
-        f->gate.ids.assign(B, {});
-        f->gate.nOld.assign(B, 0);
-        for (int b = 0; b < B; ++b) {
-            f->gate.ids[b].assign(measIds[b], measIds[b] + nb[b]);
-            f->gate.nOld[b] = int(f->ids[b].size());
-        }
-        f->gate.nb = nb;
-        f->gate.active = active;
-        f->gate.bearings = bearings;
-        f->gate.bearStride = bearStride;
-    } else if (gateOn) {
-        bool identityPerm = true;
-        for (int b = 0; b < B && identityPerm; ++b)
-            for (size_t i = 0; i < perm[b].size(); ++i)
-                if (perm[b][i] != int(i)) {
-                    identityPerm = false;
-                    break;
-                }
-        int rc = identityPerm ? EQF_OK : uploadPerm(f, perm);
-        if (rc) return rc;
-        rc = probe(f, bearings, bearStride, !identityPerm, true);
-        if (rc) return rc;
-        bool anyOut = false;
-        for (int b = 0; b < B; ++b) {
-            keep[b].clear();
-            for (size_t i = 0; i < f->ids[b].size(); ++i) {
-                const bool out = active[b] && f->hChord[(size_t)b * cap + i] > f->set.outlierThreshold;
-                if (out) {
-                    anyOut = true;
-                    dropped[b][perm[b][i]] = 1;
-                } else {
-                    keep[b].push_back(int(i));
-                }
-            }
-        }
-        if (anyOut) {
-            rc = compact(f, keep);
-            if (rc) return rc;
-            for (int b = 0; b < B; ++b) {
-                std::vector<int> nid;
-                for (int o : keep[b]) nid.push_back(f->ids[b][o]);
-                f->ids[b] = nid;
-            }
-            buildPerm();
-        }
-        depthFresh = !anyOut;  // (the probe also left the squared depths -- of the set before any removal)
-    }
-    // ---- addNewLandmarks (:345-391)
+    f->gate.nb = m.n;
+    return EQF_OK;
+}
+
+// addNewLandmarks (:345-391) and the update proper (:258-297).  perm: of the state as it is; dropped: the measurement entries the gate
+// erased together with their landmark; depthFresh: dDepth2 holds the squared depths of the CURRENT landmark set
+int addNewAndUpdate(eqf_filter* f, const frame::Meas& m, const double* bearings, long long bearStride, int* status, frame::Lists& perm,
+    const frame::Marks& dropped, bool depthFresh) {
+    const int B = f->B, cap = f->cap;
     bool needDepth = false;
-    std::vector<std::vector<int>> fresh(B);  // measurement indices of new landmarks, in measurement order
+    frame::Lists fresh(B);  // measurement indices of new landmarks, in measurement order
     for (int b = 0; b < B; ++b) {
-        if (!active[b]) continue;
-        {
-            // (every state id is in the measurement by now: perm marks the measurement entries that have a landmark)
-            std::vector<char> used(nb[b], 0);
-            for (int k : perm[b])
-                if (k >= 0 && k < nb[b]) used[k] = 1;
-            for (int k = 0; k < nb[b]; ++k)
-                if (!used[k] && !dropped[b][k]) fresh[b].push_back(k);
-        }
+        if (!m.active[b]) continue;
+        // (every state id is in the measurement by now: perm marks the measurement entries that have a landmark)
+        frame::forUnmatched(perm[b].data(), int(perm[b].size()), m.n[b], dropped[b].data(), [&](int k) { fresh[b].push_back(k); });
         if (!fresh[b].empty()) {
             // (cannot happen: every entry point checks nb <= capacity and strictly ascending ids before any effect)
             if (f->ids[b].size() + fresh[b].size() > (size_t)cap) return EQF_ERR_CAPACITY;
@@ -1457,22 +1339,21 @@ int visionCore(eqf_filter* f, const std::vector<const int*>& measIds, const std:
     std::vector<int> nOldV(B, 0);
     for (int b = 0; b < B; ++b) {
         nOldV[b] = int(f->ids[b].size());
-        for (int k : fresh[b]) f->ids[b].push_back(measIds[b][k]);
+        for (int k : fresh[b]) f->ids[b].push_back(m.ids[b][k]);
     }
-    buildPerm();
-    bool identity = true, anyWork = false;
+    frame::matchPerm(f->ids, m, perm);
+    bool anyWork = false;
     int Nmax = 0;
     for (int b = 0; b < B; ++b) {
-        if (!active[b]) continue;
+        if (!m.active[b]) continue;
         if (f->ids[b].empty()) {
             if (status) status[b] = EQF_SKIPPED_NO_BEARINGS;
             continue;
         }
         anyWork = true;
         Nmax = std::max(Nmax, int(f->ids[b].size()));
-        for (size_t i = 0; i < perm[b].size(); ++i)
-            if (perm[b][i] != int(i)) identity = false;
     }
+    const bool identity = frame::isIdentity(perm, &m.active);
     if (anyWork && !identity) {
         int rc = uploadPerm(f, perm);
         if (rc) return rc;
@@ -1483,45 +1364,88 @@ int visionCore(eqf_filter* f, const std::vector<const int*>& measIds, const std:
         // itself, or by a launch of its own for sets too large for that
         // (k_append computes the squared depths itself, round 5: no probe launch in front of it; only sets too large for its LDS take the
         // probe + the selection launch)
-        int rc = EQF_OK;
-        for (int b = 0; b < B; ++b)
+        int nmx = 1;
+        for (int b = 0; b < B; ++b) {
             if (!fresh[b].empty() && nOldV[b] > kMedianInAppend) medianLaunch = true;
-        if (medianLaunch && !depthFresh) rc = probe(f, nullptr, 0, false, false);
-        if (rc) return rc;
-        if (medianLaunch) {
-            int nmx = 1;
-            for (int b = 0; b < B; ++b) nmx = std::max(nmx, nOldV[b]);
-            // (k_median_depth reads N from the device state, which still holds the old counts)
-            rc = profiled(f, EQF_PROF_CHURN, [&] {
-                hipLaunchKernelGGL(k_median_depth, dim3((nmx + 255) / 256, B), dim3(256), 0, f->stream, f->g[f->pG], f->dDepth2, cap, f->dDepthSel);
-            });
-            if (rc) return rc;
+            nmx = std::max(nmx, nOldV[b]);
         }
+        int rc = (medianLaunch && !depthFresh) ? probe(f, nullptr, 0, false, false) : EQF_OK;
+        if (!rc && medianLaunch) rc = launchMedianDepth(f, nmx);
+        if (rc) return rc;
     }
     for (int b = 0; b < B; ++b) {
         if (fresh[b].empty()) continue;
-        f->csValid = false;
-        const int nOld = nOldV[b], nNew = int(fresh[b].size());
-        const long long work = (long long)3 * nNew * (kLm0 + 3 * (nOld + nNew)) * 2;
-        const int blocks = int(std::min<long long>(1024, (work + 255) / 256));
-        const double* depthSel = medianLaunch ? f->dDepthSel : nullptr;
-        const int* permDev = identity ? nullptr : f->dPerm;
-        int rc = profiled(f, EQF_PROF_CHURN, [&] {
-            if (f->precision == EQF_PRECISION_F32)
-                hipLaunchKernelGGL(k_append<float>, dim3(std::max(1, blocks)), dim3(256), 0, f->stream, f->g[f->pG], b, nOld, nNew, depthSel, (const double*)nullptr,
-                    f->set.initialSceneDepth, f->set.initialPointVariance, cap, bearings + (long long)b * bearStride, permDev, f->p0,
-                    f->Q[f->pG], f->lmc, f->errflag, static_cast<float*>(f->Sigma[f->pS]), f->sigmaStride, f->ld);
-            else
-                hipLaunchKernelGGL(k_append<double>, dim3(std::max(1, blocks)), dim3(256), 0, f->stream, f->g[f->pG], b, nOld, nNew, depthSel, (const double*)nullptr,
-                    f->set.initialSceneDepth, f->set.initialPointVariance, cap, bearings + (long long)b * bearStride, permDev, f->p0,
-                    f->Q[f->pG], f->lmc, f->errflag, static_cast<double*>(f->Sigma[f->pS]), f->sigmaStride, f->ld);
-        });
+        int rc = launchAppend(f, b, nOldV[b], int(fresh[b].size()), medianLaunch ? f->dDepthSel : nullptr, bearings + (long long)b * bearStride,
+            identity ? nullptr : f->dPerm);
         if (rc) return rc;
-        HIPC(hipGetLastError());
     }
-    // ---- the update proper (:258-297)
     if (!anyWork) return EQF_OK;
     return launchUpdate(f, bearings, bearStride, identity ? nullptr : f->dPerm, Nmax);
+}
+
+// The frame as separate launches: compaction of the lost landmarks, the gate's probe (and the compaction of what it removed), an append
+// launch per filter that gains landmarks, the update.
+// Where this path commits: f->ids changes right behind each compaction launch (compactIds) and, for the new landmarks, BEFORE their
+// permutation upload and append launches (addNewAndUpdate); status[] there as well.  An error after one of these points leaves the host ahead
+// of the device.  That is how it was before this code was split into functions and is kept so on purpose: changing it is a change of
+// behaviour for a pull request of its own.
+int visionSeparate(eqf_filter* f, const frame::Meas& m, const double* bearings, long long bearStride, int* status, frame::Lists& keep,
+    bool anyLost, const frame::Marks* gated) {
+    const int B = f->B;
+    int rc = flushMeas(f);
+    if (!rc && anyLost) rc = compactIds(f, keep);
+    if (rc) return rc;
+    // ---- matchMeasurementsToState (:211-230): perm[b][i] = measurement index of state landmark i
+    frame::Lists perm;
+    frame::matchPerm(f->ids, m, perm);
+    // ---- removeOutliers (:429-443).  A chord between unit vectors never exceeds 2.
+    frame::Marks dropped(B);  // measurement indices erased together with their landmark
+    for (int b = 0; b < B; ++b) dropped[b].assign(m.n[b], 0);
+    if (gated) dropped = *gated;
+    const bool gateOn = !gated && f->set.outlierThreshold < 2.0 && maxN(f) > 0;
+    bool depthFresh = false;
+    if (gateOn && f->gateSpeculative && !f->gate.pending) {  // (lost landmarks are already compacted away)
+        rc = gateSpeculatively(f, m, bearings, bearStride, perm);
+        if (rc) return rc;
+        depthFresh = true;
+    } else if (gateOn) {
+        const bool identityPerm = frame::isIdentity(perm);
+        rc = identityPerm ? EQF_OK : uploadPerm(f, perm);
+        if (!rc) rc = probe(f, bearings, bearStride, !identityPerm, true);
+        if (rc) return rc;
+        const bool anyOut = frame::gateSync(f->ids, perm, m.active, f->hChord, f->cap, f->set.outlierThreshold, keep, dropped);
+        if (anyOut) {
+            rc = compactIds(f, keep);
+            if (rc) return rc;
+            frame::matchPerm(f->ids, m, perm);
+        }
+        depthFresh = !anyOut;  // (the probe also left the squared depths -- of the set before any removal)
+    }
+    return addNewAndUpdate(f, m, bearings, bearStride, status, perm, dropped, depthFresh);
+}
+
+// processVisionData after integrateUpToTime: bookkeeping + update.  measIds[b] ascending ids of filter b,
+// device bearings at bearings + b*bearStride.  active[b] = integration succeeded && initialised.
+// (the index arithmetic of all of it: eqf_frame.hpp)
+int visionCore(eqf_filter* f, const std::vector<const int*>& measIds, const std::vector<int>& nb, const double* bearings,
+    long long bearStride, const std::vector<char>& active, int* status, const frame::Marks* gated = nullptr) {
+    // gated (resolveGate's redo of a frame whose speculative gate tripped): the outliers are known and already removed, (*gated)[b][k] marks
+    // their measurement entries -- the gate is not evaluated again
+    // innovation statistics: every filter's record starts the vision call with valid = 0; k_innov_stats sets it for the filters whose
+    // update runs (a redo of a gated frame only concerns the filters it flags: the others keep what the first pass left)
+    if (f->innovStats && !gated) HIPC(hipMemsetAsync(f->dInnov, 0, sizeof(double) * (size_t)(kInnovHead + f->cap) * f->B, f->stream));
+    const frame::Meas m{measIds, nb, active};
+    // ---- removeOldLandmarks (VIOFilter.cpp:393-419): state ids absent from the measurement
+    frame::Lists keep;
+    const bool anyLost = frame::keepPresent(f->ids, m, keep);
+    // The one-launch path is not for a redo itself, filters beyond kEditMax landmarks, a gate whose previous answer is still pending or
+    // switched to the synchronous mode, and -- gate armed -- filters so small that losing a landmark could make their two chains equally
+    // long (the update's launch shape is chosen from the host's count).
+    const bool gateArmed = !gated && f->set.outlierThreshold < 2.0 && maxN(f) > 0;
+    const bool handleOk = f->deviceEdit && !gated && f->dEdit && (!gateArmed || (f->gateSpeculative && !f->gate.pending));
+    const frame::EditChoice e = frame::editEligible(f->ids, keep, m, handleOk, gateArmed, kEditMax, kEditSafeN);
+    if (e.ok && (anyLost || e.anyFresh || gateArmed)) return visionOneLaunch(f, m, bearings, bearStride, status, keep, anyLost, gateArmed);
+    return visionSeparate(f, m, bearings, bearStride, status, keep, anyLost, gated);
 }
 
 // Look at the answer of a speculative outlier gate.  No outlier (the common case): nothing to do.  Otherwise the filters
@@ -1535,77 +1459,26 @@ int resolveGate(eqf_filter* f) {
     const int B = f->B, cap = f->cap;
     if (f->gate.onDevice) {
         // k_edit took the outliers out before the update ran: the ids follow (kept landmark j of the frame is f->ids[b][j])
-        for (int b = 0; b < B; ++b) {
-            if (!f->hGate[b] || !f->gate.active[b]) continue;
-            std::vector<int> nid;
-            const int nK = f->gate.nKept[b];
-            for (int j = 0; j < int(f->ids[b].size()); ++j)
-                if (j >= nK || !(f->hChord[(size_t)b * cap + j] > f->set.outlierThreshold)) nid.push_back(f->ids[b][j]);
-            f->ids[b] = nid;
-        }
         // (flag 2: the outliers left the filter with so few landmarks that k_edit switched the queued update off -- it runs now, shaped for
         // the count the host knows by now; nothing else of the frame is repeated)
-        bool deferred = false;
-        int Nmax = 0;
-        for (int b = 0; b < B; ++b) {
-            const bool d = f->hGate[b] == 2 && f->gate.active[b] && !f->ids[b].empty();
-            f->hGate[b] = d ? 1 : 0;
-            if (d) {
-                deferred = true;
-                Nmax = std::max(Nmax, int(f->ids[b].size()));
-            }
-        }
-        if (!deferred) return EQF_OK;
-        hipLaunchKernelGGL(k_set_update_ok, dim3((B + 63) / 64), dim3(64), 0, f->stream, f->g[f->pG], f->hGateDev, B);
-        HIPC(hipEventRecord(f->evMask, f->stream));
-        f->maskPending = true;
-        return launchUpdate(f, f->gate.bearings, f->gate.bearStride, f->dPerm, Nmax);
+        const frame::DeviceGate d = frame::gateOnDevice(f->ids, f->hGate, f->gate.active, f->gate.nKept, f->hChord, cap, f->set.outlierThreshold);
+        if (!d.deferred) return EQF_OK;
+        int rc = launchSetUpdateOk(f);
+        if (rc) return rc;
+        return launchUpdate(f, f->gate.bearings, f->gate.bearStride, f->dPerm, d.Nmax);
     }
-    bool any = false;
-    std::vector<char> act(B, 0);
-    for (int b = 0; b < B; ++b) {
-        const bool hit = f->hGate[b] && f->gate.active[b];
-        f->hGate[b] = hit ? 1 : 0;  // the mask k_set_update_ok reads: only the flagged filters take part in the redo
-        if (hit) {
-            any = true;
-            act[b] = 1;
-        }
-    }
-    if (!any) return EQF_OK;
-    hipLaunchKernelGGL(k_set_update_ok, dim3((B + 63) / 64), dim3(64), 0, f->stream, f->g[f->pG], f->hGateDev, B);
-    HIPC(hipEventRecord(f->evMask, f->stream));
-    f->maskPending = true;
     // The flagged filters: their update did not run, their new landmarks of that frame were appended.  One compaction takes out the
     // outliers -- the probe left every chord in pinned memory: no second probe, no readback -- and the appended landmarks (the redo
     // initialises them again, at the median depth of what is left: the reference's order, VIOFilter.cpp:429-443 then :345-391).
-    std::vector<std::vector<int>> keep(B);
-    std::vector<std::vector<char>> gated(B);
-    for (int b = 0; b < B; ++b) {
-        const int n = int(f->ids[b].size());
-        gated[b].assign(f->gate.nb[b], 0);
-        if (!act[b]) {
-            keep[b].resize(n);
-            for (int i = 0; i < n; ++i) keep[b][i] = i;
-            continue;
-        }
-        const int nOld = std::min(n, f->gate.nOld[b]);
-        const int* mi = f->gate.ids[b].data();
-        for (int i = 0; i < nOld; ++i) {
-            if (f->hChord[(size_t)b * cap + i] > f->set.outlierThreshold) {
-                const int* it = std::lower_bound(mi, mi + f->gate.nb[b], f->ids[b][i]);
-                gated[b][int(it - mi)] = 1;
-            } else {
-                keep[b].push_back(i);
-            }
-        }
-    }
-    int rc = compact(f, keep);
+    // (hGate becomes the mask k_set_update_ok reads: only the flagged filters take part in the redo)
+    std::vector<char> act;
+    frame::Lists keep;
+    frame::Marks gated;
+    if (!frame::gateRedo(f->ids, f->hGate, f->gate.active, f->gate.ids, f->gate.nb, f->gate.nOld, f->hChord, cap, f->set.outlierThreshold, act, keep, gated))
+        return EQF_OK;
+    int rc = launchSetUpdateOk(f);
+    if (!rc) rc = compactIds(f, keep);
     if (rc) return rc;
-    for (int b = 0; b < B; ++b) {
-        std::vector<int> nid;
-        for (int o : keep[b]) nid.push_back(f->ids[b][o]);
-        f->ids[b] = nid;
-    }
     std::vector<const int*> mids(B);
     for (int b = 0; b < B; ++b) mids[b] = f->gate.ids[b].data();
     return visionCore(f, mids, f->gate.nb, f->gate.bearings, f->gate.bearStride, act, nullptr, &gated);
@@ -2006,11 +1879,7 @@ int eqf_process_vision(eqf_filter* f, const double* stamps, const int* nb, const
     }
     f->measPending = true;
     rc = visionCore(f, mids, nbv, f->dMeas, (long long)3 * cap, active, st.data());
-    if (f->measPending) {  // (visionCore left before it needed them)
-        f->measPending = false;
-        HIPC(hipMemcpyAsync(f->dMeas, f->hMeas, sizeof(double) * 3 * cap * B, hipMemcpyHostToDevice, f->stream));
-        HIPC(hipEventRecord(f->evMeas, f->stream));
-    }
+    if (flushMeas(f)) return EQF_ERR_HIP;  // (visionCore left before it needed them)
     if (status) std::copy(st.begin(), st.end(), status);
     return rc;
 }
