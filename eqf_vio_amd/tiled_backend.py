@@ -256,6 +256,12 @@ class HipBackend:
         self.b._check(self.lib.eqf_tile_trsm(self.dev, self._cur(), self._p(L), L.stride(0), L.shape[0], self._p(drec), self._p(Bm),
                                              Bm.stride(0), Bm.shape[1], 0), "eqf_tile_trsm")
 
+    def trsm_right(self, L, drec, Bm):
+        """In place: Bm (m x n view) <- Bm L^-T: one workgroup per 64 ROWS of Bm, each a chain over L's block columns (what the blocked
+        eqf_tile_potrf runs on the panel below a diagonal block, there with n <= 64)."""
+        self.b._check(self.lib.eqf_tile_trsm(self.dev, self._cur(), self._p(L), L.stride(0), L.shape[0], self._p(drec), self._p(Bm),
+                                             Bm.stride(0), Bm.shape[0], 1), "eqf_tile_trsm")
+
     def gemm_tn(self, Cm, A, B, alpha, mask=None):
         """Cm (m x n view) += alpha A^T B; A (k x m), B (k x n) views with unit column stride.  mask = (rb, cb, rblk0, Pr, pr, cblk0, Pc,
         pc): skip tiles entirely below the block diagonal of a block-cyclic local matrix."""
