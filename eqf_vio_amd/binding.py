@@ -19,6 +19,7 @@ SKIPPED_NOT_INITIALISED = 3
 SKIPPED_NO_BEARINGS = 4
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_UNSORTED, ERR_NUMERIC, ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6, -7
 PRECISION_F64, PRECISION_F32 = 0, 1
+GATE_CHORD, GATE_MAHALANOBIS = 0, 1
 PROF_CLASSES = 11
 
 _ERR_NAMES = {
@@ -72,6 +73,7 @@ EXPORTED_SYMBOLS = [
     "eqf_stream_upload", "eqf_stream_imu", "eqf_stream_vision", "eqf_synchronize", "eqf_get_time", "eqf_num_landmarks",
     "eqf_get_ids", "eqf_get_state_estimate", "eqf_get_origin", "eqf_get_group", "eqf_get_bias", "eqf_get_sigma",
     "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
+    "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
     "eqf_set_sigma", "eqf_set_state", "eqf_copy_filters", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
     "eqf_tiled_create", "eqf_tiled_destroy", "eqf_tiled_set_stream", "eqf_tiled_set_geometry", "eqf_tiled_propagate", "eqf_tiled_add_landmarks",
@@ -133,6 +135,10 @@ def lib():
             L.eqf_get_innovation_stats.argtypes = [vp, C.c_int, C.POINTER(InnovationStats), _dp]
         if hasattr(L, "eqf_get_nees"):
             L.eqf_get_nees.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, C.POINTER(SigmaStats)]
+        if hasattr(L, "eqf_set_outlier_gate"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
+            L.eqf_set_outlier_gate.argtypes = [vp, C.c_int, C.c_double]
+            L.eqf_get_outlier_gate.argtypes = [vp, _ip, _dp]
+            L.eqf_get_gate_report.argtypes = [vp, C.c_int, _ip, _ip, _dp, _ip]
         L.eqf_get_last_update.argtypes = [vp, C.c_int, _dp, _dp, _dp]
         L.eqf_set_state.argtypes = [vp, C.c_int, C.c_int, _ip] + [_dp] * 11 + [C.c_int, C.c_double, _dp, _dp, C.c_double, C.c_int]
         L.eqf_get_integrator.argtypes = [vp, C.c_int, _dp, _dp, _dp, _ip]
@@ -426,6 +432,27 @@ class FilterBatch:
         st, lm = InnovationStats(), np.zeros(max(N, 1))
         _check(lib().eqf_get_innovation_stats(self._h, b, C.byref(st), _p(lm)), "eqf_get_innovation_stats")
         return dict(nis=st.nis, logdet_S=st.logdet_S, loglik=st.loglik, dof=st.dof, valid=bool(st.valid), nis_lm=lm[:N] if st.valid else np.zeros(0))
+
+    def set_outlier_gate(self, kind, threshold):
+        """The handle's outlier gate (include/eqf_vio_amd.h: eqf_set_outlier_gate): GATE_CHORD, the reference's chord between measured and
+        predicted bearing, or GATE_MAHALANOBIS, d2 = delta_i^T (C_i Sigma_ii C_i^T + r I)^-1 delta_i (chi-square with 2 degrees of freedom:
+        consistency.chi2_gate_threshold(p)); a landmark goes when its number exceeds `threshold`.  From the next vision call on."""
+        _check(lib().eqf_set_outlier_gate(self._h, int(kind), float(threshold)), "eqf_set_outlier_gate")
+
+    def outlier_gate(self):
+        """(kind, threshold) of the handle's outlier gate."""
+        kind, thr = C.c_int(), C.c_double()
+        _check(lib().eqf_get_outlier_gate(self._h, C.byref(kind), C.byref(thr)), "eqf_get_outlier_gate")
+        return kind.value, thr.value
+
+    def gate_report(self, b=0):
+        """What the outlier gate of filter b's most recent vision call looked at: dict with ids (n,), stat (n,) -- the chord or d2 -- and
+        removed (n,) bool, in the state's order before the removals; n = 0 when the gate was disarmed or the call skipped."""
+        n = C.c_int()
+        ids, stat, rem = np.zeros(self.cap, dtype=np.int32), np.zeros(self.cap), np.zeros(self.cap, dtype=np.int32)
+        _check(lib().eqf_get_gate_report(self._h, b, C.byref(n), ids.ctypes.data_as(_ip), _p(stat), rem.ctypes.data_as(_ip)),
+               "eqf_get_gate_report")
+        return dict(ids=ids[: n.value].copy(), stat=stat[: n.value].copy(), removed=rem[: n.value].astype(bool))
 
     def nees(self, err=None, local=True, first=0):
         """Joint NEES e^T A^-1 e, log det A and the definiteness of A for EVERY filter of the handle in one call, A the trailing principal

@@ -12,6 +12,7 @@ to first order eps_loc = J eps with the block-diagonal J of local_jacobian_block
   nees_joint(Sigma, e, first)            the joint NEES e^T A^-1 e, log det A and the smallest pivot over the whole state or a trailing part of
                                          it -- the host counterpart of FilterBatch.nees (include/eqf_vio_amd.h: eqf_get_nees)
   systematic_resample(loglik, u)         log-likelihoods (FilterBatch.innovation_stats) -> parents for FilterBatch.resample
+  chi2_gate_threshold(p)                 the chi-square quantile (2 dof) for FilterBatch.set_outlier_gate(GATE_MAHALANOBIS, ...)
 
 `origin`, `group`, `estimate` are the dicts of FilterBatch.origin() / group() / state_estimate(): quaternions (w, x, y, z), Eigen semantics.
 """
@@ -196,6 +197,16 @@ def nees_joint(Sigma, e, first=0):
         z = np.linalg.solve(L, E.T)
         nees, logdet, mp = np.sum(z * z, axis=0), 2.0 * float(np.sum(np.log(d))), float(np.min(d * d))
     return dict(nees=float(nees[0]) if ev.ndim == 1 else nees, logdet=logdet, min_pivot=mp, dof=A.shape[0])
+
+
+def chi2_gate_threshold(p):
+    """Threshold of the Mahalanobis outlier gate that keeps an honest landmark with probability p: the quantile of the chi-square
+    distribution with 2 degrees of freedom, whose CDF is 1 - exp(-x / 2) -- exactly -2 ln(1 - p) (5.991 / 9.210 / 13.816 at 0.95 / 0.99 /
+    0.999).  It presumes a converged, consistent filter: while Sigma is as wide as initialPointVariance leaves it, d2 of a gross error is small."""
+    p = float(p)
+    if not 0.0 < p < 1.0:
+        raise ValueError("p must lie in (0, 1)")
+    return -2.0 * float(np.log1p(-p))
 
 
 def systematic_resample(loglik, u):

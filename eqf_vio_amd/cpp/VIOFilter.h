@@ -256,6 +256,27 @@ class VIOFilter {
         st.nis_lm.resize(st.valid ? size_t(N) : 0);
         return st;
     }
+    // The outlier gate (eqf_set_outlier_gate): EQF_GATE_CHORD, the reference's removeOutliers with settings->outlierThreshold (the default),
+    // or EQF_GATE_MAHALANOBIS, delta_i^T (C_i Sigma_ii C_i^T + r I)^-1 delta_i against a chi-square threshold (2 degrees of freedom:
+    // -2 ln(1 - p)).  From the next vision call on; throws std::runtime_error for an unknown kind, a NaN or (kind 1) non-positive threshold.
+    void setOutlierGate(int kind, double threshold) { check(eqf_set_outlier_gate(handle_.get(), kind, threshold), "eqf_set_outlier_gate"); }
+    // What the gate of the most recent vision call examined (eqf_get_gate_report): ids, chord or d2, and whether the landmark was thrown
+    // out, in the state's order before the removals; empty when the gate was disarmed or the call skipped.
+    struct GateReport {
+        std::vector<int> ids;
+        std::vector<double> stat;
+        std::vector<int> removed;
+    };
+    GateReport gateReport() const {
+        GateReport r;
+        int n = 0;
+        check(eqf_get_gate_report(handle_.get(), 0, &n, nullptr, nullptr, nullptr), "eqf_get_gate_report");
+        r.ids.resize(n);
+        r.stat.resize(n);
+        r.removed.resize(n);
+        check(eqf_get_gate_report(handle_.get(), 0, &n, r.ids.data(), r.stat.data(), r.removed.data()), "eqf_get_gate_report");
+        return r;
+    }
     // Joint NEES err^T A^-1 err with log det A, the smallest pivot and the definiteness word (eqf_get_nees): A = the covariance in the
     // coordinates of the estimate (local) or of the origin, from reference index `first` (0 whole state | 6 without the bias | 11 landmarks
     // only) on; err has 11 + 3 N entries in Sigma's index map (those below `first` are ignored).  A matrix that is not positive definite is

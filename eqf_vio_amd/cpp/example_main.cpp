@@ -1,6 +1,6 @@
 // Minimal C++ caller of the facade, shaped like the reference's offline runner (eqf_vio/src/main.cpp:111-170):
 // events are interleaved by "imu.stamp < meas.stamp", the state is read after every vision call.
-// Usage: eqf_example <N landmarks> <frames> [aux | level | init | local | nees | clone]  -- runs a small synthetic sequence and prints the final
+// Usage: eqf_example <N landmarks> <frames> [aux | level | init | local | nees | clone | gate]  -- runs a small synthetic sequence and prints the final
 // pose and |Sigma|_F.  With "aux" the filter starts from AuxiliaryFilterData + setInertialPoints (VIOFilter.cpp:51-58,
 // 74-118) instead of the gravity alignment at the first IMU sample; with "init" from an explicit initialiseFromIMUData
 // call (VIOFilter.cpp:133-144; same result as the lazy one).  With "level" the vehicle rests level: the reference's gravity
@@ -14,6 +14,10 @@
 // With "clone", after frames / 2 frames a second VIOFilter with twice the measurement variance is forked off the first
 // (VIOFilter::copyStateFrom) and both run on; after the last frame one line each, "clone_a" for the first and "clone_b" for the fork: N,
 // then pose q (4), pose x (3), velocity (3) and the n x n covariance as hexadecimal floats.
+// With "gate" the filter runs under the Mahalanobis outlier gate (VIOFilter::setOutlierGate) at threshold 0.5; bearing i of frame f is
+// disturbed by 1e-3 (sin(7 i + 3 f), cos(5 i + 2 f), 0) before it is normalised (an exact measurement leaves residuals of rounding size), the
+// bearing of landmark 3 is turned by 0.2 rad about the x axis on frame frames - 3, and after every frame one line follows: "gate" frame n, then per examined landmark
+// its id, the statistic as a hexadecimal float and the removed flag (VIOFilter::gateReport).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -38,6 +42,7 @@ int main(int argc, char** argv) {
     const bool local = argc > 3 && std::string(argv[3]) == "local";
     const bool nees = argc > 3 && std::string(argv[3]) == "nees";
     const bool clone = argc > 3 && std::string(argv[3]) == "clone";
+    const bool gate = argc > 3 && std::string(argv[3]) == "gate";
     std::unique_ptr<VIOFilter> fork;
     auto printState = [](const char* tag, const VIOFilter& flt) {
         const VIOState e = flt.stateEstimate();
@@ -78,6 +83,7 @@ int main(int argc, char** argv) {
     if (level) imu.accel = {0, 0, GRAVITY_CONSTANT};
     if (init) filter.initialiseFromIMUData(imu);
     if (local) filter.setOption("innovation_stats", 1);
+    if (gate) filter.setOutlierGate(EQF_GATE_MAHALANOBIS, 0.5);
     int k = 0;
     try {
     for (int f = 0; f < frames; ++f) {
@@ -93,10 +99,28 @@ int main(int argc, char** argv) {
         for (int i = 0; i < N; ++i) {
             const double n = std::sqrt(lm[i][0] * lm[i][0] + lm[i][1] * lm[i][1] + lm[i][2] * lm[i][2]);
             meas.bearings[i].p = {lm[i][0] / n, lm[i][1] / n, lm[i][2] / n};
+            if (gate) {
+                Vector3d& p = meas.bearings[i].p;
+                p[0] += 1e-3 * std::sin(7.0 * i + 3.0 * f);
+                p[1] += 1e-3 * std::cos(5.0 * i + 2.0 * f);
+                const double m = std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+                p = {p[0] / m, p[1] / m, p[2] / m};
+            }
             meas.bearings[i].id = aux ? 100 + 2 * i : i;
+        }
+        if (gate && f == frames - 3 && N > 3) {
+            const Vector3d y = meas.bearings[3].p;
+            const double c = std::cos(0.2), sn = std::sin(0.2);
+            meas.bearings[3].p = {y[0], c * y[1] - sn * y[2], sn * y[1] + c * y[2]};
         }
         filter.processVisionData(meas);
         if (fork) fork->processVisionData(meas);
+        if (gate) {
+            const VIOFilter::GateReport r = filter.gateReport();
+            std::printf("gate %d %zu", f, r.ids.size());
+            for (size_t i = 0; i < r.ids.size(); ++i) std::printf(" %d %a %d", r.ids[i], r.stat[i], r.removed[i]);
+            std::printf("\n");
+        }
         const VIOState est = filter.stateEstimate();
         if (clone && f + 1 == frames / 2) {
             VIOFilter::Settings s2 = s;

@@ -167,6 +167,18 @@ struct eqf_filter {
     int csInBurst = 1;           // bursts closed by a vision step also leave C Sigma' and S (BurstArgs::csOut; eqf_debug_option "cs_in_burst")
     bool csValid = false;        // ... and they are still what the update would compute (nothing moved a landmark since)
     int gateSpeculative = 1;     // EQF_GATE_SPECULATIVE = 0: always wait for the gate's answer before the update
+    // the outlier gate of the handle (eqf_set_outlier_gate): what is compared -- the chord or the Mahalanobis distance -- and with what.
+    // eqf_create sets (EQF_GATE_CHORD, settings.outlierThreshold); a setting, not state: eqf_reset / eqf_set_state / eqf_copy_filters leave it
+    int gateKind = EQF_GATE_CHORD;
+    double gateThr = 0.0;
+    // eqf_get_gate_report: what the gate of the most recent vision call looked at, per filter, in the state's order before the removals --
+    // taken from the pinned hChord where the host applies the device's decision (recordGate); empty: not examined
+    struct GateReport {
+        std::vector<int> ids;
+        std::vector<double> stat;
+        std::vector<char> removed;
+    };
+    std::vector<GateReport> report;
     // IMU bursts (eqf_burst.hpp): processIMUData calls are queued on the host and launched together -- when the queue is
     // full, when the vision call that follows them arrives (whose integrateUpToTime joins the burst), or when the host
     // touches the handle in any other way.  burstMax = 0: every call launches at once through k_propagate.
@@ -356,6 +368,7 @@ int initState(eqf_filter* f) {
     f->csValid = false;
     f->editOnDevice.clear();
     f->ids.assign(B, {});
+    f->report.assign(B, {});
     f->curTime.assign(B, -1.0);
     f->init.assign(B, 0);
     f->devInit.assign(B, 0);
@@ -378,6 +391,24 @@ int maxN(const eqf_filter* f) {
     size_t m = 0;
     for (auto& v : f->ids) m = std::max(m, v.size());
     return int(m);
+}
+
+// Can the handle's gate remove anything?  A chord between unit vectors never exceeds 2; a Mahalanobis distance is finite.
+bool gateCanTrip(const eqf_filter* f) { return f->gateKind == EQF_GATE_MAHALANOBIS ? f->gateThr < HUGE_VAL : f->gateThr < 2.0; }
+MahaArgs mahaArgs(const eqf_filter* f) {
+    return MahaArgs{f->lmc, static_cast<const double*>(f->Sigma[f->pS]), f->sigmaStride, f->ld, f->set.measurementVariance};
+}
+// The report of filter b: its first n landmarks (ids as the host holds them BEFORE it applies the decision) with the statistics the device left
+// in pinned memory; `tripped`: the device acted on them (a filter it did not flag has none above the threshold anyway)
+void recordGate(eqf_filter* f, int b, int n, bool tripped) {
+    auto& r = f->report[b];
+    n = std::min(n, int(f->ids[b].size()));
+    const double* st = f->hChord + (size_t)b * f->cap;
+    r.ids.assign(f->ids[b].begin(), f->ids[b].begin() + n);
+    r.stat.assign(st, st + n);
+    r.removed.assign(n, 0);
+    if (tripped)
+        for (int i = 0; i < n; ++i) r.removed[i] = st[i] > f->gateThr;
 }
 
 // Slot of the record ring holding `recs` ([B]) on the device; B == 1 passes the record inline.
@@ -1147,9 +1178,15 @@ int probe(eqf_filter* f, const double* bearings, long long bearStride, bool with
     const int nmax = std::max(1, maxN(f));
     // with readback the kernel writes the chords straight into pinned host memory (no copy command behind it)
     double* chordDst = (readback || speculative) ? f->hChordDev : f->dChord;  // (speculative: resolveGate reads them if the gate tripped)
+    // (the Mahalanobis statistic only where a gate looks at it: the depth-only probe of addNewAndUpdate stays k_probe)
+    const bool maha = f->gateKind == EQF_GATE_MAHALANOBIS && bearings && (readback || speculative);
     int rc = profiled(f, EQF_PROF_CHURN, [&] {
-        hipLaunchKernelGGL(k_probe, dim3((nmax + 127) / 128, B), dim3(128), 0, f->stream, f->g[f->pG], f->p0, f->Q[f->pG], cap, bearings,
-            bearStride, withPerm ? f->dPerm : nullptr, chordDst, f->dDepth2, f->set.outlierThreshold, speculative ? f->hGateDev : nullptr);
+        if (maha)
+            hipLaunchKernelGGL(k_probe_maha, dim3((nmax + 127) / 128, B), dim3(128), 0, f->stream, f->g[f->pG], f->p0, f->Q[f->pG], cap, bearings,
+                bearStride, withPerm ? f->dPerm : nullptr, chordDst, f->dDepth2, f->gateThr, speculative ? f->hGateDev : nullptr, mahaArgs(f));
+        else
+            hipLaunchKernelGGL(k_probe, dim3((nmax + 127) / 128, B), dim3(128), 0, f->stream, f->g[f->pG], f->p0, f->Q[f->pG], cap, bearings,
+                bearStride, withPerm ? f->dPerm : nullptr, chordDst, f->dDepth2, f->gateThr, speculative ? f->hGateDev : nullptr);
     });
     if (rc) return rc;
     if (readback) HIPC(hipStreamSynchronize(f->stream));
@@ -1256,7 +1293,8 @@ int visionOneLaunch(eqf_filter* f, const frame::Meas& m, const double* bearings,
     ea.permOut = f->dPerm;
     ea.B = B; ea.cap = cap;
     ea.bearings = bearings; ea.bearStride = bearStride;
-    ea.gateThr = f->set.outlierThreshold;
+    ea.gateThr = f->gateThr;
+    ea.measVar = f->set.measurementVariance;
     ea.gateFlag = gateArmed ? f->hGateDev : nullptr;
     ea.chordOut = gateArmed ? f->hChordDev : nullptr;
     ea.depthDefault = f->set.initialSceneDepth; ea.pointVar = f->set.initialPointVariance;
@@ -1271,7 +1309,10 @@ int visionOneLaunch(eqf_filter* f, const frame::Meas& m, const double* bearings,
     const int coRes = std::max(1, std::min(64, std::max(f->numCUs, 1) / B));
     const int G = (anyLost || !gateArmed) ? std::max(coRes, std::min(1024, (kLm0 + 3 * plan.Nmax + 3) / 4)) : coRes;  // (no gate: nothing can trip)
     rc = profiled(f, EQF_PROF_CHURN, [&] {
-        withSigmaType(f, [&](auto t) { hipLaunchKernelGGL(k_edit<decltype(t)>, dim3(G, B), dim3(256), 0, f->stream, ea); });
+        if (gateArmed && f->gateKind == EQF_GATE_MAHALANOBIS)  // (fp64 handles only: eqf_set_outlier_gate)
+            hipLaunchKernelGGL((k_edit<double, 1>), dim3(G, B), dim3(256), 0, f->stream, ea);
+        else
+            withSigmaType(f, [&](auto t) { hipLaunchKernelGGL((k_edit<decltype(t), 0>), dim3(G, B), dim3(256), 0, f->stream, ea); });
     });
     if (rc) return rc;
     HIPC(hipGetLastError());
@@ -1402,7 +1443,7 @@ int visionSeparate(eqf_filter* f, const frame::Meas& m, const double* bearings, 
     frame::Marks dropped(B);  // measurement indices erased together with their landmark
     for (int b = 0; b < B; ++b) dropped[b].assign(m.n[b], 0);
     if (gated) dropped = *gated;
-    const bool gateOn = !gated && f->set.outlierThreshold < 2.0 && maxN(f) > 0;
+    const bool gateOn = !gated && gateCanTrip(f) && maxN(f) > 0;
     bool depthFresh = false;
     if (gateOn && f->gateSpeculative && !f->gate.pending) {  // (lost landmarks are already compacted away)
         rc = gateSpeculatively(f, m, bearings, bearStride, perm);
@@ -1413,7 +1454,9 @@ int visionSeparate(eqf_filter* f, const frame::Meas& m, const double* bearings, 
         rc = identityPerm ? EQF_OK : uploadPerm(f, perm);
         if (!rc) rc = probe(f, bearings, bearStride, !identityPerm, true);
         if (rc) return rc;
-        const bool anyOut = frame::gateSync(f->ids, perm, m.active, f->hChord, f->cap, f->set.outlierThreshold, keep, dropped);
+        for (int b = 0; b < B; ++b)
+            if (m.active[b]) recordGate(f, b, int(f->ids[b].size()), true);
+        const bool anyOut = frame::gateSync(f->ids, perm, m.active, f->hChord, f->cap, f->gateThr, keep, dropped);
         if (anyOut) {
             rc = compactIds(f, keep);
             if (rc) return rc;
@@ -1434,6 +1477,7 @@ int visionCore(eqf_filter* f, const std::vector<const int*>& measIds, const std:
     // innovation statistics: every filter's record starts the vision call with valid = 0; k_innov_stats sets it for the filters whose
     // update runs (a redo of a gated frame only concerns the filters it flags: the others keep what the first pass left)
     if (f->innovStats && !gated) HIPC(hipMemsetAsync(f->dInnov, 0, sizeof(double) * (size_t)(kInnovHead + f->cap) * f->B, f->stream));
+    if (!gated) f->report.assign(f->B, {});  // (eqf_get_gate_report describes THIS call from here on)
     const frame::Meas m{measIds, nb, active};
     // ---- removeOldLandmarks (VIOFilter.cpp:393-419): state ids absent from the measurement
     frame::Lists keep;
@@ -1441,7 +1485,7 @@ int visionCore(eqf_filter* f, const std::vector<const int*>& measIds, const std:
     // The one-launch path is not for a redo itself, filters beyond kEditMax landmarks, a gate whose previous answer is still pending or
     // switched to the synchronous mode, and -- gate armed -- filters so small that losing a landmark could make their two chains equally
     // long (the update's launch shape is chosen from the host's count).
-    const bool gateArmed = !gated && f->set.outlierThreshold < 2.0 && maxN(f) > 0;
+    const bool gateArmed = !gated && gateCanTrip(f) && maxN(f) > 0;
     const bool handleOk = f->deviceEdit && !gated && f->dEdit && (!gateArmed || (f->gateSpeculative && !f->gate.pending));
     const frame::EditChoice e = frame::editEligible(f->ids, keep, m, handleOk, gateArmed, kEditMax, kEditSafeN);
     if (e.ok && (anyLost || e.anyFresh || gateArmed)) return visionOneLaunch(f, m, bearings, bearStride, status, keep, anyLost, gateArmed);
@@ -1461,7 +1505,9 @@ int resolveGate(eqf_filter* f) {
         // k_edit took the outliers out before the update ran: the ids follow (kept landmark j of the frame is f->ids[b][j])
         // (flag 2: the outliers left the filter with so few landmarks that k_edit switched the queued update off -- it runs now, shaped for
         // the count the host knows by now; nothing else of the frame is repeated)
-        const frame::DeviceGate d = frame::gateOnDevice(f->ids, f->hGate, f->gate.active, f->gate.nKept, f->hChord, cap, f->set.outlierThreshold);
+        for (int b = 0; b < B; ++b)
+            if (f->gate.active[b]) recordGate(f, b, f->gate.nKept[b], f->hGate[b] != 0);
+        const frame::DeviceGate d = frame::gateOnDevice(f->ids, f->hGate, f->gate.active, f->gate.nKept, f->hChord, cap, f->gateThr);
         if (!d.deferred) return EQF_OK;
         int rc = launchSetUpdateOk(f);
         if (rc) return rc;
@@ -1474,7 +1520,9 @@ int resolveGate(eqf_filter* f) {
     std::vector<char> act;
     frame::Lists keep;
     frame::Marks gated;
-    if (!frame::gateRedo(f->ids, f->hGate, f->gate.active, f->gate.ids, f->gate.nb, f->gate.nOld, f->hChord, cap, f->set.outlierThreshold, act, keep, gated))
+    for (int b = 0; b < B; ++b)
+        if (f->gate.active[b]) recordGate(f, b, f->gate.nOld[b], f->hGate[b] != 0);
+    if (!frame::gateRedo(f->ids, f->hGate, f->gate.active, f->gate.ids, f->gate.nb, f->gate.nOld, f->hChord, cap, f->gateThr, act, keep, gated))
         return EQF_OK;
     int rc = launchSetUpdateOk(f);
     if (!rc) rc = compactIds(f, keep);
@@ -1640,6 +1688,7 @@ int eqf_create(const eqf_settings* settings, int capacity_landmarks, int batch, 
     f->precision = precision;
     f->esz = precision == EQF_PRECISION_F32 ? 4 : 8;
     f->set = *settings;
+    f->gateThr = settings->outlierThreshold;
     Params& p = f->prm;
     p.biasOmegaProcessVariance = settings->biasOmegaProcessVariance;
     p.biasAccelProcessVariance = settings->biasAccelProcessVariance;
@@ -2257,6 +2306,7 @@ int eqf_set_state(eqf_filter* f, int b, int N, const int* ids, const double* pos
     HIPC(hipMemcpy(f->p0 + (size_t)b * 3 * cap, tp.data(), sizeof(double) * 3 * cap, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(f->Q[f->pG] + (size_t)b * 5 * cap, tq.data(), sizeof(double) * 5 * cap, hipMemcpyHostToDevice));
     f->ids[b].assign(ids, ids + N);
+    f->report[b] = {};
     f->curTime[b] = currentTime;
     f->init[b] = initialised ? 1 : 0;
     f->devInit[b] = f->init[b];
@@ -2442,6 +2492,7 @@ int eqf_copy_filters(eqf_filter* dst, eqf_filter* src, int n, const int* dst_idx
     for (size_t k = 0; k < pairs.size(); ++k) {
         const int d = pairs[k].dst;
         dst->ids[d] = std::move(ids[k]); dst->curTime[d] = t[k]; dst->init[d] = ini[k]; dst->devInit[d] = dini[k];
+        dst->report[d] = {};  // (the gate and its threshold are settings: they stay dst's)
     }
     dst->csValid = false;
     dst->permOnDevice.clear();
@@ -2633,6 +2684,34 @@ int eqf_set_option(eqf_filter* f, const char* name, int value) {
         return EQF_OK;
     }
     return EQF_ERR_INVALID;
+}
+
+int eqf_set_outlier_gate(eqf_filter* f, int kind, double threshold) {
+    if (!f || (kind != EQF_GATE_CHORD && kind != EQF_GATE_MAHALANOBIS) || threshold != threshold) return EQF_ERR_INVALID;
+    if (kind == EQF_GATE_MAHALANOBIS && !(threshold > 0.0)) return EQF_ERR_INVALID;
+    if (kind == EQF_GATE_MAHALANOBIS && f->precision == EQF_PRECISION_F32) return EQF_ERR_UNSUPPORTED;
+    GATE(f);  // (a pending speculative gate is resolved with the kind and the threshold it was evaluated under)
+    f->gateKind = kind;
+    f->gateThr = threshold;
+    return EQF_OK;
+}
+
+int eqf_get_outlier_gate(eqf_filter* f, int* kind, double* threshold) {
+    if (!f) return EQF_ERR_INVALID;
+    if (kind) *kind = f->gateKind;
+    if (threshold) *threshold = f->gateThr;
+    return EQF_OK;
+}
+
+int eqf_get_gate_report(eqf_filter* f, int b, int* n, int* ids, double* stat, int* removed) {
+    if (!f || b < 0 || b >= f->B || !n) return EQF_ERR_INVALID;
+    GATE(f);
+    const auto& r = f->report[b];
+    *n = int(r.ids.size());
+    if (ids) std::copy(r.ids.begin(), r.ids.end(), ids);
+    if (stat) std::copy(r.stat.begin(), r.stat.end(), stat);
+    if (removed) std::copy(r.removed.begin(), r.removed.end(), removed);
+    return EQF_OK;
 }
 
 int eqf_get_innovation_stats(eqf_filter* f, int b, eqf_innovation_stats* out, double* nis_lm) {

@@ -41,6 +41,71 @@ __global__ void k_probe(Glob* g, const double* p0, const double* Q, int cap, con
         gateFlag[b] = 1;
     }
 }
+// The Mahalanobis gate's statistic (eqf_set_outlier_gate, kind 1): d2 = delta_i^T (C_i Sigma_ii C_i^T + r I)^-1 delta_i of ONE landmark, from
+// what belongs to it alone -- C0 is block diagonal (EqFMatrices.cpp:319-344), so the 2 x 2 diagonal block of S needs no other landmark
+// and no factorisation.  delta_i is the residual the update will form (k_update_prep64: yerr = R(Q_i) y, delta = e3ProjectSphere(R_s yerr));
+// c[0..5] = C_i (2 x 3), c[6..14] = R_s, both from lmc; S = Sigma_ii (3 x 3, row-major) of the Sigma the update will read; r =
+// measurementVariance.  The 2 x 2 Cholesky and the solve are k_innov_stats' (eqf_innov.hpp), on the LOWER triangle like the chain.
+EQF_DI double gateMahalanobis(const quat Qq, const d3 y, const double* c, const double* S, double r) {
+    const d3 yerr = qrot(qinv(qinv(Qq)), y);
+    m33 Rs;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rs.a[k] = c[6 + k];
+    const d3 rr = mv33(Rs, yerr);
+    const double d0 = rr.x / (1 - rr.z), d1 = rr.y / (1 - rr.z);  // VIOState.cpp:199-204
+    double T[6];  // C Sigma_ii (2 x 3)
+#pragma unroll
+    for (int rw = 0; rw < 2; ++rw)
+#pragma unroll
+        for (int cc = 0; cc < 3; ++cc) T[3 * rw + cc] = dot3(c[3 * rw], S[cc], c[3 * rw + 1], S[3 + cc], c[3 * rw + 2], S[6 + cc]);
+    const double s00 = dot3(T[0], c[0], T[1], c[1], T[2], c[2]) + r;
+    const double s10 = dot3(T[3], c[0], T[4], c[1], T[5], c[2]);
+    const double s11 = dot3(T[3], c[3], T[4], c[4], T[5], c[5]) + r;
+    const double l00 = sqrt(s00), l10 = s10 / l00, l11 = sqrt(fma(-l10, l10, s11));
+    const double w0 = d0 / l00, w1 = fma(-l10, w0, d1) / l11;
+    return fma(w1, w1, w0 * w0);
+}
+// What the Mahalanobis gate reads besides k_probe's / k_edit's own arguments (fp64 handles only)
+struct MahaArgs {
+    const double* lmc;     // [B][15][cap]
+    const double* S;       // the current Sigma
+    long long sigmaStride;
+    int ld;
+    double measVar;
+};
+// k_probe under the Mahalanobis gate: the same outputs, with d2 in the chord's place.  A kernel of its own, so that k_probe stays the code it is.
+__global__ void k_probe_maha(Glob* g, const double* p0, const double* Q, int cap, const double* bearings, long long bearStride, const int* perm,
+    double* stat, double* depth2, double gateThr, int* gateFlag, MahaArgs ma) {
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= g[b].N) return;
+    const double* P = p0 + (long long)b * 3 * cap;
+    const double* q = Q + (long long)b * 5 * cap;
+    const int k = perm ? perm[(long long)b * cap + i] : i;
+    // (everything the landmark needs is requested before anything is computed: one round trip behind the permutation entry)
+    double yv[3] = {0.0, 0.0, 1.0}, c[15], S[9];
+    if (k >= 0) {
+        const double* y = bearings + (long long)b * bearStride + 3 * k;
+        yv[0] = y[0]; yv[1] = y[1]; yv[2] = y[2];
+        const double* lc = ma.lmc + (long long)b * 15 * cap + i;
+#pragma unroll
+        for (int e = 0; e < 15; ++e) c[e] = lc[(long long)e * cap];
+        const double* d = ma.S + (long long)b * ma.sigmaStride + (long long)(kLm0 + 3 * i) * ma.ld + kLm0 + 3 * i;
+#pragma unroll
+        for (int rw = 0; rw < 3; ++rw)
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc) S[3 * rw + cc] = d[(long long)rw * ma.ld + cc];
+    }
+    const quat Qq = quat{q[i], q[cap + i], q[2 * cap + i], q[3 * cap + i]};
+    const d3 qhat = scl(1.0 / q[4 * cap + i], qrot(qinv(Qq), mk3(P[i], P[cap + i], P[2 * cap + i])));
+    depth2[(long long)b * cap + i] = dot3(qhat, qhat);
+    const double st = k >= 0 ? gateMahalanobis(Qq, mk3(yv[0], yv[1], yv[2]), c, S, ma.measVar) : 0.0;
+    stat[(long long)b * cap + i] = st;
+    if (gateFlag && st > gateThr) {
+        g[b].updateOk = 0;
+        gateFlag[b] = 1;
+    }
+}
 // updateOk[b] = mask[b] (redo of a speculatively skipped update: only the flagged filters take part)
 __global__ void k_set_update_ok(Glob* g, const int* mask, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -259,8 +324,11 @@ struct EditArgs {
     long long sigmaStride;
     int ld, hostFlip;
     int* bar;               // [B][4] barrier arrivals, barrier generation, first-phase arrivals, - (zero-initialised once)
+    double measVar;         // KIND 1 only: measurementVariance (the statistic also reads lmc and Scur)
 };
-template <typename T>
+// KIND: what the gate compares with gateThr -- 0 the chord (removeOutliers as the reference has it), 1 the Mahalanobis distance
+// (gateMahalanobis, in chordOut as well; T = double).  Everything behind `keep` is the same code.
+template <typename T, int KIND = 0>
 __global__ __launch_bounds__(256) void k_edit(EditArgs a) {
     const int b = blockIdx.y, w = blockIdx.x, G = gridDim.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int cap = a.cap;
@@ -291,6 +359,20 @@ __global__ __launch_bounds__(256) void k_edit(EditArgs a) {
                 const double* y = a.bearings + (long long)b * a.bearStride + 3 * k;
                 yv[0] = y[0]; yv[1] = y[1]; yv[2] = y[2];
             }
+            // (KIND 1: the landmark's 15 constants and its block of Sigma, at the OLD index, leave in the same round trip as the bearing)
+            [[maybe_unused]] double c[15], S[9];
+            if constexpr (KIND == 1) {
+                if (gate && k >= 0) {
+                    const double* lc = a.lmc + (long long)b * 15 * cap + o;
+#pragma unroll
+                    for (int e = 0; e < 15; ++e) c[e] = lc[(long long)e * cap];
+                    const double* d = static_cast<const double*>(a.Scur) + (long long)b * a.sigmaStride + (long long)(kLm0 + 3 * o) * a.ld + kLm0 + 3 * o;
+#pragma unroll
+                    for (int rw = 0; rw < 3; ++rw)
+#pragma unroll
+                        for (int cc = 0; cc < 3; ++cc) S[3 * rw + cc] = d[(long long)rw * a.ld + cc];
+                }
+            }
             const quat Qq = quat{q[o], q[cap + o], q[2 * cap + o], q[3 * cap + o]};
             const d3 qhat = scl(1.0 / q[4 * cap + o], qrot(qinv(Qq), mk3(P[o], P[cap + o], P[2 * cap + o])));
             sD2[j] = dot3(qhat, qhat);
@@ -298,7 +380,8 @@ __global__ __launch_bounds__(256) void k_edit(EditArgs a) {
             if (gate) {
                 if (k >= 0) {
                     const double* y = yv;
-                    ch = nrm3(sub(mk3(y[0], y[1], y[2]), unit3(qhat)));
+                    if constexpr (KIND == 1) ch = gateMahalanobis(Qq, mk3(y[0], y[1], y[2]), c, S, a.measVar);
+                    else ch = nrm3(sub(mk3(y[0], y[1], y[2]), unit3(qhat)));
                 }
                 if (w == 0 && a.chordOut) a.chordOut[(long long)b * cap + j] = ch;
             }

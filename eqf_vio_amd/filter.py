@@ -140,6 +140,19 @@ class VIOFilter:
         first); include/eqf_vio_amd.h: eqf_get_innovation_stats."""
         return self._fb.innovation_stats(0)
 
+    def setOutlierGate(self, kind, threshold):
+        """Which number removeOutliers compares with its threshold: binding.GATE_CHORD (the reference's chord, the default with
+        settings.outlierThreshold) or binding.GATE_MAHALANOBIS (chi-square with 2 degrees of freedom; consistency.chi2_gate_threshold);
+        include/eqf_vio_amd.h: eqf_set_outlier_gate."""
+        self._fb.set_outlier_gate(kind, threshold)
+
+    def outlierGate(self):
+        return self._fb.outlier_gate()
+
+    def gateReport(self):
+        """ids, statistic and removed flag of every landmark the gate of the most recent vision call examined; eqf_get_gate_report."""
+        return self._fb.gate_report(0)
+
     def stateNEES(self, err, local=True, first=0):
         """Joint NEES err^T A^-1 err, log det A, smallest pivot, dof and the definiteness word `info` of the covariance from reference index
         `first` on, in the coordinates of the estimate (local) or of the origin; include/eqf_vio_amd.h: eqf_get_nees."""

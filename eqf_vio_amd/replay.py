@@ -93,8 +93,11 @@ def format_state(t, est):
     return ", ".join(vals)
 
 
-def replay(filt, imu, frames, start_time=0.0, out=None):
-    """Drives `filt` through the two streams; returns (#imu processed, #vision processed, list of (t, state))."""
+def replay(filt, imu, frames, start_time=0.0, out=None, gate=None):
+    """Drives `filt` through the two streams; returns (#imu processed, #vision processed, list of (t, state)).
+    gate: (kind, threshold) handed to filt.setOutlierGate before the first event (None: the filter's own gate)."""
+    if gate is not None:
+        filt.setOutlierGate(*gate)
     k, f = 0, 0
     n_imu = n_vis = 0
     states = []
@@ -126,6 +129,8 @@ def main(argv=None):
     ap.add_argument("config_file", nargs="?")
     ap.add_argument("-o", "--output")
     ap.add_argument("--capacity", type=int, default=256)
+    ap.add_argument("--gate", nargs=2, metavar=("KIND", "THRESHOLD"),
+                    help="outlier gate: chord | mahalanobis and its threshold (default: the chord gate at outlierThreshold)")
     args = ap.parse_args(argv)
     from .filter import VIOFilter
 
@@ -134,7 +139,8 @@ def main(argv=None):
     imu = read_imu_csv(args.imu_file)
     frames = read_vision_csv(args.meas_file)
     out = open(args.output, "w") if args.output else None
-    n_imu, n_vis, _ = replay(filt, imu, frames, start, out)
+    gate = None if not args.gate else ({"chord": 0, "mahalanobis": 1}[args.gate[0]], float(args.gate[1]))
+    n_imu, n_vis, _ = replay(filt, imu, frames, start, out, gate=gate)
     if out:
         out.close()
     print(f"Processed {n_imu} IMU and {n_vis} vision measurements.")  # main.cpp:172-173

@@ -243,6 +243,37 @@ typedef struct eqf_innovation_stats {
     int valid;
 } eqf_innovation_stats;
 int eqf_get_innovation_stats(eqf_filter* f, int b, eqf_innovation_stats* out, double* nis_lm);
+/* The outlier gate of a handle: which number removeOutliers (VIOFilter.cpp:429-443) compares with its threshold, for every landmark that is
+ * in the state after removeOldLandmarks (the frame's new landmarks are not examined, as in the reference), before the update:
+ *   EQF_GATE_CHORD        the reference's: |y_i - yHat_i|, the chord between the measured and the predicted bearing -- the same for a
+ *                         landmark initialised a frame ago and a converged one;
+ *   EQF_GATE_MAHALANOBIS  d2_i = delta_i^T (C_i Sigma_ii C_i^T + r I)^-1 delta_i: the residual delta_i the update will form, against the 2 x 2
+ *                         diagonal block of S from the landmark's own 3 x 3 block of the CURRENT Sigma and r = measurementVariance -- what
+ *                         eqf_get_innovation_stats reports as nis_lm[i], but BEFORE the outlier is absorbed.  Chi-square with 2 degrees of
+ *                         freedom for a consistent filter: the quantile at probability p is -2 ln(1 - p) (5.991 / 9.210 / 13.816 at 0.95 /
+ *                         0.99 / 0.999).  A quantile is a threshold for a CONVERGED filter: while Sigma is still as wide as
+ *                         initialPointVariance leaves it, a gross error (0.2 rad) measures d2 of about 2.
+ * A landmark goes when its number is GREATER than the threshold (a NaN stays).  Both kinds are decided and carried out on the device, in the
+ * launches of the frame (csrc/eqf_churn.hpp); O(1) per landmark, no factorisation (C0 is block diagonal, EqFMatrices.cpp:319-344).
+ * Until eqf_set_outlier_gate is called a handle is (EQF_GATE_CHORD, settings.outlierThreshold), and every launch and output bit are what they
+ * were before this call existed.  The setter first settles what the handle has deferred (queued IMU calls; a pending gate answer is
+ * resolved with the OLD kind and threshold) and takes effect at the next vision call, per call and in stream mode alike.  The chord gate is
+ * disarmed from threshold 2 on, the Mahalanobis gate at +inf: no probe, no read of pinned memory.  EQF_ERR_INVALID, before any effect, for an
+ * unknown kind, a NaN threshold, or kind 1 with threshold <= 0; EQF_ERR_UNSUPPORTED for kind 1 on an EQF_PRECISION_F32 handle.  The gate is a
+ * setting of the handle: eqf_reset keeps it, eqf_set_state does not touch it, eqf_copy_filters does not copy it (settings stay dst's);
+ * eqf_settings and settings.outlierThreshold are unchanged.
+ * eqf_get_gate_report: what the gate of the most recent vision call of filter b looked at -- *n landmarks, in the state's order before the
+ * removals: their ids, the chord or d2, and removed[i] = 1 for those thrown out.  ids / stat / removed hold capacity entries, any may be
+ * NULL.  *n = 0 when the gate was disarmed, the call was skipped, the filter had no landmarks, after eqf_reset, and for a filter that
+ * eqf_set_state or eqf_copy_filters has overwritten since.  The numbers are the ones the device left in pinned memory for the host's id
+ * bookkeeping: the report costs no transfer.  Flushes and resolves like every getter.
+ * Out of scope: the partitioned filter (eqf_tf_*, eqf_tiled_*) keeps its host-side chord gate -- a landmark's diagonal block lives on one
+ * rank of the grid, a gate on it needs an exchange; fp32 handles (kind 1 refused). */
+#define EQF_GATE_CHORD 0       /* removeOutliers as the reference has it: |y - yHat| > threshold */
+#define EQF_GATE_MAHALANOBIS 1 /* delta_i^T (C_i Sigma_ii C_i^T + r I)^-1 delta_i > threshold, chi-square with 2 dof */
+int eqf_set_outlier_gate(eqf_filter* f, int kind, double threshold);
+int eqf_get_outlier_gate(eqf_filter* f, int* kind, double* threshold);
+int eqf_get_gate_report(eqf_filter* f, int b, int* n, int* ids, double* stat, int* removed);
 /* The joint NEES e^T A^-1 e, log det A and the definiteness of the covariance, for EVERY filter of the handle in one call, from a batched
  * Cholesky factorisation A = L L^T with the forward solve z = L^-1 e on the device (csrc/eqf_nees.hpp) -- the marginals of
  * eqf_get_marginals ignore every landmark-landmark and landmark-base correlation, and the host route is eqf_get_sigma_local for every filter

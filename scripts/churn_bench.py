@@ -1,5 +1,7 @@
 """Dev tool: cost of landmark churn.  A pool of 260 landmarks, ~200 visible, a few entering / leaving every frame
-(VIOFilter.cpp:345-443 path: removeOldLandmarks, addNewLandmarks with median depth); per-call API (host buffers)."""
+(VIOFilter.cpp:345-443 path: removeOldLandmarks, addNewLandmarks with median depth); per-call API (host buffers).
+GATE_KIND=1 runs the "+outlier-gate" modes under the Mahalanobis gate (eqf_set_outlier_gate; GATE_THR is then its d2 threshold, default
+0.5) instead of the chord gate; CHURN_PROFILE=1 adds the event-bracketed time of the landmark-set launches (k_edit / k_probe) per mode."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -15,11 +17,17 @@ length = rng.integers(F // 2, F, size=NP)
 start[:120] = -1
 length[:120] = 10 * F
 d = synth.template_settings_dict()
+GATE_KIND = int(os.environ.get("GATE_KIND", "0"))
+PROFILE = os.environ.get("CHURN_PROFILE") == "1"
 def run(mode):
     dd = dict(d)
-    if "gate" in mode:
+    if "gate" in mode and GATE_KIND == 0:
         dd["outlierThreshold"] = float(os.environ.get("GATE_THR", "0.01"))  # the reference default is 0.01 (VIOFilterSettings.h)
     fb = hip.FilterBatch(dd, capacity=NP, batch=1)
+    if "gate" in mode and GATE_KIND == 1:
+        fb.set_outlier_gate(hip.GATE_MAHALANOBIS, float(os.environ.get("GATE_THR", "0.5")))
+    if PROFILE:
+        fb.profile_enable(True)
     ev = list(st.events())
     nvis, nch = 0, 0
     prev = None
@@ -37,6 +45,9 @@ def run(mode):
             nvis += 1
     fb.synchronize()
     dt = time.perf_counter() - t0
+    if PROFILE:
+        n, ms = fb.profile()["churn"]
+        print(f"    {mode}: landmark-set launches {n}, {1e3 * ms / max(n, 1):.2f} us each, {1e3 * ms / max(nvis, 1):.2f} us per frame")
     return dt, len(ev), fb.num_landmarks(), nch / max(nvis - 1, 1), fb.device_error()
 
 
