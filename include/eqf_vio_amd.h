@@ -181,9 +181,13 @@ int eqf_get_integrator(eqf_filter* f, int b, double* currentVelocity6, double* a
 /* Internals of the most recent update of filter b: delta[2N], gamma[11+3N] (K*delta), Gamma[9+3N]. */
 int eqf_get_last_update(eqf_filter* f, int b, double* delta, double* gamma, double* Gamma);
 /* Sticky device-side error flag, 0 if none; a bit mask (any bit -> the C++ facade throws std::domain_error, like the reference's
- * SO3FromVectors, SO3.cpp:160): 1 antipodal vectors / singular gravity chart in a propagate step; 2 the same while building the residual
- * or C0i; 4 a pivot of S or Sigma_e not positive; 8 antipodal vectors in the innovation lift (numeric, one filter: the other filters of a
- * batch handle keep running); 16 / 32 a new / restored landmark on the chart pole; 64 singular gravity chart in the dense Riccati backend;
+ * SO3FromVectors, SO3.cpp:160): 1 antipodal vectors / singular gravity chart in a propagate step; 2 reserved, never raised (the residual
+ * and C0i are built from per-landmark constants: a landmark on the chart pole raises 16 or 32 when it comes in); 4 a pivot of S or Sigma_e
+ * not positive; 8 antipodal vectors in the innovation lift (numeric, one filter: the other filters of a batch handle keep running);
+ * 16 / 32 a new / restored landmark on the chart pole (exactly ON the pole its constants are not finite and the update of the same call
+ * raises 4 as well; the other filters of the handle are not touched); 64 singular gravity chart met by the builder of the dense Riccati
+ * backend, which computes the chart constants itself only in a call that both initialises the pose and steps (a restored filter with a
+ * valid time and initialised = 0); an ordinary level start raises 1 under either backend;
  * 128 an in-launch hand-off of k_chol_resident / k_burst_fused timed out (0.5 s: the GPU was taken away from the launch for that long) --
  * that launch did not write Sigma and the handle must be reset (eqf_reset) or restored (eqf_set_state on EVERY filter of the handle: the call
  * that restores the last one clears bit 128, and bit 4 with it -- a chain that unwinds may have judged pivots of operands it never got): until
