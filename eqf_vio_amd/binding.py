@@ -73,6 +73,7 @@ EXPORTED_SYMBOLS = [
     "eqf_stream_upload", "eqf_stream_imu", "eqf_stream_vision", "eqf_synchronize", "eqf_get_time", "eqf_num_landmarks",
     "eqf_get_ids", "eqf_get_state_estimate", "eqf_get_origin", "eqf_get_group", "eqf_get_bias", "eqf_get_sigma",
     "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
+    "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters",
     "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
     "eqf_set_sigma", "eqf_set_state", "eqf_copy_filters", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
@@ -135,6 +136,10 @@ def lib():
             L.eqf_get_innovation_stats.argtypes = [vp, C.c_int, C.POINTER(InnovationStats), _dp]
         if hasattr(L, "eqf_get_nees"):
             L.eqf_get_nees.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, C.POINTER(SigmaStats)]
+        if hasattr(L, "eqf_sample_sigma"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
+            L.eqf_sample_sigma.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.POINTER(SigmaStats)]
+            L.eqf_apply_increment.argtypes = [vp, _dp, C.c_int, C.POINTER(C.c_ubyte)]
+            L.eqf_perturb_filters.argtypes = [vp, C.c_int, _dp, C.c_int, _dp, C.POINTER(SigmaStats)]
         if hasattr(L, "eqf_set_outlier_gate"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
             L.eqf_set_outlier_gate.argtypes = [vp, C.c_int, C.c_double]
             L.eqf_get_outlier_gate.argtypes = [vp, _ip, _dp]
@@ -478,6 +483,76 @@ class FilterBatch:
                "eqf_get_nees")
         return dict(nees=out[:, :nrhs], logdet=np.array([s.logdet for s in st]), min_pivot=np.array([s.min_pivot for s in st]),
                     dof=np.array([s.dof for s in st], dtype=np.int32), info=np.array([s.info for s in st], dtype=np.int32))
+
+    def _rows(self, v, what):
+        """(B, k, n_max) from an array (B, k, n) / (B, n) or a list of per-filter arrays (k, n_b) / (n_b,), zero beyond a filter's own order"""
+        B = self.B
+        if isinstance(v, np.ndarray) and v.ndim == 3:
+            out = np.ascontiguousarray(v, dtype=np.float64)
+        elif isinstance(v, np.ndarray) and v.ndim == 2 and v.shape[0] == B and B > 1:
+            out = np.ascontiguousarray(v[:, None, :], dtype=np.float64)
+        else:
+            rows = [np.atleast_2d(np.asarray(e, dtype=np.float64)) for e in v]
+            if len(rows) != B or any(r.shape[0] != rows[0].shape[0] for r in rows):
+                raise ValueError(f"{what}: one array per filter, all with the same number of vectors")
+            out = np.zeros((B, rows[0].shape[0], max(max(r.shape[1] for r in rows), 1)))
+            for b, r in enumerate(rows):
+                out[b, :, : r.shape[1]] = r
+        if out.shape[0] != B:
+            raise ValueError(f"{what}: first dimension must be the batch ({B})")
+        return out
+
+    @staticmethod
+    def _stats(st):
+        return dict(logdet=np.array([s.logdet for s in st]), min_pivot=np.array([s.min_pivot for s in st]),
+                    dof=np.array([s.dof for s in st], dtype=np.int32), info=np.array([s.info for s in st], dtype=np.int32))
+
+    def sample_sigma(self, z, local=True, first=0, scale=None):
+        """Draws from the covariance of EVERY filter of the handle in one call: eps = scale[b] L_b z with L_b L_b^T the matrix nees() factors
+        for the same `local` and `first` (include/eqf_vio_amd.h: eqf_sample_sigma).  z: array (B, nsamp, n_max) or a list of per-filter
+        arrays (nsamp, n_b) of standard normal numbers in the reference's index map, nsamp <= 64 (entries below `first` are ignored); a
+        numpy.random.Generator draws (B, 1, n_max) itself.  Returns a dict with eps (B, nsamp, n_max: zero below `first` and beyond a
+        filter's own order, NaN rows where info != 0), z as used, and logdet, min_pivot, dof, info (B,)."""
+        B = self.B
+        if isinstance(z, np.random.Generator):
+            z = z.standard_normal((B, 1, 11 + 3 * max(self.num_landmarks(b) for b in range(B))))
+        Z = self._rows(z, "sample_sigma")
+        nsamp, ld = int(Z.shape[1]), int(Z.shape[2])
+        eps = np.zeros_like(Z)
+        sc = None if scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (B,)))
+        st = (SigmaStats * B)()
+        _check(lib().eqf_sample_sigma(self._h, int(bool(local)), int(first), nsamp, _p(Z), ld, None if sc is None else _p(sc), _p(eps), ld, st),
+               "eqf_sample_sigma")
+        return dict(eps=eps, z=Z, **self._stats(st))
+
+    def apply_increment(self, gamma, mask=None):
+        """Moves the filters by increments of the origin chart (the coordinates of sigma() and of last_update()["gamma"]): bias +=
+        gamma[0:6], X <- VIOExp(liftInnovation(gamma[6:], xi0)) X, whatever the lift settings are; Sigma, the origin, the clock and the
+        integrator stay (include/eqf_vio_amd.h: eqf_apply_increment).  gamma: array (B, n_max) or a list of per-filter vectors (n_b,);
+        mask (B,): 0 leaves a filter alone, every bit.  Enqueues and returns."""
+        B = self.B
+        G = self._rows(gamma, "apply_increment")
+        if G.shape[1] != 1:
+            raise ValueError("apply_increment: one increment per filter")
+        m = None if mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mask), (B,)) != 0, dtype=np.uint8)
+        _check(lib().eqf_apply_increment(self._h, _p(G), int(G.shape[2]), None if m is None else m.ctypes.data_as(C.POINTER(C.c_ubyte))),
+               "eqf_apply_increment")
+
+    def perturb(self, z, first=0, scale=None, stats=False):
+        """sample_sigma(z, local=False, first, scale) with one z per filter and apply_increment of the result as one enqueued sequence on the
+        device -- the same bits, no host round trip (include/eqf_vio_amd.h: eqf_perturb_filters).  scale[b] = 0 leaves filter b alone, every
+        bit (roughen only the duplicates of a resample(): consistency.systematic_resample's parents tell which).  z as in sample_sigma
+        (one vector per filter) or a numpy.random.Generator.  stats: wait for the device and return logdet, min_pivot, dof, info (B,)."""
+        B = self.B
+        if isinstance(z, np.random.Generator):
+            z = z.standard_normal((B, 1, 11 + 3 * max(self.num_landmarks(b) for b in range(B))))
+        Z = self._rows(z, "perturb")
+        if Z.shape[1] != 1:
+            raise ValueError("perturb: one z per filter")
+        sc = None if scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (B,)))
+        st = (SigmaStats * B)() if stats else None
+        _check(lib().eqf_perturb_filters(self._h, int(first), _p(Z), int(Z.shape[2]), None if sc is None else _p(sc), st), "eqf_perturb_filters")
+        return self._stats(st) if stats else None
 
     def debug_sigma_local_all(self):
         """k_sigma_local for every filter of the handle in one launch, nothing copied (include/eqf_vio_amd_debug.h)."""

@@ -7,6 +7,7 @@ to first order eps_loc = J eps with the block-diagonal J of local_jacobian_block
 
   local_jacobian_blocks(origin, group)   the J blocks (the device builds the same ones: FilterBatch.local_jacobian)
   local_error(estimate, truth, ...)      eps_loc for gravity direction, velocity and landmarks, plus the bias difference
+  local_retract(estimate, eps, ...)      its inverse: a drawn eps_loc (FilterBatch.sample_sigma) -> a sampled truth for a Monte-Carlo start
   nees_marginal(marginals, error)        navigation-state NEES (11 or 5 dof) and per-landmark NEES (3 dof), O(N)
   error_vector(error)                    local_error's dict flattened into Sigma's index map
   nees_joint(Sigma, e, first)            the joint NEES e^T A^-1 e, log det A and the smallest pivot over the whole state or a trailing part of
@@ -156,6 +157,50 @@ def local_error(estimate, truth, bias=None, true_bias=None):
         velocity=np.asarray(truth["v"], dtype=float) - np.asarray(estimate["v"], dtype=float),
         lm=np.asarray(truth["p"], dtype=float).reshape(-1, 3) - np.asarray(estimate["p"], dtype=float).reshape(-1, 3),
     )
+
+
+def stereo_sphere_chart_inv(y, pole):
+    """VIOState.cpp:236-240 (e3ProjectSphereInv, :206-211, turned back by the chart's rotation)."""
+    ybar = np.array([y[0], y[1], 0.0])
+    r = E3 + 2.0 / (float(ybar @ ybar) + 1.0) * (ybar - E3)
+    return _quat_rotate(_quat_inverse(_sphere_rot(pole)), r)
+
+
+def _quat_mul(a, b):
+    """SO3.cpp:76."""
+    return np.array([a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+                     a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1], a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]])
+
+
+def local_retract(estimate, eps, bias=None):
+    """Inverse of local_error: the state xi = chart_xiHat^-1(eps) whose error against `estimate` is eps -- what turns a draw eps_loc ~ N(0,
+    Sigma_loc) (FilterBatch.sample_sigma(local=True)) into a sampled TRUTH for a Monte-Carlo start.
+    eps: local_error's dict, or one vector in the reference's index map (error_vector; (11 + 3N,)).  Returns a dict with q, v, p, and
+    `bias` = bias + eps_bias when a bias is given.  The gravity direction is stereo_sphere_chart^-1(eps_gravity, etaHat); the attitude is the
+    estimate's turned by the SHORTEST rotation that takes its gravity direction there.  The chart only fixes the direction of gravity: yaw
+    is unobservable, is not part of the error and stays the estimate's.  A tilt of pi (eps_gravity at infinity) has no shortest rotation."""
+    if not isinstance(eps, dict):
+        e = np.asarray(eps, dtype=float)
+        eps = dict(bias=e[0:6], gravity=e[6:8], velocity=e[8:11], lm=e[11:].reshape(-1, 3))
+    q = np.asarray(estimate["q"], dtype=float)
+    etaHat = gravity_dir(q)
+    eta = stereo_sphere_chart_inv(np.asarray(eps["gravity"], dtype=float), etaHat)
+    # R_true^T e3 = eta with R_true = R_hat D^T, D the rotation etaHat -> eta about etaHat x eta (Rodrigues, as SO3.cpp:155-167)
+    v = np.cross(etaHat, eta)
+    c = float(etaHat @ eta)
+    if abs(1.0 + c) <= 1e-8:
+        raise ValueError("a gravity tilt of pi has no shortest rotation")
+    vx = _skew(v)
+    D = np.eye(3) + vx + vx @ vx / (1.0 + c)
+    # (eps_gravity = 0 is the estimate's own direction: the attitude keeps every bit)
+    qn = _quat_mul(q, _quat_inverse(_quat_from_matrix(D))) if np.any(np.asarray(eps["gravity"], dtype=float) != 0.0) else q.copy()
+    out = dict(q=qn, v=np.asarray(estimate["v"], dtype=float) + np.asarray(eps["velocity"], dtype=float),
+               p=np.asarray(estimate["p"], dtype=float).reshape(-1, 3) + np.asarray(eps["lm"], dtype=float).reshape(-1, 3))
+    if "x" in estimate:
+        out["x"] = np.asarray(estimate["x"], dtype=float).copy()
+    if bias is not None:
+        out["bias"] = np.asarray(bias, dtype=float) + np.asarray(eps["bias"], dtype=float)
+    return out
 
 
 def nees_marginal(marginals, error, with_bias=True):

@@ -294,6 +294,38 @@ class VIOFilter {
         check(eqf_get_nees(handle_.get(), local ? 1 : 0, first, 1, e.data(), n, &st.nees, &st), "eqf_get_nees");
         return st;
     }
+    // A draw from the covariance (eqf_sample_sigma): scale * L z with L L^T = the covariance in the coordinates of the estimate (local) or of
+    // the origin, from reference index `first` on; z has 11 + 3 N standard normal entries in Sigma's index map (those below `first` are
+    // ignored, the result is 0 there).  With local = true this is a sampled estimation error (eqf_vio_amd.consistency.local_retract turns
+    // it into a sampled truth).  A matrix that is not positive definite is reported in `info` (the draw is NaN then), not thrown.
+    struct StateSample : eqf_sigma_stats {
+        std::vector<double> eps;
+    };
+    template <typename Vec>
+    StateSample sampleStateError(const Vec& z, bool local = true, int first = 0, double scale = 1.0) const {
+        StateSample st;
+        const int n = 11 + 3 * eqf_num_landmarks(handle_.get(), 0);
+        if (int(z.size()) < n) throw std::invalid_argument("sampleStateError: z needs 11 + 3 N entries");
+        std::vector<double> zz(size_t(n), 0.0);
+        for (int i = 0; i < n; ++i) zz[i] = z[i];
+        st.eps.assign(size_t(n), 0.0);
+        check(eqf_sample_sigma(handle_.get(), local ? 1 : 0, first, 1, zz.data(), n, &scale, st.eps.data(), n, &st), "eqf_sample_sigma");
+        return st;
+    }
+    // Moves the filter by scale * L z, L L^T = the covariance in the coordinates of the origin from `first` on, on the device
+    // (eqf_perturb_filters): bias += gamma[0:6], X <- VIOExp(liftInnovation(gamma[6:], xi0)) X; the covariance, the origin, the clock and the
+    // integrator stay.  Two forks of one filter (copyStateFrom) that see the same stream stay equal for ever; this tells them apart.  The
+    // filter is not moved when the covariance is not positive definite (`info`).
+    template <typename Vec>
+    eqf_sigma_stats perturbState(const Vec& z, int first = 0, double scale = 1.0) {
+        eqf_sigma_stats st;
+        const int n = 11 + 3 * eqf_num_landmarks(handle_.get(), 0);
+        if (int(z.size()) < n) throw std::invalid_argument("perturbState: z needs 11 + 3 N entries");
+        std::vector<double> zz(size_t(n), 0.0);
+        for (int i = 0; i < n; ++i) zz[i] = z[i];
+        check(eqf_perturb_filters(handle_.get(), first, zz.data(), n, &scale, &st), "eqf_perturb_filters");
+        return st;
+    }
     // This filter continues from the state of `other` (fork, or snapshot and roll back), copied on the device (eqf_copy_filters): landmarks,
     // origin, group element, bias, covariance, time and integrator.  Settings, camera offset and capacity stay this filter's own; throws
     // std::runtime_error if `other` tracks more landmarks than this filter's capacity or differs in precision or device.

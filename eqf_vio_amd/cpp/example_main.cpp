@@ -11,6 +11,9 @@
 // coordinates of the estimate (VIOFilter::stateCovarianceLocal).
 // With "nees", after the last frame, one line per (local, first) in {1, 0} x {0, 6, 11} of VIOFilter::stateNEES for the error vector
 // e_i = 0.01 sin(0.9 i + 0.3): "nees" local first dof info, then nees logdet min_pivot as hexadecimal floats.
+// With "sample", after the last frame, with z_i = sin(1.7 i + 0.2): one line per (local, first) in {1, 0} x {0, 6, 11} of
+// VIOFilter::sampleStateError(z, local, first, 0.5): "sample" local first dof info, then the 11 + 3 N entries as hexadecimal floats; then
+// VIOFilter::perturbState(z, 6, 0.25) and one line "perturbed" as "clone_a" below.
 // With "clone", after frames / 2 frames a second VIOFilter with twice the measurement variance is forked off the first
 // (VIOFilter::copyStateFrom) and both run on; after the last frame one line each, "clone_a" for the first and "clone_b" for the fork: N,
 // then pose q (4), pose x (3), velocity (3) and the n x n covariance as hexadecimal floats.
@@ -41,6 +44,7 @@ int main(int argc, char** argv) {
     const bool init = argc > 3 && std::string(argv[3]) == "init";
     const bool local = argc > 3 && std::string(argv[3]) == "local";
     const bool nees = argc > 3 && std::string(argv[3]) == "nees";
+    const bool sample = argc > 3 && std::string(argv[3]) == "sample";
     const bool clone = argc > 3 && std::string(argv[3]) == "clone";
     const bool gate = argc > 3 && std::string(argv[3]) == "gate";
     std::unique_ptr<VIOFilter> fork;
@@ -147,6 +151,19 @@ int main(int argc, char** argv) {
             if (clone) {
                 printState("clone_a", filter);
                 if (fork) printState("clone_b", *fork);
+            }
+            if (sample) {
+                std::vector<double> z(size_t(S.n));
+                for (int i = 0; i < S.n; ++i) z[i] = std::sin(1.7 * i + 0.2);
+                for (int loc = 1; loc >= 0; --loc)
+                    for (int first : {0, 6, 11}) {
+                        const VIOFilter::StateSample r = filter.sampleStateError(z, loc != 0, first, 0.5);
+                        std::printf("sample %d %d %d %d", loc, first, r.dof, r.info);
+                        for (double v : r.eps) std::printf(" %a", v);
+                        std::printf("\n");
+                    }
+                filter.perturbState(z, 6, 0.25);
+                printState("perturbed", filter);
             }
             if (nees) {
                 std::vector<double> e(size_t(S.n));

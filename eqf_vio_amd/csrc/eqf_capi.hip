@@ -27,6 +27,8 @@
 #include "eqf_nees.hpp"
 #include "eqf_clone.hpp"
 #include "eqf_frame.hpp"
+#include "eqf_sample.hpp"
+#include "eqf_sample_host.hpp"
 
 using namespace eqf;
 
@@ -225,6 +227,14 @@ struct eqf_filter {
     double *dNeesE = nullptr, *dNeesD = nullptr, *dNeesOut = nullptr;
     int* dNeesBad = nullptr;
     bool neesLdsSet = false;
+    // draws from the covariance (eqf_sample.hpp; eqf_sample_sigma / eqf_apply_increment / eqf_perturb_filters), allocated on first need: the
+    // samples and their images [B][sampRows][ld]; and the small operands of a call that does not wait for the device -- scale [B] | vectors
+    // [B][kLm0 + 3 cap] (z of a perturbation or the increments) | mask [B] bytes -- as a pinned image and its device copy (evSamp: the last
+    // upload from the pinned image has been read)
+    double *dSampZ = nullptr, *dSampE = nullptr;
+    int sampRows = 0;
+    char *hSampSmall = nullptr, *dSampSmall = nullptr;
+    hipEvent_t evSamp = nullptr;
     // eqf_copy_filters (eqf_clone.hpp): the pair table (pinned image + device copy, grown on demand), the small-state staging image of the
     // in-place case (allocated on first need) and two events -- evCloneSrc orders a copy behind this handle's work when it is the source,
     // evCloneDone marks the end of the last copy INTO this handle (its pair table may be reused, the source may go on)
@@ -1544,8 +1554,10 @@ void freeAll(eqf_filter* f) {
              (void*)f->dPerm, (void*)f->dChord, (void*)f->dDepth2, (void*)f->dDepthSel, (void*)f->dScratch, (void*)f->dMeas,
              (void*)f->dOut, (void*)f->dRing, (void*)f->sImu, (void*)f->sVis, (void*)f->sBear, f->dF, f->dG, f->dBn, f->dBlk, (void*)f->dBlkCommon, f->dColRec, f->dRowRec, (void*)f->dSteps, (void*)f->dFlags, (void*)f->dReadyA, (void*)f->dReadyY, (void*)f->dResCounters, (void*)f->dTicket, (void*)f->dStageFlags, (void*)f->dPrepFlags, (void*)f->dBuildFlags, (void*)f->dGammaPart,
              (void*)f->dG11Part, (void*)f->dRoles, (void*)f->dI8Ws, (void*)f->dI8Expo, (void*)f->dJac, (void*)f->dSigmaLoc, (void*)f->dInnov,
-             (void*)f->dNeesE, (void*)f->dNeesD, (void*)f->dNeesOut, (void*)f->dNeesBad})
+             (void*)f->dNeesE, (void*)f->dNeesD, (void*)f->dNeesOut, (void*)f->dNeesBad, (void*)f->dSampZ, (void*)f->dSampE, (void*)f->dSampSmall})
         hipFree(p);
+    if (f->hSampSmall) hipHostFree(f->hSampSmall);
+    if (f->evSamp) hipEventDestroy(f->evSamp);
     if (f->hGate) hipHostFree(f->hGate);
     if (f->dMask) hipFree(f->dMask);
     if (f->evGate) hipEventDestroy(f->evGate);
@@ -2824,6 +2836,218 @@ int eqf_get_nees(eqf_filter* f, int local, int first, int nrhs, const double* er
         stats[b].info = int(o[3]);
         for (int k = 0; k < nrhs; ++k) nees[size_t(b) * nrhs + k] = o[kNeesHead + k];
     }
+    return EQF_OK;
+}
+
+// ---- draws from the covariance and the group step (eqf_sample.hpp; index arithmetic and argument checks: eqf_sample_host.hpp)
+namespace {
+size_t sampVecLen(const eqf_filter* f) { return size_t(kLm0) + 3 * size_t(f->cap); }
+size_t sampSmallBytes(const eqf_filter* f) { return sizeof(double) * f->B * (1 + sampVecLen(f)) + size_t(f->B); }
+struct SampSmall {
+    double *scale, *vec;
+    unsigned char* mask;
+};
+SampSmall sampCarve(const eqf_filter* f, char* p) {
+    double* d = reinterpret_cast<double*>(p);
+    return SampSmall{d, d + f->B, reinterpret_cast<unsigned char*>(d + f->B * (1 + sampVecLen(f)))};
+}
+// the small operands' two images and their event; a failure leaves the handle as it was
+int sampSmallAlloc(eqf_filter* f) {
+    if (f->dSampSmall) return EQF_OK;
+    void *h = nullptr, *d = nullptr;
+    hipEvent_t ev = nullptr;
+    if (hipHostMalloc(&h, sampSmallBytes(f), hipHostMallocDefault) != hipSuccess || hipMalloc(&d, sampSmallBytes(f)) != hipSuccess ||
+        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        if (h) hipHostFree(h);
+        if (d) hipFree(d);
+        return EQF_ERR_HIP;
+    }
+    f->hSampSmall = static_cast<char*>(h);
+    f->dSampSmall = static_cast<char*>(d);
+    f->evSamp = ev;
+    return EQF_OK;
+}
+// room for `rows` samples per filter
+int sampRowsAlloc(eqf_filter* f, int rows) {
+    if (rows <= f->sampRows) return EQF_OK;
+    void *z = nullptr, *e = nullptr;
+    const size_t bytes = sizeof(double) * size_t(rows) * f->ld * f->B;
+    if (hipMalloc(&z, bytes) != hipSuccess || hipMalloc(&e, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        if (z) hipFree(z);
+        return EQF_ERR_HIP;
+    }
+    HIPC(hipStreamSynchronize(f->stream));  // (an earlier call's launches may still read the old ones)
+    hipFree(f->dSampZ);
+    hipFree(f->dSampE);
+    f->dSampZ = static_cast<double*>(z);
+    f->dSampE = static_cast<double*>(e);
+    f->sampRows = rows;
+    return EQF_OK;
+}
+// A = L L^T of every filter's submatrix from internal index off, in place in the scratch image, and the report in dNeesOut: eqf_get_nees's
+// launches without error vectors.  Enqueues; the buffers are there (neesAlloc).
+int sampFactor(eqf_filter* f, int local, int off) {
+    const int B = f->B, nMax = maxN(f);
+    if (!f->neesLdsSet) {  // (dynamic LDS beyond 64 KB: see allowUpdateLds)
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nees_panel), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesPanelLdsBytes));
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nees_trail), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesTrailLdsBytes));
+        f->neesLdsSet = true;
+    }
+    const int mMax = sample::paddedOrder(nMax, off), nb = sample::blockColumns(mMax);
+    if (local) {
+        int rc = launchLocal(f, 0, B, true);
+        if (rc) return rc;
+    } else {
+        HIPC(hipMemcpyAsync(f->dSigmaLoc, f->Sigma[f->pS], sizeof(double) * size_t(f->sigmaStride) * B, hipMemcpyDeviceToDevice, f->stream));
+    }
+    NeesArgs a{};
+    a.g = f->g[f->pG]; a.A = f->dSigmaLoc; a.ld = f->ld; a.strideA = f->sigmaStride; a.E = f->dNeesE; a.ldE = std::max(mMax, 1); a.D = f->dNeesD;
+    a.bad = f->dNeesBad; a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.off = off; a.nrhs = 0; a.out = f->dNeesOut;
+    hipLaunchKernelGGL(k_nees_diag, dim3(1, B), dim3(256), kLdsFactorBytes, f->stream, a, 0);
+    for (int K = 0; K < nb; ++K) {
+        const int t = nb - K - 1;
+        if (K > 0) hipLaunchKernelGGL(k_nees_diag, dim3(1, B), dim3(256), kLdsFactorBytes, f->stream, a, K);
+        if (t > 0) hipLaunchKernelGGL(k_nees_panel, dim3(t, B), dim3(256), kNeesPanelLdsBytes, f->stream, a, K, t);
+        if (t > 0) hipLaunchKernelGGL(k_nees_trail, dim3(t * (t + 1) / 2, B), dim3(256), kNeesTrailLdsBytes, f->stream, a, K, t);
+    }
+    hipLaunchKernelGGL(k_nees_tail, dim3(B), dim3(256), 0, f->stream, a);
+    HIPC(hipGetLastError());
+    return EQF_OK;
+}
+// E = scale Z L^T behind sampFactor (nsamp >= 1 rows per filter in dSampZ -> dSampE, row pitch ldE)
+void sampTrmm(eqf_filter* f, int off, int nsamp, int ldE, const double* dScale) {
+    const int mMax = sample::paddedOrder(maxN(f), off);
+    if (mMax <= 0) return;
+    SampleArgs s{};
+    s.g = f->g[f->pG]; s.A = f->dSigmaLoc; s.ld = f->ld; s.strideA = f->sigmaStride; s.Z = f->dSampZ; s.E = f->dSampE; s.ldE = ldE;
+    s.nsamp = nsamp; s.scale = dScale; s.off = off;
+    hipLaunchKernelGGL(k_sample_trmm, dim3(sample::blockColumns(mMax), sample::rowTiles(nsamp), f->B), dim3(256), kSampleLdsBytes, f->stream, s);
+}
+void sampStats(const double* hO, int B, eqf_sigma_stats* stats) {
+    for (int b = 0; b < B; ++b) {
+        const double* o = hO + size_t(b) * (kNeesHead + kNeesRhs);
+        stats[b].logdet = o[0];
+        stats[b].min_pivot = o[1];
+        stats[b].dof = int(o[2]);
+        stats[b].info = int(o[3]);
+    }
+}
+}  // namespace
+
+int eqf_sample_sigma(eqf_filter* f, int local, int first, int nsamp, const double* z, int ldz, const double* scale, double* eps, int lde,
+    eqf_sigma_stats* stats) {
+    if (!f) return EQF_ERR_INVALID;
+    // (the landmark counts are only known for certain behind GATE: the arguments that do not depend on them first, the strides after it)
+    if (!sample::drawArgsOk(local, first, nsamp, z, ldz, eps, lde, stats, 0)) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);
+    const int B = f->B, nMax = maxN(f);
+    if (!sample::drawArgsOk(local, first, nsamp, z, ldz, eps, lde, stats, nMax)) return EQF_ERR_INVALID;
+    int rc = neesAlloc(f);
+    if (!rc && nsamp > 0) rc = sampRowsAlloc(f, nsamp);
+    if (!rc && scale) rc = sampSmallAlloc(f);
+    if (rc) return rc;
+    const int off = sample::cutOffset(first), ldE = std::max(sample::paddedOrder(nMax, off), 1);
+    rc = sampFactor(f, local, off);
+    if (rc) return rc;
+    std::vector<double> hZ;
+    if (nsamp > 0) {
+        hZ.resize(size_t(B) * nsamp * ldE);
+        for (int b = 0; b < B; ++b)
+            for (int k = 0; k < nsamp; ++k)
+                sample::packRow(z + (size_t(b) * nsamp + k) * ldz, first, int(f->ids[b].size()), hZ.data() + (size_t(b) * nsamp + k) * ldE, ldE);
+        HIPC(hipMemcpyAsync(f->dSampZ, hZ.data(), sizeof(double) * hZ.size(), hipMemcpyHostToDevice, f->stream));
+        const double* dScale = nullptr;
+        if (scale) {
+            HIPC(hipEventSynchronize(f->evSamp));
+            SampSmall h = sampCarve(f, f->hSampSmall), d = sampCarve(f, f->dSampSmall);
+            std::copy(scale, scale + B, h.scale);
+            HIPC(hipMemcpyAsync(d.scale, h.scale, sizeof(double) * B, hipMemcpyHostToDevice, f->stream));
+            dScale = d.scale;
+        }
+        sampTrmm(f, off, nsamp, ldE, dScale);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(hZ.data(), f->dSampE, sizeof(double) * hZ.size(), hipMemcpyDeviceToHost, f->stream));
+    }
+    std::vector<double> hO(size_t(B) * (kNeesHead + kNeesRhs));
+    HIPC(hipMemcpyAsync(hO.data(), f->dNeesOut, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipStreamSynchronize(f->stream));
+    if (stats) sampStats(hO.data(), B, stats);
+    const double nan = std::nan("");
+    for (int b = 0; b < B; ++b) {
+        const bool bad = hO[size_t(b) * (kNeesHead + kNeesRhs) + 3] != 0.0;
+        for (int k = 0; k < nsamp; ++k)
+            sample::unpackRow(hZ.data() + (size_t(b) * nsamp + k) * ldE, first, int(f->ids[b].size()), eps + (size_t(b) * nsamp + k) * lde,
+                bad ? &nan : nullptr);
+    }
+    return EQF_OK;
+}
+
+int eqf_apply_increment(eqf_filter* f, const double* gamma, int ldg, const unsigned char* mask) {
+    if (!f || !gamma) return EQF_ERR_INVALID;
+    GATE(f);
+    const int B = f->B;
+    std::vector<int> N(B);
+    for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
+    if (!sample::incrementArgsOk(gamma, ldg, mask, B, N.data())) return EQF_ERR_INVALID;
+    int rc = sampSmallAlloc(f);
+    if (rc) return rc;
+    HIPC(hipEventSynchronize(f->evSamp));
+    SampSmall h = sampCarve(f, f->hSampSmall), d = sampCarve(f, f->dSampSmall);
+    const int len = int(sampVecLen(f));
+    for (int b = 0; b < B; ++b) {
+        sample::packRow(gamma + size_t(b) * ldg, 0, N[b], h.vec + size_t(b) * len, kLm0 + 3 * N[b]);
+        h.mask[b] = mask ? mask[b] : 1;
+    }
+    HIPC(hipMemcpyAsync(d.vec, h.vec, sizeof(double) * size_t(B) * len + size_t(B), hipMemcpyHostToDevice, f->stream));  // (the mask lies behind)
+    HIPC(hipEventRecord(f->evSamp, f->stream));
+    IncArgs a{};
+    a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.cap = f->cap; a.gamma = d.vec; a.strideG = len; a.off = 0; a.mask = d.mask;
+    hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, a);
+    HIPC(hipGetLastError());
+    f->csValid = false;  // (C Sigma / S left by an earlier burst were built around the landmarks as they were)
+    return EQF_OK;
+}
+
+int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, const double* scale, eqf_sigma_stats* stats) {
+    if (!f || !sample::perturbArgsOk(first, z, ldz, scale, f->B, 0)) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);
+    const int B = f->B, nMax = maxN(f);
+    if (!sample::perturbArgsOk(first, z, ldz, scale, B, nMax)) return EQF_ERR_INVALID;
+    int rc = neesAlloc(f);
+    if (!rc) rc = sampRowsAlloc(f, 1);
+    if (!rc) rc = sampSmallAlloc(f);
+    if (rc) return rc;
+    const int off = sample::cutOffset(first), ldE = std::max(sample::paddedOrder(nMax, off), 1);
+    rc = sampFactor(f, 0, off);
+    if (rc) return rc;
+    HIPC(hipEventSynchronize(f->evSamp));
+    SampSmall h = sampCarve(f, f->hSampSmall), d = sampCarve(f, f->dSampSmall);
+    for (int b = 0; b < B; ++b) {
+        h.scale[b] = scale ? scale[b] : 1.0;
+        h.mask[b] = h.scale[b] != 0.0;
+        sample::packRow(z + size_t(b) * ldz, first, int(f->ids[b].size()), h.vec + size_t(b) * ldE, ldE);
+    }
+    HIPC(hipMemcpyAsync(d.scale, h.scale, sizeof(double) * B, hipMemcpyHostToDevice, f->stream));
+    HIPC(hipMemcpyAsync(d.mask, h.mask, size_t(B), hipMemcpyHostToDevice, f->stream));
+    HIPC(hipMemcpyAsync(f->dSampZ, h.vec, sizeof(double) * size_t(B) * ldE, hipMemcpyHostToDevice, f->stream));
+    HIPC(hipEventRecord(f->evSamp, f->stream));
+    // (a submatrix of order 0 -- first = 11, no landmarks anywhere -- has no sample: k_apply_increment then reads no entry of the image)
+    sampTrmm(f, off, 1, ldE, d.scale);
+    IncArgs a{};
+    a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.cap = f->cap; a.gamma = f->dSampE; a.strideG = ldE; a.off = off; a.mask = d.mask;
+    a.info = f->dNeesOut;
+    hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, a);
+    HIPC(hipGetLastError());
+    f->csValid = false;
+    if (!stats) return EQF_OK;
+    std::vector<double> hO(size_t(B) * (kNeesHead + kNeesRhs));
+    HIPC(hipMemcpyAsync(hO.data(), f->dNeesOut, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipStreamSynchronize(f->stream));
+    sampStats(hO.data(), B, stats);
     return EQF_OK;
 }
 

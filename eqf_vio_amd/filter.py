@@ -160,6 +160,23 @@ class VIOFilter:
         return dict(nees=float(r["nees"][0, 0]), logdet=float(r["logdet"][0]), min_pivot=float(r["min_pivot"][0]), dof=int(r["dof"][0]),
                     info=int(r["info"][0]))
 
+    def sampleStateError(self, z, local=True, first=0, scale=1.0):
+        """A draw from the covariance: scale * L z with L L^T the covariance from reference index `first` on, in the coordinates of the
+        estimate (local; consistency.local_retract turns it into a sampled truth) or of the origin.  z: 11 + 3 N standard normal numbers, or
+        a numpy.random.Generator.  Returns dict(eps (11 + 3 N,), logdet, min_pivot, dof, info); include/eqf_vio_amd.h: eqf_sample_sigma."""
+        r = self._fb.sample_sigma(z if isinstance(z, np.random.Generator) else [np.asarray(z, dtype=float).reshape(1, -1)], local=local,
+                                  first=first, scale=[scale])
+        return dict(eps=r["eps"][0, 0], logdet=float(r["logdet"][0]), min_pivot=float(r["min_pivot"][0]), dof=int(r["dof"][0]),
+                    info=int(r["info"][0]))
+
+    def perturbState(self, z, first=0, scale=1.0):
+        """Moves the filter by scale * L z (origin chart, from `first` on) on the device: bias += gamma[0:6], X <- VIOExp(liftInnovation(
+        gamma[6:], xi0)) X; covariance, origin, clock and integrator stay (include/eqf_vio_amd.h: eqf_perturb_filters).  Returns dict(logdet,
+        min_pivot, dof, info); the filter is not moved when info != 0."""
+        r = self._fb.perturb(z if isinstance(z, np.random.Generator) else [np.asarray(z, dtype=float).reshape(1, -1)], first=first,
+                             scale=[scale], stats=True)
+        return dict(logdet=float(r["logdet"][0]), min_pivot=float(r["min_pivot"][0]), dof=int(r["dof"][0]), info=int(r["info"][0]))
+
     def copyStateFrom(self, other):
         """This filter continues from the state of `other` (fork, or snapshot and roll back), copied on the device
         (include/eqf_vio_amd.h: eqf_copy_filters).  Settings, camera offset and capacity stay this filter's own."""

@@ -303,6 +303,39 @@ typedef struct eqf_sigma_stats {
 } eqf_sigma_stats;
 int eqf_get_nees(eqf_filter* f, int local, int first, int nrhs, const double* err, int lde, double* nees /* [batch][nrhs] */,
     eqf_sigma_stats* stats /* [batch] */);
+/* Draws from the covariance, for EVERY filter of the handle in one call: eps = scale[b] L_b z with L_b L_b^T = A_b, the matrix eqf_get_nees
+ * factors for the same `local` and `first` (the same launches; then one product on the matrix cores, csrc/eqf_sample.hpp).  With z ~ N(0, I)
+ * eps ~ N(0, scale^2 A): the initial error of a Monte-Carlo run, or the move of a roughened resample.  The caller supplies z: there is no
+ * random-number generator on the device.
+ *   z[(b * nsamp + k) * ldz + i], eps[(b * nsamp + k) * lde + i]: entry i (reference index map) of sample k of filter b.  Entries of z below
+ *       `first` are ignored, entries of eps below `first` are written as 0, entries from 11 + 3 N_b on are left alone.  ldz, lde >= 11 + 3 N_b
+ *       for every b.  1 <= nsamp <= 64 (row tiles of 16); nsamp = 0 needs stats and answers what eqf_get_nees(nrhs = 0) answers.
+ *   scale [batch] may be NULL (all 1), stats [batch] may be NULL.
+ * Flushes queued IMU calls and synchronises like every getter; Sigma, the state and the ping-pong indices are only read.  EQF_ERR_INVALID for
+ * bad arguments, before any effect; EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle; EQF_ERR_HIP if the buffers, allocated on first need,
+ * cannot be had (the handle stays as it was).  Trouble of ONE filter goes into stats[b].info (eqf_get_nees's codes): that filter's eps rows
+ * are NaN, the call returns EQF_OK and eqf_device_error is not touched.  Feeding eps (scale 1) back to eqf_get_nees gives z^T z.  Bit for bit
+ * the same from run to run and for a filter alone in a handle or anywhere in a batch (no atomics, one fixed summation order). */
+int eqf_sample_sigma(eqf_filter* f, int local, int first, int nsamp, const double* z, int ldz, const double* scale /* [batch] or NULL */,
+    double* eps, int lde, eqf_sigma_stats* stats /* [batch] or NULL */);
+/* Moves filters by an increment of the origin chart, without an update around it: for every filter b with mask[b] != 0 (mask = NULL: all),
+ * gamma_b = gamma[b * ldg + .] in the reference index map (the coordinates of eqf_get_sigma and of eqf_get_last_update's gamma),
+ *   bias += gamma_b[0:6],   X <- VIOExp(liftInnovation(gamma_b[6:], xi0)) X
+ * -- what processVisionData does with useInnovationLift = false (VIOFilter.cpp:292-296, EqFMatrices.cpp:35-67, VIOGroup.cpp:92-110,
+ * :245-255), WHATEVER the handle's lift settings are (bundleLift needs a factorisation of Sigma_e, which is an update's business).  Sigma,
+ * xi0, the clock, the integrator, the ids, eqf_get_last_update, the innovation statistics and the gate report stay as they are; a masked-out
+ * filter keeps every bit.  ldg >= 11 + 3 N_b for every b.  A NaN or Inf in the increment of a filter that takes part refuses the call
+ * (EQF_ERR_INVALID, like every bad argument before any effect).  Settles what the handle has deferred first, enqueues one launch
+ * (csrc/eqf_sample.hpp) and returns without waiting for the device.  Works in both precisions (the state is fp64 in either). */
+int eqf_apply_increment(eqf_filter* f, const double* gamma, int ldg, const unsigned char* mask /* [batch] or NULL */);
+/* eqf_sample_sigma(local = 0, nsamp = 1) and eqf_apply_increment in one enqueued sequence: filter b moves by scale[b] L_b z_b, which never
+ * leaves the device -- bit for bit what the two calls give.  z[b * ldz + i], one vector per filter; scale [batch] may be NULL (all 1).
+ * scale[b] == 0 leaves filter b untouched, every bit (roughen only the duplicates of a resample); so does a failed factorisation (info != 0)
+ * and a product that is not finite.  With stats == NULL the call enqueues and returns, with stats [batch] it synchronises and reports per
+ * filter as eqf_sample_sigma does.  EQF_ERR_INVALID for bad arguments (a scale that is not finite among them), before any effect;
+ * EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle. */
+int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, const double* scale /* [batch] or NULL */,
+    eqf_sigma_stats* stats /* [batch] or NULL */);
 
 /* Propagate backend: 0 = block-structured HBM-bound kernel (default, product path),
  * 1 = dense F Sigma F^T on MFMA (what the reference executes; BASELINE cfg 3 cross-check). */

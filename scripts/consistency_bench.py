@@ -22,6 +22,11 @@
   copykern B N     a workload for `rocprofv3 --kernel-trace --stats -- python scripts/consistency_bench.py copykern B N`: k_clone_sigma (a
                    whole-handle copy into a second handle) next to k_sigma_local (eqf_debug_sigma_local_all) on the same Sigma, 30 each.
   copysum DIR      kernel-trace stats CSVs under DIR/copykern_B_N -> k_clone_sigma against k_sigma_local (both 2 n^2 * 8 * B bytes).
+  sample B N       DESIGN.md section 4.5e: FilterBatch.perturb (stats=True: ends in a synchronise) against the host route it replaces, for
+                   every filter dump_state (the covariance over the bus) + numpy Cholesky + L z + restore_state -- WITHOUT the group
+                   arithmetic the host would also have to redo, so the host route is timed in its favour -- on the same states after three
+                   frames, scale 1e-3 so that forty moves leave the filters where they were to first order.  Both warmed up, alternated over
+                   20 repetitions; prints one JSON line with medians, min / max and the ratio.  No threshold is asserted.
 """
 import csv
 import glob
@@ -178,6 +183,43 @@ def nees(B, N, reps=20):
     q = lambda v: dict(median_ms=round(float(np.median(v)), 3), min_ms=round(min(v), 3), max_ms=round(max(v), 3))
     print(json.dumps(dict(B=B, N=N, reps=reps, device=q(ta), host=q(th), speedup_of_medians=round(float(np.median(th) / np.median(ta)), 1),
                           device_vs_host_rel=rel)))
+
+
+def sample(B, N, reps=20):
+    import numpy as np
+
+    fg, _ = _nees_setup(B, N)
+    n = 11 + 3 * N
+    z = np.random.default_rng(2).standard_normal((B, 1, n))
+    scale = np.full(B, 1e-3)
+
+    def device():
+        return fg.perturb(z, first=0, scale=scale, stats=True)["info"]
+
+    def host():
+        for b in range(B):
+            snap = fg.dump_state(b)
+            S = np.tril(snap["sigma"])
+            gamma = scale[b] * (np.linalg.cholesky(S + np.tril(S, -1).T) @ z[b, 0])
+            snap["bias"] = snap["bias"] + gamma[0:6]  # (the group step is left out: see the module docstring)
+            fg.restore_state(snap, b)
+
+    assert not np.any(device())  # (first calls: allocations)
+    host()
+    device(), host()
+    ta, th = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        device()
+        t1 = time.perf_counter()
+        host()
+        t2 = time.perf_counter()
+        ta.append((t1 - t0) * 1e3)
+        th.append((t2 - t1) * 1e3)
+    assert fg.device_error() == 0
+    q = lambda v: dict(median_ms=round(float(np.median(v)), 3), min_ms=round(min(v), 3), max_ms=round(max(v), 3))
+    print(json.dumps(dict(case="perturb", B=B, N=N, reps=reps, device=q(ta), host=q(th),
+                          speedup_of_medians=round(float(np.median(th) / np.median(ta)), 1))))
 
 
 def neeskern(B, N):
@@ -364,6 +406,8 @@ if __name__ == "__main__":
         copykern(int(sys.argv[2]), int(sys.argv[3]))
     elif cmd == "copysum":
         copysum(sys.argv[2])
+    elif cmd == "sample":
+        sample(int(sys.argv[2]), int(sys.argv[3]))
     elif cmd == "summarize":
         summarize(sys.argv[2])
     else:
