@@ -95,6 +95,13 @@ def outer(a, b):
     return [[x * y for y in b] for x in a]
 
 
+def inv3(A):
+    """The inverse of a 3 x 3 matrix from its definition (adjugate / determinant)."""
+    c = [cross(A[1], A[2]), cross(A[2], A[0]), cross(A[0], A[1])]
+    det = dot(A[0], c[0])
+    return [[c[j][i] / det for j in range(3)] for i in range(3)]
+
+
 def to_np(A):
     return np.array([[float(x) for x in row] for row in A]) if isinstance(A[0], list) else np.array([float(x) for x in A])
 
