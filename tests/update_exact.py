@@ -383,7 +383,8 @@ def update_bounds(ref, E_ric, fp32=False, tau=None, k_delta=None, slices=0):
     dsol = (np.abs(Pk) @ db6 + np.where(np.isfinite(lin), lin, np.inf)
             + aMinv @ (dM @ np.abs(sol) + gamma(OPS_B) * (aKp.T @ np.abs(b6)) + dsym + gamma(OPS_SOLVE4) * (Pm @ (np.abs(Lm) @ np.abs(Um)) @ np.abs(sol))))
     out["Gamma6"] = ddU + aKp @ dsol + 2 * u * np.abs(f64(ref["Gamma6"]))
-    out["parts"] = dict(cond_M=float(np.linalg.cond(M)), hV=hV, G6=G6, T65=T65)
+    # (dS .. T: what the bounds of the innovation statistics, tests/consistency_exact.py part C, are made of)
+    out["parts"] = dict(cond_M=float(np.linalg.cond(M)), hV=hV, G6=G6, T65=T65, dS=dS, E1=E1, E2z=E2z, ddelta=ddelta, aw=aw, CEC=CEC, T=T)
     return out
 
 
