@@ -20,7 +20,7 @@ SKIPPED_NO_BEARINGS = 4
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_UNSORTED, ERR_NUMERIC, ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6, -7
 PRECISION_F64, PRECISION_F32 = 0, 1
 GATE_CHORD, GATE_MAHALANOBIS = 0, 1
-PROF_CLASSES = 11
+PROF_CLASSES = 15
 
 _ERR_NAMES = {
     -1: "EQF_ERR_INVALID", -2: "EQF_ERR_NO_DEVICE", -3: "EQF_ERR_HIP", -4: "EQF_ERR_CAPACITY",
@@ -64,6 +64,12 @@ class SigmaStats(C.Structure):
     _fields_ = [("logdet", C.c_double), ("min_pivot", C.c_double), ("dof", C.c_int), ("info", C.c_int)]
 
 
+class LinearReport(C.Structure):
+    """eqf_linear_report (include/eqf_vio_amd.h)."""
+
+    _fields_ = [("nis", C.c_double), ("logdet_S", C.c_double), ("loglik", C.c_double), ("dof", C.c_int), ("info", C.c_int)]
+
+
 _lib = None
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -73,7 +79,7 @@ EXPORTED_SYMBOLS = [
     "eqf_stream_upload", "eqf_stream_imu", "eqf_stream_vision", "eqf_synchronize", "eqf_get_time", "eqf_num_landmarks",
     "eqf_get_ids", "eqf_get_state_estimate", "eqf_get_origin", "eqf_get_group", "eqf_get_bias", "eqf_get_sigma",
     "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
-    "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters",
+    "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters", "eqf_update_linear",
     "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
     "eqf_set_sigma", "eqf_set_state", "eqf_copy_filters", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
@@ -140,6 +146,9 @@ def lib():
             L.eqf_sample_sigma.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.POINTER(SigmaStats)]
             L.eqf_apply_increment.argtypes = [vp, _dp, C.c_int, C.POINTER(C.c_ubyte)]
             L.eqf_perturb_filters.argtypes = [vp, C.c_int, _dp, C.c_int, _dp, C.POINTER(SigmaStats)]
+        if hasattr(L, "eqf_update_linear"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
+            L.eqf_update_linear.argtypes = [vp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double, C.POINTER(C.c_ubyte), _dp, C.c_int,
+                                            C.POINTER(LinearReport)]
         if hasattr(L, "eqf_set_outlier_gate"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
             L.eqf_set_outlier_gate.argtypes = [vp, C.c_int, C.c_double]
             L.eqf_get_outlier_gate.argtypes = [vp, _ip, _dp]
@@ -553,6 +562,39 @@ class FilterBatch:
         st = (SigmaStats * B)() if stats else None
         _check(lib().eqf_perturb_filters(self._h, int(first), _p(Z), int(Z.shape[2]), None if sc is None else _p(sc), st), "eqf_perturb_filters")
         return self._stats(st) if stats else None
+
+    def update_linear(self, H, resid, R, local=True, gate=float("inf"), mask=None, want_gamma=False, stats=True):
+        """A measurement update with m <= 16 linear rows for EVERY filter of the handle in one call (include/eqf_vio_amd.h:
+        eqf_update_linear): resid = H eps + noise, noise ~ N(0, R), eps "truth minus estimate" in the coordinates of sigma_local() (local)
+        or of sigma().  H: one (m, n) array for a single-filter handle, an array (B, m, n_max) or a list of per-filter arrays (m, n_b) in the
+        reference's index map (consistency.velocity_rows / landmark_rows / gravity_rows write the usual ones); resid (m,), (B, m) or a list;
+        R (m, m), broadcast to every filter, (B, m, m) or a list: only the lower triangle is read.  gate: chi-square threshold on the m-dof
+        nis (consistency.chi2_gate_threshold(p, dof=m)); mask (B,): 0 leaves a filter alone.  A filter whose info is not 0 keeps every bit.
+        With stats or want_gamma the call waits for the device and returns a dict: nis, logdet_S, loglik (B,), dof, info (B,) and, if
+        asked for, gamma (B, n_max) in the reference's index map (rows of untouched filters 0); otherwise it enqueues and returns None."""
+        B = self.B
+        if isinstance(H, np.ndarray) and H.ndim == 2:
+            H = H[None]
+        Hs = self._rows(H, "update_linear")
+        m, ldh = int(Hs.shape[1]), int(Hs.shape[2])
+        r = np.asarray(resid, dtype=np.float64) if not isinstance(resid, (list, tuple)) else np.stack([np.asarray(x, dtype=np.float64) for x in resid])
+        r = np.ascontiguousarray(np.broadcast_to(r, (B, m)))
+        Rs = np.asarray(R, dtype=np.float64) if not isinstance(R, (list, tuple)) else np.stack([np.asarray(x, dtype=np.float64) for x in R])
+        Rs = np.ascontiguousarray(np.broadcast_to(Rs, (B, m, m)))
+        mk = None if mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mask), (B,)) != 0, dtype=np.uint8)
+        ldg = max(ldh, 11 + 3 * max(self.num_landmarks(b) for b in range(B))) if want_gamma else 0
+        G = np.zeros((B, ldg)) if want_gamma else None
+        rep = (LinearReport * B)() if (stats or want_gamma) else None
+        _check(lib().eqf_update_linear(self._h, int(bool(local)), m, _p(Hs), ldh, _p(r), _p(Rs), float(gate),
+                                       None if mk is None else mk.ctypes.data_as(C.POINTER(C.c_ubyte)), None if G is None else _p(G), ldg, rep),
+               "eqf_update_linear")
+        if rep is None:
+            return None
+        out = dict(nis=np.array([s.nis for s in rep]), logdet_S=np.array([s.logdet_S for s in rep]), loglik=np.array([s.loglik for s in rep]),
+                   dof=np.array([s.dof for s in rep], dtype=np.int32), info=np.array([s.info for s in rep], dtype=np.int32))
+        if want_gamma:
+            out["gamma"] = G
+        return out
 
     def debug_sigma_local_all(self):
         """k_sigma_local for every filter of the handle in one launch, nothing copied (include/eqf_vio_amd_debug.h)."""

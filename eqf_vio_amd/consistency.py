@@ -13,7 +13,10 @@ to first order eps_loc = J eps with the block-diagonal J of local_jacobian_block
   nees_joint(Sigma, e, first)            the joint NEES e^T A^-1 e, log det A and the smallest pivot over the whole state or a trailing part of
                                          it -- the host counterpart of FilterBatch.nees (include/eqf_vio_amd.h: eqf_get_nees)
   systematic_resample(loglik, u)         log-likelihoods (FilterBatch.innovation_stats) -> parents for FilterBatch.resample
-  chi2_gate_threshold(p)                 the chi-square quantile (2 dof) for FilterBatch.set_outlier_gate(GATE_MAHALANOBIS, ...)
+  chi2_gate_threshold(p, dof)            the chi-square quantile: dof = 2 for FilterBatch.set_outlier_gate(GATE_MAHALANOBIS, ...), dof = m for
+                                         FilterBatch.update_linear's gate
+  velocity_rows / gravity_rows / landmark_rows(N, i)   measurement rows in the estimate's chart for FilterBatch.update_linear(local=True)
+  linear_update_host(Sigma, H, resid, R) the numpy statement of that update (include/eqf_vio_amd.h: eqf_update_linear)
 
 `origin`, `group`, `estimate` are the dicts of FilterBatch.origin() / group() / state_estimate(): quaternions (w, x, y, z), Eigen semantics.
 """
@@ -244,14 +247,136 @@ def nees_joint(Sigma, e, first=0):
     return dict(nees=float(nees[0]) if ev.ndim == 1 else nees, logdet=logdet, min_pivot=mp, dof=A.shape[0])
 
 
-def chi2_gate_threshold(p):
-    """Threshold of the Mahalanobis outlier gate that keeps an honest landmark with probability p: the quantile of the chi-square
-    distribution with 2 degrees of freedom, whose CDF is 1 - exp(-x / 2) -- exactly -2 ln(1 - p) (5.991 / 9.210 / 13.816 at 0.95 / 0.99 /
-    0.999).  It presumes a converged, consistent filter: while Sigma is as wide as initialPointVariance leaves it, d2 of a gross error is small."""
+def _gamma_p(a, t):
+    """Regularised lower incomplete gamma function P(a, t), a > 0, t >= 0: the series t^a e^-t sum_n t^n / Gamma(a + n + 1) for t < a + 1,
+    otherwise 1 - Q from the continued fraction (modified Lentz).  Both stop at the rounding level."""
+    import math
+
+    if t <= 0.0:
+        return 0.0
+    pre = math.exp(-t + a * math.log(t) - math.lgamma(a))
+    if t < a + 1.0:
+        term = total = 1.0 / a
+        n = 0
+        while abs(term) > 1e-17 * abs(total) and n < 10000:
+            n += 1
+            term *= t / (a + n)
+            total += term
+        return pre * total
+    tiny = 1e-300
+    b = t + 1.0 - a
+    c, d = 1.0 / tiny, 1.0 / b
+    h = d
+    for i in range(1, 10000):
+        an = -i * (i - a)
+        b += 2.0
+        d = an * d + b
+        d = tiny if abs(d) < tiny else d
+        c = b + an / c
+        c = tiny if abs(c) < tiny else c
+        d = 1.0 / d
+        delta = d * c
+        h *= delta
+        if abs(delta - 1.0) < 1e-16:
+            break
+    return 1.0 - pre * h
+
+
+def chi2_cdf(x, dof):
+    """CDF of the chi-square distribution with `dof` degrees of freedom.  Even dof: the closed form 1 - e^(-x/2) sum_{j < dof/2} (x/2)^j / j!;
+    odd dof: the regularised gamma function P(dof / 2, x / 2) (series / continued fraction).  No scipy."""
+    import math
+
+    x, dof = float(x), int(dof)
+    if dof < 1:
+        raise ValueError("dof must be at least 1")
+    if x <= 0.0:
+        return 0.0
+    t = 0.5 * x
+    if dof % 2 == 0 and t < 30.0:  # (beyond, 1 - tail cancels less well than the continued fraction's 1 - Q: both are 1 to rounding)
+        term = total = 1.0
+        for j in range(1, dof // 2):
+            term *= t / j
+            total += term
+        return -math.expm1(-t + math.log(total))
+    return _gamma_p(0.5 * dof, t)
+
+
+def chi2_gate_threshold(p, dof=2):
+    """Threshold of a chi-square gate that keeps an honest measurement with probability p: the quantile of the chi-square distribution with
+    `dof` degrees of freedom.  dof = 2 (the Mahalanobis outlier gate of a landmark's bearing, FilterBatch.set_outlier_gate(GATE_MAHALANOBIS,
+    ...)): the CDF is 1 - exp(-x / 2), the quantile exactly -2 ln(1 - p) (5.991 / 9.210 / 13.816 at 0.95 / 0.99 / 0.999).  Any other dof
+    (FilterBatch.update_linear's gate: dof = m): bisection on chi2_cdf down to neighbouring doubles.  It presumes a converged, consistent
+    filter: while Sigma is as wide as initialPointVariance leaves it, d2 of a gross error is small."""
     p = float(p)
     if not 0.0 < p < 1.0:
         raise ValueError("p must lie in (0, 1)")
-    return -2.0 * float(np.log1p(-p))
+    if int(dof) != dof or dof < 1:
+        raise ValueError("dof must be a positive integer")
+    if dof == 2:
+        return -2.0 * float(np.log1p(-p))
+    lo, hi = 0.0, float(dof)
+    while chi2_cdf(hi, dof) < p:
+        lo, hi = hi, 2.0 * hi
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if mid <= lo or mid >= hi:
+            break
+        if chi2_cdf(mid, dof) < p:
+            lo = mid
+        else:
+            hi = mid
+    return hi
+
+
+# ---- rows of the usual linear measurements for FilterBatch.update_linear(local=True): eps_loc is "truth minus estimate" in the estimate's
+# chart -- gravity direction [6, 8), body velocity [8, 11), body-frame landmark i [11 + 3 i, 14 + 3 i) -- so a measurement of one of these
+# quantities has unit rows, and its residual is "measured minus the estimate's value"
+def _unit_rows(N, first, count):
+    H = np.zeros((count, 11 + 3 * int(N)))
+    H[np.arange(count), first + np.arange(count)] = 1.0
+    return H
+
+
+def velocity_rows(N):
+    """(3, 11 + 3N): the body velocity -- a zero-velocity detection (resid = 0 - v_hat), wheel or GNSS speed in the body frame."""
+    return _unit_rows(N, 8, 3)
+
+
+def gravity_rows(N):
+    """(2, 11 + 3N): the gravity direction in the stereographic chart around the estimate's (resid = stereo_sphere_chart(eta_measured,
+    gravity_dir(q_hat))) -- an attitude reference."""
+    return _unit_rows(N, 6, 2)
+
+
+def landmark_rows(N, i):
+    """(3, 11 + 3N): body-frame position of landmark i -- a surveyed or range-and-bearing point (resid = p_measured - p_hat[i])."""
+    if not 0 <= int(i) < int(N):
+        raise ValueError("no such landmark")
+    return _unit_rows(N, 11 + 3 * int(i), 3)
+
+
+def linear_update_host(Sigma, H, resid, R):
+    """The numpy statement of FilterBatch.update_linear's arithmetic for one filter (include/eqf_vio_amd.h: eqf_update_linear), H already in
+    Sigma's coordinates (for local rows pass H @ jacobian_matrix(blocks), or Sigma_loc):
+        B = Sigma H^T, S = H B + R = L L^T (lower triangle of R), Y = L^-1 B^T, z = L^-1 resid, gamma = Y^T z, Sigma+ = Sigma - Y^T Y.
+    Returns dict(Sigma, gamma, nis = z^T z, logdet_S = 2 sum log L_kk, loglik = -(nis + logdet_S + m log 2 pi) / 2, dof = m, Y, L).
+    Raises numpy.linalg.LinAlgError if S is not positive definite."""
+    Sg = np.asarray(Sigma, dtype=float)
+    H = np.atleast_2d(np.asarray(H, dtype=float))
+    r = np.asarray(resid, dtype=float).reshape(-1)
+    m = H.shape[0]
+    Rl = np.tril(np.asarray(R, dtype=float).reshape(m, m))
+    Rl = Rl + np.tril(Rl, -1).T
+    B = Sg @ H.T
+    S = H @ B + Rl
+    L = np.linalg.cholesky(np.tril(S) + np.tril(S, -1).T)
+    Y = np.linalg.solve(L, B.T)
+    z = np.linalg.solve(L, r)
+    nis = float(z @ z)
+    logdet = 2.0 * float(np.sum(np.log(np.diag(L))))
+    return dict(Sigma=Sg - Y.T @ Y, gamma=Y.T @ z, nis=nis, logdet_S=logdet, loglik=-0.5 * (nis + logdet + m * float(np.log(2.0 * np.pi))), dof=m,
+                Y=Y, L=L)
 
 
 def systematic_resample(loglik, u):

@@ -8,6 +8,7 @@
 #pragma once
 #include <array>
 #include <cmath>
+#include <limits>
 #include <memory>
 #include <ostream>
 #include <stdexcept>
@@ -325,6 +326,17 @@ class VIOFilter {
         for (int i = 0; i < n; ++i) zz[i] = z[i];
         check(eqf_perturb_filters(handle_.get(), first, zz.data(), n, &scale, &st), "eqf_perturb_filters");
         return st;
+    }
+    // A measurement update with m <= 16 linear rows (eqf_update_linear): resid = H eps + noise, noise ~ N(0, R), eps "truth minus estimate"
+    // in the coordinates of stateCovarianceLocal() (local: gravity direction 6..7, body velocity 8..10, body-frame landmark i 11 + 3 i ..) or
+    // of stateCovariance().  H: m rows of 11 + 3 N entries, row-major without gaps; resid: m; R: m x m row-major, lower triangle read; gate: a
+    // chi-square threshold on the m-dof nis (the default never trips).  The filter is untouched when the report's info is not 0.
+    eqf_linear_report processLinearMeasurement(const double* H, int m, const double* resid, const double* R, bool local = true,
+        double gate = std::numeric_limits<double>::infinity()) {
+        eqf_linear_report rep;
+        const int n = 11 + 3 * eqf_num_landmarks(handle_.get(), 0);
+        check(eqf_update_linear(handle_.get(), local ? 1 : 0, m, H, n, resid, R, gate, nullptr, nullptr, 0, &rep), "eqf_update_linear");
+        return rep;
     }
     // This filter continues from the state of `other` (fork, or snapshot and roll back), copied on the device (eqf_copy_filters): landmarks,
     // origin, group element, bias, covariance, time and integrator.  Settings, camera offset and capacity stay this filter's own; throws

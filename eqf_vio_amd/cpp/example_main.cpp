@@ -1,6 +1,6 @@
 // Minimal C++ caller of the facade, shaped like the reference's offline runner (eqf_vio/src/main.cpp:111-170):
 // events are interleaved by "imu.stamp < meas.stamp", the state is read after every vision call.
-// Usage: eqf_example <N landmarks> <frames> [aux | level | init | local | nees | clone | gate]  -- runs a small synthetic sequence and prints the final
+// Usage: eqf_example <N landmarks> <frames> [aux | level | init | local | nees | sample | linear | clone | gate]  -- runs a small synthetic sequence and prints the final
 // pose and |Sigma|_F.  With "aux" the filter starts from AuxiliaryFilterData + setInertialPoints (VIOFilter.cpp:51-58,
 // 74-118) instead of the gravity alignment at the first IMU sample; with "init" from an explicit initialiseFromIMUData
 // call (VIOFilter.cpp:133-144; same result as the lazy one).  With "level" the vehicle rests level: the reference's gravity
@@ -14,6 +14,9 @@
 // With "sample", after the last frame, with z_i = sin(1.7 i + 0.2): one line per (local, first) in {1, 0} x {0, 6, 11} of
 // VIOFilter::sampleStateError(z, local, first, 0.5): "sample" local first dof info, then the 11 + 3 N entries as hexadecimal floats; then
 // VIOFilter::perturbState(z, 6, 0.25) and one line "perturbed" as "clone_a" below.
+// With "linear", after the last frame, two VIOFilter::processLinearMeasurement calls: a zero-velocity update (the velocity rows of the estimate's
+// chart, resid = -v_hat, R = 1e-4 I), then two rows H_ki = sin(0.3 i + k) in the origin chart with resid (0.01, -0.02) and R = [0.02 . ; 0.005
+// 0.03] under a gate of 50; after each one line "linear" dof info nis logdet_S loglik (hexadecimal floats) and one line "updated" as "clone_a" below.
 // With "clone", after frames / 2 frames a second VIOFilter with twice the measurement variance is forked off the first
 // (VIOFilter::copyStateFrom) and both run on; after the last frame one line each, "clone_a" for the first and "clone_b" for the fork: N,
 // then pose q (4), pose x (3), velocity (3) and the n x n covariance as hexadecimal floats.
@@ -45,6 +48,7 @@ int main(int argc, char** argv) {
     const bool local = argc > 3 && std::string(argv[3]) == "local";
     const bool nees = argc > 3 && std::string(argv[3]) == "nees";
     const bool sample = argc > 3 && std::string(argv[3]) == "sample";
+    const bool linear = argc > 3 && std::string(argv[3]) == "linear";
     const bool clone = argc > 3 && std::string(argv[3]) == "clone";
     const bool gate = argc > 3 && std::string(argv[3]) == "gate";
     std::unique_ptr<VIOFilter> fork;
@@ -164,6 +168,24 @@ int main(int argc, char** argv) {
                     }
                 filter.perturbState(z, 6, 0.25);
                 printState("perturbed", filter);
+            }
+            if (linear) {
+                const int n = S.n;
+                std::vector<double> H(size_t(3) * n, 0.0);
+                for (int k = 0; k < 3; ++k) H[size_t(k) * n + 8 + k] = 1.0;
+                const double r1[3] = {-est.velocity[0], -est.velocity[1], -est.velocity[2]};
+                const double R1[9] = {1e-4, 0, 0, 0, 1e-4, 0, 0, 0, 1e-4};
+                eqf_linear_report rep = filter.processLinearMeasurement(H.data(), 3, r1, R1);
+                std::printf("linear %d %d %a %a %a\n", rep.dof, rep.info, rep.nis, rep.logdet_S, rep.loglik);
+                printState("updated", filter);
+                std::vector<double> H2(size_t(2) * n);
+                for (int k = 0; k < 2; ++k)
+                    for (int i = 0; i < n; ++i) H2[size_t(k) * n + i] = std::sin(0.3 * i + k);
+                const double r2[2] = {0.01, -0.02};
+                const double R2[4] = {0.02, 7.0, 0.005, 0.03};  // (the upper triangle is never read)
+                rep = filter.processLinearMeasurement(H2.data(), 2, r2, R2, false, 50.0);
+                std::printf("linear %d %d %a %a %a\n", rep.dof, rep.info, rep.nis, rep.logdet_S, rep.loglik);
+                printState("updated", filter);
             }
             if (nees) {
                 std::vector<double> e(size_t(S.n));

@@ -29,6 +29,8 @@
 #include "eqf_frame.hpp"
 #include "eqf_sample.hpp"
 #include "eqf_sample_host.hpp"
+#include "eqf_linear.hpp"
+#include "eqf_linear_host.hpp"
 
 using namespace eqf;
 
@@ -235,6 +237,12 @@ struct eqf_filter {
     int sampRows = 0;
     char *hSampSmall = nullptr, *dSampSmall = nullptr;
     hipEvent_t evSamp = nullptr;
+    // the low-rank linear measurement update (eqf_linear.hpp; eqf_update_linear), allocated by its first call: the operands of a call as a
+    // pinned image and its device copy (linear::SmallLayout; evLin: the last upload from the pinned image has been read), the workspace
+    // [B][linear::WorkLayout::stride()] and the result records [B][kLinHead]
+    char *hLinSmall = nullptr, *dLinSmall = nullptr;
+    double *dLinWs = nullptr, *dLinOut = nullptr;
+    hipEvent_t evLin = nullptr;
     // eqf_copy_filters (eqf_clone.hpp): the pair table (pinned image + device copy, grown on demand), the small-state staging image of the
     // in-place case (allocated on first need) and two events -- evCloneSrc orders a copy behind this handle's work when it is the source,
     // evCloneDone marks the end of the last copy INTO this handle (its pair table may be reused, the source may go on)
@@ -1558,6 +1566,11 @@ void freeAll(eqf_filter* f) {
         hipFree(p);
     if (f->hSampSmall) hipHostFree(f->hSampSmall);
     if (f->evSamp) hipEventDestroy(f->evSamp);
+    hipFree(f->dLinSmall);
+    hipFree(f->dLinWs);
+    hipFree(f->dLinOut);
+    if (f->hLinSmall) hipHostFree(f->hLinSmall);
+    if (f->evLin) hipEventDestroy(f->evLin);
     if (f->hGate) hipHostFree(f->hGate);
     if (f->dMask) hipFree(f->dMask);
     if (f->evGate) hipEventDestroy(f->evGate);
@@ -3051,6 +3064,112 @@ int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, cons
     return EQF_OK;
 }
 
+// ---- the low-rank linear measurement update (eqf_linear.hpp; index arithmetic and argument checks: eqf_linear_host.hpp)
+static_assert(linear::kRefBase == kBase && linear::kPadBase == kLm0 && linear::kRows == kLinRows && linear::kTile == kSB &&
+              linear::kHead == kLinHead, "eqf_linear_host.hpp repeats the layout constants");
+namespace {
+// every buffer of eqf_update_linear in one go; a failure frees what this call got and leaves the handle as it was
+int linAlloc(eqf_filter* f) {
+    if (f->dLinWs) return EQF_OK;
+    const linear::SmallLayout sl{f->B, linear::refOrder(f->cap)};
+    const linear::WorkLayout wl{f->ld};
+    void *h = nullptr, *d = nullptr, *w = nullptr, *o = nullptr;
+    hipEvent_t ev = nullptr;
+    if (hipHostMalloc(&h, sl.bytes(), hipHostMallocDefault) != hipSuccess || hipMalloc(&d, sl.bytes()) != hipSuccess ||
+        hipMalloc(&w, sizeof(double) * size_t(wl.stride()) * f->B) != hipSuccess ||
+        hipMalloc(&o, sizeof(double) * size_t(kLinHead) * f->B) != hipSuccess ||
+        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        if (h) hipHostFree(h);
+        for (void* p : {d, w, o})
+            if (p) hipFree(p);
+        return EQF_ERR_HIP;
+    }
+    f->hLinSmall = static_cast<char*>(h);
+    f->dLinSmall = static_cast<char*>(d);
+    f->dLinWs = static_cast<double*>(w);
+    f->dLinOut = static_cast<double*>(o);
+    f->evLin = ev;
+    return EQF_OK;
+}
+}  // namespace
+
+int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh, const double* resid, const double* R, double gate,
+    const unsigned char* mask, double* gamma, int ldg, eqf_linear_report* report) {
+    if (!f || !linear::headArgsOk(local, m, H, resid, R, gate)) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);  // (queued IMU calls and a pending gate first: the gate may still change the landmark counts)
+    const int B = f->B;
+    std::vector<int> N(B);
+    for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
+    if (!linear::argsOk(m, H, ldh, resid, R, mask, gamma, ldg, B, N.data())) return EQF_ERR_INVALID;
+    int rc = linAlloc(f);
+    if (rc) return rc;
+    if (local) {
+        rc = launchLocal(f, 0, B, false);  // (only writes the J records)
+        if (rc) return rc;
+    }
+    const linear::SmallLayout sl{B, linear::refOrder(f->cap)};
+    const linear::WorkLayout wl{f->ld};
+    HIPC(hipEventSynchronize(f->evLin));
+    double* hs = reinterpret_cast<double*>(f->hLinSmall);
+    double* ds = reinterpret_cast<double*>(f->dLinSmall);
+    unsigned char* hm = reinterpret_cast<unsigned char*>(hs + sl.offMask());
+    for (int b = 0; b < B; ++b) {
+        linear::packFilter(m, N[b], H + size_t(b) * m * ldh, ldh, resid + size_t(b) * m, R + size_t(b) * m * m,
+            hs + sl.offH() + size_t(b) * kLinRows * sl.ldr, sl.ldr, hs + sl.offResid() + size_t(b) * kLinRows,
+            hs + sl.offR() + size_t(b) * kLinRows * kLinRows);
+        hm[b] = mask ? (mask[b] ? 1 : 0) : 1;
+    }
+    HIPC(hipMemcpyAsync(f->dLinSmall, f->hLinSmall, sl.bytes(), hipMemcpyHostToDevice, f->stream));
+    HIPC(hipEventRecord(f->evLin, f->stream));
+    const int nMax = maxN(f), nt = linear::rowTiles(nMax);
+    LinArgs a{};
+    a.g = f->g[f->pG]; a.Sigma = static_cast<double*>(f->Sigma[f->pS]); a.ld = f->ld; a.sigmaStride = f->sigmaStride;
+    a.H = ds + sl.offH(); a.ldr = sl.ldr; a.resid = ds + sl.offResid(); a.R = ds + sl.offR();
+    a.mask = reinterpret_cast<const unsigned char*>(ds + sl.offMask());
+    a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.m = m; a.gate = gate;
+    a.ws = f->dLinWs; a.wsStride = wl.stride(); a.out = f->dLinOut;
+    rc = profiled(f, EQF_PROF_LIN_ROWS, [&] { hipLaunchKernelGGL(k_lin_rows, dim3(B), dim3(256), 0, f->stream, a); });
+    if (!rc) rc = profiled(f, EQF_PROF_LIN_GAIN, [&] { hipLaunchKernelGGL(k_lin_gain, dim3(nt, B), dim3(256), kLinGainLdsBytes, f->stream, a); });
+    if (!rc) rc = profiled(f, EQF_PROF_LIN_SOLVE, [&] { hipLaunchKernelGGL(k_lin_solve, dim3(B), dim3(256), 0, f->stream, a); });
+    if (!rc)
+        rc = profiled(f, EQF_PROF_LIN_DOWNDATE,
+            [&] { hipLaunchKernelGGL(k_lin_downdate, dim3(linear::triTiles(nt), B), dim3(256), 0, f->stream, a); });
+    if (rc) return rc;
+    // the group step, behind the solve's verdict (entry 3 of the record, where eqf_nees.hpp's info sits)
+    IncArgs ia{};
+    ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = f->dLinWs + wl.offGamma(); ia.strideG = wl.stride();
+    ia.off = 0; ia.mask = nullptr; ia.info = f->dLinOut;
+    hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, ia);
+    HIPC(hipGetLastError());
+    f->csValid = false;  // (C Sigma / S left by an earlier burst describe the old Sigma and the old landmarks)
+    if (!gamma && !report) return EQF_OK;
+    std::vector<double> hO(size_t(B) * kLinHead), hG;
+    HIPC(hipMemcpyAsync(hO.data(), f->dLinOut, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
+    if (gamma) {
+        hG.resize(size_t(B) * f->ld);
+        HIPC(hipMemcpy2DAsync(hG.data(), sizeof(double) * f->ld, f->dLinWs + wl.offGamma(), sizeof(double) * wl.stride(),
+            sizeof(double) * f->ld, B, hipMemcpyDeviceToHost, f->stream));
+    }
+    HIPC(hipStreamSynchronize(f->stream));
+    for (int b = 0; b < B; ++b) {
+        const double* o = hO.data() + size_t(b) * kLinHead;
+        const int info = int(o[3]);
+        if (report) {
+            const bool solved = info == 0 || info == 2;
+            const double nan = std::nan("");
+            report[b].nis = solved ? o[0] : nan;
+            report[b].logdet_S = solved ? o[1] : nan;
+            report[b].loglik = solved ? o[2] : nan;
+            report[b].dof = m;
+            report[b].info = info;
+        }
+        if (gamma) linear::unpackGamma(hG.data() + size_t(b) * f->ld, N[b], gamma + size_t(b) * ldg, info != 0);
+    }
+    return EQF_OK;
+}
+
 int eqf_tile_syrk_i8(int device, void* stream, int batch, const int* nv, const int* mp, const double* Y, int ldY, long long strideY,
     const double* Sin, double* Sout, int ld, long long sigmaStride, int slices, void* workspace, size_t workspace_bytes) {
     if (batch < 1 || !nv || !mp || !Y || !Sin || !Sout || !workspace || slices < 5 || slices > 7 || Sin == Sout) return EQF_ERR_INVALID;
@@ -3187,7 +3306,8 @@ int eqf_profile_get(eqf_filter* f, int cls, long long* launches, double* total_m
 
 const char* eqf_profile_class_name(int cls) {
     static const char* names[EQF_PROF_CLASSES] = {"k_propagate", "k_update_prep", "k_chol_step", "k_update_reduce", "k_update_finish",
-        "k_downdate", "churn", "k_dense_riccati", "k_imu_burst", "k_chol_step_dd", "k_chol_resident"};
+        "k_downdate", "churn", "k_dense_riccati", "k_imu_burst", "k_chol_step_dd", "k_chol_resident", "k_lin_rows", "k_lin_gain",
+        "k_lin_solve", "k_lin_downdate"};
     return (cls >= 0 && cls < EQF_PROF_CLASSES) ? names[cls] : "?";
 }
 

@@ -177,6 +177,20 @@ class VIOFilter:
                              scale=[scale], stats=True)
         return dict(logdet=float(r["logdet"][0]), min_pivot=float(r["min_pivot"][0]), dof=int(r["dof"][0]), info=int(r["info"][0]))
 
+    def process_linear_measurement(self, H, resid, R, local=True, gate=float("inf"), want_gamma=False):
+        """A measurement update with m <= 16 linear rows: resid = H eps + noise, noise ~ N(0, R), eps "truth minus estimate" in the
+        coordinates of stateCovarianceLocal() (local; consistency.velocity_rows / gravity_rows / landmark_rows write the usual rows) or of
+        stateCovariance().  gate: chi-square threshold on the m-dof nis (consistency.chi2_gate_threshold(p, dof=m)).  Returns dict(nis,
+        logdet_S, loglik, dof, info[, gamma]); the filter is untouched when info != 0 (include/eqf_vio_amd.h: eqf_update_linear)."""
+        r = self._fb.update_linear(np.atleast_2d(np.asarray(H, dtype=float)), resid, R, local=local, gate=gate, want_gamma=want_gamma)
+        out = dict(nis=float(r["nis"][0]), logdet_S=float(r["logdet_S"][0]), loglik=float(r["loglik"][0]), dof=int(r["dof"][0]),
+                   info=int(r["info"][0]))
+        if want_gamma:
+            out["gamma"] = r["gamma"][0]
+        return out
+
+    processLinearMeasurement = process_linear_measurement
+
     def copyStateFrom(self, other):
         """This filter continues from the state of `other` (fork, or snapshot and roll back), copied on the device
         (include/eqf_vio_amd.h: eqf_copy_filters).  Settings, camera offset and capacity stay this filter's own."""

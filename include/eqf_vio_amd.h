@@ -336,6 +336,43 @@ int eqf_apply_increment(eqf_filter* f, const double* gamma, int ldg, const unsig
  * EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle. */
 int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, const double* scale /* [batch] or NULL */,
     eqf_sigma_stats* stats /* [batch] or NULL */);
+/* A measurement update with 1 <= m <= 16 caller-supplied LINEAR rows, for every filter of the handle in one call (csrc/eqf_linear.hpp): a
+ * zero-velocity detection, a wheel or GNSS speed, a range, a surveyed landmark, an attitude reference.  The convention is the header's:
+ * chart coordinates are "truth minus estimate" and the model is resid = H eps + noise, noise ~ N(0, R).
+ *   H[(b * m + k) * ldh + i]: row k of filter b's measurement matrix, i in the reference index map (eqf_get_sigma's); ldh >= 11 + 3 N_b.
+ *   resid[b * m + k]: measured minus predicted.  R[(b * m + k) * m + l]: the m x m noise covariance; only the lower triangle is read.
+ *   local = 0: eps is the error in the ORIGIN chart -- the coordinates of eqf_get_sigma, of eqf_get_last_update's gamma and of
+ *       eqf_apply_increment.  local = 1: eps is eps_loc = J eps of eqf_get_sigma_local, the error around the ESTIMATE, which is what a
+ *       user can write rows for; the library forms H J on the device from eqf_get_local_jacobian's blocks.
+ * Per filter that takes part, in fp64 (Ht = H or H J):
+ *   B = Sigma Ht^T,  S = Ht B + R = L L^T,  Y = L^-1 B^T,  z = L^-1 resid,  gamma = Y^T z,  Sigma <- Sigma - Y^T Y (in place, bit-for-bit
+ *   symmetric when Sigma was),  bias += gamma[0:6],  X <- VIOExp(liftInnovation(gamma[6:], xi0)) X  -- eqf_apply_increment's step with
+ *   gamma: ALWAYS the plain lift, whatever the handle's lift settings are (bundleLift needs Sigma_e's factorisation).
+ * xi0, the clock, the integrator, the ids, eqf_get_last_update, the innovation statistics, the gate report, the outlier gate and the
+ * sticky flag stay as they are; eqf_device_error is never touched.  Trouble of ONE filter goes into report[b].info and that filter keeps
+ * every bit, Sigma included:
+ *   gate: a chi-square threshold on the m-dof nis (consistency.chi2_gate_threshold(p, dof = m)); +inf disarms it.
+ *   mask [batch] or NULL (all): 0 leaves the filter alone.
+ *   gamma [batch][ldg] or NULL: the increments in the reference index map, rows of untouched filters written as 0; ldg >= 11 + 3 N_b.
+ * Settles what the handle has deferred first (queued IMU calls, a pending gate).  With gamma == NULL and report == NULL the call enqueues
+ * and returns; otherwise it synchronises and copies out.  EQF_ERR_INVALID, before any effect: NULL f, H, resid or R; m out of range; local
+ * not 0 or 1; ldh or ldg too small for some filter; an entry of H, resid or R's lower triangle of a filter that takes part that is not
+ * finite; a gate that is NaN or <= 0.  EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle.  EQF_ERR_HIP if the workspace, allocated by the
+ * first call from capacity and batch, cannot be had (the handle stays as it was).  Bit for bit the same from run to run and for a filter
+ * alone in a handle or anywhere in a batch (no atomics, one fixed summation order).
+ * Not covered: the partitioned filter (eqf_tf_*, eqf_tiled_*), fp32 handles, the innovation lift (bundleLift), m > 16. */
+typedef struct eqf_linear_report {
+    double nis;       /* r^T S^-1 r = z^T z                                        */
+    double logdet_S;  /* 2 sum log L_kk                                            */
+    double loglik;    /* -(nis + logdet_S + m log 2 pi) / 2                        */
+    int dof;          /* m                                                          */
+    int info;         /* 0 applied; 1 S not positive definite or a non-finite value met: filter untouched (nis, logdet_S, loglik NaN);
+                         2 gated (nis > gate): untouched; 3 masked out: untouched (NaN);
+                         -1 local = 1 and this filter's gravity chart is singular: untouched (NaN) */
+} eqf_linear_report;
+int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh, const double* resid, const double* R, double gate,
+    const unsigned char* mask /* [batch] or NULL */, double* gamma /* [batch][ldg] or NULL */, int ldg,
+    eqf_linear_report* report /* [batch] or NULL */);
 
 /* Propagate backend: 0 = block-structured HBM-bound kernel (default, product path),
  * 1 = dense F Sigma F^T on MFMA (what the reference executes; BASELINE cfg 3 cross-check). */

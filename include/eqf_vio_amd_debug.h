@@ -70,7 +70,11 @@ int eqf_debug_sigma_local_all(eqf_filter* f);
 #define EQF_PROF_BURST 8 /* k_burst_build + k_burst_riccati: one bracket per burst of integrateUpToTime steps */
 #define EQF_PROF_CHOL_DD 9 /* the one k_chol_step64 launch per update that also carries Sigma - Y^T Y (64-wide path) */
 #define EQF_PROF_CHOL_RESIDENT 10 /* k_chol_resident: the whole factorisation part of an update as one launch */
-#define EQF_PROF_CLASSES 11
+#define EQF_PROF_LIN_ROWS 11 /* eqf_update_linear's four launches (csrc/eqf_linear.hpp), one bracket each per call */
+#define EQF_PROF_LIN_GAIN 12
+#define EQF_PROF_LIN_SOLVE 13
+#define EQF_PROF_LIN_DOWNDATE 14
+#define EQF_PROF_CLASSES 15
 int eqf_profile_enable(eqf_filter* f, int on);
 int eqf_profile_get(eqf_filter* f, int cls, long long* launches, double* total_ms);
 const char* eqf_profile_class_name(int cls);

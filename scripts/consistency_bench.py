@@ -27,6 +27,17 @@
                    arithmetic the host would also have to redo, so the host route is timed in its favour -- on the same states after three
                    frames, scale 1e-3 so that forty moves leave the filters where they were to first order.  Both warmed up, alternated over
                    20 repetitions; prints one JSON line with medians, min / max and the ratio.  No threshold is asserted.
+  linear B N m     DESIGN.md section 4.5f: FilterBatch.update_linear(stats=True: ends in a synchronise) against the host route it replaces,
+                   for every filter dump_state (the covariance over the bus) + consistency.linear_update_host + restore_state -- WITHOUT
+                   the group arithmetic the host would also have to redo, so the host route is timed in its favour -- on the same states
+                   after three frames.  m = 3: the velocity rows; otherwise dense rows; R is a hundred times H Sigma H^T's mean diagonal
+                   and the residual a thousandth of a standard deviation, so that forty updates leave the filters where they were to
+                   first order.  Both warmed up, alternated over 20 repetitions; prints one JSON line with medians, min / max, the ratio
+                   and whether the spreads overlap.  No threshold is asserted.
+  linearkern B N m a workload for `rocprofv3 --kernel-trace --stats -- python scripts/consistency_bench.py linearkern B N m`: thirty updates.
+  linearsum DIR    kernel-trace stats CSVs under DIR/linearkern_B_N_m -> the four k_lin_* kernels; k_lin_gain as n^2 * 8 * B bytes (one read
+                   of Sigma) and k_lin_downdate as (2 T_lower + T_mirror) * 64^2 * 8 * B bytes (read and write of the lower-triangle tiles,
+                   write of the mirror tiles) over their average times, against the measured 6.29 TB/s.
 """
 import csv
 import glob
@@ -222,6 +233,87 @@ def sample(B, N, reps=20):
                           speedup_of_medians=round(float(np.median(th) / np.median(ta)), 1))))
 
 
+def _linear_setup(B, N, m):
+    import numpy as np
+    from eqf_vio_amd import consistency
+
+    fg, _ = _nees_setup(B, N)
+    n = 11 + 3 * N
+    H = consistency.velocity_rows(N) if m == 3 else np.random.default_rng(3).standard_normal((m, n))
+    Hs = np.ascontiguousarray(np.broadcast_to(H, (B, m, n)))
+    Sl = fg.sigma_local(0)
+    d = float(np.mean(np.diag(H @ Sl @ H.T)))
+    R = 100.0 * d * np.eye(m)
+    r = 1e-3 * np.sqrt(d) * np.random.default_rng(4).standard_normal((B, m))
+    return fg, H, Hs, r, R
+
+
+def linear(B, N, m, reps=20):
+    import numpy as np
+    from eqf_vio_amd import consistency
+
+    fg, H, Hs, r, R = _linear_setup(B, N, m)
+
+    def device():
+        return fg.update_linear(Hs, r, R, local=True, stats=True)["info"]
+
+    def host():
+        for b in range(B):
+            snap = fg.dump_state(b)
+            J = consistency.jacobian_matrix(consistency.local_jacobian_blocks(snap["origin"], snap["group"]))
+            up = consistency.linear_update_host(snap["sigma"], H @ J, r[b], R)
+            snap["sigma"] = up["Sigma"]
+            snap["bias"] = snap["bias"] + up["gamma"][0:6]  # (the group step is left out: see the module docstring)
+            fg.restore_state(snap, b)
+
+    assert not np.any(device())  # (first calls: allocations)
+    host()
+    device(), host()
+    ta, th = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        device()
+        t1 = time.perf_counter()
+        host()
+        t2 = time.perf_counter()
+        ta.append((t1 - t0) * 1e3)
+        th.append((t2 - t1) * 1e3)
+    assert fg.device_error() == 0
+    q = lambda v: dict(median_ms=round(float(np.median(v)), 3), min_ms=round(min(v), 3), max_ms=round(max(v), 3))
+    print(json.dumps(dict(case="update_linear", B=B, N=N, m=m, reps=reps, device=q(ta), host=q(th),
+                          speedup_of_medians=round(float(np.median(th) / np.median(ta)), 1), spreads_overlap=bool(max(ta) >= min(th)))), flush=True)
+
+
+def linearkern(B, N, m):
+    import numpy as np
+
+    fg, H, Hs, r, R = _linear_setup(B, N, m)
+    for _ in range(30):
+        assert not np.any(fg.update_linear(Hs, r, R, local=True, stats=True)["info"])
+    assert fg.device_error() == 0
+    print(f"linearkern B={B} N={N} m={m}: done")
+
+
+def linearsum(d):
+    print("B x N x m      kernel            avg / min / max us (calls)      bytes        TB/s (avg)   of 6.29")
+    for path in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)):
+        tag = [t for t in os.path.relpath(path, d).split(os.sep) if t.startswith("linearkern_")]
+        if not tag:
+            continue
+        _, B, N, m = tag[0].split("_")
+        B, N, m = int(B), int(N), int(m)
+        n = 12 + 3 * N
+        nt = -(-n // 64)
+        by = {"k_lin_gain": 8.0 * n * n * B, "k_lin_downdate": 8.0 * 64 * 64 * B * (2 * nt * (nt + 1) // 2 + nt * (nt - 1) // 2)}
+        for r in csv.DictReader(open(path)):
+            name = r.get("Name") or r.get("KernelName") or ""
+            for key in ("k_lin_rows", "k_lin_gain", "k_lin_solve", "k_lin_downdate", "k_apply_increment", "k_local_jacobian"):
+                if key in name:
+                    a, lo, hi = float(r["AverageNs"]) / 1e3, float(r["MinNs"]) / 1e3, float(r["MaxNs"]) / 1e3
+                    tail = f"{by[key] / 1e6:10.2f} MB   {by[key] / a / 1e6:6.3f}   {100 * by[key] / a / 1e6 / 6.29:5.1f} %" if key in by else ""
+                    print(f"{B:3d} x {N:<5d} x {m:<2d} {key:18s} {a:9.1f} / {lo:8.1f} / {hi:8.1f} ({r['Calls']:>3s})   {tail}")
+
+
 def neeskern(B, N):
     fg, E = _nees_setup(B, N)
     for _ in range(10):
@@ -408,6 +500,12 @@ if __name__ == "__main__":
         copysum(sys.argv[2])
     elif cmd == "sample":
         sample(int(sys.argv[2]), int(sys.argv[3]))
+    elif cmd == "linear":
+        linear(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
+    elif cmd == "linearkern":
+        linearkern(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
+    elif cmd == "linearsum":
+        linearsum(sys.argv[2])
     elif cmd == "summarize":
         summarize(sys.argv[2])
     else:
