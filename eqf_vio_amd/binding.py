@@ -70,6 +70,12 @@ class LinearReport(C.Structure):
     _fields_ = [("nis", C.c_double), ("logdet_S", C.c_double), ("loglik", C.c_double), ("dof", C.c_int), ("info", C.c_int)]
 
 
+class MixtureReport(C.Structure):
+    """eqf_mixture_report (include/eqf_vio_amd.h)."""
+
+    _fields_ = [("n_eff", C.c_double), ("spread_trace", C.c_double), ("total_trace", C.c_double), ("n", C.c_int), ("info", C.c_int)]
+
+
 _lib = None
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -80,6 +86,7 @@ EXPORTED_SYMBOLS = [
     "eqf_get_ids", "eqf_get_state_estimate", "eqf_get_origin", "eqf_get_group", "eqf_get_bias", "eqf_get_sigma",
     "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
     "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters", "eqf_update_linear",
+    "eqf_get_mixture_moments", "eqf_merge_filters", "eqf_debug_mixture_launches", "eqf_debug_sigma_pad",
     "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
     "eqf_set_sigma", "eqf_set_state", "eqf_copy_filters", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
@@ -149,6 +156,11 @@ def lib():
         if hasattr(L, "eqf_update_linear"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
             L.eqf_update_linear.argtypes = [vp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double, C.POINTER(C.c_ubyte), _dp, C.c_int,
                                             C.POINTER(LinearReport)]
+        if hasattr(L, "eqf_merge_filters"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
+            L.eqf_get_mixture_moments.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.POINTER(MixtureReport)]
+            L.eqf_merge_filters.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, C.POINTER(MixtureReport)]
+            L.eqf_debug_mixture_launches.argtypes = [vp]
+            L.eqf_debug_sigma_pad.argtypes = [vp, C.c_int, C.c_int, _dp]
         if hasattr(L, "eqf_set_outlier_gate"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
             L.eqf_set_outlier_gate.argtypes = [vp, C.c_int, C.c_double]
             L.eqf_get_outlier_gate.argtypes = [vp, _ip, _dp]
@@ -595,6 +607,52 @@ class FilterBatch:
         if want_gamma:
             out["gamma"] = G
         return out
+
+    @staticmethod
+    def _members(idx, w):
+        ii = np.ascontiguousarray(np.atleast_1d(idx), dtype=np.int32)
+        ww = np.ascontiguousarray(np.atleast_1d(w), dtype=np.float64)
+        if ii.ndim != 1 or ii.shape != ww.shape or len(ii) == 0:
+            raise ValueError("idx and w must be one-dimensional, of one length and not empty")
+        return ii, ww
+
+    @staticmethod
+    def _mixture_report(r):
+        return dict(n_eff=r.n_eff, spread_trace=r.spread_trace, total_trace=r.total_trace, n=r.n, info=r.info)
+
+    def mixture_moments(self, idx, w, ref, centred=True):
+        """Mean and covariance of the weighted members idx of this handle in the chart of filter ref's estimate, the spread between the
+        members included, on the device (include/eqf_vio_amd.h: eqf_get_mixture_moments; consistency.mixture_moments_host is its numpy
+        statement, consistency.mixture_weights turns log-likelihoods into w).  Returns a dict with mean (11 + 3N,), P (11 + 3N, 11 + 3N)
+        in the reference's index map -- NaN where info != 0 -- and n_eff, spread_trace, total_trace, n, info."""
+        ii, ww = self._members(idx, w)
+        n = 11 + 3 * self.num_landmarks(int(ref)) if 0 <= int(ref) < self.B else 11
+        mean, P, rep = np.zeros(n), np.zeros((n, n)), MixtureReport()
+        _check(lib().eqf_get_mixture_moments(self._h, len(ii), ii.ctypes.data_as(_ip), _p(ww), int(ref), int(bool(centred)), _p(mean), _p(P), n,
+                                             C.byref(rep)), "eqf_get_mixture_moments")
+        return dict(mean=mean, P=P, **self._mixture_report(rep))
+
+    def merge(self, idx, w, ref, dst, report=True):
+        """Filter dst becomes ONE filter that matches the first two moments of the weighted members idx: origin = the merged state, X =
+        identity, Sigma = the members' mean-square error about it (include/eqf_vio_amd.h: eqf_merge_filters; consistency.merge_host).
+        dst may be a member.  report: wait for the device and return n_eff, spread_trace, total_trace, n, info (info != 0: nothing was
+        written); otherwise enqueue and return None."""
+        ii, ww = self._members(idx, w)
+        rep = MixtureReport() if report else None
+        _check(lib().eqf_merge_filters(self._h, len(ii), ii.ctypes.data_as(_ip), _p(ww), int(ref), int(dst), C.byref(rep) if report else None),
+               "eqf_merge_filters")
+        return self._mixture_report(rep) if report else None
+
+    def debug_mixture_launches(self):
+        """Kernel launches of the most recent merge() (include/eqf_vio_amd_debug.h)."""
+        return _check(lib().eqf_debug_mixture_launches(self._h), "eqf_debug_mixture_launches")
+
+    def debug_sigma_pad(self, b=0, image=0):
+        """Largest |entry| of the pad row and column of filter b's internal covariance (image 0) or of slot b of the scratch image, where
+        mixture_moments leaves P in slot ref (image 1) (include/eqf_vio_amd_debug.h)."""
+        out = C.c_double()
+        _check(lib().eqf_debug_sigma_pad(self._h, int(b), int(image), C.byref(out)), "eqf_debug_sigma_pad")
+        return out.value
 
     def debug_sigma_local_all(self):
         """k_sigma_local for every filter of the handle in one launch, nothing copied (include/eqf_vio_amd_debug.h)."""

@@ -17,6 +17,10 @@ to first order eps_loc = J eps with the block-diagonal J of local_jacobian_block
                                          FilterBatch.update_linear's gate
   velocity_rows / gravity_rows / landmark_rows(N, i)   measurement rows in the estimate's chart for FilterBatch.update_linear(local=True)
   linear_update_host(Sigma, H, resid, R) the numpy statement of that update (include/eqf_vio_amd.h: eqf_update_linear)
+  mixture_weights(loglik)                log-likelihoods -> the normalised weights of a mixture (systematic_resample's)
+  mixture_moments_host(members, w, centre, centred)   mean and covariance of a weighted batch in the chart of a centre state, the spread
+                                         between the members included -- the numpy statement of FilterBatch.mixture_moments
+  merge_host(members, w, ref)            ... and of FilterBatch.merge: the one state and covariance that match the batch's first two moments
 
 `origin`, `group`, `estimate` are the dicts of FilterBatch.origin() / group() / state_estimate(): quaternions (w, x, y, z), Eigen semantics.
 """
@@ -402,3 +406,118 @@ def systematic_resample(loglik, u):
     parents = np.searchsorted(c, pts, side="right")
     last = int(np.flatnonzero(w > 0)[-1])
     return np.minimum(parents, last).astype(np.int32)
+
+
+# ---- moment matching over a weighted batch (include/eqf_vio_amd.h: eqf_get_mixture_moments / eqf_merge_filters)
+def mixture_weights(loglik):
+    """Normalised weights of a batch from its log-likelihoods: systematic_resample's exp(loglik - max), divided by their sum; a
+    log-likelihood of -inf or NaN gets weight 0.  Raises ValueError if no weight is positive or one is +inf."""
+    ll = np.asarray(loglik, dtype=float).reshape(-1)
+    ok = ~np.isnan(ll) & (ll > -np.inf)
+    if len(ll) == 0 or not ok.any():
+        raise ValueError("no filter with a finite log-likelihood")
+    if np.isposinf(ll[ok]).any():
+        raise ValueError("a log-likelihood of +inf")
+    w = np.zeros(len(ll))
+    w[ok] = np.exp(ll[ok] - ll[ok].max())
+    return w / w.sum()
+
+
+def normalise_weights(w):
+    """w~_k = w_k / s, s the serial sum in the order given (what the library does on the host, in double)."""
+    w = np.asarray(w, dtype=float).reshape(-1)
+    if len(w) == 0 or not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError("weights must be finite and not negative")
+    s = 0.0
+    for x in w:
+        s += float(x)
+    if not s > 0.0:
+        raise ValueError("the weight sum must be positive")
+    return w / s
+
+
+def chart_transition(eta_b, eta_c):
+    """T_b (2, 2): the differential at 0 of chi_c o chi_b^-1 on the gravity sphere, stereoSphereChartDiff(eta_b, pole eta_c)
+    stereoSphereChartInvDiff(0, pole eta_b)."""
+    return stereo_sphere_chart_diff(eta_b, eta_c) @ stereo_sphere_chart_inv_diff_at_zero(eta_b)
+
+
+def lower_mirrored(S):
+    """The Sigma the mixture kernels see.  They read the blocks on and below the block diagonal of every member's covariance -- the 11 x 11
+    base block and the diagonal 3 x 3 landmark blocks whole, as stored, the blocks below them -- never a block above it; what they compute
+    is the lower triangle of P, mirrored.  So a Sigma that its own updates have left symmetric only to rounding counts with those blocks:
+    the blocks above the block diagonal are returned as the transposes of the ones below."""
+    S = np.array(S, dtype=float)
+    edges = [0, 11] + list(range(14, S.shape[0] + 1, 3))
+    for a, b in zip(edges[:-1], edges[1:]):
+        S[a:b, b:] = S[b:, a:b].T
+    return S
+
+
+def mirror_lower(P):
+    """P's lower triangle with its mirror above it: how the mixture kernels write P (bit-for-bit symmetric)."""
+    P = np.asarray(P)
+    return np.tril(P) + np.tril(P, -1).T
+
+
+def _member_error(member, centre_est, centre_bias):
+    e = local_error(centre_est, member["estimate"], bias=centre_bias, true_bias=member["bias"])
+    return error_vector(e)
+
+
+def mixture_moments_host(members, w, centre, centred=True):
+    """The numpy statement of FilterBatch.mixture_moments.  members: a list of dicts with `estimate` (state_estimate(): q, v, p), `bias`,
+    `origin`, `group` and `sigma` (the filter's Sigma, origin chart; its blocks on and below the block diagonal count: lower_mirrored); w their weights (normalised here); centre: the index of the member
+    whose estimate is the centre c (its T is the identity by definition), or a dict with `estimate` and `bias` (every T is computed).
+    e_b = chi_c(xHat_b), J'_b = J_b with T_b G_b for G_b, eBar = sum w~ e, P = sum w~ [J' Sigma J'^T + (e - m)(e - m)^T], m = eBar if
+    centred else 0.  Returns dict(mean, P, e (n, dim), spread, n_eff, spread_trace, total_trace)."""
+    wt = normalise_weights(w)
+    if len(wt) != len(members):
+        raise ValueError("one weight per member")
+    own = centre if isinstance(centre, (int, np.integer)) else None
+    c = members[own] if own is not None else centre
+    eta_c = gravity_dir(c["estimate"]["q"])
+    E, terms = [], []
+    for k, mb in enumerate(members):
+        same = own is not None and (mb is members[own])
+        e = _member_error(mb, c["estimate"], c["bias"])
+        blocks = dict(local_jacobian_blocks(mb["origin"], mb["group"]))
+        if same:
+            e[6:8] = 0.0
+        else:
+            blocks["G"] = chart_transition(gravity_dir(mb["estimate"]["q"]), eta_c) @ blocks["G"]
+        J = jacobian_matrix(blocks)
+        E.append(e)
+        terms.append(J @ lower_mirrored(mb["sigma"]) @ J.T)
+    E = np.array(E)
+    mean = np.zeros(E.shape[1])
+    for k in range(len(wt)):
+        mean = mean + wt[k] * E[k]
+    m = mean if centred else np.zeros_like(mean)
+    P = np.zeros_like(terms[0])
+    spread = np.zeros_like(terms[0])
+    for k in range(len(wt)):
+        d = E[k] - m
+        P = P + wt[k] * terms[k]
+        spread = spread + wt[k] * np.outer(d, d)
+    P = mirror_lower(P + spread)
+    return dict(mean=mean, P=P, e=E, spread=spread, n_eff=1.0 / float(np.sum(wt * wt)), spread_trace=float(np.trace(spread)),
+                total_trace=float(np.trace(P)))
+
+
+def merge_host(members, w, ref):
+    """The numpy statement of FilterBatch.merge: eBar about member `ref`'s estimate; xBar = local_retract(xHat_ref, eBar) with bias_ref +
+    eBar[0:6] and pose position sum w~_k x_k; P about xBar with centred = 0.  Returns dict(estimate (q, x, v, p), bias, P, mean, n_eff,
+    spread_trace, total_trace): what filter dst's state_estimate(), bias() and sigma_local() show afterwards."""
+    wt = normalise_weights(w)
+    first = mixture_moments_host(members, wt, int(ref), centred=True)
+    r = members[int(ref)]
+    xbar = local_retract(r["estimate"], first["mean"], bias=r["bias"])
+    x = np.zeros(3)
+    for k, mb in enumerate(members):
+        x = x + wt[k] * np.asarray(mb["estimate"]["x"], dtype=float)
+    xbar["x"] = x
+    bias = xbar.pop("bias")
+    second = mixture_moments_host(members, wt, dict(estimate=xbar, bias=bias), centred=False)
+    return dict(estimate=xbar, bias=bias, P=second["P"], mean=first["mean"], n_eff=second["n_eff"], spread_trace=second["spread_trace"],
+                total_trace=second["total_trace"])

@@ -31,6 +31,8 @@
 #include "eqf_sample_host.hpp"
 #include "eqf_linear.hpp"
 #include "eqf_linear_host.hpp"
+#include "eqf_mixture.hpp"
+#include "eqf_mixture_host.hpp"
 
 using namespace eqf;
 
@@ -250,6 +252,14 @@ struct eqf_filter {
     int clonePairsCap = 0;
     char* dCloneSmall = nullptr;
     hipEvent_t evCloneSrc = nullptr, evCloneDone = nullptr;
+    // moment matching over the handle's filters (eqf_mixture.hpp; eqf_get_mixture_moments / eqf_merge_filters), allocated on first need
+    // from capacity and batch: the workspace (mixture::WorkLayout), the member table of a call (pinned image + device copy, grown on
+    // demand: members, then the distinct filters) and evMix: the last upload from the pinned image has been read
+    double* dMixWs = nullptr;
+    char *hMixTab = nullptr, *dMixTab = nullptr;
+    size_t mixTabBytes = 0;
+    int mixLaunches = 0;  // kernel launches of the most recent mixture call, counted as they are made (eqf_debug_mixture_launches)
+    hipEvent_t evMix = nullptr;
     // innovation statistics of every update (eqf_innov.hpp; eqf_set_option "innovation_stats"): the tail launch k_innov_stats and its
     // records [B][kInnovHead + cap], allocated when the option is first switched on
     int innovStats = 0;
@@ -1591,6 +1601,10 @@ void freeAll(eqf_filter* f) {
     if (f->hClonePairs) hipHostFree(f->hClonePairs);
     if (f->evCloneSrc) hipEventDestroy(f->evCloneSrc);
     if (f->evCloneDone) hipEventDestroy(f->evCloneDone);
+    hipFree(f->dMixWs);
+    hipFree(f->dMixTab);
+    if (f->hMixTab) hipHostFree(f->hMixTab);
+    if (f->evMix) hipEventDestroy(f->evMix);
     for (auto e : f->evPool) hipEventDestroy(e);
     for (auto& p : f->profPairs) {
         hipEventDestroy(p.a);
@@ -3167,6 +3181,242 @@ int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh,
         }
         if (gamma) linear::unpackGamma(hG.data() + size_t(b) * f->ld, N[b], gamma + size_t(b) * ldg, info != 0);
     }
+    return EQF_OK;
+}
+
+static_assert(mixture::kRefBase == kBase && mixture::kPadBase == kLm0 && mixture::kRows == kMixRows && mixture::kLanes == kMixLanes &&
+              mixture::kEstHead == kMixEstHead && sizeof(mixture::Member) == sizeof(MixMember) && sizeof(Glob) % 8 == 0,
+    "eqf_mixture_host.hpp repeats the layout constants");
+namespace {
+// every kernel launch of a mixture call is counted (eqf_debug_mixture_launches)
+#define MIX_LAUNCH(f, ...)                  \
+    do {                                    \
+        hipLaunchKernelGGL(__VA_ARGS__);    \
+        ++(f)->mixLaunches;                 \
+    } while (0)
+constexpr int kMixGlobWords = int(sizeof(Glob) / 8);
+// What both entry points check and build before any effect: the arguments, the members' landmark lists against the reference's, the
+// normalised weights and the tables.  (GATE has run: the id lists are settled.)
+struct MixCall {
+    std::vector<double> wt;
+    std::vector<mixture::Member> members;
+    std::vector<int> uniq;
+    double nEff = 0.0;
+    int N = 0;
+};
+int mixCheck(eqf_filter* f, int n, const int* idx, const double* w, int ref, bool merge, MixCall& c) {
+    const std::vector<int>& rid = f->ids[ref];
+    for (int k = 0; k < n; ++k) {
+        const int b = idx[k];
+        if (!mixture::sameIds(f->ids[b].data(), int(f->ids[b].size()), rid.data(), int(rid.size()))) return EQF_ERR_INVALID;
+        if (merge && (!f->init[b] || f->curTime[b] != f->curTime[ref])) return EQF_ERR_INVALID;
+    }
+    c.wt.resize(n);
+    c.nEff = mixture::normalise(n, w, c.wt.data());
+    mixture::buildTables(n, idx, c.wt.data(), ref, f->B, c.members, c.uniq);
+    c.N = int(rid.size());
+    return EQF_OK;  // (headArgsOk: the weight sum is positive, so at least one member is walked)
+}
+// every buffer a call needs; a failure leaves the handle as it was
+int mixAlloc(eqf_filter* f, size_t tabBytes) {
+    const mixture::WorkLayout wl{f->B, f->cap, f->ld, kMixGlobWords};
+    if (!f->dMixWs) {
+        void* w = nullptr;
+        hipEvent_t ev = nullptr;
+        if (hipMalloc(&w, sizeof(double) * wl.doubles()) != hipSuccess || hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+            (void)hipGetLastError();
+            if (w) hipFree(w);
+            return EQF_ERR_HIP;
+        }
+        f->dMixWs = static_cast<double*>(w);
+        f->evMix = ev;
+    }
+    if (tabBytes > f->mixTabBytes) {
+        HIPC(hipEventSynchronize(f->evMix));  // (the old image may still be read; nothing is held yet that a failure here would leak)
+        HIPC(hipStreamSynchronize(f->stream));
+        void *h = nullptr, *d = nullptr;
+        if (hipHostMalloc(&h, tabBytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&d, tabBytes) != hipSuccess) {
+            (void)hipGetLastError();
+            if (h) hipHostFree(h);
+            return EQF_ERR_HIP;
+        }
+        if (f->hMixTab) hipHostFree(f->hMixTab);
+        hipFree(f->dMixTab);
+        f->hMixTab = static_cast<char*>(h);
+        f->dMixTab = static_cast<char*>(d);
+        f->mixTabBytes = tabBytes;
+    }
+    if (!f->dSigmaLoc) {
+        if (hipMalloc(reinterpret_cast<void**>(&f->dSigmaLoc), sizeof(double) * size_t(f->sigmaStride) * f->B) != hipSuccess) {
+            (void)hipGetLastError();
+            f->dSigmaLoc = nullptr;
+            return EQF_ERR_HIP;
+        }
+    }
+    return EQF_OK;
+}
+// The tables' upload and the arguments of every kernel of a call; P goes to slot `slot` of the scratch image.
+int mixPrepare(eqf_filter* f, const MixCall& c, int ref, int dst, int slot, MixArgs& a) {
+    const size_t nm = c.members.size(), nu = c.uniq.size();
+    const size_t tabBytes = sizeof(MixMember) * nm + sizeof(int) * nu;
+    int rc = mixAlloc(f, tabBytes);
+    if (rc) return rc;
+    rc = launchLocal(f, 0, f->B, false);  // (only writes the J records)
+    if (rc) return rc;
+    f->mixLaunches = 1;  // (k_local_jacobian)
+    HIPC(hipEventSynchronize(f->evMix));
+    std::memcpy(f->hMixTab, c.members.data(), sizeof(MixMember) * nm);
+    std::memcpy(f->hMixTab + sizeof(MixMember) * nm, c.uniq.data(), sizeof(int) * nu);
+    HIPC(hipMemcpyAsync(f->dMixTab, f->hMixTab, tabBytes, hipMemcpyHostToDevice, f->stream));
+    HIPC(hipEventRecord(f->evMix, f->stream));
+    const mixture::WorkLayout wl{f->B, f->cap, f->ld, kMixGlobWords};
+    double* ws = f->dMixWs;
+    a = MixArgs{};
+    a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.cap = f->cap; a.B = f->B;
+    a.jac = f->dJac; a.jacT = ws + wl.offJac(); a.est = ws + wl.offEst(); a.err = ws + wl.offErr(); a.mean = ws + wl.offMean();
+    a.mem = reinterpret_cast<const MixMember*>(f->dMixTab); a.n = int(nm);
+    a.uniq = reinterpret_cast<const int*>(f->dMixTab + sizeof(MixMember) * nm); a.nUniq = int(nu);
+    a.N = c.N; a.ref = ref; a.dst = dst;
+    a.Sigma = static_cast<double*>(f->Sigma[f->pS]); a.ld = f->ld; a.sigmaStride = f->sigmaStride;
+    a.P = f->dSigmaLoc + (long long)slot * f->sigmaStride;
+    a.out = ws + wl.offOut(); a.verdict = reinterpret_cast<int*>(ws + wl.offVerdict());
+    a.stG = reinterpret_cast<Glob*>(ws + wl.offGlob()); a.stP0 = ws + wl.offP0(); a.stQ = ws + wl.offQ();
+    a.lmc = f->lmc;
+    a.delta = f->dbgDelta; a.gamma = f->dbgGamma; a.gammaTot = f->dbgGammaTot; a.innov = (f->innovStats && f->dInnov) ? f->dInnov : nullptr;
+    HIPC(hipMemsetAsync(a.verdict, 0, sizeof(int) * 4, f->stream));
+    return EQF_OK;
+}
+// errors about the centre, and P: the launches of one pass
+void mixPass(eqf_filter* f, const MixArgs& a) {
+    const int strips = std::max(1, (a.N + 255) / 256);
+    MIX_LAUNCH(f, k_mix_error, dim3(strips, a.nUniq), dim3(256), 0, f->stream, a);
+}
+void mixReduce(eqf_filter* f, const MixArgs& a) {
+    MIX_LAUNCH(f, k_mix_reduce, dim3(mixture::chunks(a.N), mixture::rowBlocks(a.N)), dim3(kMixLanes), 0, f->stream, a);
+    MIX_LAUNCH(f, k_mix_report, dim3(1), dim3(256), 0, f->stream, a);
+}
+void mixFillReport(eqf_mixture_report* r, const MixCall& c, int n, const double* out, int info) {
+    const double nan = std::nan("");
+    r->n_eff = c.nEff;
+    r->spread_trace = info ? nan : out[0];
+    r->total_trace = info ? nan : out[1];
+    r->n = n;
+    r->info = info;
+}
+}  // namespace
+
+int eqf_get_mixture_moments(eqf_filter* f, int n, const int* idx, const double* w, int ref, int centred, double* mean, double* P, int ld,
+    eqf_mixture_report* report) {
+    if (!f || !P || (centred != 0 && centred != 1) || !mixture::headArgsOk(n, idx, w, ref, f->B)) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);
+    MixCall c;
+    int rc = mixCheck(f, n, idx, w, ref, false, c);
+    if (rc) return rc;
+    const int nr = kBase + 3 * c.N, nn = kLm0 + 3 * c.N;
+    if (ld < nr) return EQF_ERR_INVALID;
+    MixArgs a;
+    rc = mixPrepare(f, c, ref, ref, ref, a);
+    if (rc) return rc;
+    a.centre = ref; a.centreFilter = ref; a.centred = centred;
+    const int strips = std::max(1, (c.N + 255) / 256);
+    MIX_LAUNCH(f, k_mix_estimate, dim3(strips, a.nUniq), dim3(256), 0, f->stream, a);
+    mixPass(f, a);
+    MIX_LAUNCH(f, k_mix_mean, dim3((nn + 255) / 256), dim3(256), 0, f->stream, a);
+    mixReduce(f, a);
+    hipLaunchKernelGGL(k_sigma_export<double>, dim3((nr + 255) / 256, nr), dim3(256), 0, f->stream, a.P, f->ld, nr, f->dOut, nr);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(f->hOut, f->dOut, sizeof(double) * (size_t)nr * nr, hipMemcpyDeviceToHost, f->stream));
+    std::vector<double> hm(nn);
+    double out[4];
+    int verdict[4];
+    HIPC(hipMemcpyAsync(hm.data(), a.mean, sizeof(double) * nn, hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipMemcpyAsync(out, a.out, sizeof(out), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipMemcpyAsync(verdict, a.verdict, sizeof(verdict), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipStreamSynchronize(f->stream));
+    const int info = verdict[2];
+    const double nan = std::nan("");
+    for (int r = 0; r < nr; ++r)
+        for (int q = 0; q < nr; ++q) P[(size_t)r * ld + q] = info ? nan : f->hOut[(size_t)r * nr + q];
+    if (mean)
+        for (int i = 0; i < nr; ++i) mean[i] = info ? nan : hm[mixture::refToPadded(i)];
+    if (report) mixFillReport(report, c, n, out, info);
+    return EQF_OK;
+}
+
+int eqf_merge_filters(eqf_filter* f, int n, const int* idx, const double* w, int ref, int dst, eqf_mixture_report* report) {
+    if (!f || dst < 0 || dst >= f->B || !mixture::headArgsOk(n, idx, w, ref, f->B)) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);
+    MixCall c;
+    int rc = mixCheck(f, n, idx, w, ref, true, c);
+    if (rc) return rc;
+    const int nn = kLm0 + 3 * c.N;
+    MixArgs a;
+    rc = mixPrepare(f, c, ref, dst, dst, a);
+    if (rc) return rc;
+    const int strips = std::max(1, (c.N + 255) / 256);
+    // first pass: eBar about the reference's own estimate; xBar; second pass: the mean-square error about xBar (centred = 0)
+    a.centre = ref; a.centreFilter = ref; a.centred = 1;
+    MIX_LAUNCH(f, k_mix_estimate, dim3(strips, a.nUniq), dim3(256), 0, f->stream, a);
+    mixPass(f, a);
+    MIX_LAUNCH(f, k_mix_mean, dim3((nn + 255) / 256), dim3(256), 0, f->stream, a);
+    MIX_LAUNCH(f, k_mix_retract, dim3(1), dim3(256), 0, f->stream, a);
+    a.centre = f->B; a.centreFilter = -1; a.centred = 0;
+    mixPass(f, a);
+    mixReduce(f, a);
+    // behind the verdict: Sigma, the small state, the constants
+    MIX_LAUNCH(f, k_mix_store, dim3((nn + 255) / 256, nn), dim3(256), 0, f->stream, a);
+    MIX_LAUNCH(f, k_mix_commit, dim3(std::max(1, (f->cap + 255) / 256)), dim3(256), 0, f->stream, a);
+    MIX_LAUNCH(f, k_mix_restore, dim3(std::max(1, (c.N + 127) / 128)), dim3(128), 0, f->stream, a);
+    HIPC(hipGetLastError());
+    // The host's bookkeeping of dst follows eqf_copy_filters(ref -> dst) -- if the device wrote.  Where that bookkeeping would not change
+    // (dst shares the reference's ids, clock and flags and has no gate report: a member, as a rule) the verdict is not waited for.
+    const bool same = f->ids[dst] == f->ids[ref] && f->curTime[dst] == f->curTime[ref] && f->init[dst] == f->init[ref] &&
+                      f->devInit[dst] == f->devInit[ref] && f->report[dst].ids.empty();
+    int info = 0;
+    if (report || !same) {
+        double out[4];
+        int verdict[4];
+        HIPC(hipMemcpyAsync(out, a.out, sizeof(out), hipMemcpyDeviceToHost, f->stream));
+        HIPC(hipMemcpyAsync(verdict, a.verdict, sizeof(verdict), hipMemcpyDeviceToHost, f->stream));
+        HIPC(hipStreamSynchronize(f->stream));
+        info = verdict[2];
+        if (report) mixFillReport(report, c, n, out, info);
+    }
+    if (info == 0) {
+        if (dst != ref) {
+            f->ids[dst] = f->ids[ref]; f->curTime[dst] = f->curTime[ref]; f->init[dst] = f->init[ref]; f->devInit[dst] = f->devInit[ref];
+        }
+        f->report[dst] = {};  // (the gate and its threshold are settings: they stay)
+        f->csValid = false;
+        f->permOnDevice.clear();
+        f->editOnDevice.clear();
+    }
+    return EQF_OK;
+}
+
+int eqf_debug_mixture_launches(eqf_filter* f) { return f ? f->mixLaunches : EQF_ERR_INVALID; }
+
+int eqf_debug_sigma_pad(eqf_filter* f, int b, int image, double* max_abs) {
+    if (!f || b < 0 || b >= f->B || (image != 0 && image != 1) || !max_abs) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);
+    if (image == 1 && !f->dSigmaLoc) return EQF_ERR_INVALID;
+    const double* S = (image ? f->dSigmaLoc : static_cast<const double*>(f->Sigma[f->pS])) + (long long)b * f->sigmaStride;
+    const int nn = kLm0 + 3 * int(f->ids[b].size());
+    std::vector<double> row(nn), col(nn);
+    HIPC(hipStreamSynchronize(f->stream));
+    HIPC(hipMemcpy(row.data(), S + (long long)kBase * f->ld, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy2D(col.data(), sizeof(double), S + kBase, sizeof(double) * f->ld, sizeof(double), nn, hipMemcpyDeviceToHost));
+    double m = 0.0;
+    for (int i = 0; i < nn; ++i) {  // (a NaN counts as not zero)
+        const double r = std::fabs(row[i]), c = std::fabs(col[i]);
+        m = (r > m || r != r) ? r : m;
+        m = (c > m || c != c) ? c : m;
+        if (m != m) break;
+    }
+    *max_abs = m;
     return EQF_OK;
 }
 

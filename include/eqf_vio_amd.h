@@ -374,6 +374,51 @@ int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh,
     const unsigned char* mask /* [batch] or NULL */, double* gamma /* [batch][ldg] or NULL */, int ldg,
     eqf_linear_report* report /* [batch] or NULL */);
 
+/* Moment matching over the filters of ONE handle, on the device (csrc/eqf_mixture.hpp): a weighted batch -- a Monte-Carlo study, a particle
+ * set, a bank of hypotheses -- turned back into one mean and one covariance that includes the spread between its members, and several
+ * filters replaced by one that matches their first two moments.  Everything is fp64 and in the reference index map of eqf_get_sigma.
+ *   idx[0..n): the members (need not be distinct: a repeated index is two members); w[k] >= 0 their weights, normalised on the host in
+ *   double (s the serial sum in the order of idx, w~_k = w_k / s); ref, one of idx: the reference member.  Every member must have the
+ *   reference's landmark ids in the reference's order.
+ * Moments are taken in the chart chi_c of a centre state c -- the chart of eqf_get_sigma_local (consistency.local_error): differences for
+ * bias, body velocity and body-frame landmarks, stereoSphereChart(eta, pole = eta_c) for the gravity direction eta = R^T e3.  Per member b
+ * with estimate xHat_b (eqf_get_state_estimate, eqf_get_bias):
+ *   e_b = chi_c(xHat_b);  J'_b = J_b of eqf_get_local_jacobian with its gravity block G_b replaced by T_b G_b, T_b =
+ *   stereoSphereChartDiff(eta_b, pole eta_c) stereoSphereChartInvDiff(0, pole eta_b), the differential at 0 of chi_c o chi_xHat_b^-1 (its
+ *   other blocks are the identity); T_b = I by definition where c is member b's own estimate.
+ *   eBar = sum_k w~_k e_k;   P = sum_k w~_k [ J'_k Sigma_k J'_k^T + (e_k - m)(e_k - m)^T ],  m = eBar (centred = 1) or 0 (centred = 0).
+ * eqf_get_mixture_moments: eBar -> mean (or NULL) and P (leading dimension ld >= 11 + 3 N) about c = xHat_ref.  Flushes queued IMU calls and
+ * synchronises like every getter; only reads the handle (it overwrites the scratch image of eqf_get_sigma_local, as eqf_get_nees does).
+ * eqf_merge_filters: eBar about xHat_ref; xBar = consistency.local_retract(xHat_ref, eBar) with bias_ref + eBar[0:6] -- the attitude turned by
+ * the shortest rotation that takes eta_ref to the merged direction, yaw the reference's, the pose position sum_k w~_k x_k (not part of the
+ * chart: it has no covariance); P about c = xBar with centred = 0, the mean-square error about the new estimate.  Filter dst then is what
+ * eqf_copy_filters(ref -> dst) would leave, except: origin = xBar, X = identity (A = (1, 0), w = 0, Q_i = (1, 1)), the merged bias,
+ * Sigma = P (with X = identity J is the identity: Sigma is Sigma_loc), pose and per-landmark constants recomputed.  dst may be a member,
+ * ref included: every member is read as it was before the call.  Settles what the handle has deferred, enqueues a fixed number of launches
+ * whatever n is and, with report == NULL, returns without waiting -- unless dst's host bookkeeping (ids, clock, flags, gate report) differs
+ * from what the merge leaves, where the verdict is waited for so that it changes only if the device wrote.
+ * P is bit-for-bit symmetric (the lower triangle is computed, the upper is its mirror), the same from run to run and for members alone in
+ * a handle or anywhere in a batch (no atomics, one fixed order: idx's); with n = 1 its lower triangle is eqf_get_sigma_local's, bit for
+ * bit, and a member of weight 0 changes no bit.
+ * report->info != 0: mean and P are NaN, a merge writes nothing (dst keeps every bit), the call returns EQF_OK; eqf_device_error is never
+ * touched.  Before any effect: EQF_ERR_INVALID for NULL arguments; n < 1; an index, ref or dst out of range; ref not among idx; ld < 11 +
+ * 3 N; a weight that is negative or not finite, or a weight sum that is not positive; centred not 0 or 1; members whose landmark count or
+ * ids differ from the reference's; for the merge, members whose eqf_get_time differs from the reference's or that are not initialised.
+ * EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle.  EQF_ERR_HIP if the workspace, allocated on first need from capacity and batch,
+ * cannot be had (the handle stays as it was).
+ * Not covered: the partitioned filter (eqf_tf_*, eqf_tiled_*), fp32 handles, members in different handles, the C++ facade VIOFilter.h
+ * (one filter per handle). */
+typedef struct eqf_mixture_report {
+    double n_eff;          /* 1 / sum w~^2                                             */
+    double spread_trace;   /* trace of the spread term sum_k w~_k (e_k - m)(e_k - m)^T */
+    double total_trace;    /* trace of P                                               */
+    int n;
+    int info;              /* 0 ok; 1 a non-finite value met; -1 a gravity chart needed is singular */
+} eqf_mixture_report;
+int eqf_get_mixture_moments(eqf_filter* f, int n, const int* idx, const double* w, int ref, int centred,
+    double* mean /* [11 + 3 N] or NULL */, double* P, int ld, eqf_mixture_report* report /* or NULL */);
+int eqf_merge_filters(eqf_filter* f, int n, const int* idx, const double* w, int ref, int dst, eqf_mixture_report* report /* or NULL */);
+
 /* Propagate backend: 0 = block-structured HBM-bound kernel (default, product path),
  * 1 = dense F Sigma F^T on MFMA (what the reference executes; BASELINE cfg 3 cross-check). */
 int eqf_set_dense_propagate(eqf_filter* f, int on);

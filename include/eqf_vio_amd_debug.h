@@ -54,6 +54,14 @@ int eqf_debug_launch_shape(eqf_filter* f, int* shape8);
  * handle's device buffer; nothing is copied to the host and nothing waits (eqf_synchronize does).  eqf_get_sigma_local launches the same
  * kernels for one filter. */
 int eqf_debug_sigma_local_all(eqf_filter* f);
+/* Test hook: the number of kernel launches the handle's most recent eqf_merge_filters or eqf_get_mixture_moments enqueued, counted
+ * as they were made (it does not depend on the number of members); 0 before the first.  Does not touch the device or flush anything; EQF_ERR_INVALID for a NULL handle. */
+int eqf_debug_mixture_launches(eqf_filter* f);
+/* Test hook: the largest |entry| of the structural pad row and column (internal index 11, csrc/eqf_device.hpp) of filter b's covariance
+ * (image = 0) or of slot b of the scratch image of eqf_get_sigma_local, where eqf_get_mixture_moments leaves P in slot ref (image = 1), over
+ * the filter's own internal order 12 + 3 N; NaN if one is NaN.  Settles what the handle has deferred and synchronises.  EQF_ERR_INVALID
+ * for bad arguments or a scratch image that does not exist yet, EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle. */
+int eqf_debug_sigma_pad(eqf_filter* f, int b, int image, double* max_abs);
 
 /* Per-kernel-class timing with HIP events on the handle's stream (bench.py roofline leg).
  * eqf_profile_get: for class c in [0, EQF_PROF_CLASSES) -> launches and total milliseconds.  The total is, per launch shape

@@ -38,6 +38,16 @@
   linearsum DIR    kernel-trace stats CSVs under DIR/linearkern_B_N_m -> the four k_lin_* kernels; k_lin_gain as n^2 * 8 * B bytes (one read
                    of Sigma) and k_lin_downdate as (2 T_lower + T_mirror) * 64^2 * 8 * B bytes (read and write of the lower-triangle tiles,
                    write of the mirror tiles) over their average times, against the measured 6.29 TB/s.
+  mixture B N      DESIGN.md section 4.5g: FilterBatch.merge of all B filters into filter 0 (report=True: ends in a synchronise) against
+                   the host route it replaces -- sigma_local(b), state_estimate(b) and bias(b) for every member (n^2 doubles over the bus
+                   each), the numpy sums of consistency.merge_host's second pass WITHOUT its Jacobians and chart transitions, so the host
+                   route is timed in its favour, then restore_state (Sigma over the bus again) -- on the same states: B copies of one
+                   filter after three frames, pulled apart by perturb(scale 1e-3), equal weights.  Both warmed up, alternated over 20
+                   repetitions; prints one JSON line with medians, min / max and the ratio.  No threshold is asserted.
+  mixturekern B N  a workload for `rocprofv3 --kernel-trace --stats -- python scripts/consistency_bench.py mixturekern B N`: thirty merges.
+  mixturesum DIR   kernel-trace stats CSVs under DIR/mixturekern_B_N -> the k_mix_* kernels; k_mix_reduce as (B T_lower + T_all) n^2-sized
+                   bytes -- it reads the lower triangle of every member's Sigma once, (n^2 + n) / 2 * 8 * B bytes, and writes P once,
+                   n^2 * 8 bytes -- over its average time, against the measured 6.29 TB/s.
 """
 import csv
 import glob
@@ -448,6 +458,97 @@ def copysum(d):
               f"{got.get('k_clone_restore', (0,))[0]:.1f} us; {c[3]} / {l[3]} calls)")
 
 
+def _mixture_setup(B, N):
+    import numpy as np
+
+    fg, _ = _copy_setup(B, N)
+    fg.resample(np.zeros(B, dtype=np.int32))
+    fg.perturb(np.random.default_rng(3), scale=1e-3)
+    fg.synchronize()
+    return fg
+
+
+def mixture(B, N, reps=20):
+    import numpy as np
+
+    from eqf_vio_amd import consistency as cs
+
+    fg = _mixture_setup(B, N)
+    idx, w = np.arange(B, dtype=np.int32), np.ones(B)
+
+    def dev():
+        assert fg.merge(idx, w, 0, 0)["info"] == 0
+
+    def host():
+        est = [fg.state_estimate(b) for b in range(B)]
+        bias = [fg.bias(b) for b in range(B)]
+        S = [fg.sigma_local(b) for b in range(B)]
+        E = np.array([cs.error_vector(cs.local_error(est[0], est[b], bias=bias[0], true_bias=bias[b])) for b in range(B)])
+        mean = E.mean(axis=0)
+        xbar = cs.local_retract(est[0], mean, bias=bias[0])
+        D = E - mean
+        P = sum(S) / B + D.T @ D / B
+        snap = fg.dump_state(0)
+        N0 = len(snap["ids"])
+        snap["origin"] = dict(q=xbar["q"], x=np.mean([e["x"] for e in est], axis=0), v=xbar["v"], p=xbar["p"])
+        snap["group"] = dict(Aq=np.array([1.0, 0, 0, 0]), Ax=np.zeros(3), w=np.zeros(3), Qq=np.tile([1.0, 0, 0, 0], (N0, 1)), Qa=np.ones(N0))
+        snap["bias"], snap["sigma"] = xbar["bias"], P
+        fg.restore_state(snap, 0)
+
+    dev(), host(), dev(), host()  # (first calls: allocations)
+    td, th = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        dev()
+        t1 = time.perf_counter()
+        host()
+        t2 = time.perf_counter()
+        td.append((t1 - t0) * 1e3)
+        th.append((t2 - t1) * 1e3)
+    q = lambda v: dict(median_ms=round(float(np.median(v)), 3), min_ms=round(min(v), 3), max_ms=round(max(v), 3))
+    print(json.dumps(dict(case="merge", B=B, N=N, reps=reps, launches=fg.debug_mixture_launches(), device=q(td), host=q(th),
+                          speedup_of_medians=round(float(np.median(th) / np.median(td)), 1),
+                          device_slower_than_fastest_host=bool(max(td) >= min(th)))), flush=True)
+    assert fg.device_error() == 0
+
+
+def mixturekern(B, N):
+    import numpy as np
+
+    fg = _mixture_setup(B, N)
+    idx, w = np.arange(B, dtype=np.int32), np.ones(B)
+    for _ in range(30):
+        fg.merge(idx, w, 0, 0, report=False)
+    fg.synchronize()
+    assert fg.device_error() == 0
+    print(f"mixturekern B={B} N={N}: done")
+
+
+def mixturesum(d):
+    print("B x N      bytes read + written   k_mix_reduce avg / min / max us   TB/s (avg)   of 6.29 TB/s   the other k_mix_* (avg us)")
+    for path in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)):
+        tag = [t for t in os.path.relpath(path, d).split(os.sep) if t.startswith("mixturekern_")]
+        if not tag:
+            continue
+        _, B, N = tag[0].split("_")
+        B, N = int(B), int(N)
+        got = {}
+        for r in csv.DictReader(open(path)):
+            name = r.get("Name") or r.get("KernelName") or ""
+            for key in ("k_mix_reduce", "k_mix_estimate", "k_mix_error", "k_mix_mean", "k_mix_retract", "k_mix_report", "k_mix_store",
+                        "k_mix_commit", "k_mix_restore", "k_local_jacobian"):
+                if key in name:
+                    got[key] = (float(r["AverageNs"]) / 1e3, float(r["MinNs"]) / 1e3, float(r["MaxNs"]) / 1e3, int(r["Calls"]))
+        if "k_mix_reduce" not in got:
+            print(B, N, "incomplete", got)
+            continue
+        n = 12 + 3 * N
+        by = 8.0 * (B * (n * n + n) / 2 + n * n)
+        c = got["k_mix_reduce"]
+        rest = ", ".join(f"{k[6:] if k.startswith('k_mix_') else k} {v[0]:.1f}" for k, v in sorted(got.items()) if k != "k_mix_reduce")
+        print(f"{B:3d} x {N:<5d} {by / 1e6:10.1f} MB   {c[0]:9.1f} / {c[1]:8.1f} / {c[2]:8.1f}   {by / c[0] / 1e6:6.2f}   {by / c[0] / 1e6 / 6.29:6.1%}   {rest}")
+
+
 def summarize(d):
     rows = []
     for path in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)):
@@ -506,6 +607,12 @@ if __name__ == "__main__":
         linearkern(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
     elif cmd == "linearsum":
         linearsum(sys.argv[2])
+    elif cmd == "mixture":
+        mixture(int(sys.argv[2]), int(sys.argv[3]))
+    elif cmd == "mixturekern":
+        mixturekern(int(sys.argv[2]), int(sys.argv[3]))
+    elif cmd == "mixturesum":
+        mixturesum(sys.argv[2])
     elif cmd == "summarize":
         summarize(sys.argv[2])
     else:
