@@ -85,7 +85,7 @@ EXPORTED_SYMBOLS = [
     "eqf_stream_upload", "eqf_stream_imu", "eqf_stream_vision", "eqf_synchronize", "eqf_get_time", "eqf_num_landmarks",
     "eqf_get_ids", "eqf_get_state_estimate", "eqf_get_origin", "eqf_get_group", "eqf_get_bias", "eqf_get_sigma",
     "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
-    "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters", "eqf_update_linear",
+    "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters", "eqf_update_linear", "eqf_update_landmarks",
     "eqf_get_mixture_moments", "eqf_merge_filters", "eqf_debug_mixture_launches", "eqf_debug_sigma_pad",
     "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
     "eqf_set_sigma", "eqf_set_state", "eqf_copy_filters", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
@@ -156,6 +156,9 @@ def lib():
         if hasattr(L, "eqf_update_linear"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
             L.eqf_update_linear.argtypes = [vp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double, C.POINTER(C.c_ubyte), _dp, C.c_int,
                                             C.POINTER(LinearReport)]
+        if hasattr(L, "eqf_update_landmarks"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
+            L.eqf_update_landmarks.argtypes = [vp, C.c_int, C.c_int, _ip, _ip, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double,
+                                               C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), _dp, C.c_int, C.POINTER(LinearReport)]
         if hasattr(L, "eqf_merge_filters"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
             L.eqf_get_mixture_moments.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.POINTER(MixtureReport)]
             L.eqf_merge_filters.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, C.POINTER(MixtureReport)]
@@ -607,6 +610,66 @@ class FilterBatch:
         if want_gamma:
             out["gamma"] = G
         return out
+
+    def update_landmarks(self, ids, H, resid, R, rows=None, local=True, gate=float("inf"), lm_gate=float("inf"), mask=None, wait=True,
+                         stride=None):
+        """A measurement update from per-landmark blocks for EVERY filter of the handle in one call (include/eqf_vio_amd.h:
+        eqf_update_landmarks): entry k of filter b measures the landmark ids[b][k] alone, resid_k = H_k eps_i + noise, noise ~ N(0, R_k),
+        eps_i "truth minus estimate" of the landmark's 3-block in the coordinates of sigma_local() (local: the plain difference of
+        camera-frame positions) or of sigma().  consistency.stereo_rows / depth_rows / position_rows write the usual blocks.
+        ids, H, resid, R: lists with one item per filter -- ids (K_b,) strictly ascending, H (K_b, rows, 3), resid (K_b, rows), R
+        (K_b, rows, rows: lower triangles read) or (rows, rows), broadcast to every entry; K_b may differ between filters and may be 0.  A
+        single-filter handle also takes the four arrays themselves.  rows: 1, 2 or 3, taken from H when not given (needed when every K_b is
+        0).  gate: chi-square threshold on the joint nis; lm_gate: on every entry's own 'rows'-dof distance
+        (consistency.chi2_gate_threshold(p, dof=rows)); mask (B,): 0 leaves a filter alone.  A filter whose info is not 0 keeps every bit.
+        stride: the entries per filter the arrays handed to the library are laid out for (default: the longest list); the launch shapes
+        follow it.
+        With wait the call waits for the device and returns a dict: nis, logdet_S, loglik, dof, info (B,), used (B, stride): 1 applied, 0 id
+        not in the state, 2 gated, and gamma (B, n_max) in the reference's index map (rows of untouched filters 0); otherwise it enqueues
+        and returns None."""
+        B = self.B
+        if B == 1 and not (isinstance(ids, (list, tuple)) and len(ids) == 1 and np.ndim(ids[0]) == 1):
+            ids, H, resid, R = [ids], [H], [resid], [R]
+        if not (len(ids) == len(H) == len(resid) == len(R) == B):
+            raise ValueError("update_landmarks: one item per filter")
+        idl = [np.asarray(x, dtype=np.int32).reshape(-1) for x in ids]
+        if rows is None:
+            shapes = {np.shape(h)[1] for h, i in zip(H, idl) if len(i)}
+            if len(shapes) != 1:
+                raise ValueError("update_landmarks: rows cannot be taken from H")
+            rows = shapes.pop()
+        rows = int(rows)
+        longest = max(1, max(len(i) for i in idl))
+        stride = longest if stride is None else int(stride)
+        if stride < longest:
+            raise ValueError("update_landmarks: stride is shorter than the longest list")
+        nk = np.array([len(i) for i in idl], dtype=np.int32)
+        idm = np.zeros((B, stride), dtype=np.int32)
+        Hs = np.zeros((B, stride, rows, 3))
+        rs = np.zeros((B, stride, rows))
+        Rs = np.zeros((B, stride, rows, rows))
+        for b in range(B):
+            k = int(nk[b])
+            if k == 0:
+                continue
+            idm[b, :k] = idl[b]
+            Hs[b, :k] = np.asarray(H[b], dtype=np.float64).reshape(k, rows, 3)
+            rs[b, :k] = np.asarray(resid[b], dtype=np.float64).reshape(k, rows)
+            Rs[b, :k] = np.broadcast_to(np.asarray(R[b], dtype=np.float64), (k, rows, rows))
+        mk = None if mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mask), (B,)) != 0, dtype=np.uint8)
+        up = C.POINTER(C.c_ubyte)
+        ldg = 11 + 3 * max(self.num_landmarks(b) for b in range(B))
+        G = np.zeros((B, ldg)) if wait else None
+        used = np.zeros((B, stride), dtype=np.uint8) if wait else None
+        rep = (LinearReport * B)() if wait else None
+        _check(lib().eqf_update_landmarks(self._h, int(bool(local)), rows, nk.ctypes.data_as(_ip), idm.ctypes.data_as(_ip), stride, _p(Hs), _p(rs),
+                                          _p(Rs), float(gate), float(lm_gate), None if mk is None else mk.ctypes.data_as(up),
+                                          None if used is None else used.ctypes.data_as(up), None if G is None else _p(G), ldg if wait else 0, rep),
+               "eqf_update_landmarks")
+        if not wait:
+            return None
+        return dict(nis=np.array([s.nis for s in rep]), logdet_S=np.array([s.logdet_S for s in rep]), loglik=np.array([s.loglik for s in rep]),
+                    dof=np.array([s.dof for s in rep], dtype=np.int32), info=np.array([s.info for s in rep], dtype=np.int32), used=used, gamma=G)
 
     @staticmethod
     def _members(idx, w):

@@ -17,6 +17,8 @@ to first order eps_loc = J eps with the block-diagonal J of local_jacobian_block
                                          FilterBatch.update_linear's gate
   velocity_rows / gravity_rows / landmark_rows(N, i)   measurement rows in the estimate's chart for FilterBatch.update_linear(local=True)
   linear_update_host(Sigma, H, resid, R) the numpy statement of that update (include/eqf_vio_amd.h: eqf_update_linear)
+  stereo_rows / depth_rows / position_rows   per-landmark blocks (H_k, resid_k) for FilterBatch.update_landmarks(local=True)
+  update_landmarks_host(Sigma, idx, H, resid, R, ...)  the dense numpy statement of that update (eqf_update_landmarks)
   mixture_weights(loglik)                log-likelihoods -> the normalised weights of a mixture (systematic_resample's)
   mixture_moments_host(members, w, centre, centred)   mean and covariance of a weighted batch in the chart of a centre state, the spread
                                          between the members included -- the numpy statement of FilterBatch.mixture_moments
@@ -381,6 +383,102 @@ def linear_update_host(Sigma, H, resid, R):
     logdet = 2.0 * float(np.sum(np.log(np.diag(L))))
     return dict(Sigma=Sg - Y.T @ Y, gamma=Y.T @ z, nis=nis, logdet_S=logdet, loglik=-0.5 * (nis + logdet + m * float(np.log(2.0 * np.pi))), dof=m,
                 Y=Y, L=L)
+
+
+# ---- per-landmark blocks for FilterBatch.update_landmarks(local=True): entry k measures landmark i_k alone, resid_k = H_k eps_i + noise with
+# eps_i = p_true - p_hat, the plain difference of camera-frame positions (the landmark block of the estimate's chart)
+def stereo_rows(p_hat, q_21, t_21, y2):
+    """The second camera of a rigid stereo rig sees landmark p_hat (first camera's frame) along the unit bearing y2.  (q_21, t_21): the pose
+    of camera 2 in camera 1's frame (quaternion w, x, y, z and position), so p_2 = R_21^T (p_hat - t_21) and y2_hat = p_2 / |p_2|.
+    Returns (H (2, 3), resid (2,)): H = stereoSphereChartDiff(y2_hat, y2_hat) (I - y2_hat y2_hat^T) R_21^T / |p_2|,
+    resid = stereoSphereChart(y2, pole y2_hat)."""
+    R21 = quat_to_matrix(np.asarray(q_21, dtype=float))
+    p2 = R21.T @ (np.asarray(p_hat, dtype=float) - np.asarray(t_21, dtype=float))
+    d = float(np.linalg.norm(p2))
+    yh = p2 / d
+    H = stereo_sphere_chart_diff(yh, yh) @ (np.eye(3) - np.outer(yh, yh)) @ R21.T / d
+    return H, stereo_sphere_chart(np.asarray(y2, dtype=float), yh)
+
+
+def depth_rows(p_hat, rng):
+    """A range to landmark p_hat (depth camera, lidar).  Returns (H (1, 3), resid (1,)): H = p_hat^T / |p_hat|, resid = rng - |p_hat|."""
+    p = np.asarray(p_hat, dtype=float)
+    d = float(np.linalg.norm(p))
+    return (p / d)[None, :], np.array([float(rng) - d])
+
+
+def position_rows(p_hat, p_meas):
+    """A surveyed position of landmark p_hat in the camera frame (relocalisation).  Returns (H = I (3, 3), resid = p_meas - p_hat)."""
+    return np.eye(3), np.asarray(p_meas, dtype=float) - np.asarray(p_hat, dtype=float)
+
+
+def landmark_blocks_matrix(N, idx, Ht):
+    """The block-sparse measurement matrix as a dense one: (rows * K, 11 + 3N) with block k (rows, 3) at landmark idx[k]'s columns."""
+    Ht = np.asarray(Ht, dtype=float)
+    K, rows = Ht.shape[0], Ht.shape[1]
+    out = np.zeros((rows * K, 11 + 3 * int(N)))
+    for k in range(K):
+        out[rows * k:rows * (k + 1), 11 + 3 * int(idx[k]):14 + 3 * int(idx[k])] = Ht[k]
+    return out
+
+
+def update_landmarks_host(Sigma, idx, H, resid, R, J=None, gate=np.inf, lm_gate=np.inf):
+    """The dense numpy statement of FilterBatch.update_landmarks' arithmetic for one filter (include/eqf_vio_amd.h: eqf_update_landmarks).
+    Sigma (n, n) in eqf_get_sigma's coordinates, read by its LOWER triangle; idx (K,): the landmark INDEX of every entry, < 0 for an id that
+    is not in the state; H (K, rows, 3), resid (K, rows), R (K, rows, rows: lower triangles read); J: local_jacobian_blocks(...)["lm"] for
+    rows written in the estimate's chart (H_k J_i is formed here), None for rows in the origin chart.  An entry whose id is absent or whose
+    own d2_k = resid_k^T (Ht_k Sigma_ii Ht_k^T + R_k)^-1 resid_k exceeds lm_gate (NaN stays in) is a decoupled block (H = 0, resid = 0,
+    R = I) that is not counted in dof.  Then
+        B = Sigma Ht^T, S = Ht B + blockdiag(R_k) = L L^T, Y = L^-1 B^T, z = L^-1 resid, gamma = Y^T z, Sigma+ = Sigma - Y^T Y.
+    Returns dict(Sigma, gamma, nis, logdet_S, loglik, dof, used (K,): 1 applied, 0 absent, 2 gated, d2 (K,), info: 0 applied, 1 S not positive
+    definite, 2 nis > gate; Sigma and gamma are the input's and 0 when info != 0)."""
+    Sg = np.asarray(Sigma, dtype=float)
+    Sg = np.tril(Sg) + np.tril(Sg, -1).T
+    n = len(Sg)
+    N = (n - 11) // 3
+    H = np.asarray(H, dtype=float)
+    K, rows = H.shape[0], H.shape[1]
+    resid = np.asarray(resid, dtype=float).reshape(K, rows)
+    R = np.asarray(R, dtype=float).reshape(K, rows, rows)
+    Rl = np.tril(R) + np.transpose(np.tril(R, -1), (0, 2, 1))
+    used = np.zeros(K, dtype=np.int32)
+    d2 = np.full(K, np.nan)
+    Ht = np.zeros((K, rows, 3))
+    for k in range(K):
+        i = int(idx[k])
+        if not 0 <= i < N:
+            continue
+        Ht[k] = H[k] @ np.asarray(J, dtype=float).reshape(-1, 3, 3)[i] if J is not None else H[k]
+        Skk = Ht[k] @ Sg[11 + 3 * i:14 + 3 * i, 11 + 3 * i:14 + 3 * i] @ Ht[k].T + Rl[k]
+        try:
+            zk = np.linalg.solve(np.linalg.cholesky(Skk), resid[k])
+            d2[k] = float(zk @ zk)
+        except np.linalg.LinAlgError:
+            pass
+        used[k] = 2 if d2[k] > lm_gate else 1
+    on = np.flatnonzero(used == 1)
+    m = rows * len(on)
+    out = dict(Sigma=Sg.copy(), gamma=np.zeros(n), nis=0.0, logdet_S=0.0, loglik=0.0, dof=m, used=used, d2=d2, info=0)
+    if m == 0:
+        return out
+    Hd = landmark_blocks_matrix(N, [idx[k] for k in on], Ht[on])
+    Rd = np.zeros((m, m))
+    for p, k in enumerate(on):
+        Rd[rows * p:rows * (p + 1), rows * p:rows * (p + 1)] = Rl[k]
+    try:
+        r = linear_update_host(Sg, Hd, resid[on].reshape(-1), Rd)
+    except np.linalg.LinAlgError:
+        r = None
+    if r is None or not (np.isfinite(r["nis"]) and np.isfinite(r["gamma"]).all() and np.isfinite(r["Sigma"]).all()):
+        out.update(nis=np.nan, logdet_S=np.nan, loglik=np.nan, info=1)
+        return out
+    out.update(nis=r["nis"], logdet_S=r["logdet_S"], loglik=r["loglik"])
+    if r["nis"] > gate:
+        out["info"] = 2
+        return out
+    Sp = np.tril(r["Sigma"])
+    out.update(Sigma=Sp + np.tril(Sp, -1).T, gamma=r["gamma"])
+    return out
 
 
 def systematic_resample(loglik, u):

@@ -338,6 +338,23 @@ class VIOFilter {
         check(eqf_update_linear(handle_.get(), local ? 1 : 0, m, H, n, resid, R, gate, nullptr, nullptr, 0, &rep), "eqf_update_linear");
         return rep;
     }
+    // A measurement update from per-landmark blocks (eqf_update_landmarks): entry k measures the landmark ids[k] (strictly ascending) alone,
+    // resid_k = H_k eps_i + noise, noise ~ N(0, R_k), with `rows` (1, 2 or 3) rows per entry -- the second camera of a stereo rig, a range, a
+    // surveyed position.  H: K blocks of rows x 3, resid: K x rows, R: K blocks of rows x rows (lower triangles read), all row-major without
+    // gaps; local: eps_i is the plain difference of camera-frame positions (the estimate's chart), else the origin chart's block.  gate: a
+    // chi-square threshold on the joint nis, lm_gate: on every entry's own distance (the defaults never trip).  used (K bytes, or nullptr):
+    // 1 applied, 0 id not in the state, 2 gated.  The filter is untouched when the report's info is not 0.
+    eqf_linear_report processLandmarkMeasurements(const int* ids, int K, int rows, const double* H, const double* resid, const double* R,
+        bool local = true, double gate = std::numeric_limits<double>::infinity(), double lm_gate = std::numeric_limits<double>::infinity(),
+        unsigned char* used = nullptr) {
+        eqf_linear_report rep;
+        const int zero = 0;
+        std::vector<double> pad(9, 0.0);  // (stride is at least 1: K = 0 hands over one unread entry)
+        check(eqf_update_landmarks(handle_.get(), local ? 1 : 0, rows, &K, K ? ids : &zero, K ? K : 1, K ? H : pad.data(), K ? resid : pad.data(),
+                  K ? R : pad.data(), gate, lm_gate, nullptr, K ? used : nullptr, nullptr, 0, &rep),
+            "eqf_update_landmarks");
+        return rep;
+    }
     // This filter continues from the state of `other` (fork, or snapshot and roll back), copied on the device (eqf_copy_filters): landmarks,
     // origin, group element, bias, covariance, time and integrator.  Settings, camera offset and capacity stay this filter's own; throws
     // std::runtime_error if `other` tracks more landmarks than this filter's capacity or differs in precision or device.

@@ -29,6 +29,8 @@
 #include "eqf_frame.hpp"
 #include "eqf_sample.hpp"
 #include "eqf_sample_host.hpp"
+#include "eqf_blocks.hpp"
+#include "eqf_blocks_host.hpp"
 #include "eqf_linear.hpp"
 #include "eqf_linear_host.hpp"
 #include "eqf_mixture.hpp"
@@ -245,6 +247,15 @@ struct eqf_filter {
     char *hLinSmall = nullptr, *dLinSmall = nullptr;
     double *dLinWs = nullptr, *dLinOut = nullptr;
     hipEvent_t evLin = nullptr;
+    // the per-landmark block measurement update (eqf_blocks.hpp; eqf_update_landmarks), allocated on first need and grown when a call's
+    // stride or rows ask for more: the operands of a call as a pinned image and its device copy (blocks::SmallLayout; evBlk: the last
+    // upload from the pinned image has been read), the workspace in doubles and in ints (blocks::WorkLayout) and the records [B][kLinHead]
+    char *hBlkSmall = nullptr, *dBlkSmall = nullptr;
+    size_t blkSmallBytes = 0, blkWsDoubles = 0, blkWiInts = 0;
+    double *dBlkWs = nullptr, *dBlkOut = nullptr;
+    int* dBlkWi = nullptr;
+    hipEvent_t evBlk = nullptr;
+    bool blkLdsSet = false;
     // eqf_copy_filters (eqf_clone.hpp): the pair table (pinned image + device copy, grown on demand), the small-state staging image of the
     // in-place case (allocated on first need) and two events -- evCloneSrc orders a copy behind this handle's work when it is the source,
     // evCloneDone marks the end of the last copy INTO this handle (its pair table may be reused, the source may go on)
@@ -1581,6 +1592,12 @@ void freeAll(eqf_filter* f) {
     hipFree(f->dLinOut);
     if (f->hLinSmall) hipHostFree(f->hLinSmall);
     if (f->evLin) hipEventDestroy(f->evLin);
+    hipFree(f->dBlkSmall);
+    hipFree(f->dBlkWs);
+    hipFree(f->dBlkWi);
+    hipFree(f->dBlkOut);
+    if (f->hBlkSmall) hipHostFree(f->hBlkSmall);
+    if (f->evBlk) hipEventDestroy(f->evBlk);
     if (f->hGate) hipHostFree(f->hGate);
     if (f->dMask) hipFree(f->dMask);
     if (f->evGate) hipEventDestroy(f->evGate);
@@ -3180,6 +3197,168 @@ int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh,
             report[b].info = info;
         }
         if (gamma) linear::unpackGamma(hG.data() + size_t(b) * f->ld, N[b], gamma + size_t(b) * ldg, info != 0);
+    }
+    return EQF_OK;
+}
+
+// ---- the per-landmark block measurement update (eqf_blocks.hpp; per-entry arithmetic, index arithmetic and argument checks:
+// eqf_blocks_host.hpp)
+static_assert(blocks::kRefBase == kBase && blocks::kPadBase == kLm0 && blocks::kTile == kSB && blocks::kHead == kLinHead,
+    "eqf_blocks_host.hpp repeats the layout constants");
+namespace {
+// The buffers of eqf_update_landmarks for this call's shape; what is there and large enough is kept.  A failure frees what this call got
+// and leaves the handle as it was.
+int blkAlloc(eqf_filter* f, const blocks::SmallLayout& sl, const blocks::WorkLayout& wl) {
+    const size_t needS = sl.bytes(), needW = size_t(wl.strideD()) * f->B, needI = size_t(wl.strideI()) * f->B;
+    void *h = nullptr, *d = nullptr, *w = nullptr, *wi = nullptr, *o = nullptr;
+    hipEvent_t ev = nullptr;
+    bool ok = true;
+    if (needS > f->blkSmallBytes) ok = ok && hipHostMalloc(&h, needS, hipHostMallocDefault) == hipSuccess && hipMalloc(&d, needS) == hipSuccess;
+    if (ok && needW > f->blkWsDoubles) ok = hipMalloc(&w, sizeof(double) * needW) == hipSuccess;
+    if (ok && needI > f->blkWiInts) ok = hipMalloc(&wi, sizeof(int) * needI) == hipSuccess;
+    if (ok && !f->dBlkOut) ok = hipMalloc(&o, sizeof(double) * size_t(kLinHead) * f->B) == hipSuccess;
+    if (ok && !f->evBlk) ok = hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (h) hipHostFree(h);
+        for (void* p : {d, w, wi, o})
+            if (p) hipFree(p);
+        return EQF_ERR_HIP;
+    }
+    // (what is replaced may still be in use by an earlier call that did not wait: the stream is drained first)
+    if ((h || w || wi) && (f->hBlkSmall || f->dBlkWs || f->dBlkWi) && hipStreamSynchronize(f->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        if (h) hipHostFree(h);
+        for (void* p : {d, w, wi, o})
+            if (p) hipFree(p);
+        if (ev) hipEventDestroy(ev);
+        return EQF_ERR_HIP;
+    }
+    if (h) {
+        if (f->hBlkSmall) hipHostFree(f->hBlkSmall);
+        hipFree(f->dBlkSmall);
+        f->hBlkSmall = static_cast<char*>(h);
+        f->dBlkSmall = static_cast<char*>(d);
+        f->blkSmallBytes = needS;
+    }
+    if (w) {
+        hipFree(f->dBlkWs);
+        f->dBlkWs = static_cast<double*>(w);
+        f->blkWsDoubles = needW;
+    }
+    if (wi) {
+        hipFree(f->dBlkWi);
+        f->dBlkWi = static_cast<int*>(wi);
+        f->blkWiInts = needI;
+    }
+    if (o) f->dBlkOut = static_cast<double*>(o);
+    if (ev) f->evBlk = ev;
+    return EQF_OK;
+}
+}  // namespace
+
+int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb, const double* resid,
+    const double* Rb, double gate, double lm_gate, const unsigned char* mask, unsigned char* used, double* gamma, int ldg,
+    eqf_linear_report* report) {
+    if (!f || !blocks::headArgsOk(local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate)) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);  // (queued IMU calls and a pending gate first: the gate may still change the landmark lists)
+    const int B = f->B;
+    std::vector<int> N(B);
+    for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
+    switch (blocks::argsCheck(rows, nk, ids, stride, Hb, resid, Rb, mask, gamma, ldg, B, N.data(), f->cap)) {
+        case 1: return EQF_ERR_INVALID;
+        case 2: return EQF_ERR_UNSORTED;
+        case 3: return EQF_ERR_CAPACITY;
+        default: break;
+    }
+    const blocks::SmallLayout sl{B, stride, rows};
+    const blocks::WorkLayout wl{f->ld, stride, rows, kDRec};
+    int rc = blkAlloc(f, sl, wl);
+    if (rc) return rc;
+    if (!f->blkLdsSet) {  // (dynamic LDS beyond 64 KB: see allowUpdateLds)
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_blk_panel), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesPanelLdsBytes));
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_blk_trail), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesTrailLdsBytes));
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_blk_downdate), hipFuncAttributeMaxDynamicSharedMemorySize, kBlkDownLdsBytes));
+        f->blkLdsSet = true;
+    }
+    if (local) {
+        rc = launchLocal(f, 0, B, false);  // (only writes the J records)
+        if (rc) return rc;
+    }
+    HIPC(hipEventSynchronize(f->evBlk));
+    char* hs = f->hBlkSmall;
+    const size_t ne = sl.entries();
+    std::memcpy(hs + sl.offH(), Hb, sizeof(double) * ne * rows * 3);
+    std::memcpy(hs + sl.offResid(), resid, sizeof(double) * ne * rows);
+    std::memcpy(hs + sl.offR(), Rb, sizeof(double) * ne * rows * rows);
+    int* hIdx = reinterpret_cast<int*>(hs + sl.offIdx());
+    int* hNk = reinterpret_cast<int*>(hs + sl.offNk());
+    unsigned char* hm = reinterpret_cast<unsigned char*>(hs + sl.offMask());
+    for (int b = 0; b < B; ++b) {
+        hNk[b] = nk[b];
+        hm[b] = mask ? (mask[b] ? 1 : 0) : 1;
+        for (int k = 0; k < stride; ++k)
+            hIdx[size_t(b) * stride + k] = (hm[b] && k < nk[b]) ? blocks::findId(f->ids[b].data(), N[b], ids[size_t(b) * stride + k]) : -1;
+    }
+    HIPC(hipMemcpyAsync(f->dBlkSmall, f->hBlkSmall, sl.bytes(), hipMemcpyHostToDevice, f->stream));
+    HIPC(hipEventRecord(f->evBlk, f->stream));
+    const int nMax = maxN(f), nt = blocks::rowTiles(nMax), nb = wl.nb(), nbTot = nb + blocks::rhsBlocks(blocks::paddedOrder(nMax));
+    const int nPT = blocks::pairTiles(stride);
+    BlkArgs a{};
+    a.g = f->g[f->pG]; a.Sigma = static_cast<double*>(f->Sigma[f->pS]); a.ld = f->ld; a.sigmaStride = f->sigmaStride;
+    a.Hb = reinterpret_cast<const double*>(f->dBlkSmall + sl.offH()); a.resid = reinterpret_cast<const double*>(f->dBlkSmall + sl.offResid());
+    a.Rb = reinterpret_cast<const double*>(f->dBlkSmall + sl.offR()); a.idx = reinterpret_cast<const int*>(f->dBlkSmall + sl.offIdx());
+    a.nk = reinterpret_cast<const int*>(f->dBlkSmall + sl.offNk()); a.mask = reinterpret_cast<const unsigned char*>(f->dBlkSmall + sl.offMask());
+    a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.rows = rows; a.stride = stride; a.mp = wl.mp(); a.nb = nb;
+    a.gate = gate; a.lmGate = lm_gate;
+    a.ws = f->dBlkWs; a.wsStride = wl.strideD(); a.offHt = wl.offHt(); a.offGamma = wl.offGamma(); a.offD = wl.offD();
+    a.wi = f->dBlkWi; a.wiStride = wl.strideI(); a.out = f->dBlkOut;
+    hipLaunchKernelGGL(k_blk_rows, dim3(B), dim3(256), 0, f->stream, a);
+    hipLaunchKernelGGL(k_blk_gain, dim3(nt + nPT * nPT, B), dim3(256), 0, f->stream, a, nt, nPT);
+    for (int K = 0; K < nb; ++K) {
+        hipLaunchKernelGGL(k_blk_diag, dim3(1, B), dim3(256), kLdsFactorBytes, f->stream, a, K);
+        hipLaunchKernelGGL(k_blk_panel, dim3(nbTot - K - 1, B), dim3(256), kNeesPanelLdsBytes, f->stream, a, K);
+        if (nb - K - 1 > 0)
+            hipLaunchKernelGGL(k_blk_trail, dim3((nbTot - K - 1) * (nb - K - 1), B), dim3(256), kNeesTrailLdsBytes, f->stream, a, K);
+    }
+    hipLaunchKernelGGL(k_blk_gamma, dim3(nt, B), dim3(64), 0, f->stream, a);
+    hipLaunchKernelGGL(k_blk_tail, dim3(B), dim3(256), 0, f->stream, a);
+    hipLaunchKernelGGL(k_blk_downdate, dim3(blocks::triTiles(nt), B), dim3(256), kBlkDownLdsBytes, f->stream, a);
+    // the group step, behind the tail's verdict (entry 3 of the record, where eqf_nees.hpp's info sits)
+    IncArgs ia{};
+    ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = f->dBlkWs + wl.offGamma(); ia.strideG = wl.strideD();
+    ia.off = 0; ia.mask = nullptr; ia.info = f->dBlkOut;
+    hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, ia);
+    HIPC(hipGetLastError());
+    f->csValid = false;  // (C Sigma / S left by an earlier burst describe the old Sigma)
+    if (!used && !gamma && !report) return EQF_OK;
+    std::vector<double> hO(size_t(B) * kLinHead), hG;
+    std::vector<int> hU(size_t(B) * wl.strideI());
+    HIPC(hipMemcpyAsync(hO.data(), f->dBlkOut, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipMemcpyAsync(hU.data(), f->dBlkWi, sizeof(int) * hU.size(), hipMemcpyDeviceToHost, f->stream));
+    if (gamma) {
+        hG.resize(size_t(B) * f->ld);
+        HIPC(hipMemcpy2DAsync(hG.data(), sizeof(double) * f->ld, f->dBlkWs + wl.offGamma(), sizeof(double) * wl.strideD(),
+            sizeof(double) * f->ld, B, hipMemcpyDeviceToHost, f->stream));
+    }
+    HIPC(hipStreamSynchronize(f->stream));
+    for (int b = 0; b < B; ++b) {
+        const double* o = hO.data() + size_t(b) * kLinHead;
+        const int* u = hU.data() + size_t(b) * wl.strideI();
+        const int word = int(o[3]), info = word == blocks::kInfoIdle ? 0 : word, cnt = word == 3 ? 0 : u[wl.offCount()];
+        if (report) {
+            const bool solved = word == 0 || word == 2;
+            const double nan = std::nan("");
+            report[b].nis = solved ? o[0] : (word == blocks::kInfoIdle ? 0.0 : nan);
+            report[b].logdet_S = solved ? o[1] : (word == blocks::kInfoIdle ? 0.0 : nan);
+            report[b].loglik = solved ? o[2] : (word == blocks::kInfoIdle ? 0.0 : nan);
+            report[b].dof = rows * cnt;
+            report[b].info = info;
+        }
+        if (used)
+            for (int k = 0; k < stride; ++k) used[size_t(b) * stride + k] = (word != 3 && k < nk[b]) ? (unsigned char)u[wl.offUsed() + k] : 0;
+        if (gamma) blocks::unpackGamma(hG.data() + size_t(b) * f->ld, N[b], gamma + size_t(b) * ldg, word != 0);
     }
     return EQF_OK;
 }

@@ -191,6 +191,18 @@ class VIOFilter:
 
     processLinearMeasurement = process_linear_measurement
 
+    def process_landmark_measurements(self, ids, H, resid, R, rows=None, local=True, gate=float("inf"), lm_gate=float("inf")):
+        """A measurement update from per-landmark blocks: entry k measures the landmark ids[k] (strictly ascending) alone with H (K, rows, 3),
+        resid (K, rows) and its own noise covariance R (K, rows, rows) or (rows, rows) -- the second camera of a stereo rig, a range, a
+        surveyed position (consistency.stereo_rows / depth_rows / position_rows).  Returns dict(nis, logdet_S, loglik, dof, info, used (K,),
+        gamma); the filter is untouched when info != 0 (include/eqf_vio_amd.h: eqf_update_landmarks)."""
+        K = len(np.asarray(ids).reshape(-1))
+        r = self._fb.update_landmarks([np.asarray(ids).reshape(-1)], [H], [resid], [R], rows=rows, local=local, gate=gate, lm_gate=lm_gate)
+        return dict(nis=float(r["nis"][0]), logdet_S=float(r["logdet_S"][0]), loglik=float(r["loglik"][0]), dof=int(r["dof"][0]),
+                    info=int(r["info"][0]), used=r["used"][0, :K], gamma=r["gamma"][0])
+
+    processLandmarkMeasurements = process_landmark_measurements
+
     def copyStateFrom(self, other):
         """This filter continues from the state of `other` (fork, or snapshot and roll back), copied on the device
         (include/eqf_vio_amd.h: eqf_copy_filters).  Settings, camera offset and capacity stay this filter's own."""

@@ -373,6 +373,45 @@ typedef struct eqf_linear_report {
 int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh, const double* resid, const double* R, double gate,
     const unsigned char* mask /* [batch] or NULL */, double* gamma /* [batch][ldg] or NULL */, int ldg,
     eqf_linear_report* report /* [batch] or NULL */);
+/* A measurement update from PER-LANDMARK blocks, for every filter of the handle in one call (csrc/eqf_blocks.hpp): the bearings of the
+ * second camera of a rigid stereo rig (2 rows per landmark), a depth camera's or a lidar's range on a tracked feature (1 row), surveyed
+ * landmark positions (3 rows) -- a few rows each for many landmarks at once, every entry with a noise covariance of its own.  `rows` is 1,
+ * 2 or 3, the same for the whole call (mixed kinds: call twice).  Filter b names nk[b] landmarks by id, 0 <= nk[b] <= stride, strictly
+ * ascending as in eqf_process_vision:
+ *   ids[b * stride + k]; Hb[((b * stride + k) * rows + r) * 3 + c]: the rows x 3 block H_k; resid[(b * stride + k) * rows + r];
+ *   Rb[((b * stride + k) * rows + r) * rows + l]: the rows x rows noise covariance R_k, only its lower triangle is read.
+ * The conventions are eqf_update_linear's: resid_k = H_k eps_i + noise, noise ~ N(0, R_k), chart coordinates "truth minus estimate", eps_i
+ * the landmark's 3-block in the ORIGIN chart (local = 0: eqf_get_sigma's coordinates) or in the ESTIMATE's chart (local = 1:
+ * eqf_get_sigma_local's, where the landmark block is the plain difference of camera-frame positions; the library forms H_k J_i with
+ * J_i = a_i^-1 R(q_i)^T on the device).  consistency.stereo_rows / depth_rows / position_rows write the usual blocks.
+ * An entry does NOT take part if its id is not in filter b's state (the vision frame's gate may have thrown it out) or if its own
+ * d2_k = resid_k^T (Ht_k Sigma_ii Ht_k^T + R_k)^-1 resid_k exceeds lm_gate (taken before anything is factored; a NaN stays in, +inf
+ * disarms).  It then is a decoupled block (H_k = 0, resid_k = 0, R_k = I): it changes no bit of Sigma or gamma, adds exactly 0 to nis and
+ * logdet_S and is not counted in dof -- the result is bit for bit the one of the call without that entry at the same stride.
+ * used[b * stride + k] reports 1 applied, 0 id not in the state (and everything of a masked filter or beyond nk[b]), 2 gated.
+ * Per filter that takes part, in fp64, with Ht the block-sparse m x n matrix of the entries that take part, m = rows * (their number),
+ * and Sigma read by its lower triangle:
+ *   B = Sigma Ht^T,  S = Ht B + blockdiag(R_k) = L L^T,  Y = L^-1 B^T,  z = L^-1 resid,  gamma = Y^T z,  Sigma <- Sigma - Y^T Y (in place,
+ *   bit-for-bit symmetric),  bias += gamma[0:6],  X <- VIOExp(liftInnovation(gamma[6:], xi0)) X  -- eqf_apply_increment's step: ALWAYS the
+ *   plain lift.
+ * report[b] is eqf_update_linear's record with the same info codes and dof = m; gate is the chi-square threshold on the joint nis.  A
+ * filter whose info is not 0 keeps every bit; a filter with no entry taking part reports info = 0, dof = 0, nis = logdet_S = loglik = 0
+ * and is untouched.  mask, gamma, ldg as in eqf_update_linear.  xi0, the clock, the integrator, the ids, eqf_get_last_update, the
+ * innovation statistics, the gate report, the outlier gate and the sticky flag stay as they are; eqf_device_error is never touched.
+ * Settles what the handle has deferred first.  With used, gamma and report all NULL the call enqueues and returns; otherwise it
+ * synchronises and copies out.  EQF_ERR_INVALID, before any effect: a NULL f, nk, ids, Hb, resid or Rb; rows not 1..3; local not 0 or 1;
+ * stride < 1; an nk[b] outside [0, stride]; ldg too small for some filter; a gate or lm_gate that is NaN or <= 0; an entry of Hb, resid or
+ * Rb's lower triangles that is not finite for k < nk[b] of a filter that is not masked out.  EQF_ERR_UNSORTED: ids of such a filter not
+ * strictly ascending.  EQF_ERR_CAPACITY: nk[b] beyond the handle's capacity.  EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle.
+ * EQF_ERR_HIP if the workspace, allocated on first need and grown when stride or rows ask for more ((rows * stride + 3 capacity)
+ * x rows * stride doubles per filter), cannot be had (the handle stays as it was).  Bit for bit the same from run to run and for a filter
+ * alone in a handle or anywhere in a batch; the number of kernel launches depends on stride and rows only.
+ * Not covered: the partitioned filter, fp32 handles, the innovation lift, a second camera offset in the state. */
+int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk /* [batch] */, const int* ids /* [batch][stride] */, int stride,
+    const double* Hb /* [batch][stride][rows][3] */, const double* resid /* [batch][stride][rows] */,
+    const double* Rb /* [batch][stride][rows][rows] */, double gate, double lm_gate, const unsigned char* mask /* [batch] or NULL */,
+    unsigned char* used /* [batch][stride] or NULL */, double* gamma /* [batch][ldg] or NULL */, int ldg,
+    eqf_linear_report* report /* [batch] or NULL */);
 
 /* Moment matching over the filters of ONE handle, on the device (csrc/eqf_mixture.hpp): a weighted batch -- a Monte-Carlo study, a particle
  * set, a bank of hypotheses -- turned back into one mean and one covariance that includes the spread between its members, and several

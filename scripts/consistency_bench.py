@@ -38,6 +38,18 @@
   linearsum DIR    kernel-trace stats CSVs under DIR/linearkern_B_N_m -> the four k_lin_* kernels; k_lin_gain as n^2 * 8 * B bytes (one read
                    of Sigma) and k_lin_downdate as (2 T_lower + T_mirror) * 64^2 * 8 * B bytes (read and write of the lower-triangle tiles,
                    write of the mirror tiles) over their average times, against the measured 6.29 TB/s.
+  blocks B N K     DESIGN.md section 4.5h: FilterBatch.update_landmarks with K stereo entries per filter (2 rows each, the rig of
+                   consistency.stereo_rows; wait=True: ends in a synchronise) against the host route it replaces, for every filter
+                   dump_state (the covariance over the bus) + consistency.update_landmarks_host + restore_state -- WITHOUT the group
+                   arithmetic the host would also have to redo, so the host route is timed in its favour -- on the same states after three
+                   frames.  The second camera's bearings agree with the estimate (residual 0) and R is a hundred times H Sigma H^T's
+                   mean diagonal, so that forty updates leave the filters where they were to first order.  Both warmed up, alternated
+                   over 20 repetitions; prints one JSON line with medians, min / max, the ratio and whether the spreads overlap.  No
+                   threshold is asserted.
+  blockskern B N K a workload for `rocprofv3 --kernel-trace --stats -- python scripts/consistency_bench.py blockskern B N K`: thirty updates.
+  blockssum DIR    kernel-trace stats CSVs under DIR/blockskern_B_N_K -> the k_blk_* kernels; k_blk_downdate as (2 T_lower + T_mirror) *
+                   64^2 * 8 * B bytes of Sigma (read and write of the lower-triangle tiles, write of the mirror tiles) plus 2 * 64 * m * 8
+                   bytes of Y per tile, over its average time, against the measured 6.29 TB/s.
   mixture B N      DESIGN.md section 4.5g: FilterBatch.merge of all B filters into filter 0 (report=True: ends in a synchronise) against
                    the host route it replaces -- sigma_local(b), state_estimate(b) and bias(b) for every member (n^2 doubles over the bus
                    each), the numpy sums of consistency.merge_host's second pass WITHOUT its Jacobians and chart transitions, so the host
@@ -324,6 +336,92 @@ def linearsum(d):
                     print(f"{B:3d} x {N:<5d} x {m:<2d} {key:18s} {a:9.1f} / {lo:8.1f} / {hi:8.1f} ({r['Calls']:>3s})   {tail}")
 
 
+def _blocks_setup(B, N, K):
+    import numpy as np
+    from eqf_vio_amd import consistency
+
+    fg, _ = _nees_setup(B, N)
+    q21, t21 = np.array([0.9987502603949663, 0.0, 0.04997916927067833, 0.0]), np.array([0.12, 0.0, 0.005])
+    R21 = consistency.quat_to_matrix(q21)
+    lm = np.linspace(0, N - 1, K).astype(int)
+    ids, Hs, rs, Rs, idx = [], [], [], [], []
+    for b in range(B):
+        est, snap = fg.state_estimate(b), fg.dump_state(b)
+        J = np.asarray(consistency.local_jacobian_blocks(snap["origin"], snap["group"])["lm"]).reshape(-1, 3, 3)
+        H = np.array([consistency.stereo_rows(est["p"][i], q21, t21, R21.T @ (est["p"][i] - t21) / np.linalg.norm(est["p"][i] - t21))[0] for i in lm])
+        d = float(np.mean([np.diag(H[k] @ J[i] @ snap["sigma"][11 + 3 * i:14 + 3 * i, 11 + 3 * i:14 + 3 * i] @ J[i].T @ H[k].T) for k, i in enumerate(lm)]))
+        ids.append(snap["ids"][lm]), Hs.append(H), rs.append(np.zeros((K, 2))), Rs.append(100.0 * d * np.eye(2)), idx.append(lm)
+    return fg, ids, Hs, rs, Rs, idx
+
+
+def blocks(B, N, K, reps=20):
+    import numpy as np
+    from eqf_vio_amd import consistency
+
+    fg, ids, Hs, rs, Rs, idx = _blocks_setup(B, N, K)
+
+    def device():
+        return fg.update_landmarks(ids, Hs, rs, Rs, rows=2, local=True)["info"]
+
+    def host():
+        for b in range(B):
+            snap = fg.dump_state(b)
+            J = consistency.local_jacobian_blocks(snap["origin"], snap["group"])["lm"]
+            up = consistency.update_landmarks_host(snap["sigma"], idx[b], Hs[b], rs[b], np.broadcast_to(Rs[b], (K, 2, 2)), J)
+            snap["sigma"] = up["Sigma"]
+            snap["bias"] = snap["bias"] + up["gamma"][0:6]  # (the group step is left out: see the module docstring)
+            fg.restore_state(snap, b)
+
+    assert not np.any(device())  # (first calls: allocations)
+    host()
+    device(), host()
+    ta, th = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        device()
+        t1 = time.perf_counter()
+        host()
+        t2 = time.perf_counter()
+        ta.append((t1 - t0) * 1e3)
+        th.append((t2 - t1) * 1e3)
+    assert fg.device_error() == 0
+    q = lambda v: dict(median_ms=round(float(np.median(v)), 3), min_ms=round(min(v), 3), max_ms=round(max(v), 3))
+    print(json.dumps(dict(case="update_landmarks", B=B, N=N, entries=K, rows=2, reps=reps, device=q(ta), host=q(th),
+                          speedup_of_medians=round(float(np.median(th) / np.median(ta)), 1), spreads_overlap=bool(max(ta) >= min(th)))), flush=True)
+
+
+def blockskern(B, N, K):
+    import numpy as np
+
+    fg, ids, Hs, rs, Rs, idx = _blocks_setup(B, N, K)
+    for _ in range(30):
+        assert not np.any(fg.update_landmarks(ids, Hs, rs, Rs, rows=2, local=True)["info"])
+    assert fg.device_error() == 0
+    print(f"blockskern B={B} N={N} K={K}: done")
+
+
+def blockssum(d):
+    print("B x N x K      kernel            avg / min / max us (calls)      bytes        TB/s (avg)   of 6.29")
+    for path in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)):
+        tag = [t for t in os.path.relpath(path, d).split(os.sep) if t.startswith("blockskern_")]
+        if not tag:
+            continue
+        _, B, N, K = tag[0].split("_")
+        B, N, K = int(B), int(N), int(K)
+        n, m = 12 + 3 * N, 2 * K
+        nt = -(-n // 64)
+        tl = nt * (nt + 1) // 2
+        by = {"k_blk_downdate": 8.0 * B * (64 * 64 * (2 * tl + nt * (nt - 1) // 2) + 2 * 64 * m * tl)}
+        for r in csv.DictReader(open(path)):
+            name = r.get("Name") or r.get("KernelName") or ""
+            for key in ("k_blk_rows", "k_blk_gain", "k_blk_diag", "k_blk_panel", "k_blk_trail", "k_blk_tail", "k_blk_downdate", "k_apply_increment",
+                        "k_local_jacobian"):
+                if key in name:
+                    a, lo, hi = float(r["AverageNs"]) / 1e3, float(r["MinNs"]) / 1e3, float(r["MaxNs"]) / 1e3
+                    tail = f"{by[key] / 1e6:10.2f} MB   {by[key] / a / 1e6:6.3f}   {100 * by[key] / a / 1e6 / 6.29:5.1f} %" if key in by else ""
+                    print(f"{B:3d} x {N:<5d} x {K:<3d} {key:18s} {a:9.1f} / {lo:8.1f} / {hi:8.1f} ({r['Calls']:>3s})   {tail}")
+
+
 def neeskern(B, N):
     fg, E = _nees_setup(B, N)
     for _ in range(10):
@@ -607,6 +705,12 @@ if __name__ == "__main__":
         linearkern(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
     elif cmd == "linearsum":
         linearsum(sys.argv[2])
+    elif cmd == "blocks":
+        blocks(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
+    elif cmd == "blockskern":
+        blockskern(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
+    elif cmd == "blockssum":
+        blockssum(sys.argv[2])
     elif cmd == "mixture":
         mixture(int(sys.argv[2]), int(sys.argv[3]))
     elif cmd == "mixturekern":
