@@ -70,6 +70,18 @@ class LinearReport(C.Structure):
     _fields_ = [("nis", C.c_double), ("logdet_S", C.c_double), ("loglik", C.c_double), ("dof", C.c_int), ("info", C.c_int)]
 
 
+class ForecastOut(C.Structure):
+    """eqf_forecast_out (include/eqf_vio_amd.h)."""
+
+    _fields_ = [("time", C.POINTER(C.c_double)), ("steps", C.POINTER(C.c_int)), ("pose_q", C.POINTER(C.c_double)),
+                ("pose_x", C.POINTER(C.c_double)), ("velocity", C.POINTER(C.c_double)), ("p", C.POINTER(C.c_double)),
+                ("bearing", C.POINTER(C.c_double)), ("base", C.POINTER(C.c_double)), ("lm", C.POINTER(C.c_double)),
+                ("S", C.POINTER(C.c_double)), ("ycov", C.POINTER(C.c_double))]
+
+
+FORECAST_OUTPUTS = ("time", "steps", "pose_q", "pose_x", "velocity", "p", "bearing", "base", "lm", "S", "ycov")
+
+
 class MixtureReport(C.Structure):
     """eqf_mixture_report (include/eqf_vio_amd.h)."""
 
@@ -84,7 +96,7 @@ EXPORTED_SYMBOLS = [
     "eqf_settings_default", "eqf_create", "eqf_destroy", "eqf_reset", "eqf_process_imu", "eqf_process_vision",
     "eqf_stream_upload", "eqf_stream_imu", "eqf_stream_vision", "eqf_synchronize", "eqf_get_time", "eqf_num_landmarks",
     "eqf_get_ids", "eqf_get_state_estimate", "eqf_get_origin", "eqf_get_group", "eqf_get_bias", "eqf_get_sigma",
-    "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
+    "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_forecast", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
     "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters", "eqf_update_linear", "eqf_update_landmarks",
     "eqf_get_mixture_moments", "eqf_merge_filters", "eqf_debug_mixture_launches", "eqf_debug_sigma_pad",
     "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
@@ -145,6 +157,7 @@ def lib():
             L.eqf_get_sigma_local.argtypes = [vp, C.c_int, _dp, C.c_int]
             L.eqf_get_marginals.argtypes = [vp, C.c_int, C.c_int, _dp, _dp]
             L.eqf_get_local_jacobian.argtypes = [vp, C.c_int, _dp, _dp, _dp]
+            L.eqf_forecast.argtypes = [vp, C.c_int, _dp, _dp, C.c_int, C.c_int, C.POINTER(ForecastOut), _ip]
             L.eqf_debug_sigma_local_all.argtypes = [vp]
             L.eqf_get_innovation_stats.argtypes = [vp, C.c_int, C.POINTER(InnovationStats), _dp]
         if hasattr(L, "eqf_get_nees"):
@@ -453,6 +466,48 @@ class FilterBatch:
         G, RAt, lm = np.zeros((2, 2)), np.zeros((3, 3)), np.zeros((max(N, 1), 3, 3))
         _check(lib().eqf_get_local_jacobian(self._h, b, _p(G), _p(RAt), _p(lm)), "eqf_get_local_jacobian")
         return dict(G=G, RAt=RAt, lm=lm[:N])
+
+    def forecast(self, imu=None, t1=None, local=True, want=FORECAST_OUTPUTS):
+        """Where the state and the features will be after the IMU samples `imu` ((K, B, 7) or (K, 7): stamp, omega, accel) and, where `t1`
+        (scalar or (B,)) is given, the integration up to t1 with which a vision call begins -- without changing the handle
+        (include/eqf_vio_amd.h: eqf_forecast; consistency.forecast_host).  Returns a dict: ``status`` (B,) and, for every name in `want`,
+        a list with one array per filter, the per-landmark ones trimmed to that filter's N: time, steps, pose_q (4,), pose_x (3,),
+        velocity (3,), p (N, 3), bearing (N, 3), base (11, 11), lm (N, 3, 3) -- base and lm in the estimate's chart (local) or the origin's
+        -- S (N, 2, 2) = C_i Sigma_ii C_i^T + r I, ycov (N, 3, 3) the covariance of the unit bearing."""
+        unknown = [w for w in want if w not in FORECAST_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown forecast outputs {unknown}")
+        B = self.B
+        K = 0
+        imu_p = None
+        if imu is not None:
+            imu = np.asarray(imu, dtype=np.float64)
+            if imu.ndim == 2:
+                imu = np.broadcast_to(imu[:, None, :], (imu.shape[0], B, 7))
+            if imu.ndim != 3 or imu.shape[1:] != (B, 7):
+                raise ValueError(f"imu must have shape (K, {B}, 7) or (K, 7)")
+            imu = np.ascontiguousarray(imu)
+            K = imu.shape[0]
+            imu_p = _p(imu) if K else None
+        t1_p = None
+        if t1 is not None:
+            t1 = np.ascontiguousarray(np.broadcast_to(np.asarray(t1, dtype=np.float64), (B,)))
+            t1_p = _p(t1)
+        Ns = [self.num_landmarks(b) for b in range(B)]
+        stride = max(Ns + [1])
+        shapes = dict(time=(B,), pose_q=(B, 4), pose_x=(B, 3), velocity=(B, 3), p=(B, stride, 3), bearing=(B, stride, 3), base=(B, 11, 11),
+                      lm=(B, stride, 3, 3), S=(B, stride, 2, 2), ycov=(B, stride, 3, 3))
+        bufs = {w: (np.zeros(B, dtype=np.int32) if w == "steps" else np.zeros(shapes[w])) for w in want}
+        out = ForecastOut()
+        for w, a in bufs.items():
+            setattr(out, w, a.ctypes.data_as(_ip if w == "steps" else _dp))
+        status = np.zeros(B, dtype=np.int32)
+        _check(lib().eqf_forecast(self._h, K, imu_p, t1_p, int(bool(local)), stride, C.byref(out), status.ctypes.data_as(_ip)), "eqf_forecast")
+        res = dict(status=status)
+        for w, a in bufs.items():
+            per_lm = w in ("p", "bearing", "lm", "S", "ycov")
+            res[w] = [a[b, :Ns[b]] if per_lm else a[b] for b in range(B)]  # (views of the call's own buffers: nothing else holds them)
+        return res
 
     def innovation_stats(self, b=0):
         """Statistics of filter b's most recent vision update (set_option("innovation_stats", 1) first): dict with nis, logdet_S, loglik,

@@ -23,6 +23,12 @@ to first order eps_loc = J eps with the block-diagonal J of local_jacobian_block
   mixture_moments_host(members, w, centre, centred)   mean and covariance of a weighted batch in the chart of a centre state, the spread
                                          between the members included -- the numpy statement of FilterBatch.mixture_moments
   merge_host(members, w, ref)            ... and of FilterBatch.merge: the one state and covariance that match the batch's first two moments
+  forecast_host(flt, imu, t1, ...)       the numpy statement of FilterBatch.forecast (include/eqf_vio_amd.h: eqf_forecast) on a filter object
+                                         with the reference's interface: a copy runs the calls, the handle's outputs are read off it
+  output_blocks(origin_p)                C_i (2 x 3) of every landmark, the diagonal blocks of the output matrix C0 (EqFMatrices.cpp:319-344)
+  bearing_cov_host(p, P_loc)             covariance of the unit bearing p / |p| from the landmark's block in the estimate's chart (`ycov`)
+  search_ellipse(ycov, dpix_dy, p)       ... as a 2 x 2 pixel covariance and the semi-axes of its chi-square ellipse, for a tracker
+  gate_distance(S, delta)                the d2 a hypothesised residual would get from forecast's S (the Mahalanobis gate's number)
 
 `origin`, `group`, `estimate` are the dicts of FilterBatch.origin() / group() / state_estimate(): quaternions (w, x, y, z), Eigen semantics.
 """
@@ -619,3 +625,119 @@ def merge_host(members, w, ref):
     second = mixture_moments_host(members, wt, dict(estimate=xbar, bias=bias), centred=False)
     return dict(estimate=xbar, bias=bias, P=second["P"], mean=first["mean"], n_eff=second["n_eff"], spread_trace=second["spread_trace"],
                 total_trace=second["total_trace"])
+
+
+# ---- the forecast (FilterBatch.forecast; include/eqf_vio_amd.h: eqf_forecast) on the host
+class ImuSample:
+    """One IMU sample with the arithmetic the reference's IMUVelocity has (IMUVelocity.cpp:35-58): minus a bias 6-vector, times a scalar,
+    plus another sample."""
+
+    def __init__(self, stamp=0.0, omega=None, accel=None):
+        self.stamp = float(stamp)
+        self.omega = np.zeros(3) if omega is None else np.array(omega, dtype=float)
+        self.accel = np.zeros(3) if accel is None else np.array(accel, dtype=float)
+
+    def __add__(self, other):
+        if hasattr(other, "omega"):
+            return ImuSample(self.stamp if self.stamp > 0 else other.stamp, self.omega + other.omega, self.accel + other.accel)
+        return ImuSample(self.stamp, self.omega + other[0:3], self.accel + other[3:6])
+
+    def __sub__(self, vec):
+        return self + (-np.asarray(vec))
+
+    def __mul__(self, c):
+        return ImuSample(self.stamp, self.omega * c, self.accel * c)
+
+    def __getitem__(self, k):  # (omega, accel) as the 6-vector a sample of another type adds to itself
+        return np.concatenate([self.omega, self.accel])[k]
+
+
+def output_blocks(origin_p):
+    """C_i = |p0_i|^-1 stereoSphereChartDiff(y0_i, y0_i) (I - y0_i y0_i^T), y0_i = p0_i / |p0_i| (EqFMatrices.cpp:319-344): (N, 2, 3) from
+    the ORIGIN's landmarks, FilterBatch.origin()["p"]."""
+    p0 = np.asarray(origin_p, dtype=float).reshape(-1, 3)
+    C = np.zeros((len(p0), 2, 3))
+    for i, q in enumerate(p0):
+        nrm = np.linalg.norm(q)
+        y = q / nrm
+        C[i] = 1.0 / nrm * stereo_sphere_chart_diff(y, y) @ (np.eye(3) - np.outer(y, y))
+    return C
+
+
+def bearing_cov_host(p, P_loc):
+    """D P_loc D^T with D = (I - yhat yhat^T) / |p|, yhat = p / |p|: the covariance of the predicted unit bearing of a landmark at p (camera
+    frame) whose position has covariance P_loc in the estimate's chart.  Rank 2 (yhat is its null vector); no measurement noise.  p (3,) and
+    P_loc (3, 3), or (N, 3) and (N, 3, 3)."""
+    p = np.asarray(p, dtype=float)
+    P = np.asarray(P_loc, dtype=float)
+    if p.ndim == 2:
+        return np.array([bearing_cov_host(p[i], P[i]) for i in range(len(p))]).reshape(len(p), 3, 3)
+    n = np.linalg.norm(p)
+    y = p / n
+    D = (np.eye(3) - np.outer(y, y)) / n
+    return D @ P @ D.T
+
+
+def search_ellipse(ycov, dpix_dy, p=0.99):
+    """The region of the image in which a tracker should look for a feature: dpix_dy (2 x 3) is the caller's camera Jacobian d pixel / d
+    bearing at the predicted bearing, ycov (3 x 3) forecast's covariance of that bearing.  Returns dict(cov (2, 2) = J ycov J^T, axes (2,)
+    the semi-axes in pixels, long one first, of the ellipse that holds the feature with chi-square probability p, and dirs (2, 2) their unit
+    directions as rows).  Add the detector's own pixel variance to cov before use if it matters."""
+    J = np.asarray(dpix_dy, dtype=float).reshape(2, 3)
+    cov = J @ np.asarray(ycov, dtype=float).reshape(3, 3) @ J.T
+    cov = 0.5 * (cov + cov.T)
+    lam, vec = np.linalg.eigh(cov)
+    k2 = chi2_gate_threshold(p, 2)
+    order = [1, 0]
+    return dict(cov=cov, axes=np.sqrt(k2 * np.maximum(lam[order], 0.0)), dirs=vec[:, order].T.copy())
+
+
+def gate_distance(S, delta):
+    """delta^T S^-1 delta through the Cholesky factor of S's LOWER triangle, as the device's gate forms it: what a residual delta (2,) in
+    the update's coordinates would score against forecast's S (2, 2).  S (N, 2, 2) with delta (N, 2) gives (N,)."""
+    S = np.asarray(S, dtype=float)
+    d = np.asarray(delta, dtype=float)
+    if S.ndim == 3:
+        return np.array([gate_distance(S[i], d[i]) for i in range(len(S))])
+    l00 = np.sqrt(S[0, 0])
+    l10 = S[1, 0] / l00
+    l11 = np.sqrt(S[1, 1] - l10 * l10)
+    w0 = d[0] / l00
+    w1 = (d[1] - l10 * w0) / l11
+    return float(w0 * w0 + w1 * w1)
+
+
+def forecast_host(flt, imu=None, t1=None, local=True, measurement_variance=0.0, sample=ImuSample):
+    """The numpy statement of FilterBatch.forecast for ONE filter.  `flt` is a filter object with the reference's interface (processIMUData
+    (sample), integrateUpToTime(t), getTime(), initialisedFlag, xi0, X, Sigma, stateEstimate()); it is deep-copied, the copy is given the
+    samples imu (K, 7) -- stamp, omega, accel; the filter subtracts its bias -- and, where t1 is given, integrateUpToTime(t1), and the
+    handle's outputs are read off the copy: time, steps, pose_q, pose_x, velocity, p, bearing, base, lm (in the estimate's chart if local),
+    S = C_i Sigma_ii C_i^T + r I from the origin-chart block and ycov from the estimate-chart block.  `sample(stamp, omega, accel)` builds the
+    filter's own sample type."""
+    import copy
+
+    f = copy.deepcopy(flt)
+    steps = 0
+    for r in ([] if imu is None else np.asarray(imu, dtype=float).reshape(-1, 7)):
+        steps += int(f.getTime() >= 0 and r[0] - f.getTime() > 0)
+        f.processIMUData(sample(r[0], r[1:4], r[4:7]))
+    if t1 is not None:
+        steps += int(bool(f.integrateUpToTime(float(t1))))
+    est = f.stateEstimate()
+    N = len(f.xi0.ids)
+    origin = dict(q=f.xi0.pose.q, x=f.xi0.pose.x, v=f.xi0.velocity, p=np.asarray(f.xi0.p, dtype=float).reshape(N, 3))
+    group = dict(Aq=f.X.A.q, Ax=f.X.A.x, w=f.X.w, Qq=np.array([Q.q for Q in f.X.Q]).reshape(N, 4), Qa=np.array([Q.a for Q in f.X.Q]).reshape(N))
+    Sg = np.asarray(f.Sigma, dtype=float)
+    blocks = local_jacobian_blocks(origin, group)
+    lm0 = np.array([Sg[11 + 3 * i:14 + 3 * i, 11 + 3 * i:14 + 3 * i] for i in range(N)]).reshape(N, 3, 3)
+    lmloc = np.array([blocks["lm"][i] @ lm0[i] @ blocks["lm"][i].T for i in range(N)]).reshape(N, 3, 3)
+    base = Sg[:11, :11].copy()
+    if local:
+        Jb = jacobian_matrix(dict(G=blocks["G"], RAt=blocks["RAt"], lm=np.zeros((0, 3, 3))))
+        base = Jb @ base @ Jb.T
+    p = np.asarray(est.p, dtype=float).reshape(N, 3)
+    C = output_blocks(origin["p"])
+    S = np.array([C[i] @ lm0[i] @ C[i].T + measurement_variance * np.eye(2) for i in range(N)]).reshape(N, 2, 2)
+    return dict(time=float(f.getTime()), steps=steps, pose_q=np.array(est.pose.q, dtype=float), pose_x=np.array(est.pose.x, dtype=float),
+                velocity=np.array(est.velocity, dtype=float), p=p, bearing=p / np.linalg.norm(p, axis=1, keepdims=True) if N else p,
+                base=base, lm=lmloc if local else lm0, S=S, ycov=bearing_cov_host(p, lmloc) if N else np.zeros((0, 3, 3)))

@@ -244,6 +244,63 @@ class VIOFilter {
         check(eqf_get_sigma_local(handle_.get(), 0, S.data.data(), S.n), "eqf_get_sigma_local");
         return S;
     }
+    // Where the state and the features WILL be (eqf_forecast): what this filter would hold after the IMU samples `imu` and, with hasStamp,
+    // the integration up to `stamp` with which processVisionData begins -- the filter itself is only read.  state: the estimate at the time
+    // reached; base (11 x 11) and lm (3 x 3 per landmark) its marginal covariances, in the estimate's chart (local) or the origin's;
+    // bearing the predicted unit bearings; S (2 x 2 per landmark) what the Mahalanobis gate will divide by; ycov (3 x 3 per landmark) the
+    // covariance of the predicted bearing, for a search region.  status: EQF_OK, an EQF_SKIPPED_* code (not initialised: everything zero;
+    // no step integrated: the present values) -- EQF_ERR_NUMERIC throws.
+    struct Forecast {
+        int status = 0, steps = 0;
+        double time = 0.0;
+        VIOState state;
+        std::vector<std::array<double, 3>> bearing;
+        std::array<double, 121> base{};
+        std::vector<std::array<double, 9>> lm, ycov;
+        std::vector<std::array<double, 4>> S;
+    };
+    Forecast forecast(const std::vector<IMUVelocity>& imu, bool hasStamp, double stamp, bool local = true) const {
+        Forecast fc;
+        const int N = eqf_num_landmarks(handle_.get(), 0), K = int(imu.size()), M = N > 0 ? N : 1;
+        std::vector<double> rec(size_t(7) * (K > 0 ? K : 1)), p(size_t(3) * M), y(size_t(3) * M), lm(size_t(9) * M), S(size_t(4) * M), yc(size_t(9) * M);
+        for (int k = 0; k < K; ++k) {
+            rec[7 * k] = imu[k].stamp;
+            for (int c = 0; c < 3; ++c) {
+                rec[7 * k + 1 + c] = imu[k].omega[c];
+                rec[7 * k + 4 + c] = imu[k].accel[c];
+            }
+        }
+        std::vector<int> ids(M);
+        double q[4], x[3], v[3];
+        eqf_forecast_out out{&fc.time, &fc.steps, q, x, v, p.data(), y.data(), fc.base.data(), lm.data(), S.data(), yc.data()};
+        check(eqf_forecast(handle_.get(), K, K > 0 ? rec.data() : nullptr, hasStamp ? &stamp : nullptr, local ? 1 : 0, M, &out, &fc.status),
+            "eqf_forecast");
+        check(fc.status < 0 ? fc.status : 0, "eqf_forecast");
+        check(eqf_get_ids(handle_.get(), 0, ids.data()), "eqf_get_ids");
+        fc.state.pose.R = {q[0], q[1], q[2], q[3]};
+        fc.state.pose.x = {x[0], x[1], x[2]};
+        fc.state.velocity = {v[0], v[1], v[2]};
+        fc.state.cameraOffset = settings->cameraOffsetSE3();
+        fc.state.bodyLandmarks.resize(N);
+        fc.bearing.resize(N);
+        fc.lm.resize(N);
+        fc.ycov.resize(N);
+        fc.S.resize(N);
+        for (int i = 0; i < N; ++i) {
+            fc.state.bodyLandmarks[i].p = {p[3 * i], p[3 * i + 1], p[3 * i + 2]};
+            fc.state.bodyLandmarks[i].id = ids[i];
+            fc.bearing[i] = {y[3 * i], y[3 * i + 1], y[3 * i + 2]};
+            for (int e = 0; e < 9; ++e) {
+                fc.lm[i][e] = lm[9 * i + e];
+                fc.ycov[i][e] = yc[9 * i + e];
+            }
+            for (int e = 0; e < 4; ++e) fc.S[i][e] = S[4 * i + e];
+        }
+        return fc;
+    }
+    // The features of the frame that is about to be matched, stamped `stamp`: predicted bearings, gate matrices and search covariances
+    // from the samples the filter already has (the K = 0 forecast).
+    Forecast predictFeatures(double stamp) const { return forecast({}, true, stamp, true); }
     // Innovation statistics of the most recent vision update (setOption("innovation_stats", 1) first; eqf_get_innovation_stats):
     // NIS, log det S, log-likelihood, degrees of freedom and the per-landmark NIS in the state's landmark order.
     struct InnovationStats : eqf_innovation_stats {

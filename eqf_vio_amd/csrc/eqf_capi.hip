@@ -35,6 +35,8 @@
 #include "eqf_linear_host.hpp"
 #include "eqf_mixture.hpp"
 #include "eqf_mixture_host.hpp"
+#include "eqf_forecast.hpp"
+#include "eqf_forecast_host.hpp"
 
 using namespace eqf;
 
@@ -289,6 +291,12 @@ struct eqf_filter {
     double profMs[EQF_PROF_CLASSES] = {};
     std::vector<ProfSample> profSamples[EQF_PROF_CLASSES];  // per-bracket times with their launch shape
     double profOverheadMs = 0.0;  // elapsed time of an EMPTY event bracket (calibrated when profiling is switched on)
+    // the non-mutating forecast (eqf_forecast.hpp; eqf_forecast), allocated by its first call from capacity and batch: the samples of a call
+    // as a pinned image and its device copy, the per-step records the builder leaves for the landmark lanes, and the output records as a
+    // device image and its pinned copy (forecast::imageCapacityDoubles / recDoubles / outStride).  The call synchronises before it returns,
+    // so the pinned images need no event.  (Last in the handle: what the per-step calls touch keeps its place.)
+    ImuRec *hFcImu = nullptr, *dFcImu = nullptr;
+    double *dFcRec = nullptr, *dFcOut = nullptr, *hFcOut = nullptr;
 };
 
 namespace {
@@ -1618,6 +1626,11 @@ void freeAll(eqf_filter* f) {
     if (f->hClonePairs) hipHostFree(f->hClonePairs);
     if (f->evCloneSrc) hipEventDestroy(f->evCloneSrc);
     if (f->evCloneDone) hipEventDestroy(f->evCloneDone);
+    hipFree(f->dFcImu);
+    hipFree(f->dFcRec);
+    hipFree(f->dFcOut);
+    if (f->hFcImu) hipHostFree(f->hFcImu);
+    if (f->hFcOut) hipHostFree(f->hFcOut);
     hipFree(f->dMixWs);
     hipFree(f->dMixTab);
     if (f->hMixTab) hipHostFree(f->hMixTab);
@@ -2277,6 +2290,126 @@ int eqf_get_local_jacobian(eqf_filter* f, int b, double* G, double* RAt, double*
     std::copy(f->hOut, f->hOut + 4, G);
     std::copy(f->hOut + 4, f->hOut + 13, RAt);
     if (N > 0) std::copy(f->hOut + kJacHead, f->hOut + kJacHead + (size_t)9 * N, lmJ);
+    return EQF_OK;
+}
+
+// eqf_forecast's workspace, all or nothing: a failed allocation leaves the handle as it was
+static int forecastWorkspace(eqf_filter* f) {
+    if (f->dFcOut) return EQF_OK;
+    const size_t nImg = sizeof(double) * forecast::imageCapacityDoubles(f->B), nRec = sizeof(double) * forecast::recDoubles(f->B),
+                 nOut = sizeof(double) * forecast::outStride(f->cap) * f->B;
+    void *hImu = nullptr, *dImu = nullptr, *dRec = nullptr, *dOut = nullptr, *hOut = nullptr;
+    const bool ok = hipHostMalloc(&hImu, nImg, hipHostMallocDefault) == hipSuccess && hipMalloc(&dImu, nImg) == hipSuccess &&
+                    hipMalloc(&dRec, nRec) == hipSuccess && hipMalloc(&dOut, nOut) == hipSuccess &&
+                    hipHostMalloc(&hOut, nOut, hipHostMallocDefault) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (hImu) hipHostFree(hImu);
+        if (hOut) hipHostFree(hOut);
+        hipFree(dImu);
+        hipFree(dRec);
+        hipFree(dOut);
+        return EQF_ERR_HIP;
+    }
+    f->hFcImu = static_cast<ImuRec*>(hImu);
+    f->dFcImu = static_cast<ImuRec*>(dImu);
+    f->dFcRec = static_cast<double*>(dRec);
+    f->dFcOut = static_cast<double*>(dOut);
+    f->hFcOut = static_cast<double*>(hOut);
+    return EQF_OK;
+}
+
+int eqf_forecast(eqf_filter* f, int K, const double* imu, const double* t1, int local, int stride, const eqf_forecast_out* out, int* status) {
+    namespace fc = forecast;
+    if (!fc::headArgsOk(f, out, K, imu, local, stride)) return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64 || f->set.fastRiccati) return EQF_ERR_UNSUPPORTED;
+    const int B = f->B, cap = f->cap;
+    if (!fc::stampsOk(K, imu, t1, B)) return EQF_ERR_INVALID;
+    GATE(f);
+    std::vector<int> N(B);
+    for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
+    const fc::Wants wants{out->p != nullptr, out->bearing != nullptr, out->lm != nullptr, out->S != nullptr, out->ycov != nullptr};
+    if (!fc::strideOk(wants, stride, B, N.data())) return EQF_ERR_INVALID;
+    int rc = forecastWorkspace(f);
+    if (rc) return rc;
+    const int nSteps = fc::steps(K, t1 != nullptr);
+    double* img = reinterpret_cast<double*>(f->hFcImu);
+    for (int k = 0; k < K; ++k)
+        for (int b = 0; b < B; ++b) fc::packSample(imu + ((size_t)k * B + b) * 7, img + fc::imageIndex(k, b, B));
+    if (t1)
+        for (int b = 0; b < B; ++b) fc::packStamp(t1[b], img + fc::imageIndex(K, b, B));
+    if (nSteps > 0)
+        HIPC(hipMemcpyAsync(f->dFcImu, f->hFcImu, sizeof(double) * fc::imageDoubles(K, t1 != nullptr, B), hipMemcpyHostToDevice, f->stream));
+    FcArgs a{};
+    a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.lmc = f->lmc;
+    a.Sin = static_cast<const double*>(f->Sigma[f->pS]); a.sigmaStride = f->sigmaStride; a.cap = cap; a.ld = f->ld; a.B = B;
+    a.K = K; a.nSteps = nSteps; a.local = local; a.imu = f->dFcImu; a.rec = f->dFcRec; a.out = f->dFcOut;
+    a.outStride = (long long)fc::outStride(cap); a.prm = f->prm;
+    const fc::Grid gb = fc::buildGrid(B), gl = fc::lmGrid(maxN(f), B);
+    hipLaunchKernelGGL(k_forecast_build, dim3(gb.x, gb.y), dim3(gb.threads), 0, f->stream, a);
+    hipLaunchKernelGGL(k_forecast_lm, dim3(gl.x, gl.y), dim3(gl.threads), 0, f->stream, a);
+    HIPC(hipGetLastError());
+    // the filters that answer: initialised, and past their first IMU sample (a forecast does not initialise a filter)
+    std::vector<int> st(B, EQF_OK);
+    size_t used = 0, first = 0, end = 0;  // doubles the answering filters wrote, and the span of the image that holds them
+    for (int b = 0; b < B; ++b) {
+        if (!f->init[b]) st[b] = EQF_SKIPPED_NOT_INITIALISED;
+        else if (f->curTime[b] < 0) st[b] = EQF_SKIPPED_BEFORE_FIRST_IMU;
+        else {
+            if (!used) first = fc::outStride(cap) * b;
+            used += fc::outUsed(N[b]);
+            end = fc::outStride(cap) * b + fc::outUsed(N[b]);
+        }
+    }
+    // one copy for the whole batch while the span is not mostly unused capacity (a copy costs microseconds before its first byte), one per filter otherwise
+    if (used && end - first <= 4 * used) {
+        HIPC(hipMemcpyAsync(f->hFcOut + first, f->dFcOut + first, sizeof(double) * (end - first), hipMemcpyDeviceToHost, f->stream));
+    } else {
+        for (int b = 0; b < B; ++b)
+            if (st[b] == EQF_OK)
+                HIPC(hipMemcpyAsync(f->hFcOut + fc::outStride(cap) * b, f->dFcOut + fc::outStride(cap) * b, sizeof(double) * fc::outUsed(N[b]),
+                    hipMemcpyDeviceToHost, f->stream));
+    }
+    HIPC(hipStreamSynchronize(f->stream));
+    const double nan = std::nan("");
+    for (int b = 0; b < B; ++b) {
+        const double* h = f->hFcOut + fc::outStride(cap) * b;
+        const double* hb = f->hFcOut + fc::outBase(cap, b);
+        const bool skipped = st[b] != EQF_OK;
+        bool numeric = false;
+        if (!skipped) {
+            numeric = h[fc::kHeadFlag] != 0.0;
+            for (int i = 0; i < N[b] && !numeric; ++i) numeric = f->hFcOut[fc::outLm(cap, b, i) + fc::kLmFlag] != 0.0;
+            if (numeric) st[b] = EQF_ERR_NUMERIC;
+            else if (nSteps > 0 && h[fc::kHeadSteps] == 0.0) st[b] = EQF_SKIPPED_NONPOSITIVE_DT;
+        }
+        // one value of an output: zero for a filter that was skipped, NaN for one in numeric trouble
+        auto put = [&](double* dst, const double* src, int n) {
+            for (int e = 0; e < n; ++e) dst[e] = skipped ? 0.0 : (numeric ? nan : src[e]);
+        };
+        if (out->time) put(out->time + b, h + fc::kHeadTime, 1);
+        if (out->steps) out->steps[b] = (skipped || numeric) ? 0 : int(h[fc::kHeadSteps]);
+        if (out->pose_q) put(out->pose_q + 4 * b, h + fc::kHeadPoseQ, 4);
+        if (out->pose_x) put(out->pose_x + 3 * b, h + fc::kHeadPoseX, 3);
+        if (out->velocity) put(out->velocity + 3 * b, h + fc::kHeadVel, 3);
+        if (out->base) put(out->base + 121 * (size_t)b, hb, 121);
+        for (int i = 0; i < (wants.perLandmark() ? stride : 0); ++i) {
+            const bool live = i < N[b] && !skipped;
+            static const double zeros[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+            const double* l = live ? f->hFcOut + fc::outLm(cap, b, i) : nullptr;
+            const size_t row = (size_t)b * stride + i;
+            // (rows behind a filter's landmarks are written as zero)
+            auto putLm = [&](double* dst, int off, int n) {
+                for (int e = 0; e < n; ++e) dst[e] = live ? (numeric ? nan : l[off + e]) : zeros[e];
+            };
+            if (out->p) putLm(out->p + 3 * row, fc::kLmP, 3);
+            if (out->bearing) putLm(out->bearing + 3 * row, fc::kLmBearing, 3);
+            if (out->lm) putLm(out->lm + 9 * row, fc::kLmCov, 9);
+            if (out->S) putLm(out->S + 4 * row, fc::kLmS, 4);
+            if (out->ycov) putLm(out->ycov + 9 * row, fc::kLmYcov, 9);
+        }
+        if (status) status[b] = st[b];
+    }
     return EQF_OK;
 }
 

@@ -145,6 +145,49 @@ int eqf_get_marginals(eqf_filter* f, int b, int local, double* base, double* lm)
 /* The blocks of J as the device built them: G[2][2], RAt[3][3] = R_A^T, lmJ[N][3][3] = a_i^-1 R(q_i)^T -- what a caller needs to map
  * vectors of its own between the two charts. */
 int eqf_get_local_jacobian(eqf_filter* f, int b, double* G, double* RAt, double* lmJ);
+/* A forecast that changes nothing (csrc/eqf_forecast.hpp): where the state and the features will be after K more IMU samples and, where t1
+ * is given, the integrateUpToTime(t1) with which processVisionData begins (VIOFilter.cpp:120-131, :234) -- and how sure the filter is of
+ * that.  Per filter the call computes what the filter WOULD hold: each sample has the filter's bias subtracted; each step integrates with
+ * the previous sample (zero-order hold) and then replaces it; a step with dt <= 0 integrates nothing and still replaces the sample; every
+ * step is the reference's step at the state after the step before, nothing is composed algebraically.  Both velocity lifts are supported.
+ * O(N): with F = [[F_bb, 0], [L, D]] and D block-diagonal the base block, each landmark's 3 x 11 panel and each landmark's own diagonal
+ * block evolve without the rest of Sigma, so the call reads those and writes nothing of the handle -- every getter answers with the same
+ * bits afterwards (sticky error flags included), every later call gives the bits it gives on a handle that never forecast.  Two kernel
+ * launches whatever K, N and the batch; results are bit for bit the same from run to run and for a filter alone or anywhere in a batch.
+ * Like every getter the call first settles what the handle has deferred (queued IMU calls, the speculative gate) and synchronises.
+ *   imu     [K][batch][7]: eqf_stream_upload's record (stamp, omega, accel); NULL iff K = 0
+ *   t1      [batch] or NULL
+ *   local   the chart of base and lm, as in eqf_get_marginals; the Jacobian is that of the FORECAST state
+ *   stride  rows per filter of the per-landmark outputs (rows behind a filter's landmarks are written as zero)
+ * status[b]: EQF_OK; EQF_SKIPPED_NOT_INITIALISED / EQF_SKIPPED_BEFORE_FIRST_IMU: every output of that filter is zero (a forecast does not
+ * initialise a filter); EQF_SKIPPED_NONPOSITIVE_DT: samples or t1 were given and no step integrated, the outputs are the present values;
+ * EQF_ERR_NUMERIC: a singular chart or a value that is not finite was met on the way -- nothing is raised in the handle, that filter's
+ * outputs are NaN (steps 0).  With K = 0 and t1 NULL, or when no step integrates, pose_*, velocity, p, base and lm equal
+ * eqf_get_state_estimate and eqf_get_marginals(local) bit for bit.  base and lm in the origin chart, S and ycov are exactly symmetric; base
+ * and lm in the estimate chart are what eqf_get_marginals' products give.
+ * Before any effect: EQF_ERR_INVALID (NULL f or out; K < 0 or K > 256; imu NULL with K > 0 or given with K = 0; local not 0 or 1; stride
+ * smaller than a filter's landmark count while a per-landmark output is requested; a stamp that is not finite); EQF_ERR_UNSUPPORTED on an
+ * EQF_PRECISION_F32 handle and with settings.fastRiccati = 1, whose accumulated-velocity Riccati step is a different recursion;
+ * EQF_ERR_HIP if the workspace, allocated by the first call from capacity and batch, cannot be had (nothing else is affected). */
+typedef struct eqf_forecast_out {   /* any pointer may be NULL: that output is not produced */
+    double* time;      /* [batch]            time reached                                             */
+    int*    steps;     /* [batch]            integrateUpToTime calls that integrated (dt > 0)          */
+    double* pose_q;    /* [batch][4]  pose_x [batch][3]  velocity [batch][3]: eqf_get_state_estimate's */
+    double* pose_x;
+    double* velocity;
+    double* p;         /* [batch][stride][3] landmarks of the estimate, camera frame, state order      */
+    double* bearing;   /* [batch][stride][3] p / |p|                                                    */
+    double* base;      /* [batch][11][11]    eqf_get_marginals' base block at the time reached          */
+    double* lm;        /* [batch][stride][3][3]  ... and its diagonal blocks                            */
+    double* S;         /* [batch][stride][2][2]  C_i Sigma_ii C_i^T + r I: what EQF_GATE_MAHALANOBIS and
+                          nis_lm divide by, in the update's delta coordinates, from the ORIGIN-chart block
+                          whatever `local` is                                                            */
+    double* ycov;      /* [batch][stride][3][3]  D Sigma_loc,ii D^T, D = (I - yhat yhat^T) / |p|: covariance
+                          of the predicted unit bearing (rank 2, no measurement noise), from the
+                          ESTIMATE-chart block whatever `local` is                                       */
+} eqf_forecast_out;
+int eqf_forecast(eqf_filter* f, int K, const double* imu /* [K][batch][7]; NULL iff K = 0 */, const double* t1 /* [batch] or NULL */,
+    int local, int stride, const eqf_forecast_out* out, int* status /* [batch] or NULL */);
 /* Test hook: overwrite Sigma (same layout as eqf_get_sigma). */
 int eqf_set_sigma(eqf_filter* f, int b, const double* src, int ld);
 /* Checkpoint / resume (full precision; the reference's only dump is the lossy, write-only operator<<,
