@@ -88,6 +88,14 @@ class MixtureReport(C.Structure):
     _fields_ = [("n_eff", C.c_double), ("spread_trace", C.c_double), ("total_trace", C.c_double), ("n", C.c_int), ("info", C.c_int)]
 
 
+class PairCost(C.Structure):
+    """eqf_pair_cost (include/eqf_vio_amd.h)."""
+
+    _fields_ = [("cost", C.c_double), ("logdet_pair", C.c_double), ("maha", C.c_double), ("info", C.c_int), ("pad_", C.c_int)]
+
+
+COST_KINDS = {"runnalls": 0, "bhattacharyya": 1}
+
 _lib = None
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -99,6 +107,7 @@ EXPORTED_SYMBOLS = [
     "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_forecast", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
     "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters", "eqf_update_linear", "eqf_update_landmarks",
     "eqf_get_mixture_moments", "eqf_merge_filters", "eqf_debug_mixture_launches", "eqf_debug_sigma_pad",
+    "eqf_get_merge_costs",
     "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
     "eqf_set_sigma", "eqf_set_state", "eqf_copy_filters", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
@@ -177,6 +186,9 @@ def lib():
             L.eqf_merge_filters.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, C.POINTER(MixtureReport)]
             L.eqf_debug_mixture_launches.argtypes = [vp]
             L.eqf_debug_sigma_pad.argtypes = [vp, C.c_int, C.c_int, _dp]
+        if hasattr(L, "eqf_get_merge_costs"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
+            L.eqf_get_merge_costs.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.POINTER(PairCost),
+                                              C.POINTER(SigmaStats)]
         if hasattr(L, "eqf_set_outlier_gate"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
             L.eqf_set_outlier_gate.argtypes = [vp, C.c_int, C.c_double]
             L.eqf_get_outlier_gate.argtypes = [vp, _ip, _dp]
@@ -760,6 +772,79 @@ class FilterBatch:
         _check(lib().eqf_merge_filters(self._h, len(ii), ii.ctypes.data_as(_ip), _p(ww), int(ref), int(dst), C.byref(rep) if report else None),
                "eqf_merge_filters")
         return self._mixture_report(rep) if report else None
+
+    def merge_costs(self, idx, w, ref=None, kind="runnalls", first=0, pairs=None):
+        """Pairwise merge costs of the weighted members idx of this handle, on the device (include/eqf_vio_amd.h: eqf_get_merge_costs;
+        consistency.merge_costs_host is its numpy statement).  ref: the member whose estimate is the chart centre (default: the heaviest,
+        the first of them).  kind: "runnalls" or "bhattacharyya"; first: 0, 6 or 11.  pairs: (npairs, 2) POSITIONS in idx, or None: all
+        i < j in lexicographic order.  Returns a dict: pairs (npairs, 2) as asked, cost, logdet_pair, maha, info (npairs,), member_logdet,
+        member_min_pivot, member_dof, member_info (n,), ref, and with pairs=None the symmetric (n, n) matrix of costs, zero diagonal."""
+        ii, ww = self._members(idx, w)
+        n = len(ii)
+        if ref is None:
+            ref = int(ii[int(np.argmax(ww))])
+        if pairs is None:
+            pp = np.array([(i, j) for i in range(n) for j in range(i + 1, n)], dtype=np.int32).reshape(-1, 2)
+        else:
+            pp = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        npairs = len(pp)
+        out = (PairCost * max(npairs, 1))()
+        mem = (SigmaStats * n)()
+        _check(lib().eqf_get_merge_costs(self._h, n, ii.ctypes.data_as(_ip), _p(ww), int(ref), COST_KINDS[kind], int(first), npairs,
+                                         None if pairs is None or npairs == 0 else pp.ctypes.data_as(_ip), out, mem), "eqf_get_merge_costs")
+        res = dict(pairs=pp, cost=np.array([out[k].cost for k in range(npairs)]), logdet_pair=np.array([out[k].logdet_pair for k in range(npairs)]),
+                   maha=np.array([out[k].maha for k in range(npairs)]), info=np.array([out[k].info for k in range(npairs)], dtype=np.int32),
+                   member_logdet=np.array([s.logdet for s in mem]), member_min_pivot=np.array([s.min_pivot for s in mem]),
+                   member_dof=np.array([s.dof for s in mem], dtype=np.int32), member_info=np.array([s.info for s in mem], dtype=np.int32),
+                   ref=int(ref))
+        if pairs is None:
+            M = np.zeros((n, n))
+            for k in range(npairs):
+                M[pp[k, 0], pp[k, 1]] = M[pp[k, 1], pp[k, 0]] = res["cost"][k]
+            res["matrix"] = M
+        return res
+
+    def reduce_mixture(self, idx, w, target, max_cost=float("inf"), kind="runnalls"):
+        """Greedy mixture reduction on the device: while more than `target` members are left, the pair of least merge cost (ties: the
+        lower pair in lexicographic order of positions) is merged with merge() into the slot of the lower position -- into the centre's
+        slot if the higher position holds the chart centre, the heaviest member at the start, so that it stays valid --, the weights are
+        added and the other slot is dropped; only the pairs that involve the merged slot are asked for again.  Stops early when the
+        cheapest cost exceeds max_cost.  Returns (surviving indices, their weights, log) with log a list of ((position kept, position
+        dropped), cost), positions in idx.  consistency.reduce_mixture_host is its numpy statement."""
+        ii, ww = self._members(idx, w)
+        ww = ww / ww.sum()
+        alive = list(range(len(ii)))
+        wt = {k: float(ww[k]) for k in alive}
+        centre = int(np.argmax(ww))
+        log = []
+
+        def ask(pairs_pos):  # (every member left is named, so that the weights are normalised as a whole; `pairs` picks what is factored)
+            loc = {p: k for k, p in enumerate(alive)}
+            r = self.merge_costs(ii[alive], [wt[p] for p in alive], ref=int(ii[centre]), kind=kind,
+                                 pairs=[(loc[a], loc[b]) for a, b in pairs_pos])
+            return {pr: (float(c) if i == 0 else float("inf")) for pr, c, i in zip(pairs_pos, r["cost"], r["info"])}
+
+        cache = {}
+        if len(alive) > 1:
+            cache = ask([(a, b) for x, a in enumerate(alive) for b in alive[x + 1:]])
+        while len(alive) > max(int(target), 1):
+            (a, b), c = min(cache.items(), key=lambda kv: (kv[1], kv[0]))
+            if not c <= max_cost:
+                break
+            keep, drop = (b, a) if b == centre else (a, b)
+            s = wt[a] + wt[b]
+            rep = self.merge([ii[a], ii[b]], [wt[a], wt[b]], ref=int(ii[keep]), dst=int(ii[keep]))
+            if rep["info"] != 0:
+                raise RuntimeError(f"reduce_mixture: merge of {(a, b)} reported info {rep['info']}")
+            log.append(((keep, drop), c))
+            wt[keep] = s
+            del wt[drop]
+            alive.remove(drop)
+            cache = {pr: v for pr, v in cache.items() if a not in pr and b not in pr}
+            fresh = [tuple(sorted((keep, o))) for o in alive if o != keep]
+            if fresh:
+                cache.update(ask(fresh))
+        return ii[alive].copy(), np.array([wt[k] for k in alive]), log
 
     def debug_mixture_launches(self):
         """Kernel launches of the most recent merge() (include/eqf_vio_amd_debug.h)."""

@@ -569,15 +569,9 @@ def _member_error(member, centre_est, centre_bias):
     return error_vector(e)
 
 
-def mixture_moments_host(members, w, centre, centred=True):
-    """The numpy statement of FilterBatch.mixture_moments.  members: a list of dicts with `estimate` (state_estimate(): q, v, p), `bias`,
-    `origin`, `group` and `sigma` (the filter's Sigma, origin chart; its blocks on and below the block diagonal count: lower_mirrored); w their weights (normalised here); centre: the index of the member
-    whose estimate is the centre c (its T is the identity by definition), or a dict with `estimate` and `bias` (every T is computed).
-    e_b = chi_c(xHat_b), J'_b = J_b with T_b G_b for G_b, eBar = sum w~ e, P = sum w~ [J' Sigma J'^T + (e - m)(e - m)^T], m = eBar if
-    centred else 0.  Returns dict(mean, P, e (n, dim), spread, n_eff, spread_trace, total_trace)."""
-    wt = normalise_weights(w)
-    if len(wt) != len(members):
-        raise ValueError("one weight per member")
+def mixture_member_images(members, centre):
+    """The pieces of mixture_moments_host per member, in the chart of the centre (an index into members: T = I for that member by
+    definition; or a dict with `estimate` and `bias`: every T is computed): (E, terms) with E[k] = e_k and terms[k] = J'_k Sigma_k J'_k^T."""
     own = centre if isinstance(centre, (int, np.integer)) else None
     c = members[own] if own is not None else centre
     eta_c = gravity_dir(c["estimate"]["q"])
@@ -593,6 +587,19 @@ def mixture_moments_host(members, w, centre, centred=True):
         J = jacobian_matrix(blocks)
         E.append(e)
         terms.append(J @ lower_mirrored(mb["sigma"]) @ J.T)
+    return E, terms
+
+
+def mixture_moments_host(members, w, centre, centred=True):
+    """The numpy statement of FilterBatch.mixture_moments.  members: a list of dicts with `estimate` (state_estimate(): q, v, p), `bias`,
+    `origin`, `group` and `sigma` (the filter's Sigma, origin chart; its blocks on and below the block diagonal count: lower_mirrored); w their weights (normalised here); centre: the index of the member
+    whose estimate is the centre c (its T is the identity by definition), or a dict with `estimate` and `bias` (every T is computed).
+    e_b = chi_c(xHat_b), J'_b = J_b with T_b G_b for G_b, eBar = sum w~ e, P = sum w~ [J' Sigma J'^T + (e - m)(e - m)^T], m = eBar if
+    centred else 0.  Returns dict(mean, P, e (n, dim), spread, n_eff, spread_trace, total_trace)."""
+    wt = normalise_weights(w)
+    if len(wt) != len(members):
+        raise ValueError("one weight per member")
+    E, terms = mixture_member_images(members, centre)
     E = np.array(E)
     mean = np.zeros(E.shape[1])
     for k in range(len(wt)):
@@ -625,6 +632,111 @@ def merge_host(members, w, ref):
     second = mixture_moments_host(members, wt, dict(estimate=xbar, bias=bias), centred=False)
     return dict(estimate=xbar, bias=bias, P=second["P"], mean=first["mean"], n_eff=second["n_eff"], spread_trace=second["spread_trace"],
                 total_trace=second["total_trace"])
+
+
+# ---- which members to merge (FilterBatch.merge_costs / reduce_mixture; include/eqf_vio_amd.h: eqf_get_merge_costs) on the host
+COST_KINDS = ("runnalls", "bhattacharyya")
+
+
+def _logdet_maha(A, d):
+    """log det A and d^T A^-1 d of a symmetric A (numpy.linalg.slogdet / solve); (nan, nan) if A is not positive definite to slogdet."""
+    if A.shape[0] == 0:
+        return 0.0, 0.0
+    sign, ld = np.linalg.slogdet(A)
+    if not sign > 0:
+        return np.nan, np.nan
+    return float(ld), float(d @ np.linalg.solve(A, d))
+
+
+def pair_cost(kind, ld_i, ld_j, ld_ij, maha, wi, wj):
+    """The two costs from the three log-determinants, the quadratic form and the normalised weights (include/eqf_vio_amd.h)."""
+    if kind == "bhattacharyya":
+        return 0.125 * maha + 0.25 * ((ld_ij - ld_i) + (ld_ij - ld_j))
+    if kind != "runnalls":
+        raise ValueError(f"kind must be one of {COST_KINDS}")
+    a = pair_alpha(kind, wi, wj)
+    return 0.5 * (wi * (ld_ij - ld_i) + wj * (ld_ij - ld_j) + (wi + wj) * np.log1p(a * (1.0 - a) * maha))
+
+
+def pair_alpha(kind, wi, wj):
+    return 0.5 if (kind == "bhattacharyya" or not wi + wj > 0.0) else wj / (wi + wj)
+
+
+def merge_costs_host(members, w, ref, kind="runnalls", first=0, pairs=None):
+    """The numpy statement of FilterBatch.merge_costs.  members, w: as mixture_moments_host; ref: the POSITION in members of the member whose
+    estimate is the chart centre; first: 0, 6 or 11; pairs: (npairs, 2) positions or None (all i < j).  Per pair, ordered so that i < j:
+    SigmaBar = S'_i + alpha (S'_j - S'_i) over the lower triangles, d = e_j - e_i, slogdet and solve.  Returns the dict of
+    FilterBatch.merge_costs (without the info words: a matrix that is not positive definite gives NaN)."""
+    wt = normalise_weights(w)
+    n = len(members)
+    if len(wt) != n:
+        raise ValueError("one weight per member")
+    E, terms = mixture_member_images(members, int(ref))
+    S = [mirror_lower(t)[first:, first:] for t in terms]
+    e = [np.asarray(x)[first:] for x in E]
+    mld = np.array([_logdet_maha(S[k], np.zeros(S[k].shape[0]))[0] for k in range(n)])
+    if pairs is None:
+        pp = np.array([(i, j) for i in range(n) for j in range(i + 1, n)], dtype=np.int32).reshape(-1, 2)
+    else:
+        pp = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    cost, ldp, maha = np.zeros(len(pp)), np.zeros(len(pp)), np.zeros(len(pp))
+    for k, (i, j) in enumerate(pp):
+        i, j = (int(i), int(j)) if i <= j else (int(j), int(i))
+        a = pair_alpha(kind, wt[i], wt[j])
+        ldp[k], maha[k] = _logdet_maha(S[i] + a * (S[j] - S[i]), e[j] - e[i])
+        cost[k] = pair_cost(kind, mld[i], mld[j], ldp[k], maha[k], wt[i], wt[j])
+    out = dict(pairs=pp, cost=cost, logdet_pair=ldp, maha=maha, member_logdet=mld, ref=int(ref))
+    if pairs is None:
+        M = np.zeros((n, n))
+        for k, (i, j) in enumerate(pp):
+            M[i, j] = M[j, i] = cost[k]
+        out["matrix"] = M
+    return out
+
+
+def merged_member(members, w, ref):
+    """What FilterBatch.merge leaves in filter dst, as a member dict: merge_host's state with origin = the merged estimate, X = identity,
+    Sigma = P."""
+    m = merge_host(members, w, ref)
+    est = m["estimate"]
+    N = len(np.asarray(est["p"]).reshape(-1, 3))
+    group = dict(Aq=np.array([1.0, 0, 0, 0]), Ax=np.zeros(3), w=np.zeros(3), Qq=np.tile([1.0, 0, 0, 0], (N, 1)), Qa=np.ones(N))
+    return dict(estimate=est, bias=m["bias"], origin=dict(q=est["q"], x=est["x"], v=est["v"], p=est["p"]), group=group, sigma=m["P"])
+
+
+def reduce_mixture_host(members, w, target, max_cost=np.inf, kind="runnalls"):
+    """The numpy statement of FilterBatch.reduce_mixture: greedy merging of the cheapest pair (ties: the lower pair in lexicographic order of
+    positions) into the lower position -- into the centre's if the higher position is the centre, the heaviest member at the start -- until
+    `target` members are left or the cheapest cost exceeds max_cost.  Returns (surviving positions, their weights, the surviving member
+    dicts, log) with log a list of ((position kept, position dropped), cost)."""
+    wt = normalise_weights(w)
+    ms = {k: m for k, m in enumerate(members)}
+    wk = {k: float(wt[k]) for k in ms}
+    alive = sorted(ms)
+    centre = int(np.argmax(wt))
+    log = []
+
+    def ask(pairs_pos):
+        loc = {p: k for k, p in enumerate(alive)}
+        r = merge_costs_host([ms[p] for p in alive], [wk[p] for p in alive], loc[centre], kind, 0, [(loc[a], loc[b]) for a, b in pairs_pos])
+        return {pr: (float(c) if np.isfinite(c) else np.inf) for pr, c in zip(pairs_pos, r["cost"])}
+
+    cache = ask([(a, b) for x, a in enumerate(alive) for b in alive[x + 1:]]) if len(alive) > 1 else {}
+    while len(alive) > max(int(target), 1):
+        (a, b), c = min(cache.items(), key=lambda kv: (kv[1], kv[0]))
+        if not c <= max_cost:
+            break
+        keep, drop = (b, a) if b == centre else (a, b)
+        ms[keep] = merged_member([ms[a], ms[b]], [wk[a], wk[b]], 0 if keep == a else 1)
+        wk[keep] = wk[a] + wk[b]
+        del ms[drop], wk[drop]
+        alive.remove(drop)
+        log.append(((keep, drop), c))
+        cache = {pr: v for pr, v in cache.items() if a not in pr and b not in pr}
+        fresh = [tuple(sorted((keep, o))) for o in alive if o != keep]
+        if fresh:
+            cache.update(ask(fresh))
+    return alive, np.array([wk[k] for k in alive]), [ms[k] for k in alive], log
 
 
 # ---- the forecast (FilterBatch.forecast; include/eqf_vio_amd.h: eqf_forecast) on the host

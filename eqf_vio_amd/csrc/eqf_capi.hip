@@ -35,6 +35,8 @@
 #include "eqf_linear_host.hpp"
 #include "eqf_mixture.hpp"
 #include "eqf_mixture_host.hpp"
+#include "eqf_mergecost.hpp"
+#include "eqf_mergecost_host.hpp"
 #include "eqf_forecast.hpp"
 #include "eqf_forecast_host.hpp"
 
@@ -297,6 +299,13 @@ struct eqf_filter {
     // so the pinned images need no event.  (Last in the handle: what the per-step calls touch keeps its place.)
     ImuRec *hFcImu = nullptr, *dFcImu = nullptr;
     double *dFcRec = nullptr, *dFcOut = nullptr, *hFcOut = nullptr;
+    // pairwise merge costs (eqf_mergecost.hpp; eqf_get_merge_costs), allocated on first need: one block for a chunk of images with their
+    // right-hand sides, records and orders (grown when the option "merge_cost_chunk" asks for more), one for a call's items and records.
+    // (Behind everything else, for the same reason.)
+    char* dMcWs = nullptr;
+    int mcChunkCap = 0, mcChunkOpt = 0;
+    char* dMcItems = nullptr;
+    size_t mcItemCap = 0;
 };
 
 namespace {
@@ -1632,6 +1641,8 @@ void freeAll(eqf_filter* f) {
     if (f->hFcImu) hipHostFree(f->hFcImu);
     if (f->hFcOut) hipHostFree(f->hFcOut);
     hipFree(f->dMixWs);
+    hipFree(f->dMcWs);
+    hipFree(f->dMcItems);
     hipFree(f->dMixTab);
     if (f->hMixTab) hipHostFree(f->hMixTab);
     if (f->evMix) hipEventDestroy(f->evMix);
@@ -2872,6 +2883,11 @@ int eqf_set_option(eqf_filter* f, const char* name, int value) {
         f->innovStats = value;
         return EQF_OK;
     }
+    if (!std::strcmp(name, "merge_cost_chunk")) {  // images per round of eqf_get_merge_costs (0: as many as the handle has filters)
+        if (value != 0 && !mergecost::chunkOptionOk(value)) return EQF_ERR_INVALID;
+        f->mcChunkOpt = value;
+        return EQF_OK;
+    }
     return EQF_ERR_INVALID;
 }
 
@@ -3704,6 +3720,144 @@ int eqf_merge_filters(eqf_filter* f, int n, const int* idx, const double* w, int
         f->csValid = false;
         f->permOnDevice.clear();
         f->editOnDevice.clear();
+    }
+    return EQF_OK;
+}
+
+// ---- pairwise merge costs (eqf_mergecost.hpp; argument checks, items, chunk plan and cost formulas: eqf_mergecost_host.hpp)
+static_assert(mergecost::kRefBase == kBase && mergecost::kPadBase == kLm0 && mergecost::kBlock == kSB &&
+              sizeof(mergecost::Item) == sizeof(PairItem) && sizeof(Glob) % 8 == 0,
+    "eqf_mergecost_host.hpp repeats the layout constants");
+namespace {
+struct McWs {
+    double *W, *E, *D, *out;
+    Glob* g;
+    int* bad;
+};
+size_t mcWsDoubles(const eqf_filter* f, int C) {
+    return size_t(C) * (size_t(f->sigmaStride) + size_t(f->nTot) + size_t(kDRec) + size_t(kNeesHead + kNeesRhs) + sizeof(Glob) / 8) + size_t(C + 1) / 2;
+}
+McWs mcCarve(const eqf_filter* f, char* p, int C) {
+    McWs w;
+    w.W = reinterpret_cast<double*>(p);
+    w.E = w.W + size_t(C) * size_t(f->sigmaStride);
+    w.D = w.E + size_t(C) * size_t(f->nTot);
+    w.out = w.D + size_t(C) * size_t(kDRec);
+    w.g = reinterpret_cast<Glob*>(w.out + size_t(C) * size_t(kNeesHead + kNeesRhs));
+    w.bad = reinterpret_cast<int*>(w.g + C);
+    return w;
+}
+// both blocks of a call; a failure frees what this call got and leaves the handle as it was
+int mcAlloc(eqf_filter* f, int chunk, size_t nItems) {
+    void *w = nullptr, *t = nullptr;
+    const size_t itemBytes = nItems * (sizeof(PairItem) + sizeof(double) * kPairRec);
+    const bool needW = chunk > f->mcChunkCap, needT = nItems > f->mcItemCap;
+    if (!needW && !needT) return EQF_OK;
+    if ((needW && hipMalloc(&w, sizeof(double) * mcWsDoubles(f, chunk)) != hipSuccess) || (needT && hipMalloc(&t, itemBytes) != hipSuccess)) {
+        (void)hipGetLastError();
+        if (w) hipFree(w);
+        return EQF_ERR_HIP;
+    }
+    HIPC(hipStreamSynchronize(f->stream));
+    if (needW) {
+        hipFree(f->dMcWs);
+        f->dMcWs = static_cast<char*>(w);
+        f->mcChunkCap = chunk;
+        HIPC(hipMemsetAsync(w, 0, sizeof(double) * mcWsDoubles(f, chunk), f->stream));  // (upper triangles and the Globs are read, never used)
+    }
+    if (needT) {
+        hipFree(f->dMcItems);
+        f->dMcItems = static_cast<char*>(t);
+        f->mcItemCap = nItems;
+    }
+    return EQF_OK;
+}
+}  // namespace
+
+int eqf_get_merge_costs(eqf_filter* f, int n, const int* idx, const double* w, int ref, int kind, int first, int npairs, const int* pairs,
+    eqf_pair_cost* out, eqf_sigma_stats* member) {
+    if (!f || !mixture::headArgsOk(n, idx, w, ref, f->B) || !mergecost::pairArgsOk(n, kind, first, npairs, pairs) || (npairs > 0 && !out))
+        return EQF_ERR_INVALID;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);
+    MixCall c;
+    int rc = mixCheck(f, n, idx, w, ref, false, c);
+    if (rc) return rc;
+    mergecost::distinct(n, idx, f->B, c.uniq);  // (every member's image is needed, a member of weight 0 too)
+    std::vector<mergecost::Item> items;
+    mergecost::buildItems(n, idx, c.wt.data(), kind, npairs, pairs, items);
+    const int chunk = mergecost::chunkSize(f->mcChunkOpt, f->B);
+    rc = mcAlloc(f, chunk, items.size());
+    if (rc) return rc;
+    if (!f->neesLdsSet) {  // (dynamic LDS beyond 64 KB: see allowUpdateLds)
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nees_panel), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesPanelLdsBytes));
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nees_trail), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesTrailLdsBytes));
+        f->neesLdsSet = true;
+    }
+    // e_b, J'_b and Sigma'_b of every distinct member about c = xHat_ref
+    const int launchesBefore = f->mixLaunches;  // (eqf_debug_mixture_launches keeps answering for the most recent MIXTURE call)
+    MixArgs a;
+    rc = mixPrepare(f, c, ref, ref, ref, a);
+    f->mixLaunches = launchesBefore;
+    if (rc) return rc;
+    a.centre = ref; a.centreFilter = ref; a.centred = 0;
+    const int N = c.N, strips = std::max(1, (N + 255) / 256);
+    hipLaunchKernelGGL(k_mix_estimate, dim3(strips, a.nUniq), dim3(256), 0, f->stream, a);
+    hipLaunchKernelGGL(k_mix_error, dim3(strips, a.nUniq), dim3(256), 0, f->stream, a);
+    for (int u : c.uniq) {
+        LocalArgs la = localArgs(f, u);
+        la.jac = a.jacT;
+        hipLaunchKernelGGL(k_sigma_local, dim3(strips, std::max(1, (N + kLocalRows - 1) / kLocalRows), 1), dim3(256), 0, f->stream, la);
+    }
+    HIPC(hipGetLastError());
+    const int off = mergecost::offsetOf(first), m = mergecost::paddedOrder(N, off), nb = mergecost::blockColumns(m);
+    const McWs ws = mcCarve(f, f->dMcWs, f->mcChunkCap);
+    PairItem* dItems = reinterpret_cast<PairItem*>(f->dMcItems);
+    double* dRec = reinterpret_cast<double*>(f->dMcItems + sizeof(PairItem) * f->mcItemCap);
+    HIPC(hipMemcpyAsync(dItems, items.data(), sizeof(PairItem) * items.size(), hipMemcpyHostToDevice, f->stream));
+    PairArgs pa{};
+    pa.items = dItems; pa.S = f->dSigmaLoc; pa.ld = f->ld; pa.strideS = f->sigmaStride; pa.err = a.err; pa.jacT = a.jacT; pa.cap = f->cap;
+    pa.N = N; pa.off = off; pa.kind = kind; pa.W = ws.W; pa.E = ws.E; pa.ldE = std::max(m, 1); pa.wg = ws.g; pa.neesOut = ws.out; pa.rec = dRec;
+    NeesArgs na{};
+    na.g = ws.g; na.A = ws.W; na.ld = f->ld; na.strideA = f->sigmaStride; na.E = ws.E; na.ldE = pa.ldE; na.D = ws.D; na.bad = ws.bad;
+    na.jac = nullptr; na.cap = f->cap; na.off = off; na.nrhs = 1; na.out = ws.out;
+    // the members, then the pairs: chunks of at most `chunk` images, never both kinds in one
+    const long long seg0[2] = {0, n}, segLen[2] = {n, npairs};
+    for (int s = 0; s < 2; ++s)
+        for (int ch = 0; ch < mergecost::numChunks(segLen[s], chunk); ++ch) {
+            const int cnt = mergecost::chunkCount(segLen[s], chunk, ch);
+            pa.item0 = int(seg0[s] + (long long)ch * chunk);
+            pa.count = cnt;
+            hipLaunchKernelGGL(k_pair_form, dim3(kLm0 + 3 * N + 1, cnt), dim3(256), 0, f->stream, pa);
+            hipLaunchKernelGGL(k_nees_diag, dim3(1, cnt), dim3(256), kLdsFactorBytes, f->stream, na, 0);
+            for (int K = 0; K < nb; ++K) {
+                const int t = nb - K - 1;
+                if (K > 0) hipLaunchKernelGGL(k_nees_diag, dim3(1, cnt), dim3(256), kLdsFactorBytes, f->stream, na, K);
+                hipLaunchKernelGGL(k_nees_panel, dim3(t + 1, cnt), dim3(256), kNeesPanelLdsBytes, f->stream, na, K, t);
+                if (t > 0) hipLaunchKernelGGL(k_nees_trail, dim3(t * (t + 1) / 2 + t, cnt), dim3(256), kNeesTrailLdsBytes, f->stream, na, K, t);
+            }
+            hipLaunchKernelGGL(k_nees_tail, dim3(cnt), dim3(256), 0, f->stream, na);
+            hipLaunchKernelGGL(k_pair_tail, dim3((cnt + 255) / 256), dim3(256), 0, f->stream, pa);
+        }
+    HIPC(hipGetLastError());
+    std::vector<double> hR(items.size() * kPairRec);
+    HIPC(hipMemcpyAsync(hR.data(), dRec, sizeof(double) * hR.size(), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipStreamSynchronize(f->stream));
+    if (member)
+        for (int k = 0; k < n; ++k) {
+            const double* r = hR.data() + size_t(k) * kPairRec;
+            member[k].logdet = r[1];
+            member[k].min_pivot = r[4];
+            member[k].dof = int(r[5]);
+            member[k].info = int(r[3]);
+        }
+    for (int p = 0; p < npairs; ++p) {
+        const double* r = hR.data() + (size_t(n) + p) * kPairRec;
+        out[p].cost = r[0];
+        out[p].logdet_pair = r[1];
+        out[p].maha = r[2];
+        out[p].info = int(r[3]);
+        out[p].pad_ = 0;
     }
     return EQF_OK;
 }

@@ -501,6 +501,55 @@ int eqf_get_mixture_moments(eqf_filter* f, int n, const int* idx, const double* 
     double* mean /* [11 + 3 N] or NULL */, double* P, int ld, eqf_mixture_report* report /* or NULL */);
 int eqf_merge_filters(eqf_filter* f, int n, const int* idx, const double* w, int ref, int dst, eqf_mixture_report* report /* or NULL */);
 
+/* WHICH members to merge: the pairwise merge costs of the members of a mixture, on the device (csrc/eqf_mergecost.hpp).  Members, weights,
+ * ref, the normalisation of w and the checks on ids are eqf_get_mixture_moments'; first is eqf_get_nees's (0 | 6 | 11: the trailing
+ * principal submatrix from that reference index).  Everything is taken in the ONE chart chi_c, c = xHat_ref: e_b and J'_b as above,
+ * Sigma'_b = J'_b Sigma_b J'_b^T (the lower triangle of Sigma is read).  A cost is invariant under a common LINEAR change of chart --
+ * log-determinants shift by the same constant, the quadratic form does not move -- and to first order the transition between two members'
+ * charts is linear: that is why one centre serves all pairs.
+ * For the pair of POSITIONS (i, j) in idx, ordered by the library so that i < j, alpha = w~_j / (w~_i + w~_j) (1/2 if both weights are 0):
+ *   SigmaBar_ij = Sigma'_i + alpha (Sigma'_j - Sigma'_i)  entry by entry,   d = e_j - e_i,   SigmaBar_ij = L L^T (blocked fp64 Cholesky on
+ *   the matrix cores, d carried as a right-hand side),   logdet_pair = 2 sum log L_kk,   maha = |L^-1 d|^2;
+ * per member ld_b from the same route applied to Sigma'_b.
+ *   EQF_COST_RUNNALLS        cost = 1/2 [ w~_i (ld_ij - ld_i) + w~_j (ld_ij - ld_j) + (w~_i + w~_j) log1p(alpha (1 - alpha) maha) ]
+ *                            (Runnalls' bound on the Kullback-Leibler discrimination; log det(SigmaBar + alpha (1 - alpha) d d^T) through
+ *                            the determinant lemma: no second factorisation)
+ *   EQF_COST_BHATTACHARYYA   weights ignored, alpha = 1/2:  cost = 1/8 maha + 1/4 [ (ld_ij - ld_i) + (ld_ij - ld_j) ]
+ * pairs: npairs pairs of positions, or NULL: the first npairs (at most n (n - 1) / 2) of all i < j in lexicographic order.  out [npairs];
+ * member [n] (by position) or NULL.  npairs = 0 with member given is allowed.
+ *   Read-only: settles what the handle has deferred and synchronises like every getter; every getter answers with the same bits afterwards
+ *   and every later call gives the bits it gives on a handle that never asked (the scratch image of eqf_get_sigma_local is overwritten, as
+ *   eqf_get_nees does).
+ *   Reproducible: no atomics, one fixed summation order; bit for bit the same from run to run.
+ *   Independent of context: the record of a pair does not depend on which other pairs are in the call, on their order, on the chunking, on
+ *   whether it was named (i, j) or (j, i), or on which slots of which handle hold the members.
+ *   Identical members cost exactly 0: a pair whose two members are the same filter, or bit-identical copies made by eqf_copy_filters, has
+ *   cost == 0.0, maha == 0.0 and logdet_pair == member[i].logdet exactly -- members and pairs go through the same kernels.  (A copy OF ref
+ *   is not identical to ref in this sense where its T_b, computed, is not the identity that ref has by definition.)
+ *   member[k].logdet, min_pivot, dof and info of the member that IS ref equal bit for bit what eqf_get_nees(local = 1, first, nrhs = 0)
+ *   reports for that filter.
+ *   Trouble of ONE pair goes into its info (fields NaN): the call returns EQF_OK and eqf_device_error is never touched.
+ * Before any effect: EQF_ERR_INVALID for everything eqf_get_mixture_moments refuses, a kind or first out of range, npairs < 0 (or beyond all
+ * pairs with pairs == NULL), a pair position out of range, out == NULL with npairs > 0.  EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle.
+ * EQF_ERR_HIP if the workspace cannot be had (the handle stays as it was): one image per item of a chunk -- by default as many as the
+ * handle has filters, one more scratch image set; eqf_set_option(f, "merge_cost_chunk", c), 1 <= c <= 4096 (0: the default), overrides it.
+ * Members are factored first, then the pairs, never in one chunk together; the number of launches depends only on the number of distinct
+ * members, n, npairs, N, first and the chunk.
+ * Not covered: the partitioned filter, members in different handles, the C++ facade. */
+#define EQF_COST_RUNNALLS 0
+#define EQF_COST_BHATTACHARYYA 1
+typedef struct eqf_pair_cost {
+    double cost;         /* see above                                                        */
+    double logdet_pair;  /* log det SigmaBar_ij                                              */
+    double maha;         /* d^T SigmaBar_ij^-1 d,  d = e_j - e_i                              */
+    int info;            /* 0 ok; 1 a pivot not positive or a non-finite value (NaN fields);  */
+                         /* -1 a gravity chart needed by either member is singular (NaN)      */
+    int pad_;
+} eqf_pair_cost;
+int eqf_get_merge_costs(eqf_filter* f, int n, const int* idx, const double* w, int ref, int kind, int first, int npairs,
+    const int* pairs /* [npairs][2] POSITIONS in idx, or NULL: all i < j in lexicographic order */, eqf_pair_cost* out /* [npairs] */,
+    eqf_sigma_stats* member /* [n] or NULL */);
+
 /* Propagate backend: 0 = block-structured HBM-bound kernel (default, product path),
  * 1 = dense F Sigma F^T on MFMA (what the reference executes; BASELINE cfg 3 cross-check). */
 int eqf_set_dense_propagate(eqf_filter* f, int on);
