@@ -8,13 +8,14 @@
 // An entry that does not take part -- its id is not in the state, or its own d2 = resid^T (Ht_k Sigma_ii Ht_k^T + R_k)^-1 resid exceeds
 // lm_gate -- is a decoupled block (H = 0, resid = 0, R = I) in the statement of the update; here such a block is never formed: k_blk_rows
 // packs the entries that take part to the front, S has the filter's own order m_b = rows * count_b, and what lies past m_b is the
-// identity of eqf_nees.hpp's convention (supplied when a block is loaded, never stored).  The result is therefore the one of the call
+// identity of eqf_factor.hpp's convention (supplied when a block is loaded, never stored).  The result is therefore the one of the call
 // without that entry, bit for bit, and the launch shapes depend on stride, rows and the handle's capacity only.
 //
 // The work of a filter sits in one tall matrix M [mp + n + 1][mp], mp = rows * stride rounded up to 64: rows [0, mp) hold S, rows mp + i
-// the row i of B (n x m, state index by measurement index), row mp + n the residual.  A right-looking blocked Cholesky in 64-wide block
-// columns over ALL block rows turns S into L, B into B L^-T = Y^T and resid^T into z^T (eqf_nees.hpp carries its error vectors the same
-// way): the right-hand side is n + 1 rows tall, as wide as S, and needs no kernel of its own.
+// the row i of B (n x m, state index by measurement index), row mp + n the residual.  eqf_factor.hpp's blocked Cholesky
+// (k_factor_diag / _panel / _trail<BlkArgs>) turns S into L and, as its right-hand side of n + 1 rows, B into B L^-T = Y^T and resid^T
+// into z^T: no kernel of this file's own.  factorView is what it sees of a filter: M, order m_b (0 when the verdict word is not 0: such
+// a filter takes no part), no pad index, the record BlkArgs::D, the pivot word, and the rows from mp on.
 //
 //   k_blk_rows      one workgroup per filter.  The verdict word starts here (3 masked out, -1 local and the gravity chart singular, 4 no
 //                   entry takes part, else 0).  One thread per entry: Ht_k = H_k or H_k J_i, S_kk from Sigma_ii, d2_k, used[k]; then the
@@ -23,9 +24,6 @@
 //                   of its entry by the lower triangle (a row segment or a column segment of Sigma) and writes rows dot3's: n x 3 x rows
 //                   multiply-adds per entry, no dense product.  The others: 16 x 16 pairs of entries each, thread (p, q <= p) forms
 //                   Ht_p Sigma_{pq} Ht_q^T (+ R_p when p = q) from the 3 x 3 block of Sigma, the lower triangle of S only.
-//   k_blk_diag      block (K, K) of S -> LDS (identity past m_b, lower triangle only), factor64, L_KK back, the record to BlkArgs::D
-//   k_blk_panel     M_RK <- M_RK L_KK^-T for every block row R > K, of S and of the right-hand side alike (solveStrip<true>)
-//   k_blk_trail     M_RC -= M_RK L_CK^T for the block columns C > K and the block rows R >= C on v_mfma_f64_16x16x4_f64 (mmTile)
 //   k_blk_gamma     gamma_i = sum_k Y_ki z_k, one thread per i (64 of them per workgroup), k ascending, one fused multiply-add each; a value
 //                   of Y or gamma that is not finite raises the filter's non-finite word (every writer stores the same 1)
 //   k_blk_tail      one workgroup per filter: nis = z^T z and log det S = 2 sum log L_kk (thread t the terms t, t + 256, .. in sequence,
@@ -36,15 +34,15 @@
 //                   comes out bit-for-bit symmetric.  Leaves at once when the verdict is not 0.
 // Row and column 11 of Sigma are zero, so B's row 11, Y's and gamma's entry 11 are exact zeros and the pad stays zero.  Nothing is shared
 // between filters and every sum runs in one fixed order: bit for bit the same from run to run and for a filter alone or anywhere in a
-// batch.  No atomics.  Launches per call: 2 + (3 nb - 1) + 4 (the last block column has no trailing tiles), nb = mp / 64.
+// batch.  No atomics.  Launches per call: 2 + (3 nb - 1) + 4 (the factorisation's schedule: the last block column has no trailing
+// tiles), nb = mp / 64.
 #pragma once
 #include "eqf_blocks_host.hpp"
-#include "eqf_chol64.hpp"
 #include "eqf_device.hpp"
+#include "eqf_factor.hpp"
 #include "eqf_linear.hpp"
 #include "eqf_local.hpp"
 #include "eqf_math.hpp"
-#include "eqf_nees.hpp"
 
 namespace eqf {
 
@@ -63,7 +61,7 @@ struct BlkArgs {
     const unsigned char* mask;  // [B]
     const double* jac;    // k_local_jacobian's records, or nullptr (local = 0)
     int cap, rows, stride;
-    int mp, nb;           // order of S padded to 64 (= M's leading dimension), its block columns
+    int mp, nb;           // order of S padded to 64 (= M's leading dimension), its block columns (nb: the host's, no kernel reads it)
     double gate, lmGate;
     double* ws;           // [B][wsStride]: M | Ht [stride][9] | gamma [ld] | D [kDRec]   (blocks::WorkLayout)
     long long wsStride, offHt, offGamma, offD;
@@ -81,6 +79,11 @@ EQF_DI int* blkPos(const BlkArgs& a, int b) { return a.wi + (long long)b * a.wiS
 EQF_DI int* blkEnt(const BlkArgs& a, int b) { return a.wi + (long long)b * a.wiStride + 2 * a.stride; }
 EQF_DI int* blkCount(const BlkArgs& a, int b) { return a.wi + (long long)b * a.wiStride + 3 * a.stride; }
 EQF_DI int blkOrder(const BlkArgs& a, int b) { return a.rows * *blkCount(a, b); }
+EQF_DI FactorView factorView(const BlkArgs& a, int b) {
+    double* M = blkM(a, b);
+    const int m = a.out[(long long)b * kLinHead + 3] != 0.0 ? 0 : blkOrder(a, b);
+    return FactorView{M, a.mp, m, -1, blkD(a, b), blkCount(a, b) + 1, M + (long long)a.mp * a.mp, a.mp, kLm0 + 3 * a.g[b].N + 1};
+}
 // Sigma(r, c) by the lower triangle
 EQF_DI double blkSym(const double* S, int ld, int r, int c) { return r >= c ? S[(long long)r * ld + c] : S[(long long)c * ld + r]; }
 
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(256) void k_blk_rows(BlkArgs a) {
         out[2] = 0.0;
         out[3] = (double)info;
         blkCount(a, b)[0] = 0;
-        blkCount(a, b)[1] = 0;  // (the pivot word of k_blk_diag)
+        blkCount(a, b)[1] = 0;  // (the pivot word of k_factor_diag)
         blkCount(a, b)[2] = 0;  // (the non-finite word of k_blk_gamma)
         sInfo = info;
     }
@@ -189,114 +192,6 @@ __global__ __launch_bounds__(256) void k_blk_gain(BlkArgs a, int nIB, int nPT) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) s = fma(Ht[3 * r + j], tv[j], s);
             M[(long long)(rows * p + r) * mp + rows * q + r2] = s;
-        }
-    }
-}
-
-// Block row R (>= 0) of the tall matrix of a filter of order m (of S) and n (of the state): its first row and how many rows it holds
-// (0: none).  R < nb: rows of S; R >= nb: rows of the right-hand side (B, then the residual).
-EQF_DI int blkBlockRows(int R, int nb, int mp, int m, int n, int* r0) {
-    if (R < nb) {
-        *r0 = kSB * R;
-        return max(0, min(kSB, m - kSB * R));
-    }
-    const int q0 = kSB * (R - nb);
-    *r0 = mp + q0;
-    return max(0, min(kSB, n + 1 - q0));
-}
-
-// grid = (1, B), block = 256, LDS = kLdsFactorBytes
-__global__ __launch_bounds__(256) void k_blk_diag(BlkArgs a, int K) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smemBk[];
-    const Lds64 s = ldsFactor(smemBk);
-    const int b = blockIdx.y, tid = threadIdx.x;
-    if (a.out[(long long)b * kLinHead + 3] != 0.0) return;
-    const int m = blkOrder(a, b), c0 = kSB * K;
-    if (c0 >= m) return;
-    double* M = blkM(a, b);
-    for (int e = tid; e < kSB * kSB; e += 256) {
-        const int r = e >> 6, c = e & 63, gr = c0 + r, gc = c0 + c;
-        double v = r == c ? 1.0 : 0.0;
-        if (gr < m && c <= r) v = M[(long long)gr * a.mp + gc];
-        s.L[r][c] = v;
-    }
-    __syncthreads();
-    factorPrologue(s, tid);
-    __syncthreads();
-    int bad = 0;
-    factor64(s, tid, &bad, blkD(a, b), nullptr, realStages(m, c0));
-    __syncthreads();
-    for (int e = tid; e < kSB * kSB; e += 256) {
-        const int r = e >> 6, c = e & 63, gr = c0 + r, gc = c0 + c;
-        if (gr < m && c <= r) M[(long long)gr * a.mp + gc] = s.L[r][c];
-    }
-    if (bad && tid == 0) blkCount(a, b)[1] = 1;
-}
-
-// grid = (nbTot - K - 1, B) with nbTot = nb + blocks::rhsBlocks(order of the largest filter), block = 256, LDS = kNeesPanelLdsBytes
-__global__ __launch_bounds__(256) void k_blk_panel(BlkArgs a, int K) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smemBk[];
-    const Lds64 s = ldsNeesPanel(smemBk);
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (a.out[(long long)b * kLinHead + 3] != 0.0) return;
-    const int m = blkOrder(a, b), n = kLm0 + 3 * a.g[b].N, c0 = kSB * K, mp = a.mp;
-    if (c0 >= m) return;
-    int r0;
-    const int rows = blkBlockRows(K + 1 + (int)blockIdx.x, a.nb, mp, m, n, &r0);
-    if (rows <= 0) return;
-    double* Mr = blkM(a, b) + (long long)r0 * mp;
-    const double* Dk = blkD(a, b);
-    for (int e = tid; e < kSB * kSB; e += 256) {
-        const int r = e >> 6, c = e & 63, gc = c0 + c;
-        s.P[r][c] = (r < rows && gc < m) ? Mr[(long long)r * mp + gc] : 0.0;
-        s.L[r][c] = Dk[e];
-    }
-    for (int e = tid; e < 4 * kQB * kQB; e += 256) s.Wd[e >> 8][(e >> 4) & 15][e & 15] = Dk[kSB * kSB + e];
-    __syncthreads();
-    if (kQB * wv < rows) solveStrip<true>(&s.P[0][0], kSP, s, kQB * wv, lane);
-    __syncthreads();
-    for (int e = tid; e < kSB * kSB; e += 256) {
-        const int r = e >> 6, c = e & 63, gc = c0 + c;
-        if (r < rows && gc < m) Mr[(long long)r * mp + gc] = s.P[r][c];
-    }
-}
-
-// grid = ((nbTot - K - 1) (nb - K - 1), B), block = 256, LDS = kNeesTrailLdsBytes: workgroup x is tile (R, C) = (K + 1 + x / t, K + 1 + x % t),
-// t = nb - K - 1; the tiles R < C leave at once
-__global__ __launch_bounds__(256) void k_blk_trail(BlkArgs a, int K) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smemBk[];
-    double (*sP)[kSP] = reinterpret_cast<double (*)[kSP]>(smemBk);
-    double (*sQ)[kSP] = sP + kSB;
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (a.out[(long long)b * kLinHead + 3] != 0.0) return;
-    const int m = blkOrder(a, b), n = kLm0 + 3 * a.g[b].N, c0 = kSB * K, mp = a.mp, t = a.nb - K - 1;
-    const int R = K + 1 + (int)blockIdx.x / t, C = K + 1 + (int)blockIdx.x % t, C0 = kSB * C;
-    if (R < C || C0 >= m) return;
-    int r0;
-    const int rows = blkBlockRows(R, a.nb, mp, m, n, &r0);
-    if (rows <= 0) return;
-    const bool tri = R < a.nb;  // (a tile of S: the lower triangle only)
-    double* M = blkM(a, b);
-    double* Mr = M + (long long)r0 * mp;
-    for (int e = tid; e < kSB * kSB; e += 256) {
-        const int rr = e >> 6, cc = e & 63, gc = c0 + cc, gq = C0 + rr;  // (gc < m: block column K is a full one, block column C lies behind it)
-        sP[rr][cc] = rr < rows ? Mr[(long long)rr * mp + gc] : 0.0;
-        sQ[rr][cc] = gq < m ? M[(long long)gq * mp + gc] : 0.0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f64x4 acc;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int rr = kQB * wv + (lane >> 4) + 4 * q, gc = C0 + kQB * i + (lane & 15);
-            acc[q] = (rr < rows && gc < m && (!tri || gc <= r0 + rr)) ? Mr[(long long)rr * mp + gc] : 0.0;
-        }
-        acc = mmTile<true, kSB>(acc, &sP[0][0], kSP, kQB * wv, &sQ[0][0], kSP, kQB * i, lane, -1.0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int rr = kQB * wv + (lane >> 4) + 4 * q, gc = C0 + kQB * i + (lane & 15);
-            if (rr < rows && gc < m && (!tri || gc <= r0 + rr)) Mr[(long long)rr * mp + gc] = acc[q];
         }
     }
 }

@@ -24,6 +24,7 @@
 #include "eqf_i8.hpp"
 #include "eqf_local.hpp"
 #include "eqf_innov.hpp"
+#include "eqf_factor.hpp"
 #include "eqf_nees.hpp"
 #include "eqf_clone.hpp"
 #include "eqf_frame.hpp"
@@ -1655,6 +1656,29 @@ void freeAll(eqf_filter* f) {
     delete f;
 }
 
+// ---- the blocked factorisation (eqf_factor.hpp): the one launch loop of every route that factors
+// Enqueues A = L L^T of `images` images (grid.y) of order at most mMax each (nb block columns: the one place on the host where an order
+// becomes a block-column count for a launch of these kernels), with rhsRows block rows of right-hand side carried along: diag(0) always (it clears the pivot word, also for an empty matrix), then per block column the diagonal block, the panel if a
+// block row lies below and the trailing tiles if a block column lies behind.  ldsSet: the handle's flag for the dynamic-LDS attributes
+// of this instantiation.
+template <class Args>
+int enqueueFactor(hipStream_t stream, bool& ldsSet, const Args& a, int images, int mMax, int rhsRows) {
+    const int nb = mMax <= 0 ? 0 : (mMax + kSB - 1) / kSB;
+    if (!ldsSet) {  // (dynamic LDS beyond 64 KB: see allowUpdateLds)
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_factor_panel<Args>), hipFuncAttributeMaxDynamicSharedMemorySize, kFactorPanelLdsBytes));
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_factor_trail<Args>), hipFuncAttributeMaxDynamicSharedMemorySize, kFactorTrailLdsBytes));
+        ldsSet = true;
+    }
+    hipLaunchKernelGGL(k_factor_diag<Args>, dim3(1, images), dim3(256), kLdsFactorBytes, stream, a, 0);
+    for (int K = 0; K < nb; ++K) {
+        const int t = nb - K - 1;
+        if (K > 0) hipLaunchKernelGGL(k_factor_diag<Args>, dim3(1, images), dim3(256), kLdsFactorBytes, stream, a, K);
+        if (t + rhsRows > 0) hipLaunchKernelGGL(k_factor_panel<Args>, dim3(t + rhsRows, images), dim3(256), kFactorPanelLdsBytes, stream, a, K, t);
+        if (t > 0) hipLaunchKernelGGL(k_factor_trail<Args>, dim3(t * (t + 1) / 2 + rhsRows * t, images), dim3(256), kFactorTrailLdsBytes, stream, a, K, t);
+    }
+    return EQF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2967,6 +2991,38 @@ static int neesAlloc(eqf_filter* f) {
     return EQF_OK;
 }
 
+// A = L L^T of every filter's submatrix from internal index off, in place in the scratch image -- Sigma_loc (k_sigma_local) or a copy of
+// Sigma --, the nrhs error vectors that lie in dNeesE carried along, and k_nees_tail's report in dNeesOut: what eqf_get_nees and the draws
+// (nrhs = 0) share.  Enqueues; the buffers are there (neesAlloc).
+static int neesFactor(eqf_filter* f, int local, int off, int nrhs) {
+    const int B = f->B, mMax = kLm0 + 3 * maxN(f) - off;
+    int rc = EQF_OK;
+    if (local) {
+        rc = launchLocal(f, 0, B, true);
+        if (rc) return rc;
+    } else {
+        HIPC(hipMemcpyAsync(f->dSigmaLoc, f->Sigma[f->pS], sizeof(double) * size_t(f->sigmaStride) * B, hipMemcpyDeviceToDevice, f->stream));
+    }
+    NeesArgs a{};
+    a.g = f->g[f->pG]; a.A = f->dSigmaLoc; a.ld = f->ld; a.strideA = f->sigmaStride; a.E = f->dNeesE; a.ldE = std::max(mMax, 1); a.D = f->dNeesD;
+    a.bad = f->dNeesBad; a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.off = off; a.nrhs = nrhs; a.out = f->dNeesOut;
+    rc = enqueueFactor(f->stream, f->neesLdsSet, a, B, mMax, nrhs > 0 ? 1 : 0);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_nees_tail, dim3(B), dim3(256), 0, f->stream, a);
+    HIPC(hipGetLastError());
+    return EQF_OK;
+}
+// k_nees_tail's records [B][kNeesHead + kNeesRhs] -> the caller's
+static void neesStats(const double* hO, int B, eqf_sigma_stats* stats) {
+    for (int b = 0; b < B; ++b) {
+        const double* o = hO + size_t(b) * (kNeesHead + kNeesRhs);
+        stats[b].logdet = o[0];
+        stats[b].min_pivot = o[1];
+        stats[b].dof = int(o[2]);
+        stats[b].info = int(o[3]);
+    }
+}
+
 int eqf_get_nees(eqf_filter* f, int local, int first, int nrhs, const double* err, int lde, double* nees, eqf_sigma_stats* stats) {
     if (!f || !stats || (local != 0 && local != 1) || (first != 0 && first != 6 && first != kBase) || nrhs < 0 || nrhs > kNeesRhs)
         return EQF_ERR_INVALID;
@@ -2977,20 +3033,7 @@ int eqf_get_nees(eqf_filter* f, int local, int first, int nrhs, const double* er
     if (nrhs > 0 && lde < kBase + 3 * nMax) return EQF_ERR_INVALID;
     int rc = neesAlloc(f);
     if (rc) return rc;
-    if (!f->neesLdsSet) {  // (dynamic LDS beyond 64 KB: see allowUpdateLds)
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nees_panel), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesPanelLdsBytes));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nees_trail), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesTrailLdsBytes));
-        f->neesLdsSet = true;
-    }
-    const int off = first == kBase ? kLm0 : first;
-    const int mMax = kLm0 + 3 * nMax - off, nb = (mMax + kSB - 1) / kSB, ldE = std::max(mMax, 1);
-    // the image that is factored in place: Sigma_loc (k_sigma_local) or a copy of Sigma
-    if (local) {
-        rc = launchLocal(f, 0, B, true);
-        if (rc) return rc;
-    } else {
-        HIPC(hipMemcpyAsync(f->dSigmaLoc, f->Sigma[f->pS], sizeof(double) * size_t(f->sigmaStride) * B, hipMemcpyDeviceToDevice, f->stream));
-    }
+    const int off = first == kBase ? kLm0 : first, ldE = std::max(kLm0 + 3 * nMax - off, 1);
     // the error vectors in the submatrix' own (padded) index map: entry i of the reference -> column (i < 11 ? i : i + 1) - off
     std::vector<double> hE;
     if (nrhs > 0) {
@@ -3005,30 +3048,14 @@ int eqf_get_nees(eqf_filter* f, int local, int first, int nrhs, const double* er
         }
         HIPC(hipMemcpyAsync(f->dNeesE, hE.data(), sizeof(double) * hE.size(), hipMemcpyHostToDevice, f->stream));
     }
-    NeesArgs a{};
-    a.g = f->g[f->pG]; a.A = f->dSigmaLoc; a.ld = f->ld; a.strideA = f->sigmaStride; a.E = f->dNeesE; a.ldE = ldE; a.D = f->dNeesD;
-    a.bad = f->dNeesBad; a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.off = off; a.nrhs = nrhs; a.out = f->dNeesOut;
-    const int rhsWg = nrhs > 0 ? 1 : 0;
-    hipLaunchKernelGGL(k_nees_diag, dim3(1, B), dim3(256), kLdsFactorBytes, f->stream, a, 0);  // (also for an empty submatrix: the pivot word)
-    for (int K = 0; K < nb; ++K) {
-        const int t = nb - K - 1;
-        if (K > 0) hipLaunchKernelGGL(k_nees_diag, dim3(1, B), dim3(256), kLdsFactorBytes, f->stream, a, K);
-        if (t + rhsWg > 0) hipLaunchKernelGGL(k_nees_panel, dim3(t + rhsWg, B), dim3(256), kNeesPanelLdsBytes, f->stream, a, K, t);
-        if (t > 0) hipLaunchKernelGGL(k_nees_trail, dim3(t * (t + 1) / 2 + rhsWg * t, B), dim3(256), kNeesTrailLdsBytes, f->stream, a, K, t);
-    }
-    hipLaunchKernelGGL(k_nees_tail, dim3(B), dim3(256), 0, f->stream, a);
-    HIPC(hipGetLastError());
+    rc = neesFactor(f, local, off, nrhs);
+    if (rc) return rc;
     std::vector<double> hO(size_t(B) * (kNeesHead + kNeesRhs));
     HIPC(hipMemcpyAsync(hO.data(), f->dNeesOut, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
     HIPC(hipStreamSynchronize(f->stream));
-    for (int b = 0; b < B; ++b) {
-        const double* o = hO.data() + size_t(b) * (kNeesHead + kNeesRhs);
-        stats[b].logdet = o[0];
-        stats[b].min_pivot = o[1];
-        stats[b].dof = int(o[2]);
-        stats[b].info = int(o[3]);
-        for (int k = 0; k < nrhs; ++k) nees[size_t(b) * nrhs + k] = o[kNeesHead + k];
-    }
+    neesStats(hO.data(), B, stats);
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < nrhs; ++k) nees[size_t(b) * nrhs + k] = hO[size_t(b) * (kNeesHead + kNeesRhs) + kNeesHead + k];
     return EQF_OK;
 }
 
@@ -3079,37 +3106,7 @@ int sampRowsAlloc(eqf_filter* f, int rows) {
     f->sampRows = rows;
     return EQF_OK;
 }
-// A = L L^T of every filter's submatrix from internal index off, in place in the scratch image, and the report in dNeesOut: eqf_get_nees's
-// launches without error vectors.  Enqueues; the buffers are there (neesAlloc).
-int sampFactor(eqf_filter* f, int local, int off) {
-    const int B = f->B, nMax = maxN(f);
-    if (!f->neesLdsSet) {  // (dynamic LDS beyond 64 KB: see allowUpdateLds)
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nees_panel), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesPanelLdsBytes));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nees_trail), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesTrailLdsBytes));
-        f->neesLdsSet = true;
-    }
-    const int mMax = sample::paddedOrder(nMax, off), nb = sample::blockColumns(mMax);
-    if (local) {
-        int rc = launchLocal(f, 0, B, true);
-        if (rc) return rc;
-    } else {
-        HIPC(hipMemcpyAsync(f->dSigmaLoc, f->Sigma[f->pS], sizeof(double) * size_t(f->sigmaStride) * B, hipMemcpyDeviceToDevice, f->stream));
-    }
-    NeesArgs a{};
-    a.g = f->g[f->pG]; a.A = f->dSigmaLoc; a.ld = f->ld; a.strideA = f->sigmaStride; a.E = f->dNeesE; a.ldE = std::max(mMax, 1); a.D = f->dNeesD;
-    a.bad = f->dNeesBad; a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.off = off; a.nrhs = 0; a.out = f->dNeesOut;
-    hipLaunchKernelGGL(k_nees_diag, dim3(1, B), dim3(256), kLdsFactorBytes, f->stream, a, 0);
-    for (int K = 0; K < nb; ++K) {
-        const int t = nb - K - 1;
-        if (K > 0) hipLaunchKernelGGL(k_nees_diag, dim3(1, B), dim3(256), kLdsFactorBytes, f->stream, a, K);
-        if (t > 0) hipLaunchKernelGGL(k_nees_panel, dim3(t, B), dim3(256), kNeesPanelLdsBytes, f->stream, a, K, t);
-        if (t > 0) hipLaunchKernelGGL(k_nees_trail, dim3(t * (t + 1) / 2, B), dim3(256), kNeesTrailLdsBytes, f->stream, a, K, t);
-    }
-    hipLaunchKernelGGL(k_nees_tail, dim3(B), dim3(256), 0, f->stream, a);
-    HIPC(hipGetLastError());
-    return EQF_OK;
-}
-// E = scale Z L^T behind sampFactor (nsamp >= 1 rows per filter in dSampZ -> dSampE, row pitch ldE)
+// E = scale Z L^T behind neesFactor (nsamp >= 1 rows per filter in dSampZ -> dSampE, row pitch ldE)
 void sampTrmm(eqf_filter* f, int off, int nsamp, int ldE, const double* dScale) {
     const int mMax = sample::paddedOrder(maxN(f), off);
     if (mMax <= 0) return;
@@ -3117,15 +3114,6 @@ void sampTrmm(eqf_filter* f, int off, int nsamp, int ldE, const double* dScale) 
     s.g = f->g[f->pG]; s.A = f->dSigmaLoc; s.ld = f->ld; s.strideA = f->sigmaStride; s.Z = f->dSampZ; s.E = f->dSampE; s.ldE = ldE;
     s.nsamp = nsamp; s.scale = dScale; s.off = off;
     hipLaunchKernelGGL(k_sample_trmm, dim3(sample::blockColumns(mMax), sample::rowTiles(nsamp), f->B), dim3(256), kSampleLdsBytes, f->stream, s);
-}
-void sampStats(const double* hO, int B, eqf_sigma_stats* stats) {
-    for (int b = 0; b < B; ++b) {
-        const double* o = hO + size_t(b) * (kNeesHead + kNeesRhs);
-        stats[b].logdet = o[0];
-        stats[b].min_pivot = o[1];
-        stats[b].dof = int(o[2]);
-        stats[b].info = int(o[3]);
-    }
 }
 }  // namespace
 
@@ -3143,7 +3131,7 @@ int eqf_sample_sigma(eqf_filter* f, int local, int first, int nsamp, const doubl
     if (!rc && scale) rc = sampSmallAlloc(f);
     if (rc) return rc;
     const int off = sample::cutOffset(first), ldE = std::max(sample::paddedOrder(nMax, off), 1);
-    rc = sampFactor(f, local, off);
+    rc = neesFactor(f, local, off, 0);
     if (rc) return rc;
     std::vector<double> hZ;
     if (nsamp > 0) {
@@ -3167,7 +3155,7 @@ int eqf_sample_sigma(eqf_filter* f, int local, int first, int nsamp, const doubl
     std::vector<double> hO(size_t(B) * (kNeesHead + kNeesRhs));
     HIPC(hipMemcpyAsync(hO.data(), f->dNeesOut, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
     HIPC(hipStreamSynchronize(f->stream));
-    if (stats) sampStats(hO.data(), B, stats);
+    if (stats) neesStats(hO.data(), B, stats);
     const double nan = std::nan("");
     for (int b = 0; b < B; ++b) {
         const bool bad = hO[size_t(b) * (kNeesHead + kNeesRhs) + 3] != 0.0;
@@ -3215,7 +3203,7 @@ int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, cons
     if (!rc) rc = sampSmallAlloc(f);
     if (rc) return rc;
     const int off = sample::cutOffset(first), ldE = std::max(sample::paddedOrder(nMax, off), 1);
-    rc = sampFactor(f, 0, off);
+    rc = neesFactor(f, 0, off, 0);
     if (rc) return rc;
     HIPC(hipEventSynchronize(f->evSamp));
     SampSmall h = sampCarve(f, f->hSampSmall), d = sampCarve(f, f->dSampSmall);
@@ -3240,7 +3228,7 @@ int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, cons
     std::vector<double> hO(size_t(B) * (kNeesHead + kNeesRhs));
     HIPC(hipMemcpyAsync(hO.data(), f->dNeesOut, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
     HIPC(hipStreamSynchronize(f->stream));
-    sampStats(hO.data(), B, stats);
+    neesStats(hO.data(), B, stats);
     return EQF_OK;
 }
 
@@ -3425,12 +3413,8 @@ int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, cons
     const blocks::WorkLayout wl{f->ld, stride, rows, kDRec};
     int rc = blkAlloc(f, sl, wl);
     if (rc) return rc;
-    if (!f->blkLdsSet) {  // (dynamic LDS beyond 64 KB: see allowUpdateLds)
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_blk_panel), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesPanelLdsBytes));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_blk_trail), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesTrailLdsBytes));
+    if (!f->blkLdsSet)  // (dynamic LDS beyond 64 KB: see allowUpdateLds; enqueueFactor sets its own kernels' and the flag)
         HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_blk_downdate), hipFuncAttributeMaxDynamicSharedMemorySize, kBlkDownLdsBytes));
-        f->blkLdsSet = true;
-    }
     if (local) {
         rc = launchLocal(f, 0, B, false);  // (only writes the J records)
         if (rc) return rc;
@@ -3452,25 +3436,21 @@ int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, cons
     }
     HIPC(hipMemcpyAsync(f->dBlkSmall, f->hBlkSmall, sl.bytes(), hipMemcpyHostToDevice, f->stream));
     HIPC(hipEventRecord(f->evBlk, f->stream));
-    const int nMax = maxN(f), nt = blocks::rowTiles(nMax), nb = wl.nb(), nbTot = nb + blocks::rhsBlocks(blocks::paddedOrder(nMax));
+    const int nMax = maxN(f), nt = blocks::rowTiles(nMax);
     const int nPT = blocks::pairTiles(stride);
     BlkArgs a{};
     a.g = f->g[f->pG]; a.Sigma = static_cast<double*>(f->Sigma[f->pS]); a.ld = f->ld; a.sigmaStride = f->sigmaStride;
     a.Hb = reinterpret_cast<const double*>(f->dBlkSmall + sl.offH()); a.resid = reinterpret_cast<const double*>(f->dBlkSmall + sl.offResid());
     a.Rb = reinterpret_cast<const double*>(f->dBlkSmall + sl.offR()); a.idx = reinterpret_cast<const int*>(f->dBlkSmall + sl.offIdx());
     a.nk = reinterpret_cast<const int*>(f->dBlkSmall + sl.offNk()); a.mask = reinterpret_cast<const unsigned char*>(f->dBlkSmall + sl.offMask());
-    a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.rows = rows; a.stride = stride; a.mp = wl.mp(); a.nb = nb;
+    a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.rows = rows; a.stride = stride; a.mp = wl.mp(); a.nb = wl.nb();
     a.gate = gate; a.lmGate = lm_gate;
     a.ws = f->dBlkWs; a.wsStride = wl.strideD(); a.offHt = wl.offHt(); a.offGamma = wl.offGamma(); a.offD = wl.offD();
     a.wi = f->dBlkWi; a.wiStride = wl.strideI(); a.out = f->dBlkOut;
     hipLaunchKernelGGL(k_blk_rows, dim3(B), dim3(256), 0, f->stream, a);
     hipLaunchKernelGGL(k_blk_gain, dim3(nt + nPT * nPT, B), dim3(256), 0, f->stream, a, nt, nPT);
-    for (int K = 0; K < nb; ++K) {
-        hipLaunchKernelGGL(k_blk_diag, dim3(1, B), dim3(256), kLdsFactorBytes, f->stream, a, K);
-        hipLaunchKernelGGL(k_blk_panel, dim3(nbTot - K - 1, B), dim3(256), kNeesPanelLdsBytes, f->stream, a, K);
-        if (nb - K - 1 > 0)
-            hipLaunchKernelGGL(k_blk_trail, dim3((nbTot - K - 1) * (nb - K - 1), B), dim3(256), kNeesTrailLdsBytes, f->stream, a, K);
-    }
+    rc = enqueueFactor(f->stream, f->blkLdsSet, a, B, wl.mp(), blocks::rhsBlocks(blocks::paddedOrder(nMax)));
+    if (rc) return rc;
     hipLaunchKernelGGL(k_blk_gamma, dim3(nt, B), dim3(64), 0, f->stream, a);
     hipLaunchKernelGGL(k_blk_tail, dim3(B), dim3(256), 0, f->stream, a);
     hipLaunchKernelGGL(k_blk_downdate, dim3(blocks::triTiles(nt), B), dim3(256), kBlkDownLdsBytes, f->stream, a);
@@ -3789,11 +3769,6 @@ int eqf_get_merge_costs(eqf_filter* f, int n, const int* idx, const double* w, i
     const int chunk = mergecost::chunkSize(f->mcChunkOpt, f->B);
     rc = mcAlloc(f, chunk, items.size());
     if (rc) return rc;
-    if (!f->neesLdsSet) {  // (dynamic LDS beyond 64 KB: see allowUpdateLds)
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nees_panel), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesPanelLdsBytes));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nees_trail), hipFuncAttributeMaxDynamicSharedMemorySize, kNeesTrailLdsBytes));
-        f->neesLdsSet = true;
-    }
     // e_b, J'_b and Sigma'_b of every distinct member about c = xHat_ref
     const int launchesBefore = f->mixLaunches;  // (eqf_debug_mixture_launches keeps answering for the most recent MIXTURE call)
     MixArgs a;
@@ -3810,7 +3785,7 @@ int eqf_get_merge_costs(eqf_filter* f, int n, const int* idx, const double* w, i
         hipLaunchKernelGGL(k_sigma_local, dim3(strips, std::max(1, (N + kLocalRows - 1) / kLocalRows), 1), dim3(256), 0, f->stream, la);
     }
     HIPC(hipGetLastError());
-    const int off = mergecost::offsetOf(first), m = mergecost::paddedOrder(N, off), nb = mergecost::blockColumns(m);
+    const int off = mergecost::offsetOf(first), m = mergecost::paddedOrder(N, off);
     const McWs ws = mcCarve(f, f->dMcWs, f->mcChunkCap);
     PairItem* dItems = reinterpret_cast<PairItem*>(f->dMcItems);
     double* dRec = reinterpret_cast<double*>(f->dMcItems + sizeof(PairItem) * f->mcItemCap);
@@ -3829,13 +3804,8 @@ int eqf_get_merge_costs(eqf_filter* f, int n, const int* idx, const double* w, i
             pa.item0 = int(seg0[s] + (long long)ch * chunk);
             pa.count = cnt;
             hipLaunchKernelGGL(k_pair_form, dim3(kLm0 + 3 * N + 1, cnt), dim3(256), 0, f->stream, pa);
-            hipLaunchKernelGGL(k_nees_diag, dim3(1, cnt), dim3(256), kLdsFactorBytes, f->stream, na, 0);
-            for (int K = 0; K < nb; ++K) {
-                const int t = nb - K - 1;
-                if (K > 0) hipLaunchKernelGGL(k_nees_diag, dim3(1, cnt), dim3(256), kLdsFactorBytes, f->stream, na, K);
-                hipLaunchKernelGGL(k_nees_panel, dim3(t + 1, cnt), dim3(256), kNeesPanelLdsBytes, f->stream, na, K, t);
-                if (t > 0) hipLaunchKernelGGL(k_nees_trail, dim3(t * (t + 1) / 2 + t, cnt), dim3(256), kNeesTrailLdsBytes, f->stream, na, K, t);
-            }
+            rc = enqueueFactor(f->stream, f->neesLdsSet, na, cnt, m, 1);
+            if (rc) return rc;
             hipLaunchKernelGGL(k_nees_tail, dim3(cnt), dim3(256), 0, f->stream, na);
             hipLaunchKernelGGL(k_pair_tail, dim3((cnt + 255) / 256), dim3(256), 0, f->stream, pa);
         }

@@ -13,10 +13,11 @@
 //                 image: one writer per entry, only the lower triangle (row >= column) is written, as only it is read.  A self item is a
 //                 plain copy.  The structural pad row 11 is written as a row of the identity.  The extra workgroup writes d in the padded
 //                 index map of the submatrix into the item's right-hand-side row, and the item's landmark count.
-//   k_nees_diag / k_nees_panel / k_nees_trail / k_nees_tail (eqf_nees.hpp), UNCHANGED: the blocked fp64 Cholesky on the matrix cores with
-//                 the right-hand side carried along, the images of the chunk in grid.y.  They take an image's order from Glob[b].N: the
-//                 workspace carries one Glob per image of which only N is ever written or read.  Members and pairs go through the same
-//                 kernels, so identical inputs give identical bits: a pair of bit-identical members has ld_ij == ld_i, maha == 0, cost == 0.
+//   the factorisation (eqf_factor.hpp: k_factor_diag / _panel / _trail<NeesArgs>) and k_nees_tail (eqf_nees.hpp), as eqf_get_nees runs
+//                 them: the blocked fp64 Cholesky on the matrix cores with the right-hand side carried along, the images of the chunk in
+//                 grid.y.  eqf_nees.hpp's factorView takes an image's order from Glob[b].N: the workspace carries one Glob per image of
+//                 which only N is ever written or read.  Members and pairs go through the same kernels, so identical inputs give
+//                 identical bits: a pair of bit-identical members has ld_ij == ld_i, maha == 0, cost == 0.
 //   k_pair_tail   one lane per item of the chunk: the info word (-1 if a chart either member needs is singular, else k_nees_tail's), log1p,
 //                 the cost (eqf_mergecost_host.hpp's text) from the item's record and the two members' records, which earlier launches
 //                 have written: the member items come first, in chunks of their own.

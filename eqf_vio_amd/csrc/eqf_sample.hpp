@@ -1,11 +1,11 @@
 // Draws from a filter's covariance and the group step that moves a filter by one (eqf_sample_sigma, eqf_apply_increment,
 // eqf_perturb_filters).
 //
-// eqf_nees.hpp's launches with nrhs = 0 leave A = L L^T of a trailing principal submatrix of Sigma or Sigma_loc in the lower triangle of the
+// eqf_get_nees's launches with nrhs = 0 (eqf_factor.hpp, k_nees_tail) leave A = L L^T of a trailing principal submatrix of Sigma or Sigma_loc in the lower triangle of the
 // scratch image (padded layout of eqf_device.hpp, the structural pad index 11 a row of the identity).  Two kernels are added:
 //   k_sample_trmm      E = Z L^T, sixteen samples (one MFMA tile of rows) per workgroup and 64-wide block column C of the result:
 //                        E[:, C] = sum_{K <= C} Z[:, K] L[C, K]^T,   K ascending,
-//                      each term a 16 x 64 x 64 product on v_mfma_f64_16x16x4_f64 (mmTile: the error-vector branch of k_nees_trail with the
+//                      each term a 16 x 64 x 64 product on v_mfma_f64_16x16x4_f64 (mmTile: the short-block-row branch of k_factor_trail with the
 //                      sign turned).  The workgroup walks block row C of L, whose rows are contiguous, once; the diagonal block contributes
 //                      its lower triangle only.  Rows of Z and E are in the submatrix' own padded index map (column = internal index - off),
 //                      which is the host's to build (eqf_sample_host.hpp).  The sum over K and the k-steps of an MFMA run in one fixed order

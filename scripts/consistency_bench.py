@@ -12,8 +12,8 @@
                    (a) FilterBatch.nees (one call, ends in a synchronise), (b) the host route it replaces, sigma_local(b) for every b +
                    consistency.nees_joint.  Both warmed up, alternated over 20 repetitions; prints one JSON line with medians, min / max.
   neeskern B N     a workload for `rocprofv3 --kernel-trace --stats -- python scripts/consistency_bench.py neeskern B N`: ten nees calls.
-  neessum DIR      kernel-trace stats CSVs under DIR/neeskern_B_N -> summed time of the k_nees_* kernels per call against B n^3 / 3 flops at
-                   the fp64 matrix peak (78.6 Tflop/s).
+  neessum DIR      kernel-trace stats CSVs under DIR/neeskern_B_N -> summed time of the factorisation's kernels (k_factor_*<NeesArgs>) and
+                   k_nees_tail per call against B n^3 / 3 flops at the fp64 matrix peak (78.6 Tflop/s).
   summarize DIR    kernel-trace stats CSVs under DIR -> the table of the `kernels` legs (achieved bytes/s, ratio).
   copy B N         DESIGN.md section 4.5d: FilterBatch.copy_filters (ends in a synchronise of both handles here) against the host route it
                    replaces, dump_state + restore_state for every filter, on the same states after three frames; once for a whole-handle copy
@@ -47,9 +47,9 @@
                    over 20 repetitions; prints one JSON line with medians, min / max, the ratio and whether the spreads overlap.  No
                    threshold is asserted.
   blockskern B N K a workload for `rocprofv3 --kernel-trace --stats -- python scripts/consistency_bench.py blockskern B N K`: thirty updates.
-  blockssum DIR    kernel-trace stats CSVs under DIR/blockskern_B_N_K -> the k_blk_* kernels; k_blk_downdate as (2 T_lower + T_mirror) *
-                   64^2 * 8 * B bytes of Sigma (read and write of the lower-triangle tiles, write of the mirror tiles) plus 2 * 64 * m * 8
-                   bytes of Y per tile, over its average time, against the measured 6.29 TB/s.
+  blockssum DIR    kernel-trace stats CSVs under DIR/blockskern_B_N_K -> the k_blk_* kernels and the factorisation's (k_factor_*<BlkArgs>);
+                   k_blk_downdate as (2 T_lower + T_mirror) * 64^2 * 8 * B bytes of Sigma (read and write of the lower-triangle tiles, write
+                   of the mirror tiles) plus 2 * 64 * m * 8 bytes of Y per tile, over its average time, against the measured 6.29 TB/s.
   mixture B N      DESIGN.md section 4.5g: FilterBatch.merge of all B filters into filter 0 (report=True: ends in a synchronise) against
                    the host route it replaces -- sigma_local(b), state_estimate(b) and bias(b) for every member (n^2 doubles over the bus
                    each), the numpy sums of consistency.merge_host's second pass WITHOUT its Jacobians and chart transitions, so the host
@@ -65,6 +65,7 @@ import csv
 import glob
 import json
 import os
+import re
 import sys
 import time
 
@@ -333,7 +334,7 @@ def linearsum(d):
                 if key in name:
                     a, lo, hi = float(r["AverageNs"]) / 1e3, float(r["MinNs"]) / 1e3, float(r["MaxNs"]) / 1e3
                     tail = f"{by[key] / 1e6:10.2f} MB   {by[key] / a / 1e6:6.3f}   {100 * by[key] / a / 1e6 / 6.29:5.1f} %" if key in by else ""
-                    print(f"{B:3d} x {N:<5d} x {m:<2d} {key:18s} {a:9.1f} / {lo:8.1f} / {hi:8.1f} ({r['Calls']:>3s})   {tail}")
+                    print(f"{B:3d} x {N:<5d} x {m:<2d} {key:24s} {a:9.1f} / {lo:8.1f} / {hi:8.1f} ({r['Calls']:>3s})   {tail}")
 
 
 def _blocks_setup(B, N, K):
@@ -400,6 +401,18 @@ def blockskern(B, N, K):
     print(f"blockskern B={B} N={N} K={K}: done")
 
 
+def kernel_name(raw):
+    """A traced kernel's name without return type, namespaces and argument list; an instantiation keeps its argument type, which tells the
+    routes of the shared factorisation apart: 'void eqf::k_factor_trail<eqf::BlkArgs>(eqf::BlkArgs, int, int)' -> 'k_factor_trail<BlkArgs>'"""
+    head = re.sub(r"\b\w+::", "", raw.split("(")[0]).split()
+    return head[-1] if head else ""
+
+
+# the three kernels of the blocked factorisation by route (csrc/eqf_factor.hpp; a library from before it: the per-route names)
+FACTOR = {"NeesArgs": ("k_factor_diag<NeesArgs>", "k_factor_panel<NeesArgs>", "k_factor_trail<NeesArgs>", "k_nees_diag", "k_nees_panel", "k_nees_trail"),
+          "BlkArgs": ("k_factor_diag<BlkArgs>", "k_factor_panel<BlkArgs>", "k_factor_trail<BlkArgs>", "k_blk_diag", "k_blk_panel", "k_blk_trail")}
+
+
 def blockssum(d):
     print("B x N x K      kernel            avg / min / max us (calls)      bytes        TB/s (avg)   of 6.29")
     for path in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)):
@@ -413,13 +426,13 @@ def blockssum(d):
         tl = nt * (nt + 1) // 2
         by = {"k_blk_downdate": 8.0 * B * (64 * 64 * (2 * tl + nt * (nt - 1) // 2) + 2 * 64 * m * tl)}
         for r in csv.DictReader(open(path)):
-            name = r.get("Name") or r.get("KernelName") or ""
-            for key in ("k_blk_rows", "k_blk_gain", "k_blk_diag", "k_blk_panel", "k_blk_trail", "k_blk_tail", "k_blk_downdate", "k_apply_increment",
-                        "k_local_jacobian"):
-                if key in name:
+            name = kernel_name(r.get("Name") or r.get("KernelName") or "")
+            for key in ("k_blk_rows", "k_blk_gain") + FACTOR["BlkArgs"] + ("k_blk_gamma", "k_blk_tail", "k_blk_downdate", "k_apply_increment",
+                                                                         "k_local_jacobian"):
+                if key == name:
                     a, lo, hi = float(r["AverageNs"]) / 1e3, float(r["MinNs"]) / 1e3, float(r["MaxNs"]) / 1e3
                     tail = f"{by[key] / 1e6:10.2f} MB   {by[key] / a / 1e6:6.3f}   {100 * by[key] / a / 1e6 / 6.29:5.1f} %" if key in by else ""
-                    print(f"{B:3d} x {N:<5d} x {K:<3d} {key:18s} {a:9.1f} / {lo:8.1f} / {hi:8.1f} ({r['Calls']:>3s})   {tail}")
+                    print(f"{B:3d} x {N:<5d} x {K:<3d} {key:24s} {a:9.1f} / {lo:8.1f} / {hi:8.1f} ({r['Calls']:>3s})   {tail}")
 
 
 def neeskern(B, N):
@@ -438,18 +451,18 @@ def neessum(d):
         B, N = int(B), int(N)
         tot, calls, parts = 0.0, 0, []
         for r in csv.DictReader(open(path)):
-            name = r.get("Name") or r.get("KernelName") or ""
-            if "k_nees_" in name:
+            name = kernel_name(r.get("Name") or r.get("KernelName") or "")
+            if name in FACTOR["NeesArgs"] or name == "k_nees_tail":
                 tot += float(r["TotalDurationNs"])
-                parts.append(f"{name.split('(')[0].split('::')[-1]} {float(r['TotalDurationNs']) / 1e3:.0f} us / {r['Calls']}")
-                if "k_nees_tail" in name:
+                parts.append(f"{name} {float(r['TotalDurationNs']) / 1e3:.0f} us / {r['Calls']}")
+                if name == "k_nees_tail":
                     calls = int(r["Calls"])
         if not calls:
             continue
         n = 11 + 3 * N
         us = tot / calls / 1e3
         fl = B * n ** 3 / 3.0
-        print(f"{B:3d} x {N:<5d} k_nees_* {us:10.1f} us per call, {fl / 1e9:8.2f} Gflop -> {fl / us / 1e6:7.2f} Tflop/s = {100 * fl / us / 1e6 / 78.6:5.2f} % of 78.6"
+        print(f"{B:3d} x {N:<5d} factorisation + k_nees_tail {us:10.1f} us per call, {fl / 1e9:8.2f} Gflop -> {fl / us / 1e6:7.2f} Tflop/s = {100 * fl / us / 1e6 / 78.6:5.2f} % of 78.6"
               f"   [{'; '.join(parts)}]")
 
 

@@ -21,6 +21,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from consistency_bench import FACTOR, kernel_name  # noqa: E402  (scripts/: the directory of this file)
 CALLS = 5
 
 
@@ -101,14 +102,14 @@ def summarize(d):
         B, N = int(B), int(N)
         rows = {}
         for r in csv.DictReader(open(path)):
-            name = (r.get("Name") or r.get("KernelName") or "").split("(")[0].split("::")[-1]
+            name = kernel_name(r.get("Name") or r.get("KernelName") or "")
             rows[name] = (float(r["TotalDurationNs"]) / 1e3, int(r["Calls"]))
         m, pairs = 12 + 3 * N, B * (B - 1) // 2
         tri = 8.0 * m * (m + 1) / 2
         by = CALLS * (pairs * 3 * tri + B * 2 * tri)
         fl = CALLS * (pairs + B) * m ** 3 / 3.0
         form = rows.get("k_pair_form", (0.0, 0))
-        fac = [(k, v) for k, v in rows.items() if k.startswith(("k_nees_diag", "k_nees_panel", "k_nees_trail"))]
+        fac = [(k, v) for k, v in rows.items() if k in FACTOR["NeesArgs"]]
         tf = sum(v[0] for _, v in fac)
         print(f"{B} x {N} ({pairs} pairs, order {m}, {CALLS} calls):")
         if form[1]:
@@ -118,7 +119,7 @@ def summarize(d):
             print(f"    factorisation {tf / CALLS:10.1f} us per call in {sum(v[1] for _, v in fac) // CALLS} launches; {fl / CALLS / 1e9:.2f} Gflop -> "
                   f"{fl / tf / 1e6:.2f} TFLOP/s = {100 * fl / tf / 1e6 / 63.5:.1f} % of 63.5")
             for k, v in sorted(fac, key=lambda kv: -kv[1][0]):
-                print(f"        {k:14s} {v[0] / CALLS:10.1f} us per call, {v[1] // CALLS} launches")
+                print(f"        {k:24s} {v[0] / CALLS:10.1f} us per call, {v[1] // CALLS} launches")
         for k in ("k_nees_tail", "k_pair_tail", "k_sigma_local", "k_mix_error", "k_mix_estimate", "k_local_jacobian"):
             if k in rows:
                 print(f"    {k:14s}{rows[k][0] / CALLS:10.1f} us per call, {rows[k][1] / CALLS:.0f} launches")

@@ -159,7 +159,7 @@ NEES_FAULTS = ("dropped trailing tile", "stale pad row", "error vectors miss the
 
 
 def model_nees(A, E, first, fault=None):
-    """k_nees_diag / _panel / _trail / _tail composed in numpy fp64 from chol_bounds.model_chol16 (64-wide block columns, 16-wide stages) and
+    """k_factor_diag / _panel / _trail and k_nees_tail composed in numpy fp64 from chol_bounds.model_chol16 (64-wide block columns, 16-wide stages) and
     model_trsm16 (the explicit inverses W_j), on the PADDED matrix: the pad row is a row of the identity, the error vectors are more rows
     under the panel.  Returns (nees (k,), logdet, min_pivot, the padded factor)."""
     pad = cx.pad_index(first)
