@@ -96,6 +96,26 @@ class PairCost(C.Structure):
 
 COST_KINDS = {"runnalls": 0, "bhattacharyya": 1}
 
+
+class FrameScore(C.Structure):
+    """eqf_frame_score (include/eqf_vio_amd.h)."""
+
+    _fields_ = [("nis", C.c_double), ("logdet_S", C.c_double), ("loglik", C.c_double), ("dof", C.c_int), ("info", C.c_int)]
+
+
+class FrameScores:
+    """What FilterBatch.score_vision returns: nis, logdet_S, loglik, dof, info as arrays (B, ncand) -- and nis_lm, used (B, ncand, stride)
+    when asked for --, by attribute or by key."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def __getitem__(self, key):
+        return self.__dict__[key]
+
+    def keys(self):
+        return self.__dict__.keys()
+
 _lib = None
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -107,7 +127,7 @@ EXPORTED_SYMBOLS = [
     "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_forecast", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
     "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters", "eqf_update_linear", "eqf_update_landmarks",
     "eqf_get_mixture_moments", "eqf_merge_filters", "eqf_debug_mixture_launches", "eqf_debug_sigma_pad",
-    "eqf_get_merge_costs",
+    "eqf_get_merge_costs", "eqf_score_vision",
     "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
     "eqf_set_sigma", "eqf_set_state", "eqf_copy_filters", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
@@ -189,6 +209,9 @@ def lib():
         if hasattr(L, "eqf_get_merge_costs"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
             L.eqf_get_merge_costs.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.POINTER(PairCost),
                                               C.POINTER(SigmaStats)]
+        if hasattr(L, "eqf_score_vision"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
+            L.eqf_score_vision.argtypes = [vp, C.c_int, _ip, _ip, _dp, C.c_int, C.POINTER(C.c_ubyte), C.POINTER(FrameScore), _dp,
+                                           C.POINTER(C.c_ubyte)]
         if hasattr(L, "eqf_set_outlier_gate"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
             L.eqf_set_outlier_gate.argtypes = [vp, C.c_int, C.c_double]
             L.eqf_get_outlier_gate.argtypes = [vp, _ip, _dp]
@@ -802,6 +825,65 @@ class FilterBatch:
             for k in range(npairs):
                 M[pp[k, 0], pp[k, 1]] = M[pp[k, 1], pp[k, 0]] = res["cost"][k]
             res["matrix"] = M
+        return res
+
+    def score_vision(self, ids, bearings, mask=None, want_lm=False, nb=None, stride=None):
+        """How likely candidate vision frames are under every filter of the handle, WITHOUT applying any of them (include/eqf_vio_amd.h:
+        eqf_score_vision; consistency.score_vision_host is its numpy statement, consistency.joint_compatible the chi-square test on the
+        result).  ids[b][c]: the strictly ascending ids of candidate c of filter b, bearings[b][c] (n, 3) its bearings -- ragged lists, every
+        filter with the same number of candidates -- or padded arrays (B, ncand, stride) / (B, ncand, stride, 3) with nb (B, ncand) the
+        entries that count (default: all).  A single-filter handle also takes the candidates themselves.  mask (B,): 0 leaves a filter out
+        (info = 3).  stride: the entries per candidate the arrays handed to the library are laid out for (default: the longest list).
+        Returns a FrameScores: nis, logdet_S, loglik, dof, info (B, ncand), and with want_lm nis_lm and used (B, ncand, stride) at the
+        caller's entry positions.  The handle is only read."""
+        B = self.B
+        if isinstance(ids, np.ndarray) and ids.ndim == 3:
+            idm = np.ascontiguousarray(ids, dtype=np.int32)
+            ncand, st = idm.shape[1], idm.shape[2]
+            ys = np.ascontiguousarray(bearings, dtype=np.float64).reshape(idm.shape[0], ncand, st, 3)
+            nbv = np.full((idm.shape[0], ncand), st, dtype=np.int32) if nb is None else np.ascontiguousarray(nb, dtype=np.int32).reshape(-1, ncand)
+            if stride is not None and int(stride) != st:
+                raise ValueError("score_vision: stride differs from the padded arrays'")
+        else:
+            def flat(x):  # one candidate's ids, not a list of candidates
+                return (isinstance(x, np.ndarray) and x.ndim == 1) or (isinstance(x, (list, tuple)) and all(np.isscalar(e) for e in x))
+
+            if B == 1 and len(ids) > 0 and flat(ids[0]):
+                ids, bearings = [ids], [bearings]
+            ncand = len(ids[0]) if len(ids) else 0
+            if len(ids) != B or len(bearings) != B or any(len(i) != ncand or len(y) != ncand for i, y in zip(ids, bearings)):
+                raise ValueError("score_vision: one list of candidates per filter, of one length")
+            idl = [[np.asarray(x, dtype=np.int32).reshape(-1) for x in row] for row in ids]
+            longest = max([1] + [len(x) for row in idl for x in row])
+            st = longest if stride is None else int(stride)
+            if st < longest:
+                raise ValueError("score_vision: stride is shorter than the longest list")
+            nbv = np.array([[len(x) for x in row] for row in idl], dtype=np.int32).reshape(B, ncand)
+            idm = np.zeros((B, ncand, st), dtype=np.int32)
+            ys = np.zeros((B, ncand, st, 3))
+            for b in range(B):
+                for c in range(ncand):
+                    k = int(nbv[b, c])
+                    if k:
+                        idm[b, c, :k] = idl[b][c]
+                        ys[b, c, :k] = np.asarray(bearings[b][c], dtype=np.float64).reshape(k, 3)
+        if idm.shape[0] != B or nbv.shape != (B, ncand):
+            raise ValueError("score_vision: one row of candidates per filter")
+        mk = None if mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mask), (B,)) != 0, dtype=np.uint8)
+        up = C.POINTER(C.c_ubyte)
+        out = (FrameScore * max(B * ncand, 1))()
+        lm = np.zeros((B, ncand, st)) if want_lm else None
+        used = np.zeros((B, ncand, st), dtype=np.uint8) if want_lm else None
+        _check(lib().eqf_score_vision(self._h, int(ncand), nbv.ctypes.data_as(_ip), idm.ctypes.data_as(_ip), _p(ys), int(st),
+                                      None if mk is None else mk.ctypes.data_as(up), out, None if lm is None else _p(lm),
+                                      None if used is None else used.ctypes.data_as(up)), "eqf_score_vision")
+        rec = [out[k] for k in range(B * ncand)]
+        res = FrameScores(nis=np.array([r.nis for r in rec]).reshape(B, ncand), logdet_S=np.array([r.logdet_S for r in rec]).reshape(B, ncand),
+                          loglik=np.array([r.loglik for r in rec]).reshape(B, ncand),
+                          dof=np.array([r.dof for r in rec], dtype=np.int32).reshape(B, ncand),
+                          info=np.array([r.info for r in rec], dtype=np.int32).reshape(B, ncand))
+        if want_lm:
+            res.nis_lm, res.used = lm, used
         return res
 
     def reduce_mixture(self, idx, w, target, max_cost=float("inf"), kind="runnalls"):

@@ -819,6 +819,47 @@ def gate_distance(S, delta):
     return float(w0 * w0 + w1 * w1)
 
 
+def score_vision_host(Sigma, C, delta, r, slots):
+    """The numpy statement of FilterBatch.score_vision for ONE candidate of one filter (include/eqf_vio_amd.h: eqf_score_vision).  Sigma
+    (11 + 3 N square, the reference's index map, FilterBatch.sigma(); its lower triangle is read), C (N, 2, 3) = output_blocks(origin p),
+    delta (N, 2) the residual the update would form per landmark of the state (rows of landmarks that do not take part are not read), r the
+    measurement variance, slots the state slots of the matching landmarks IN THE STATE'S ORDER.  S = C_M Sigma_MM C_M^T + r I = L L^T by a
+    dense Cholesky, z = L^-1 delta_M.  Returns dict(nis, logdet_S, loglik, dof, nis_lm (len(slots),), S); an empty list scores exactly 0."""
+    Sg = np.asarray(Sigma, dtype=float)
+    Cb = np.asarray(C, dtype=float).reshape(-1, 2, 3)
+    d = np.asarray(delta, dtype=float).reshape(-1, 2)
+    sl = [int(k) for k in slots]
+    if any(b <= a for a, b in zip(sl, sl[1:])):
+        raise ValueError("score_vision_host: slots must be strictly ascending (the state's own order)")
+    m = 2 * len(sl)
+    if m == 0:
+        return dict(nis=0.0, logdet_S=0.0, loglik=0.0, dof=0, nis_lm=np.zeros(0), S=np.zeros((0, 0)))
+    S = np.zeros((m, m))
+    for a, sa in enumerate(sl):
+        for b, sb in enumerate(sl[:a + 1]):
+            blk = Cb[sa] @ Sg[11 + 3 * sa:14 + 3 * sa, 11 + 3 * sb:14 + 3 * sb] @ Cb[sb].T
+            S[2 * a:2 * a + 2, 2 * b:2 * b + 2] = blk
+            S[2 * b:2 * b + 2, 2 * a:2 * a + 2] = blk.T
+    S = np.tril(S) + np.tril(S, -1).T + float(r) * np.eye(m)
+    dm = np.concatenate([d[k] for k in sl])
+    L = np.linalg.cholesky(S)
+    z = np.linalg.solve(L, dm)
+    nis = float(z @ z)
+    logdet = 2.0 * float(np.sum(np.log(np.diag(L))))
+    nis_lm = np.array([gate_distance(S[2 * a:2 * a + 2, 2 * a:2 * a + 2], dm[2 * a:2 * a + 2]) for a in range(len(sl))])
+    return dict(nis=nis, logdet_S=logdet, loglik=-0.5 * (nis + logdet + m * np.log(2.0 * np.pi)), dof=m, nis_lm=nis_lm, S=S)
+
+
+def joint_compatible(score, p):
+    """The joint-compatibility test on a result of FilterBatch.score_vision (or one record of it): nis <= the chi-square threshold of
+    probability p at the record's own dof; a record without a matching entry (dof = 0) is compatible.  Arrays give arrays.  A record whose
+    info is not 0 has nis = NaN and is not compatible."""
+    nis, dof = np.asarray(score["nis"], dtype=float), np.asarray(score["dof"])
+    thr = np.array([chi2_gate_threshold(p, dof=int(k)) if k > 0 else np.inf for k in dof.reshape(-1)]).reshape(dof.shape)
+    out = np.where(dof > 0, nis <= thr, True)
+    return bool(out) if out.ndim == 0 else out
+
+
 def forecast_host(flt, imu=None, t1=None, local=True, measurement_variance=0.0, sample=ImuSample):
     """The numpy statement of FilterBatch.forecast for ONE filter.  `flt` is a filter object with the reference's interface (processIMUData
     (sample), integrateUpToTime(t), getTime(), initialisedFlag, xi0, X, Sigma, stateEstimate()); it is deep-copied, the copy is given the

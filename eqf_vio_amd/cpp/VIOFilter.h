@@ -150,6 +150,22 @@ class VIOFilter {
         check(eqf_process_vision(handle_.get(), &measurement.stamp, &nb, ids_.data(), y_.data(), nb, &lastStatus_), "eqf_process_vision");
     }
 
+    // How likely the frame is BEFORE it is applied (eqf_score_vision): the joint NIS, log det S, log-likelihood and dof of the entries whose
+    // id the state holds, at the filter's present state -- measurement.stamp is not used: bring the IMU up to date first.  Nothing of the
+    // filter changes; entries the state does not hold take no part, landmarks the frame does not name are not removed.
+    eqf_frame_score scoreVisionData(const VisionMeasurement& measurement) const {
+        const int nb = int(measurement.bearings.size()), stride = nb > 0 ? nb : 1;
+        std::vector<int> ids(size_t(stride), 0);
+        std::vector<double> y(size_t(3) * stride, 0.0);
+        for (int i = 0; i < nb; ++i) {
+            ids[i] = measurement.bearings[i].id;
+            for (int c = 0; c < 3; ++c) y[size_t(3) * i + c] = measurement.bearings[i].p[c];
+        }
+        eqf_frame_score rec{};
+        check(eqf_score_vision(handle_.get(), 1, &nb, ids.data(), y.data(), stride, nullptr, &rec, nullptr, nullptr), "eqf_score_vision");
+        return rec;
+    }
+
     // Handle option by name (include/eqf_vio_amd.h: eqf_set_option), e.g. setOption("downdate_slices", 6): the covariance downdate on the
     // integer matrix pipe from six 7-bit slices per column of Y (off by default: fp64).
     void setOption(const char* name, int value) { check(eqf_set_option(handle_.get(), name, value), "eqf_set_option"); }

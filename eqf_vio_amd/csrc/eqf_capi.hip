@@ -40,6 +40,8 @@
 #include "eqf_mergecost_host.hpp"
 #include "eqf_forecast.hpp"
 #include "eqf_forecast_host.hpp"
+#include "eqf_score.hpp"
+#include "eqf_score_host.hpp"
 
 using namespace eqf;
 
@@ -307,6 +309,14 @@ struct eqf_filter {
     int mcChunkCap = 0, mcChunkOpt = 0;
     char* dMcItems = nullptr;
     size_t mcItemCap = 0;
+    // scoring candidate frames (eqf_score.hpp; eqf_score_vision), allocated on first need: one block for a chunk of images of order
+    // score::paddedOrder(capacity) with their right-hand-side rows, diagonal-block records and pivot words (grown when the option
+    // "score_chunk" asks for more), one for a call's items, matched slots, bearings, per-landmark statistics and records.  (Last, again.)
+    char* dScWs = nullptr;
+    int scChunkCap = 0, scChunkOpt = 0;
+    char* dScTab = nullptr;
+    size_t scTabBytes = 0;
+    bool scoreLdsSet = false;
 };
 
 namespace {
@@ -1644,6 +1654,8 @@ void freeAll(eqf_filter* f) {
     hipFree(f->dMixWs);
     hipFree(f->dMcWs);
     hipFree(f->dMcItems);
+    hipFree(f->dScWs);
+    hipFree(f->dScTab);
     hipFree(f->dMixTab);
     if (f->hMixTab) hipHostFree(f->hMixTab);
     if (f->evMix) hipEventDestroy(f->evMix);
@@ -2912,6 +2924,11 @@ int eqf_set_option(eqf_filter* f, const char* name, int value) {
         f->mcChunkOpt = value;
         return EQF_OK;
     }
+    if (!std::strcmp(name, "score_chunk")) {  // images per round of eqf_score_vision (0: as many as the handle has filters)
+        if (value != 0 && !score::chunkOptionOk(value)) return EQF_ERR_INVALID;
+        f->scChunkOpt = value;
+        return EQF_OK;
+    }
     return EQF_ERR_INVALID;
 }
 
@@ -3828,6 +3845,159 @@ int eqf_get_merge_costs(eqf_filter* f, int n, const int* idx, const double* w, i
         out[p].maha = r[2];
         out[p].info = int(r[3]);
         out[p].pad_ = 0;
+    }
+    return EQF_OK;
+}
+
+// ---- scoring candidate frames (eqf_score.hpp; argument checks, id matching, chunk plan and record arithmetic: eqf_score_host.hpp)
+static_assert(score::kBlock == kSB && sizeof(score::Item) == sizeof(ScoreItem) && score::kOk == EQF_OK && score::kInvalid == EQF_ERR_INVALID &&
+              score::kCapacity == EQF_ERR_CAPACITY && score::kUnsorted == EQF_ERR_UNSORTED,
+    "eqf_score_host.hpp repeats the layout constants and the error codes");
+namespace {
+struct ScWs {
+    double *W, *E, *D;
+    int* bad;
+};
+size_t scWsDoubles(const eqf_filter* f, int C) {
+    const size_t ldW = size_t(score::paddedOrder(f->cap));
+    return size_t(C) * (ldW * ldW + ldW + size_t(kDRec)) + size_t(C + 1) / 2;
+}
+ScWs scCarve(const eqf_filter* f, char* p, int C) {
+    const size_t ldW = size_t(score::paddedOrder(f->cap));
+    ScWs w;
+    w.W = reinterpret_cast<double*>(p);
+    w.E = w.W + size_t(C) * ldW * ldW;
+    w.D = w.E + size_t(C) * ldW;
+    w.bad = reinterpret_cast<int*>(w.D + size_t(C) * size_t(kDRec));
+    return w;
+}
+// the tables of a call in one block: records | per-landmark statistics | bearings | items | slots
+struct ScTab {
+    size_t rec, nisLm, y, items, slots, bytes;
+};
+ScTab scTabLayout(size_t nItems, size_t nMatched) {
+    ScTab t;
+    t.rec = 0;
+    t.nisLm = t.rec + sizeof(double) * score::kRec * nItems;
+    t.y = t.nisLm + sizeof(double) * nMatched;
+    t.items = t.y + sizeof(double) * 3 * nMatched;
+    t.slots = t.items + sizeof(ScoreItem) * nItems;
+    t.bytes = t.slots + sizeof(int) * nMatched;
+    return t;
+}
+// both blocks of a call; a failure frees what this call got and leaves the handle as it was
+int scAlloc(eqf_filter* f, int chunk, size_t tabBytes) {
+    void *w = nullptr, *t = nullptr;
+    const bool needW = chunk > f->scChunkCap, needT = tabBytes > f->scTabBytes;
+    if (!needW && !needT) return EQF_OK;
+    if ((needW && hipMalloc(&w, sizeof(double) * scWsDoubles(f, chunk)) != hipSuccess) || (needT && hipMalloc(&t, tabBytes) != hipSuccess)) {
+        (void)hipGetLastError();
+        if (w) hipFree(w);
+        return EQF_ERR_HIP;
+    }
+    HIPC(hipStreamSynchronize(f->stream));
+    if (needW) {
+        hipFree(f->dScWs);
+        f->dScWs = static_cast<char*>(w);
+        f->scChunkCap = chunk;
+        HIPC(hipMemsetAsync(w, 0, sizeof(double) * scWsDoubles(f, chunk), f->stream));  // (upper triangles of diagonal tiles are read, never used)
+    }
+    if (needT) {
+        hipFree(f->dScTab);
+        f->dScTab = static_cast<char*>(t);
+        f->scTabBytes = tabBytes;
+    }
+    return EQF_OK;
+}
+}  // namespace
+
+int eqf_score_vision(eqf_filter* f, int ncand, const int* nb, const int* ids, const double* bearings, int stride, const unsigned char* mask,
+    eqf_frame_score* out, double* nis_lm, unsigned char* used) {
+    if (!f || !nb || !ids || !bearings || !out || ncand < 1 || stride < 1) return EQF_ERR_INVALID;
+    const int B = f->B, cap = f->cap;
+    {
+        const int rc = score::checkArgs(B, cap, ncand, nb, ids, bearings, stride, mask);
+        if (rc) return rc;
+    }
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    GATE(f);
+    // the items: per candidate the matched slots in the state's order, the bearings permuted into it
+    const size_t nItems = size_t(B) * ncand;
+    std::vector<score::Item> items(nItems);
+    std::vector<int> slots, pos;
+    int mLm = 0;
+    for (int b = 0; b < B; ++b) {
+        const bool masked = mask && !mask[b];
+        const bool live = !masked && f->init[b];
+        for (int c = 0; c < ncand; ++c) {
+            const size_t it = size_t(b) * ncand + c;
+            const int first = int(slots.size());
+            const int m = live ? score::matchItem(int(f->ids[b].size()), f->ids[b].data(), nb[it], ids + it * stride, slots, pos) : 0;
+            items[it] = score::Item{b, m, first, masked ? 1 : 0};
+            mLm = std::max(mLm, m);
+        }
+    }
+    const size_t nMatched = slots.size();
+    std::vector<double> y(3 * nMatched);
+    for (size_t it = 0; it < nItems; ++it)
+        for (int k = 0; k < items[it].m; ++k)
+            std::memcpy(&y[3 * (size_t(items[it].first) + k)], bearings + (it * stride + size_t(pos[size_t(items[it].first) + k])) * 3, sizeof(double) * 3);
+    std::vector<double> hRec(nItems * score::kRec, 0.0), hLm(nMatched, 0.0);
+    if (nMatched > 0) {
+        const int chunk = score::chunkSize(f->scChunkOpt, B);
+        const ScTab tab = scTabLayout(nItems, nMatched);
+        int rc = scAlloc(f, chunk, tab.bytes);
+        if (rc) return rc;
+        const ScWs ws = scCarve(f, f->dScWs, f->scChunkCap);
+        ScoreArgs a{};
+        a.items = reinterpret_cast<const ScoreItem*>(f->dScTab + tab.items);
+        a.slots = reinterpret_cast<const int*>(f->dScTab + tab.slots);
+        a.y = reinterpret_cast<const double*>(f->dScTab + tab.y);
+        a.nisLm = reinterpret_cast<double*>(f->dScTab + tab.nisLm);
+        a.rec = reinterpret_cast<double*>(f->dScTab + tab.rec);
+        a.Q = f->Q[f->pG]; a.lmc = f->lmc; a.S = static_cast<const double*>(f->Sigma[f->pS]); a.sigmaStride = f->sigmaStride; a.ld = f->ld;
+        a.cap = cap; a.measVar = f->set.measurementVariance;
+        a.ldW = score::paddedOrder(cap); a.strideW = (long long)a.ldW * a.ldW; a.W = ws.W; a.E = ws.E; a.D = ws.D; a.bad = ws.bad;
+        HIPC(hipMemcpyAsync(f->dScTab + tab.items, items.data(), sizeof(ScoreItem) * nItems, hipMemcpyHostToDevice, f->stream));
+        HIPC(hipMemcpyAsync(f->dScTab + tab.slots, slots.data(), sizeof(int) * nMatched, hipMemcpyHostToDevice, f->stream));
+        HIPC(hipMemcpyAsync(f->dScTab + tab.y, y.data(), sizeof(double) * 3 * nMatched, hipMemcpyHostToDevice, f->stream));
+        for (int ch = 0; ch < score::numChunks((long long)nItems, chunk); ++ch) {
+            const int cnt = score::chunkCount((long long)nItems, chunk, ch);
+            a.item0 = ch * chunk;
+            a.count = cnt;
+            hipLaunchKernelGGL(k_score_form, dim3((mLm + 3) / 4 + 1, cnt), dim3(256), 0, f->stream, a);
+            rc = enqueueFactor(f->stream, f->scoreLdsSet, a, cnt, 2 * mLm, 1);
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_score_tail, dim3(cnt), dim3(256), 0, f->stream, a);
+        }
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(hRec.data(), f->dScTab + tab.rec, sizeof(double) * hRec.size(), hipMemcpyDeviceToHost, f->stream));
+        HIPC(hipMemcpyAsync(hLm.data(), f->dScTab + tab.nisLm, sizeof(double) * nMatched, hipMemcpyDeviceToHost, f->stream));
+    }
+    HIPC(hipStreamSynchronize(f->stream));
+    if (nis_lm) std::fill(nis_lm, nis_lm + nItems * stride, 0.0);
+    if (used) std::fill(used, used + nItems * stride, (unsigned char)0);
+    const double nan = std::nan("");
+    for (size_t it = 0; it < nItems; ++it) {
+        const score::Item& im = items[it];
+        eqf_frame_score& o = out[it];
+        if (im.masked) {
+            o.nis = o.logdet_S = o.loglik = nan;
+            o.dof = 0;
+            o.info = score::kInfoMasked;
+            continue;
+        }
+        const double* r = hRec.data() + it * score::kRec;  // (all zero where nothing matched anywhere in the call)
+        o.nis = r[0];
+        o.logdet_S = r[1];
+        o.loglik = r[2];
+        o.dof = int(r[3]);
+        o.info = int(r[4]);
+        for (int k = 0; k < im.m; ++k) {
+            const size_t e = it * stride + size_t(pos[size_t(im.first) + k]);
+            if (nis_lm) nis_lm[e] = hLm[size_t(im.first) + k];
+            if (used) used[e] = 1;
+        }
     }
     return EQF_OK;
 }

@@ -65,6 +65,16 @@ EQF_DI double gateMahalanobis(const quat Qq, const d3 y, const double* c, const 
     const double w0 = d0 / l00, w1 = fma(-l10, w0, d1) / l11;
     return fma(w1, w1, w0 * w0);
 }
+// delta_i on its own, by gateMahalanobis' own expressions (eqf_score.hpp: the right-hand side of the joint S)
+EQF_DI void gateResidual(const quat Qq, const d3 y, const double* c, double* d0, double* d1) {
+    const d3 yerr = qrot(qinv(qinv(Qq)), y);
+    m33 Rs;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rs.a[k] = c[6 + k];
+    const d3 rr = mv33(Rs, yerr);
+    *d0 = rr.x / (1 - rr.z);  // VIOState.cpp:199-204
+    *d1 = rr.y / (1 - rr.z);
+}
 // What the Mahalanobis gate reads besides k_probe's / k_edit's own arguments (fp64 handles only)
 struct MahaArgs {
     const double* lmc;     // [B][15][cap]

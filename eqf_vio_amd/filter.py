@@ -120,6 +120,20 @@ class VIOFilter:
         """VIOFilter.cpp:232-302"""
         return int(self._fb.process_vision([meas.stamp], meas.ids, meas.bearings)[0])
 
+    def scoreVisionData(self, meas, want_lm=False):
+        """NIS, log det S, log-likelihood, dof and info the frame WOULD have, at the filter's present state, without applying it; entries
+        whose id the state does not hold take no part (include/eqf_vio_amd.h: eqf_score_vision).  meas.stamp is not used: bring the IMU up
+        to date first.  With want_lm also nis_lm and used per entry."""
+        r = self._fb.score_vision([[np.asarray(meas.ids).reshape(-1)]], [[np.asarray(meas.bearings, dtype=float).reshape(-1, 3)]], want_lm=want_lm)
+        out = dict(nis=float(r.nis[0, 0]), logdet_S=float(r.logdet_S[0, 0]), loglik=float(r.loglik[0, 0]), dof=int(r.dof[0, 0]),
+                   info=int(r.info[0, 0]))
+        if want_lm:
+            n = len(np.asarray(meas.ids).reshape(-1))
+            out["nis_lm"], out["used"] = r.nis_lm[0, 0, :n], r.used[0, 0, :n]
+        return out
+
+    score = scoreVisionData
+
     def getTime(self):
         return float(self._fb.get_time()[0])
 

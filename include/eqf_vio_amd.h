@@ -550,6 +550,51 @@ int eqf_get_merge_costs(eqf_filter* f, int n, const int* idx, const double* w, i
     const int* pairs /* [npairs][2] POSITIONS in idx, or NULL: all i < j in lexicographic order */, eqf_pair_cost* out /* [npairs] */,
     eqf_sigma_stats* member /* [n] or NULL */);
 
+/* HOW LIKELY a vision frame is under a filter BEFORE the filter absorbs it: ncand candidate frames per filter scored on the device without
+ * applying any of them (csrc/eqf_score.hpp) -- alternative data associations of one frame (the joint-compatibility test), an ambiguous
+ * re-detection, a look-ahead likelihood to weight particles with before resampling.
+ *   Candidate c of filter b names nb[b * ncand + c] bearings, ids[(b * ncand + c) * stride + k] strictly ascending and
+ *   bearings[((b * ncand + c) * stride + k) * 3 ..], k < nb[b * ncand + c], as in eqf_process_vision.
+ *   An entry takes part if and only if its id is a landmark of filter b's state.  The other entries carry no information about the state
+ *   (a new landmark would only be appended): used = 0, and they add exactly nothing.  Landmarks of the state that the candidate does not
+ *   name are simply not part of the measurement: nothing is removed -- the intended difference from processVisionData, whose bookkeeping
+ *   throws out every landmark a frame does not name.
+ *   With M the matching landmarks IN THE STATE'S OWN ORDER, delta_i the residual the update would form, C_i the 2 x 3 output block of
+ *   landmark i and r = measurementVariance:
+ *     S = C_M Sigma_MM C_M^T + r I  (order 2 |M|),   S = L L^T (blocked fp64 Cholesky on the matrix cores),   z = L^-1 delta_M,
+ *     nis = z^T z,   logdet_S = 2 sum log L_kk,   dof = 2 |M|,   loglik = -(nis + logdet_S + dof log 2 pi) / 2.
+ *   nis_lm[(b * ncand + c) * stride + k] of a matching entry is delta_i^T (C_i Sigma_ii C_i^T + r I)^-1 delta_i, the number
+ *   EQF_GATE_MAHALANOBIS and eqf_get_innovation_stats report, at the caller's entry position k; 0 elsewhere.  used likewise, 1 | 0.
+ *   The score is taken at the handle's PRESENT state and Sigma.  The integrateUpToTime(stamp) with which processVisionData begins is not
+ *   part of it: the caller brings the IMU up to date first (eqf_process_imu).  What is left out is Q dt of less than one IMU period.
+ *   A candidate without a matching entry -- nb = 0, no id of the state, a filter that is not initialised or has no landmarks -- reports
+ *   info = 0, dof = 0, nis = logdet_S = loglik = 0.  A filter with mask[b] == 0 reports info = 3 and NaN; its ids and bearings are not looked at.
+ *   Trouble of ONE candidate goes into its info (fields NaN): the call returns EQF_OK and eqf_device_error is never touched.
+ *   Read-only, like eqf_forecast: settles what the handle has deferred (queued IMU calls, a pending gate) and synchronises like every
+ *   getter; writes a workspace of its own -- not the scratch image of eqf_get_sigma_local / eqf_get_nees either --; every getter answers
+ *   with the same bits afterwards, sticky flags included, and every later call gives the bits it gives on a handle that never scored.
+ *   Reproducible and independent of context: no atomics, one fixed summation order; a candidate's record and its nis_lm do not depend on
+ *   which other candidates or filters are in the call, on their order, on the chunking, or on stride.
+ * Before any effect: EQF_ERR_INVALID for a NULL f, nb, ids, bearings or out; ncand < 1; stride < 1; an nb outside [0, stride]; a bearing
+ * component that is not finite for an entry below nb of a filter that is not masked out.  EQF_ERR_UNSORTED: ids of such a filter not strictly
+ * ascending.  EQF_ERR_CAPACITY: an nb beyond the handle's capacity.  EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle.  EQF_ERR_HIP if the
+ * workspace, allocated on first need and grown when needed, cannot be had (the handle stays as it was): one image per item of a chunk, a
+ * square of the padded order 2 capacity each -- by default as many images as the handle has filters; eqf_set_option(f, "score_chunk", c),
+ * 1 <= c <= 4096 (0: the default), overrides it.  The number of launches depends only on ncand, the batch, the largest order and the chunk.
+ * Not covered: the partitioned filter (eqf_tf_*, eqf_tiled_*), fp32 handles, propagation to the stamp. */
+typedef struct eqf_frame_score {
+    double nis;       /* delta^T S^-1 delta = z^T z                                   */
+    double logdet_S;  /* 2 sum log L_kk                                                */
+    double loglik;    /* -(nis + logdet_S + dof log 2 pi) / 2                          */
+    int dof;          /* 2 x (entries that matched a landmark of the state)            */
+    int info;         /* 0 scored; 1 a pivot of S not positive or a non-finite value   */
+                      /* (nis, logdet_S, loglik NaN); 3 masked out (NaN)               */
+} eqf_frame_score;
+int eqf_score_vision(eqf_filter* f, int ncand, const int* nb /* [batch][ncand] */,
+    const int* ids /* [batch][ncand][stride] */, const double* bearings /* [batch][ncand][stride][3] */, int stride,
+    const unsigned char* mask /* [batch] or NULL */, eqf_frame_score* out /* [batch][ncand] */,
+    double* nis_lm /* [batch][ncand][stride] or NULL */, unsigned char* used /* [batch][ncand][stride] or NULL */);
+
 /* Propagate backend: 0 = block-structured HBM-bound kernel (default, product path),
  * 1 = dense F Sigma F^T on MFMA (what the reference executes; BASELINE cfg 3 cross-check). */
 int eqf_set_dense_propagate(eqf_filter* f, int on);
