@@ -70,6 +70,12 @@ class LinearReport(C.Structure):
     _fields_ = [("nis", C.c_double), ("logdet_S", C.c_double), ("loglik", C.c_double), ("dof", C.c_int), ("info", C.c_int)]
 
 
+class LiftReport(C.Structure):
+    """eqf_lift_report (include/eqf_vio_amd.h)."""
+
+    _fields_ = [("kind", C.c_int), ("info", C.c_int), ("DeltaU", C.c_double * 6), ("min_pivot", C.c_double), ("pivot_ratio", C.c_double)]
+
+
 class ForecastOut(C.Structure):
     """eqf_forecast_out (include/eqf_vio_amd.h)."""
 
@@ -127,7 +133,7 @@ EXPORTED_SYMBOLS = [
     "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_forecast", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
     "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters", "eqf_update_linear", "eqf_update_landmarks",
     "eqf_get_mixture_moments", "eqf_merge_filters", "eqf_debug_mixture_launches", "eqf_debug_sigma_pad",
-    "eqf_get_merge_costs", "eqf_score_vision",
+    "eqf_get_merge_costs", "eqf_score_vision", "eqf_get_lift_report",
     "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
     "eqf_set_sigma", "eqf_set_state", "eqf_copy_filters", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
@@ -212,6 +218,8 @@ def lib():
         if hasattr(L, "eqf_score_vision"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
             L.eqf_score_vision.argtypes = [vp, C.c_int, _ip, _ip, _dp, C.c_int, C.POINTER(C.c_ubyte), C.POINTER(FrameScore), _dp,
                                            C.POINTER(C.c_ubyte)]
+        if hasattr(L, "eqf_get_lift_report"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
+            L.eqf_get_lift_report.argtypes = [vp, C.c_int, C.POINTER(LiftReport)]
         if hasattr(L, "eqf_set_outlier_gate"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
             L.eqf_set_outlier_gate.argtypes = [vp, C.c_int, C.c_double]
             L.eqf_get_outlier_gate.argtypes = [vp, _ip, _dp]
@@ -428,7 +436,8 @@ class FilterBatch:
     def set_option(self, name, value):
         """Handle option by name (include/eqf_vio_amd.h: eqf_set_option): ``"downdate_slices"`` 0 (fp64, default) / 5 / 6 / 7 -- the
         covariance downdate on the integer matrix pipe from that many 7-bit slices (6 holds Sigma within 1e-4 of fp64, 5 does not) --
-        ``"res_tickets"`` 0 / 1 / 2, or ``"innovation_stats"`` 0 / 1 (innovation_stats())."""
+        ``"res_tickets"`` 0 / 1 / 2, ``"innovation_stats"`` 0 / 1 (innovation_stats()), or ``"innovation_lift"`` 0 / 1: with 1
+        update_linear, update_landmarks, apply_increment and perturb move the pose by the handle's innovation lift (lift_report())."""
         _check(lib().eqf_set_option(self._h, name.encode(), int(value)), "eqf_set_option")
 
     def synchronize(self):
@@ -667,6 +676,15 @@ class FilterBatch:
         st = (SigmaStats * B)() if stats else None
         _check(lib().eqf_perturb_filters(self._h, int(first), _p(Z), int(Z.shape[2]), None if sc is None else _p(sc), st), "eqf_perturb_filters")
         return self._stats(st) if stats else None
+
+    def lift_report(self, b=0):
+        """The lift of filter b in the most recent update_linear, update_landmarks, apply_increment or perturb (include/eqf_vio_amd.h:
+        eqf_get_lift_report): dict with kind (0 plain, 1 bundleLift + continuous lift, 2 bundleLift + discrete lift), info (0 applied, 3 took
+        no part, 4 lift failed: filter untouched), DeltaU (6,), min_pivot and pivot_ratio.  consistency.bundle_lift_host is its numpy
+        statement."""
+        r = LiftReport()
+        _check(lib().eqf_get_lift_report(self._h, int(b), C.byref(r)), "eqf_get_lift_report")
+        return dict(kind=r.kind, info=r.info, DeltaU=np.array(r.DeltaU[:]), min_pivot=r.min_pivot, pivot_ratio=r.pivot_ratio)
 
     def update_linear(self, H, resid, R, local=True, gate=float("inf"), mask=None, want_gamma=False, stats=True):
         """A measurement update with m <= 16 linear rows for EVERY filter of the handle in one call (include/eqf_vio_amd.h:

@@ -894,3 +894,122 @@ def forecast_host(flt, imu=None, t1=None, local=True, measurement_variance=0.0, 
     return dict(time=float(f.getTime()), steps=steps, pose_q=np.array(est.pose.q, dtype=float), pose_x=np.array(est.pose.x, dtype=float),
                 velocity=np.array(est.velocity, dtype=float), p=p, bearing=p / np.linalg.norm(p, axis=1, keepdims=True) if N else p,
                 base=base, lm=lmloc if local else lm0, S=S, ycov=bearing_cov_host(p, lmloc) if N else np.zeros((0, 3, 3)))
+
+
+# ---- the innovation lift of the calls that inform a filter outside a vision frame (include/eqf_vio_amd.h: eqf_get_lift_report)
+def _so3_exp_matrix(w):
+    """SO3.cpp:122-140."""
+    th = np.linalg.norm(w)
+    A, B = (np.sin(th) / th, (1 - np.cos(th)) / th**2) if abs(th) >= 1e-8 else (1.0, 0.5)
+    wx = _skew(w)
+    return np.eye(3) + A * wx + B * wx @ wx
+
+
+def _se3_exp(u):
+    """SE3.cpp:139-164 -> (quaternion, translation)."""
+    w, v = np.asarray(u[0:3], dtype=float), np.asarray(u[3:6], dtype=float)
+    th = np.linalg.norm(w)
+    if abs(th) >= 1e-12:
+        A = np.sin(th) / th
+        B = (1 - np.cos(th)) / th**2
+        C = (1 - A) / th**2
+    else:
+        A, B, C = 1.0, 0.5, 1.0 / 6.0
+    wx = _skew(w)
+    return _quat_from_matrix(np.eye(3) + A * wx + B * wx @ wx), (np.eye(3) + B * wx + C * wx @ wx) @ v
+
+
+def _so3_from_vectors(origin, dest):
+    """SO3.cpp:155-167."""
+    o, d = origin / np.linalg.norm(origin), dest / np.linalg.norm(dest)
+    v, c = np.cross(o, d), float(o @ d)
+    if abs(1 + c) <= 1e-8:
+        raise ValueError("the vectors cannot be exactly opposing (SO3.cpp:160)")
+    vx = _skew(v)
+    return _quat_from_matrix(np.eye(3) + (vx + 1.0 / (1.0 + c) * vx @ vx))
+
+
+def lift_rows(state):
+    """Z_P's landmark rows (3N, 6): Qhat_i R_C^T [(x0 - pHat_i)^x R0, R0] (EqFMatrices.cpp:221-235 with D and the coefficient matrix
+    multiplied out).  state: see bundle_lift_host."""
+    o, g, cam = state["origin"], state["group"], state["camera"]
+    P0q, x0 = np.asarray(o["q"], dtype=float), np.asarray(o["x"], dtype=float)
+    p0 = np.asarray(o["p"], dtype=float).reshape(-1, 3)
+    Aq, Ax = np.asarray(g["Aq"], dtype=float), np.asarray(g["Ax"], dtype=float)
+    Qq, Qa = np.asarray(g["Qq"], dtype=float).reshape(-1, 4), np.asarray(g["Qa"], dtype=float).reshape(-1)
+    cq, cx = np.asarray(cam["q"], dtype=float), np.asarray(cam["x"], dtype=float)
+    Pq, Px = _quat_mul(P0q, Aq), x0 + _quat_rotate(P0q, Ax)        # xiHat.pose = xi0.pose * X.A
+    PCq, PCx = _quat_mul(Pq, cq), Px + _quat_rotate(Pq, cx)        # ... * cameraOffset
+    RCt = quat_to_matrix(_quat_inverse(PCq))
+    R0 = quat_to_matrix(P0q)
+    Z = np.zeros((3 * len(Qa), 6))
+    for i in range(len(Qa)):
+        qhat = _quat_rotate(_quat_inverse(Qq[i]), p0[i]) / Qa[i]
+        pHat = _quat_rotate(PCq, qhat) + PCx
+        M = Qa[i] * quat_to_matrix(Qq[i]) @ RCt
+        Z[3 * i : 3 * i + 3, 0:3] = M @ _skew(x0 - pHat) @ R0
+        Z[3 * i : 3 * i + 3, 3:6] = M @ R0
+    return Z
+
+
+def bundle_lift_host(gamma, state, Sigma):
+    """The numpy statement of the innovation lift FilterBatch.update_linear / update_landmarks / apply_increment / perturb take with
+    set_option("innovation_lift", 1) (include/eqf_vio_amd.h: eqf_get_lift_report; the reference's bundleLift, EqFMatrices.cpp:173-252,
+    then the group step of VIOFilter.cpp:292-296).
+    gamma (11 + 3N,): the increment in the reference's index map.  Sigma (11 + 3N, 11 + 3N): the covariance the call STARTED from.
+    state: dict with origin (FilterBatch.origin()), group (FilterBatch.group()), bias (6,), camera = dict(q, x) the camera offset, and
+    discrete: useDiscreteInnovationLift.  Returns a dict with DeltaU (6,), group (the new X, as FilterBatch.group()), bias, min_pivot (the
+    smallest squared pivot of Sigma_e's Cholesky factor) and pivot_ratio (min / max |pivot| of the 4 x 4 elimination, here the R factor's)."""
+    gamma = np.asarray(gamma, dtype=float)
+    o, g = state["origin"], state["group"]
+    N = len(np.asarray(g["Qa"]).reshape(-1))
+    ge = gamma[6:]
+    eta0 = gravity_dir(o["q"])
+    eta0 = eta0 / np.linalg.norm(eta0)
+    dUw = -_skew(eta0) @ stereo_sphere_chart_inv_diff_at_zero(eta0) @ ge[0:2]
+    dUf = np.concatenate([(np.eye(3) - np.outer(eta0, eta0)) @ dUw, np.zeros(3)])
+    ZP = np.zeros((5 + 3 * N, 6))
+    ZP[5:] = lift_rows(state)
+    rhs = np.zeros(5 + 3 * N)
+    rhs[5:] = ge[5:]
+    L = np.linalg.cholesky(np.asarray(Sigma, dtype=float)[6:, 6:])
+    Zt = _solve_lower(L, ZP)
+    z = _solve_lower(L, rhs)
+    G6, h = Zt.T @ Zt, Zt.T @ z
+    K = np.zeros((6, 4))
+    K[0:3, 0] = eta0
+    K[3:6, 1:4] = np.eye(3)
+    M = K.T @ G6 @ K
+    x = np.linalg.solve(M, K.T @ (-h - G6 @ dUf))
+    dU = dUf + K @ x
+    piv = np.abs(np.diag(np.linalg.qr(M)[1]))
+    # X <- Delta X
+    v0 = np.asarray(o["v"], dtype=float)
+    p0 = np.asarray(o["p"], dtype=float).reshape(-1, 3)
+    DAq, DAx = _se3_exp(dU)
+    if state.get("discrete", True):
+        Dw = v0 - _quat_rotate(DAq, v0 + ge[2:5])                  # EqFMatrices.cpp:254-258
+    else:
+        Dw = -ge[2:5] - np.cross(dU[0:3], v0)                      # :69-79
+    Aq, Ax = np.asarray(g["Aq"], dtype=float), np.asarray(g["Ax"], dtype=float)
+    Qq, Qa = np.asarray(g["Qq"], dtype=float).reshape(-1, 4).copy(), np.asarray(g["Qa"], dtype=float).reshape(-1).copy()
+    for i in range(N):
+        qi, gq = p0[i], ge[5 + 3 * i : 8 + 3 * i]
+        if state.get("discrete", True):                            # :262-270
+            q1 = qi + gq
+            dq, da = _so3_from_vectors(q1, qi), np.linalg.norm(qi) / np.linalg.norm(q1)
+        else:                                                      # :84-93, SOT3Exp
+            n2 = float(qi @ qi)
+            dq, da = _quat_from_matrix(_so3_exp_matrix(-np.cross(qi, gq) / n2)), np.exp(-float(qi @ gq) / n2)
+        Qq[i], Qa[i] = _quat_mul(dq, Qq[i]), da * Qa[i]
+    group = dict(Aq=_quat_mul(DAq, Aq), Ax=DAx + _quat_rotate(DAq, Ax), w=Dw + _quat_rotate(DAq, np.asarray(g["w"], dtype=float)), Qq=Qq, Qa=Qa)
+    return dict(DeltaU=dU, group=group, bias=np.asarray(state["bias"], dtype=float) + gamma[0:6], min_pivot=float(np.min(np.diag(L)) ** 2),
+                pivot_ratio=float(piv.min() / piv.max()))
+
+
+def _solve_lower(L, B):
+    """L^-1 B by forward substitution, row by row (no inverse is formed)."""
+    X = np.array(B, dtype=float)
+    for k in range(L.shape[0]):
+        X[k] = (X[k] - L[k, :k] @ X[:k]) / L[k, k]
+    return X

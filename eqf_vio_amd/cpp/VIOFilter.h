@@ -428,6 +428,18 @@ class VIOFilter {
             "eqf_update_landmarks");
         return rep;
     }
+    // How processLinearMeasurement, processLandmarkMeasurements, perturbState (and eqf_apply_increment) turn their increment into a group
+    // step (eqf_set_option "innovation_lift"): false (default) the plain lift, which leaves the whole correction to the body-frame landmarks;
+    // true the filter's own useInnovationLift / useDiscreteInnovationLift, as a vision frame does -- a stereo, range or zero-velocity update
+    // then moves the pose.  A lift that fails (Sigma_e not positive definite) leaves the filter untouched: info = 4 in the reports.
+    void setUpdateLift(bool on) { check(eqf_set_option(handle_.get(), "innovation_lift", on ? 1 : 0), "eqf_set_option"); }
+    // The lift of the most recent of those calls (eqf_get_lift_report): kind, info, DeltaU, the smallest pivot of Sigma_e's factor and the
+    // pivot ratio of the 4 x 4 solve.  Throws std::runtime_error before the first such call.
+    eqf_lift_report lastLiftReport() const {
+        eqf_lift_report rep;
+        check(eqf_get_lift_report(handle_.get(), 0, &rep), "eqf_get_lift_report");
+        return rep;
+    }
     // This filter continues from the state of `other` (fork, or snapshot and roll back), copied on the device (eqf_copy_filters): landmarks,
     // origin, group element, bias, covariance, time and integrator.  Settings, camera offset and capacity stay this filter's own; throws
     // std::runtime_error if `other` tracks more landmarks than this filter's capacity or differs in precision or device.

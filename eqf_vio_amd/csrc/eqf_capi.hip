@@ -42,6 +42,8 @@
 #include "eqf_forecast_host.hpp"
 #include "eqf_score.hpp"
 #include "eqf_score_host.hpp"
+#include "eqf_lift.hpp"
+#include "eqf_lift_host.hpp"
 
 using namespace eqf;
 
@@ -263,6 +265,14 @@ struct eqf_filter {
     int* dBlkWi = nullptr;
     hipEvent_t evBlk = nullptr;
     bool blkLdsSet = false;
+    // the innovation lift of eqf_update_linear / eqf_update_landmarks / eqf_apply_increment / eqf_perturb_filters (eqf_lift.hpp;
+    // eqf_set_option "innovation_lift"): the records [B][kLiftRec] of the last of these calls, allocated by the first of them, and -- by
+    // the first call with the option on -- the right-hand-side rows [B][kLiftRhs][ld], the record of the current diagonal block
+    // [B][kDRec] and the pivot words [B] (the image that is factored is dSigmaLoc)
+    int liftOpt = 0;
+    bool liftCalled = false, liftLdsSet = false;
+    double *dLiftRec = nullptr, *dLiftE = nullptr, *dLiftD = nullptr;
+    int* dLiftBad = nullptr;
     // eqf_copy_filters (eqf_clone.hpp): the pair table (pinned image + device copy, grown on demand), the small-state staging image of the
     // in-place case (allocated on first need) and two events -- evCloneSrc orders a copy behind this handle's work when it is the source,
     // evCloneDone marks the end of the last copy INTO this handle (its pair table may be reused, the source may go on)
@@ -1624,6 +1634,10 @@ void freeAll(eqf_filter* f) {
     hipFree(f->dBlkWs);
     hipFree(f->dBlkWi);
     hipFree(f->dBlkOut);
+    hipFree(f->dLiftRec);
+    hipFree(f->dLiftE);
+    hipFree(f->dLiftD);
+    hipFree(f->dLiftBad);
     if (f->hBlkSmall) hipHostFree(f->hBlkSmall);
     if (f->evBlk) hipEventDestroy(f->evBlk);
     if (f->hGate) hipHostFree(f->hGate);
@@ -2919,6 +2933,12 @@ int eqf_set_option(eqf_filter* f, const char* name, int value) {
         f->innovStats = value;
         return EQF_OK;
     }
+    if (!std::strcmp(name, "innovation_lift")) {  // eqf_lift.hpp: 0 the plain lift, 1 the handle's useInnovationLift / useDiscreteInnovationLift
+        if (!lift::optionOk(value)) return EQF_ERR_INVALID;
+        if (f->precision == EQF_PRECISION_F32) return EQF_ERR_UNSUPPORTED;
+        f->liftOpt = value;
+        return EQF_OK;
+    }
     if (!std::strcmp(name, "merge_cost_chunk")) {  // images per round of eqf_get_merge_costs (0: as many as the handle has filters)
         if (value != 0 && !mergecost::chunkOptionOk(value)) return EQF_ERR_INVALID;
         f->mcChunkOpt = value;
@@ -3076,6 +3096,80 @@ int eqf_get_nees(eqf_filter* f, int local, int first, int nrhs, const double* er
     return EQF_OK;
 }
 
+// ---- the innovation lift of the calls that inform a filter outside a vision frame (eqf_lift.hpp; decisions and layout: eqf_lift_host.hpp)
+static_assert(lift::kRefBase == kBase && lift::kPadBase == kLm0 && lift::kOff == kLiftOff && lift::kRhs == kLiftRhs && lift::kRec == kLiftRec &&
+              lift::kHead == kLiftHead && kLiftHead == kLinHead && lift::kWordFailed == kLiftWordFailed &&
+              lift::kWordFailed != blocks::kInfoIdle && lift::kPadPos == kBase - kLiftOff,
+    "eqf_lift_host.hpp repeats the layout constants");
+namespace {
+int liftCallKind(const eqf_filter* f) { return lift::callKind(f->liftOpt, f->prm.useInnovationLift, f->prm.useDiscreteInnovationLift); }
+// What a call needs before any effect: the records always, the factorisation's buffers where the call factors.  A failure frees what this
+// call got and leaves the handle as it was.
+int liftAlloc(eqf_filter* f, bool factors) {
+    void *r = nullptr, *e = nullptr, *d = nullptr, *w = nullptr, *s = nullptr;
+    bool ok = true;
+    if (!f->dLiftRec) ok = hipMalloc(&r, sizeof(double) * size_t(kLiftRec) * f->B) == hipSuccess;
+    if (ok && factors && !f->dLiftE)
+        ok = hipMalloc(&e, sizeof(double) * lift::rhsDoubles(f->ld) * f->B) == hipSuccess &&
+             hipMalloc(&d, sizeof(double) * size_t(kDRec) * f->B) == hipSuccess && hipMalloc(&w, sizeof(int) * size_t(f->B)) == hipSuccess;
+    if (ok && factors && !f->dSigmaLoc) ok = hipMalloc(&s, sizeof(double) * size_t(f->sigmaStride) * f->B) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        for (void* p : {r, e, d, w, s})
+            if (p) hipFree(p);
+        return EQF_ERR_HIP;
+    }
+    if (r) f->dLiftRec = static_cast<double*>(r);
+    if (e) {
+        f->dLiftE = static_cast<double*>(e);
+        f->dLiftD = static_cast<double*>(d);
+        f->dLiftBad = static_cast<int*>(w);
+    }
+    if (s) f->dSigmaLoc = static_cast<double*>(s);
+    return EQF_OK;
+}
+// Enqueues the lift of a call behind the launches that left its increment (filter b: gamma[b * strideG + j], internal index offG + j) and,
+// for an update, its verdict (records [B][kLinHead], entry 3) -- and in front of whatever changes Sigma: a device copy of Sigma, the
+// right-hand side, the factorisation and the tail where some filter takes a bundleLift, the tail alone (the records) otherwise.  The
+// filters the tail has not dealt with are k_apply_increment's: its IncArgs get the records.  (liftAlloc has run.)
+int liftEnqueue(eqf_filter* f, const double* gamma, long long strideG, int offG, const unsigned char* dMask, double* verdict, bool writesVerdict,
+    IncArgs& ia) {
+    const int B = f->B, nMax = maxN(f), kind = liftCallKind(f);
+    LiftArgs a{};
+    a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.cap = f->cap; a.A = f->dSigmaLoc; a.ld = f->ld; a.strideA = f->sigmaStride;
+    a.E = f->dLiftE; a.ldE = lift::rhsPitch(nMax); a.D = f->dLiftD; a.bad = f->dLiftBad; a.gamma = gamma; a.strideG = strideG; a.offG = offG;
+    a.mask = dMask; a.verdict = verdict; a.fail = writesVerdict ? verdict : nullptr; a.kind = lift::callFactors(kind, nMax) ? kind : 0;
+    a.rec = f->dLiftRec; a.prm = f->prm;
+    if (a.kind) {
+        HIPC(hipMemcpyAsync(f->dSigmaLoc, f->Sigma[f->pS], sizeof(double) * size_t(f->sigmaStride) * B, hipMemcpyDeviceToDevice, f->stream));
+        hipLaunchKernelGGL(k_lift_rhs, dim3(lift::rhsGroups(nMax), B), dim3(256), 0, f->stream, a);
+        const int rc = enqueueFactor(f->stream, f->liftLdsSet, a, B, lift::order(nMax), 1);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_lift_tail, dim3(B), dim3(256), 0, f->stream, a);
+    HIPC(hipGetLastError());
+    f->liftCalled = true;
+    ia.lift = f->dLiftRec;
+    ia.liftStride = kLiftRec;
+    return EQF_OK;
+}
+}  // namespace
+
+int eqf_get_lift_report(eqf_filter* f, int b, eqf_lift_report* out) {
+    if (!f || !out || b < 0 || b >= f->B || !f->liftCalled) return EQF_ERR_INVALID;
+    double rec[kLiftRec];
+    HIPC(hipMemcpyAsync(rec, f->dLiftRec + size_t(b) * kLiftRec, sizeof(rec), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipStreamSynchronize(f->stream));
+    lift::Report r;
+    lift::unpackReport(rec, &r);
+    out->kind = r.kind;
+    out->info = r.info;
+    std::copy(r.DeltaU, r.DeltaU + 6, out->DeltaU);
+    out->min_pivot = r.min_pivot;
+    out->pivot_ratio = r.pivot_ratio;
+    return EQF_OK;
+}
+
 // ---- draws from the covariance and the group step (eqf_sample.hpp; index arithmetic and argument checks: eqf_sample_host.hpp)
 namespace {
 size_t sampVecLen(const eqf_filter* f) { return size_t(kLm0) + 3 * size_t(f->cap); }
@@ -3191,6 +3285,7 @@ int eqf_apply_increment(eqf_filter* f, const double* gamma, int ldg, const unsig
     for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
     if (!sample::incrementArgsOk(gamma, ldg, mask, B, N.data())) return EQF_ERR_INVALID;
     int rc = sampSmallAlloc(f);
+    if (!rc) rc = liftAlloc(f, lift::callFactors(liftCallKind(f), maxN(f)));
     if (rc) return rc;
     HIPC(hipEventSynchronize(f->evSamp));
     SampSmall h = sampCarve(f, f->hSampSmall), d = sampCarve(f, f->dSampSmall);
@@ -3203,6 +3298,8 @@ int eqf_apply_increment(eqf_filter* f, const double* gamma, int ldg, const unsig
     HIPC(hipEventRecord(f->evSamp, f->stream));
     IncArgs a{};
     a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.cap = f->cap; a.gamma = d.vec; a.strideG = len; a.off = 0; a.mask = d.mask;
+    rc = liftEnqueue(f, d.vec, len, 0, d.mask, nullptr, false, a);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, a);
     HIPC(hipGetLastError());
     f->csValid = false;  // (C Sigma / S left by an earlier burst were built around the landmarks as they were)
@@ -3218,6 +3315,7 @@ int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, cons
     int rc = neesAlloc(f);
     if (!rc) rc = sampRowsAlloc(f, 1);
     if (!rc) rc = sampSmallAlloc(f);
+    if (!rc) rc = liftAlloc(f, lift::callFactors(liftCallKind(f), nMax));
     if (rc) return rc;
     const int off = sample::cutOffset(first), ldE = std::max(sample::paddedOrder(nMax, off), 1);
     rc = neesFactor(f, 0, off, 0);
@@ -3238,6 +3336,9 @@ int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, cons
     IncArgs a{};
     a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.cap = f->cap; a.gamma = f->dSampE; a.strideG = ldE; a.off = off; a.mask = d.mask;
     a.info = f->dNeesOut;
+    // (the lift factors Sigma[6:, 6:] in the scratch image: the draw's factor has been consumed by sampTrmm)
+    rc = liftEnqueue(f, f->dSampE, ldE, off, d.mask, f->dNeesOut, false, a);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, a);
     HIPC(hipGetLastError());
     f->csValid = false;
@@ -3289,6 +3390,7 @@ int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh,
     for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
     if (!linear::argsOk(m, H, ldh, resid, R, mask, gamma, ldg, B, N.data())) return EQF_ERR_INVALID;
     int rc = linAlloc(f);
+    if (!rc) rc = liftAlloc(f, lift::callFactors(liftCallKind(f), maxN(f)));
     if (rc) return rc;
     if (local) {
         rc = launchLocal(f, 0, B, false);  // (only writes the J records)
@@ -3318,14 +3420,16 @@ int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh,
     rc = profiled(f, EQF_PROF_LIN_ROWS, [&] { hipLaunchKernelGGL(k_lin_rows, dim3(B), dim3(256), 0, f->stream, a); });
     if (!rc) rc = profiled(f, EQF_PROF_LIN_GAIN, [&] { hipLaunchKernelGGL(k_lin_gain, dim3(nt, B), dim3(256), kLinGainLdsBytes, f->stream, a); });
     if (!rc) rc = profiled(f, EQF_PROF_LIN_SOLVE, [&] { hipLaunchKernelGGL(k_lin_solve, dim3(B), dim3(256), 0, f->stream, a); });
-    if (!rc)
-        rc = profiled(f, EQF_PROF_LIN_DOWNDATE,
-            [&] { hipLaunchKernelGGL(k_lin_downdate, dim3(linear::triTiles(nt), B), dim3(256), 0, f->stream, a); });
-    if (rc) return rc;
     // the group step, behind the solve's verdict (entry 3 of the record, where eqf_nees.hpp's info sits)
     IncArgs ia{};
     ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = f->dLinWs + wl.offGamma(); ia.strideG = wl.stride();
     ia.off = 0; ia.mask = nullptr; ia.info = f->dLinOut;
+    // the lift reads the Sigma the call started from and may still refuse the filter: in front of the downdate
+    if (!rc) rc = liftEnqueue(f, ia.gamma, ia.strideG, 0, nullptr, f->dLinOut, true, ia);
+    if (!rc)
+        rc = profiled(f, EQF_PROF_LIN_DOWNDATE,
+            [&] { hipLaunchKernelGGL(k_lin_downdate, dim3(linear::triTiles(nt), B), dim3(256), 0, f->stream, a); });
+    if (rc) return rc;
     hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, ia);
     HIPC(hipGetLastError());
     f->csValid = false;  // (C Sigma / S left by an earlier burst describe the old Sigma and the old landmarks)
@@ -3342,13 +3446,13 @@ int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh,
         const double* o = hO.data() + size_t(b) * kLinHead;
         const int info = int(o[3]);
         if (report) {
-            const bool solved = info == 0 || info == 2;
+            const bool solved = lift::updateSolved(info);
             const double nan = std::nan("");
             report[b].nis = solved ? o[0] : nan;
             report[b].logdet_S = solved ? o[1] : nan;
             report[b].loglik = solved ? o[2] : nan;
             report[b].dof = m;
-            report[b].info = info;
+            report[b].info = lift::mergeInfo(info);
         }
         if (gamma) linear::unpackGamma(hG.data() + size_t(b) * f->ld, N[b], gamma + size_t(b) * ldg, info != 0);
     }
@@ -3429,6 +3533,7 @@ int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, cons
     const blocks::SmallLayout sl{B, stride, rows};
     const blocks::WorkLayout wl{f->ld, stride, rows, kDRec};
     int rc = blkAlloc(f, sl, wl);
+    if (!rc) rc = liftAlloc(f, lift::callFactors(liftCallKind(f), maxN(f)));
     if (rc) return rc;
     if (!f->blkLdsSet)  // (dynamic LDS beyond 64 KB: see allowUpdateLds; enqueueFactor sets its own kernels' and the flag)
         HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_blk_downdate), hipFuncAttributeMaxDynamicSharedMemorySize, kBlkDownLdsBytes));
@@ -3470,11 +3575,14 @@ int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, cons
     if (rc) return rc;
     hipLaunchKernelGGL(k_blk_gamma, dim3(nt, B), dim3(64), 0, f->stream, a);
     hipLaunchKernelGGL(k_blk_tail, dim3(B), dim3(256), 0, f->stream, a);
-    hipLaunchKernelGGL(k_blk_downdate, dim3(blocks::triTiles(nt), B), dim3(256), kBlkDownLdsBytes, f->stream, a);
     // the group step, behind the tail's verdict (entry 3 of the record, where eqf_nees.hpp's info sits)
     IncArgs ia{};
     ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = f->dBlkWs + wl.offGamma(); ia.strideG = wl.strideD();
     ia.off = 0; ia.mask = nullptr; ia.info = f->dBlkOut;
+    // the lift reads the Sigma the call started from and may still refuse the filter: in front of the downdate
+    rc = liftEnqueue(f, ia.gamma, ia.strideG, 0, nullptr, f->dBlkOut, true, ia);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_blk_downdate, dim3(blocks::triTiles(nt), B), dim3(256), kBlkDownLdsBytes, f->stream, a);
     hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, ia);
     HIPC(hipGetLastError());
     f->csValid = false;  // (C Sigma / S left by an earlier burst describe the old Sigma)
@@ -3494,13 +3602,13 @@ int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, cons
         const int* u = hU.data() + size_t(b) * wl.strideI();
         const int word = int(o[3]), info = word == blocks::kInfoIdle ? 0 : word, cnt = word == 3 ? 0 : u[wl.offCount()];
         if (report) {
-            const bool solved = word == 0 || word == 2;
+            const bool solved = lift::updateSolved(word);
             const double nan = std::nan("");
             report[b].nis = solved ? o[0] : (word == blocks::kInfoIdle ? 0.0 : nan);
             report[b].logdet_S = solved ? o[1] : (word == blocks::kInfoIdle ? 0.0 : nan);
             report[b].loglik = solved ? o[2] : (word == blocks::kInfoIdle ? 0.0 : nan);
             report[b].dof = rows * cnt;
-            report[b].info = info;
+            report[b].info = lift::mergeInfo(info);
         }
         if (used)
             for (int k = 0; k < stride; ++k) used[size_t(b) * stride + k] = (word != 3 && k < nk[b]) ? (unsigned char)u[wl.offUsed() + k] : 0;

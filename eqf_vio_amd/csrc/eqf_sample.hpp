@@ -13,7 +13,9 @@
 //   k_apply_increment  bias += gamma[0:6], X <- VIOExp(liftInnovation(gamma[6:], xi0)) X  (VIOFilter.cpp:292-296 with useInnovationLift =
 //                      false; EqFMatrices.cpp:35-67, VIOGroup.cpp:92-110, :245-255): the arithmetic of updateFinishBody's plain branch,
 //                      expression for expression, as a launch of its own -- one workgroup per filter, lane 0 the SE(3) and scalar part, the
-//                      other lanes the landmarks.  Sigma, xi0, the clock and the integrator are not touched.
+//                      other lanes the landmarks.  Sigma, xi0, the clock and the integrator are not touched.  With the option
+//                      "innovation_lift" on, k_lift_tail (eqf_lift.hpp) runs in front of it and moves the filters that take the bundleLift;
+//                      this kernel passes over them (IncArgs::lift) and moves the others exactly as before.
 #pragma once
 #include "eqf_chol64.hpp"
 #include "eqf_device.hpp"
@@ -88,6 +90,8 @@ struct IncArgs {
     int off;
     const unsigned char* mask;  // [B] or nullptr: 0 leaves the filter alone
     const double* info;         // eqf_nees.hpp's result records [B][kNeesHead + kNeesRhs] or nullptr: a failed factorisation leaves it alone
+    const double* lift;         // eqf_lift.hpp's records [B][liftStride] or nullptr: a filter whose entry 0 (the kind of its lift) is not 0
+    int liftStride;             // has been dealt with by k_lift_tail
 };
 
 // grid = B, block = 256
@@ -95,6 +99,7 @@ __global__ __launch_bounds__(256) void k_apply_increment(IncArgs a) {
     const int b = blockIdx.x, tid = threadIdx.x;
     if (a.mask && !a.mask[b]) return;
     if (a.info && a.info[(long long)b * (kNeesHead + kNeesRhs) + 3] != 0.0) return;
+    if (a.lift && a.lift[(long long)b * a.liftStride] != 0.0) return;
     Glob& g = a.g[b];
     const int N = g.N, cap = a.cap, n = kLm0 + 3 * N;
     const double* G = a.gamma + (long long)b * a.strideG;

@@ -271,8 +271,38 @@ int eqf_set_imu_burst(eqf_filter* f, int max_steps);
  *   "innovation_stats" 0 (default) | 1: every vision update that actually runs also leaves its innovation statistics (eqf_get_innovation_stats,
  *       below): one small launch behind the update's own (csrc/eqf_innov.hpp).  With 0 the launches and every output bit of an update are
  *       what they are without the option.  EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle; EQF_ERR_HIP (option unchanged) if the
- *       records cannot be allocated.  Switching the option forgets the statistics of the last update. */
+ *       records cannot be allocated.  Switching the option forgets the statistics of the last update.
+ *   "innovation_lift" 0 (default) | 1: how eqf_update_linear, eqf_update_landmarks, eqf_apply_increment and eqf_perturb_filters turn their
+ *       increment into a group step.  0: the plain lift VIOExp(liftInnovation(gamma_e, xi0)), whatever the handle's settings say; every
+ *       output bit of those calls is what it is without the option.  1: what eqf_process_vision does with the handle's useInnovationLift /
+ *       useDiscreteInnovationLift -- the reference's bundleLift (EqFMatrices.cpp:173-252), a weighted least squares over yaw and position
+ *       weighted by Sigma_e^-1 that moves the POSE so that the inertial landmark positions stay as still as possible (see
+ *       eqf_get_lift_report, below).  Any other value: EQF_ERR_INVALID.  EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle. */
 int eqf_set_option(eqf_filter* f, const char* name, int value);
+/* The lift of the most recent eqf_update_linear, eqf_update_landmarks, eqf_apply_increment or eqf_perturb_filters, for filter b
+ * (csrc/eqf_lift.hpp).  With the option "innovation_lift" at 1 and useInnovationLift set, a filter of at least two landmarks that takes part
+ * in such a call is moved by bundleLift(gamma_e, xi0, X, Sigma_e), all in fp64, with Sigma_e = Sigma[6:, 6:] of the Sigma the call STARTED
+ * from (as processVisionData passes it):
+ *   gamma_e = gamma[6:], g2 = gamma_e[0:2], gamma_L = gamma_e[5:], eta0 the unit gravity direction of xi0,
+ *   dUw = -eta0^x stereoSphereChartInvDiff(0, eta0) g2,   dU_f = ((I - eta0 eta0^T) dUw ; 0),
+ *   Z_P ((5 + 3 N) x 6): five zero rows, then Qhat_i R_C^T [(x0 - pHat_i)^x R0 , R0] per landmark,
+ *   Sigma_e = L L^T (blocked Cholesky on the matrix cores),  Zt = L^-1 Z_P,  z = L^-1 [0; gamma_L],  G6 = Zt^T Zt,  h = Zt^T z,
+ *   K = [(eta0; 0) | (0; I3)]:   K^T G6 K x = K^T (-h - G6 dU_f)  (4 x 4, partial pivoting),   DeltaU = dU_f + K x,
+ * then X <- Delta X with liftTotalSpaceInnovationDiscrete (useDiscreteInnovationLift = 1, EqFMatrices.cpp:254-275) or
+ * VIOExp(liftTotalSpaceInnovation) (:69-96), and bias += gamma[0:6].  Sigma is not touched by the lift.  A filter with fewer than two
+ * landmarks (3 N equations for 4 unknowns) takes the plain lift.  The lift's verdict comes before any effect: if Sigma_e is not positive
+ * definite or any value that would be written is not finite the filter keeps every bit, Sigma included (info = 4; an update reports
+ * info = 4 in its eqf_linear_report too); eqf_device_error and the sticky flag are not touched.  Bit for bit the same from run to run and
+ * for a filter alone in a handle or anywhere in a batch (no atomics, one fixed summation order).  EQF_ERR_INVALID for bad arguments or
+ * before the first such call.  Synchronises.  Not covered: the partitioned filter (eqf_tf_*, eqf_tiled_*). */
+typedef struct eqf_lift_report {
+    int kind;          /* 0 plain lift (option 0, useInnovationLift = 0, or N < 2); 1 bundleLift + continuous lift; 2 bundleLift + discrete lift */
+    int info;          /* 0 applied; 3 the filter took no part (masked, gated, update's own info != 0, dof = 0); 4 lift failed: untouched */
+    double DeltaU[6];  /* se(3) part of the lifted innovation (EqFMatrices.cpp:243); the plain lift's (dUw; 0) for kind 0; NaN unless info = 0 */
+    double min_pivot;  /* smallest squared pivot of Sigma_e's factor (NaN for kind 0) */
+    double pivot_ratio;/* min |pivot| / max |pivot| of the 4 x 4 elimination (NaN for kind 0) */
+} eqf_lift_report;
+int eqf_get_lift_report(eqf_filter* f, int b, eqf_lift_report* out);
 /* What the update's factorisation S = C Sigma C^T + R = L L^T and z = L^-1 delta (VIOFilter.cpp:276-280 forms S.inverse() instead) say about
  * the most recent vision update of filter b -- the numbers a filter is tuned by, which need the PRE-update Sigma that no getter can reach:
  *   nis = delta^T S^-1 delta = z^T z;  logdet_S = 2 sum_k log L_kk;  dof = 2 N of that update;
@@ -365,7 +395,8 @@ int eqf_sample_sigma(eqf_filter* f, int local, int first, int nsamp, const doubl
  * gamma_b = gamma[b * ldg + .] in the reference index map (the coordinates of eqf_get_sigma and of eqf_get_last_update's gamma),
  *   bias += gamma_b[0:6],   X <- VIOExp(liftInnovation(gamma_b[6:], xi0)) X
  * -- what processVisionData does with useInnovationLift = false (VIOFilter.cpp:292-296, EqFMatrices.cpp:35-67, VIOGroup.cpp:92-110,
- * :245-255), WHATEVER the handle's lift settings are (bundleLift needs a factorisation of Sigma_e, which is an update's business).  Sigma,
+ * :245-255) BY DEFAULT, whatever the handle's lift settings are; with the option "innovation_lift" at 1 the step follows those settings
+ * (bundleLift from the present Sigma, eqf_get_lift_report; a lift that fails leaves the filter untouched).  Sigma,
  * xi0, the clock, the integrator, the ids, eqf_get_last_update, the innovation statistics and the gate report stay as they are; a masked-out
  * filter keeps every bit.  ldg >= 11 + 3 N_b for every b.  A NaN or Inf in the increment of a filter that takes part refuses the call
  * (EQF_ERR_INVALID, like every bad argument before any effect).  Settles what the handle has deferred first, enqueues one launch
@@ -376,7 +407,7 @@ int eqf_apply_increment(eqf_filter* f, const double* gamma, int ldg, const unsig
  * scale[b] == 0 leaves filter b untouched, every bit (roughen only the duplicates of a resample); so does a failed factorisation (info != 0)
  * and a product that is not finite.  With stats == NULL the call enqueues and returns, with stats [batch] it synchronises and reports per
  * filter as eqf_sample_sigma does.  EQF_ERR_INVALID for bad arguments (a scale that is not finite among them), before any effect;
- * EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle. */
+ * EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle.  The step is eqf_apply_increment's, so it follows the option "innovation_lift" too. */
 int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, const double* scale /* [batch] or NULL */,
     eqf_sigma_stats* stats /* [batch] or NULL */);
 /* A measurement update with 1 <= m <= 16 caller-supplied LINEAR rows, for every filter of the handle in one call (csrc/eqf_linear.hpp): a
@@ -390,7 +421,9 @@ int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, cons
  * Per filter that takes part, in fp64 (Ht = H or H J):
  *   B = Sigma Ht^T,  S = Ht B + R = L L^T,  Y = L^-1 B^T,  z = L^-1 resid,  gamma = Y^T z,  Sigma <- Sigma - Y^T Y (in place, bit-for-bit
  *   symmetric when Sigma was),  bias += gamma[0:6],  X <- VIOExp(liftInnovation(gamma[6:], xi0)) X  -- eqf_apply_increment's step with
- *   gamma: ALWAYS the plain lift, whatever the handle's lift settings are (bundleLift needs Sigma_e's factorisation).
+ *   gamma: BY DEFAULT the plain lift, whatever the handle's lift settings are.  With the option "innovation_lift" at 1 the step follows
+ *   those settings: after gamma is known and before the downdate commits, the pre-update Sigma_e is factored and bundleLift forms Delta
+ *   (eqf_get_lift_report); the filter is touched only if the update's own verdict is 0 AND the lift succeeded.
  * xi0, the clock, the integrator, the ids, eqf_get_last_update, the innovation statistics, the gate report, the outlier gate and the
  * sticky flag stay as they are; eqf_device_error is never touched.  Trouble of ONE filter goes into report[b].info and that filter keeps
  * every bit, Sigma included:
@@ -403,7 +436,7 @@ int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, cons
  * finite; a gate that is NaN or <= 0.  EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle.  EQF_ERR_HIP if the workspace, allocated by the
  * first call from capacity and batch, cannot be had (the handle stays as it was).  Bit for bit the same from run to run and for a filter
  * alone in a handle or anywhere in a batch (no atomics, one fixed summation order).
- * Not covered: the partitioned filter (eqf_tf_*, eqf_tiled_*), fp32 handles, the innovation lift (bundleLift), m > 16. */
+ * Not covered: the partitioned filter (eqf_tf_*, eqf_tiled_*), fp32 handles, m > 16; the innovation lift (bundleLift) by default only. */
 typedef struct eqf_linear_report {
     double nis;       /* r^T S^-1 r = z^T z                                        */
     double logdet_S;  /* 2 sum log L_kk                                            */
@@ -411,6 +444,7 @@ typedef struct eqf_linear_report {
     int dof;          /* m                                                          */
     int info;         /* 0 applied; 1 S not positive definite or a non-finite value met: filter untouched (nis, logdet_S, loglik NaN);
                          2 gated (nis > gate): untouched; 3 masked out: untouched (NaN);
+                         4 innovation lift failed: Sigma_e not positive definite or a non-finite value; filter untouched;
                          -1 local = 1 and this filter's gravity chart is singular: untouched (NaN) */
 } eqf_linear_report;
 int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh, const double* resid, const double* R, double gate,
@@ -435,8 +469,8 @@ int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh,
  * Per filter that takes part, in fp64, with Ht the block-sparse m x n matrix of the entries that take part, m = rows * (their number),
  * and Sigma read by its lower triangle:
  *   B = Sigma Ht^T,  S = Ht B + blockdiag(R_k) = L L^T,  Y = L^-1 B^T,  z = L^-1 resid,  gamma = Y^T z,  Sigma <- Sigma - Y^T Y (in place,
- *   bit-for-bit symmetric),  bias += gamma[0:6],  X <- VIOExp(liftInnovation(gamma[6:], xi0)) X  -- eqf_apply_increment's step: ALWAYS the
- *   plain lift.
+ *   bit-for-bit symmetric),  bias += gamma[0:6],  X <- VIOExp(liftInnovation(gamma[6:], xi0)) X  -- eqf_apply_increment's step: BY DEFAULT
+ *   the plain lift; with the option "innovation_lift" at 1 the handle's lift, as in eqf_update_linear (info = 4 where it fails).
  * report[b] is eqf_update_linear's record with the same info codes and dof = m; gate is the chi-square threshold on the joint nis.  A
  * filter whose info is not 0 keeps every bit; a filter with no entry taking part reports info = 0, dof = 0, nis = logdet_S = loglik = 0
  * and is untouched.  mask, gamma, ldg as in eqf_update_linear.  xi0, the clock, the integrator, the ids, eqf_get_last_update, the
@@ -449,7 +483,7 @@ int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh,
  * EQF_ERR_HIP if the workspace, allocated on first need and grown when stride or rows ask for more ((rows * stride + 3 capacity)
  * x rows * stride doubles per filter), cannot be had (the handle stays as it was).  Bit for bit the same from run to run and for a filter
  * alone in a handle or anywhere in a batch; the number of kernel launches depends on stride and rows only.
- * Not covered: the partitioned filter, fp32 handles, the innovation lift, a second camera offset in the state. */
+ * Not covered: the partitioned filter, fp32 handles, a second camera offset in the state; the innovation lift by default only. */
 int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk /* [batch] */, const int* ids /* [batch][stride] */, int stride,
     const double* Hb /* [batch][stride][rows][3] */, const double* resid /* [batch][stride][rows] */,
     const double* Rb /* [batch][stride][rows][rows] */, double gate, double lm_gate, const unsigned char* mask /* [batch] or NULL */,
