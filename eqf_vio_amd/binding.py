@@ -133,7 +133,7 @@ EXPORTED_SYMBOLS = [
     "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_forecast", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
     "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters", "eqf_update_linear", "eqf_update_landmarks",
     "eqf_get_mixture_moments", "eqf_merge_filters", "eqf_debug_mixture_launches", "eqf_debug_sigma_pad",
-    "eqf_get_merge_costs", "eqf_score_vision", "eqf_get_lift_report",
+    "eqf_get_merge_costs", "eqf_score_vision", "eqf_get_lift_report", "eqf_edit_landmarks",
     "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
     "eqf_set_sigma", "eqf_set_state", "eqf_copy_filters", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
@@ -220,6 +220,8 @@ def lib():
                                            C.POINTER(C.c_ubyte)]
         if hasattr(L, "eqf_get_lift_report"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
             L.eqf_get_lift_report.argtypes = [vp, C.c_int, C.POINTER(LiftReport)]
+        if hasattr(L, "eqf_edit_landmarks"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
+            L.eqf_edit_landmarks.argtypes = [vp, _ip, _ip, C.c_int, _ip, _ip, C.c_int, _dp, _dp, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]
         if hasattr(L, "eqf_set_outlier_gate"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
             L.eqf_set_outlier_gate.argtypes = [vp, C.c_int, C.c_double]
             L.eqf_get_outlier_gate.argtypes = [vp, _ip, _dp]
@@ -1010,6 +1012,55 @@ class FilterBatch:
         if n == 0:  # (an empty numpy array may have no address: the C ABI wants two arrays also for n = 0)
             di = si = np.zeros(1, dtype=np.int32)
         _check(lib().eqf_copy_filters(self._h, src._h, n, di.ctypes.data_as(_ip), si.ctypes.data_as(_ip)), "eqf_copy_filters")
+
+    def edit_landmarks(self, remove=None, insert=None):
+        """Explicit landmark removal and insertion with priors for EVERY filter of the handle in one call, on the device
+        (include/eqf_vio_amd.h: eqf_edit_landmarks).  remove: a list with one array of ids per filter (strictly ascending; may be empty or None), or
+        None.  insert: a list with one (ids, p, P) per filter -- ids (K_b,) strictly ascending, p (K_b, 3) camera-frame positions, P
+        (K_b, 3, 3) their covariances (lower triangles read; consistency.depth_prior / triangulation_prior write the usual ones) -- or None
+        per filter or altogether.  A single-filter handle also takes the id array and the triple themselves.  Per filter the removals come
+        first, then the insertions are appended in the order given; an id in both lists is replaced.
+        Returns (removed, inserted): lists with one uint8 array per filter -- removed 1 gone, 0 not in the state; inserted 1 done, 0 already
+        in the state after the removals, 2 values rejected (not finite, p = 0, P not positive definite).  The verdicts are the host's: the
+        call does not wait for the device."""
+        B = self.B
+        if remove is not None and B == 1 and not (isinstance(remove, (list, tuple)) and len(remove) == 1 and np.ndim(remove[0]) == 1):
+            remove = [remove]
+        if insert is not None and B == 1 and isinstance(insert, tuple) and len(insert) == 3 and np.ndim(insert[0]) <= 1:
+            insert = [insert]
+        rem = [np.zeros(0, dtype=np.int32)] * B if remove is None else [
+            np.zeros(0, dtype=np.int32) if r is None else np.asarray(r, dtype=np.int32).reshape(-1) for r in remove]
+        insl = [None] * B if insert is None else list(insert)
+        if len(rem) != B or len(insl) != B:
+            raise ValueError("edit_landmarks: one item per filter")
+        insl = [(np.zeros(0, dtype=np.int32), np.zeros((0, 3)), np.zeros((0, 3, 3))) if t is None else
+                (np.asarray(t[0], dtype=np.int32).reshape(-1), np.asarray(t[1], dtype=np.float64).reshape(-1, 3),
+                 np.asarray(t[2], dtype=np.float64).reshape(-1, 3, 3)) for t in insl]
+        for i, p, P in insl:
+            if not (len(i) == len(p) == len(P)):
+                raise ValueError("edit_landmarks: ids, p and P of a filter differ in length")
+        rs, istr = max(1, max(len(r) for r in rem)), max(1, max(len(t[0]) for t in insl))
+        nr = np.array([len(r) for r in rem], dtype=np.int32)
+        ni = np.array([len(t[0]) for t in insl], dtype=np.int32)
+        rid, iid = np.zeros((B, rs), dtype=np.int32), np.zeros((B, istr), dtype=np.int32)
+        pp, PP = np.zeros((B, istr, 3)), np.zeros((B, istr, 3, 3))
+        for b in range(B):
+            rid[b, :nr[b]] = rem[b]
+            iid[b, :ni[b]], pp[b, :ni[b]], PP[b, :ni[b]] = insl[b]
+        removed, inserted = np.zeros((B, rs), dtype=np.uint8), np.zeros((B, istr), dtype=np.uint8)
+        up = C.POINTER(C.c_ubyte)
+        _check(lib().eqf_edit_landmarks(self._h, nr.ctypes.data_as(_ip), rid.ctypes.data_as(_ip), rs, ni.ctypes.data_as(_ip),
+                                        iid.ctypes.data_as(_ip), istr, _p(pp), _p(PP), removed.ctypes.data_as(up), inserted.ctypes.data_as(up)),
+               "eqf_edit_landmarks")
+        return [removed[b, :nr[b]].copy() for b in range(B)], [inserted[b, :ni[b]].copy() for b in range(B)]
+
+    def remove_landmarks(self, ids):
+        """edit_landmarks(remove=ids): the verdicts per filter (1 gone, 0 not in the state)."""
+        return self.edit_landmarks(remove=ids)[0]
+
+    def insert_landmarks(self, insert):
+        """edit_landmarks(insert=insert): the verdicts per filter (1 done, 0 already in the state, 2 values rejected)."""
+        return self.edit_landmarks(insert=insert)[1]
 
     def resample(self, parents):
         """In place: filter b continues from what filter parents[b] was before the call (consistency.systematic_resample gives parents

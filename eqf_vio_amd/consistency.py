@@ -418,6 +418,91 @@ def position_rows(p_hat, p_meas):
     return np.eye(3), np.asarray(p_meas, dtype=float) - np.asarray(p_hat, dtype=float)
 
 
+# ---- explicit landmark edits (FilterBatch.edit_landmarks): the host statement of the edit and the usual priors
+def edit_landmarks_host(state_dump, remove_ids, insert_ids, p, P):
+    """What FilterBatch.edit_landmarks does to ONE filter, on a dump_state dictionary, in numpy: a new dictionary with ids, origin p, group
+    Qq / Qa and sigma (reference index map, 11 + 3N) edited and everything else as it was; restore_state of it is the host route the device
+    call replaces.  The named ids the state holds leave (rows and columns of sigma with them, the order of the rest kept); then the
+    insertions are appended in the order given: p0 = p, Q the identity, zero rows and columns but for the landmark's own block, which is
+    P's lower triangle mirrored.  Entries the call would not apply (an id still in the state, values rejected) are skipped by the same
+    rules.  Returns (new dump, removed, inserted)."""
+    ids = [int(x) for x in np.asarray(state_dump["ids"]).reshape(-1)]
+    rem = [int(x) for x in np.asarray(remove_ids).reshape(-1)]
+    iid = [int(x) for x in np.asarray(insert_ids).reshape(-1)]
+    p = np.asarray(p, dtype=float).reshape(-1, 3)
+    P = np.asarray(P, dtype=float).reshape(-1, 3, 3)
+    removed = np.array([int(r in ids) for r in rem], dtype=np.uint8)
+    keep = [i for i, x in enumerate(ids) if x not in set(rem)]
+    left = {ids[i] for i in keep}
+    inserted = np.zeros(len(iid), dtype=np.uint8)
+    for k, i in enumerate(iid):
+        if i in left:
+            continue
+        low = P[k][np.tril_indices(3)]
+        ok = bool(np.all(np.isfinite(p[k])) and np.all(np.isfinite(low)) and np.any(p[k] != 0.0))
+        if ok:
+            S = mirror_lower(P[k])
+            d0 = S[0, 0]
+            ok = bool(d0 > 0)
+            if ok:
+                l10, l20 = S[1, 0] / np.sqrt(d0), S[2, 0] / np.sqrt(d0)
+                d1 = S[1, 1] - l10 * l10
+                ok = bool(d1 > 0) and bool(S[2, 2] - l20 * l20 - ((S[2, 1] - l20 * l10) / np.sqrt(d1)) ** 2 > 0)
+        inserted[k] = 1 if ok else 2
+    acc = [k for k in range(len(iid)) if inserted[k] == 1]
+    nK, nA = len(keep), len(acc)
+    rows = list(range(11)) + [11 + 3 * i + c for i in keep for c in range(3)]
+    Sold = np.asarray(state_dump["sigma"], dtype=float)
+    S = np.zeros((11 + 3 * (nK + nA), 11 + 3 * (nK + nA)))
+    S[:11 + 3 * nK, :11 + 3 * nK] = Sold[np.ix_(rows, rows)]
+    for j, k in enumerate(acc):
+        a = 11 + 3 * (nK + j)
+        S[a:a + 3, a:a + 3] = mirror_lower(P[k])
+    out = dict(state_dump)
+    o, g = dict(state_dump["origin"]), dict(state_dump["group"])
+    o["p"] = np.concatenate([np.asarray(o["p"], dtype=float).reshape(-1, 3)[keep], p[acc]]).reshape(-1, 3)
+    g["Qq"] = np.concatenate([np.asarray(g["Qq"], dtype=float).reshape(-1, 4)[keep], np.tile([1.0, 0.0, 0.0, 0.0], (nA, 1))]).reshape(-1, 4)
+    g["Qa"] = np.concatenate([np.asarray(g["Qa"], dtype=float).reshape(-1)[keep], np.ones(nA)])
+    out.update(ids=np.array([ids[i] for i in keep] + [iid[k] for k in acc], dtype=np.int32), origin=o, group=g, sigma=S)
+    return out, removed, inserted
+
+
+def depth_prior(y, rng, var_rng, var_y):
+    """A landmark seen along the unit bearing y at range rng (depth camera, lidar): p = rng y, P = var_rng y y^T + rng^2 var_y (I - y y^T)
+    -- variance var_rng along the ray, rng^2 var_y across it (var_y: the bearing's variance on the sphere, per axis).  Returns (p (3,),
+    P (3, 3)), P symmetric bit for bit."""
+    y = np.asarray(y, dtype=float).reshape(3)
+    rng, var_rng, var_y = float(rng), float(var_rng), float(var_y)
+    yy = np.outer(y, y)
+    return rng * y, var_rng * yy + (rng * rng * var_y) * (np.eye(3) - yy)
+
+
+def triangulation_prior(y1, y2, q_21, t_21, var_y):
+    """A landmark seen by both cameras of a rigid stereo rig along the unit bearings y1 (camera 1) and y2 (camera 2), (q_21, t_21) the pose
+    of camera 2 in camera 1's frame as in stereo_rows.  Everything in camera 1's frame: the rays start at c_1 = 0 and c_2 = t_21 with the
+    directions y_1 and R_21 y2; p is their least-squares intersection, the solution of the 3 x 3 normal equations of
+    sum_k |(I - y_k y_k^T)(p - c_k)|^2, and P = (sum_k (I - y_k y_k^T) / (d_k^2 var_y))^-1 with d_k = |p - c_k|.
+    P is a FIRST-ORDER covariance (the bearings' noise pushed through the linearised intersection): along the ray it grows like
+    d^4 / baseline^2 var_y, so for a distant point it says little more than "somewhere along this ray", and the point's true distribution is
+    far from Gaussian there.  Raises ValueError for parallel rays (a normal matrix that is not positive definite).  Returns (p, P)."""
+    y1 = np.asarray(y1, dtype=float).reshape(3)
+    R21 = quat_to_matrix(np.asarray(q_21, dtype=float))
+    c = [np.zeros(3), np.asarray(t_21, dtype=float).reshape(3)]
+    ys = [y1, R21 @ np.asarray(y2, dtype=float).reshape(3)]
+    M = [np.eye(3) - np.outer(y, y) for y in ys]
+    A = M[0] + M[1]
+    try:
+        L = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:
+        raise ValueError("triangulation_prior: the rays are parallel") from None
+    if not np.all(np.isfinite(L)) or np.min(np.diag(L)) ** 2 <= 4.0 * np.finfo(float).eps:
+        raise ValueError("triangulation_prior: the rays are parallel")
+    p = np.linalg.solve(A, M[0] @ c[0] + M[1] @ c[1])
+    W = sum(Mk / (float(np.dot(p - ck, p - ck)) * float(var_y)) for Mk, ck in zip(M, c))
+    P = np.linalg.inv(W)
+    return p, 0.5 * (P + P.T)
+
+
 def landmark_blocks_matrix(N, idx, Ht):
     """The block-sparse measurement matrix as a dense one: (rows * K, 11 + 3N) with block k (rows, 3) at landmark idx[k]'s columns."""
     Ht = np.asarray(Ht, dtype=float)

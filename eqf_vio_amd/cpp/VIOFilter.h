@@ -447,6 +447,33 @@ class VIOFilter {
         const int zero = 0;
         check(eqf_copy_filters(handle_.get(), other.handle_.get(), 1, &zero, &zero), "eqf_copy_filters");
     }
+    // The landmarks `ids` (strictly ascending) leave the filter, on the device (eqf_edit_landmarks): their rows and columns of the covariance
+    // go, the order of the rest is kept.  Returns one verdict per id: 1 gone, 0 not in the state (no error).  Throws std::runtime_error for
+    // ids that are not strictly ascending.
+    std::vector<unsigned char> removeLandmarks(const std::vector<int>& ids) {
+        const int K = int(ids.size()), zero = 0;
+        std::vector<unsigned char> removed(size_t(K ? K : 1), 0);
+        check(eqf_edit_landmarks(handle_.get(), &K, K ? ids.data() : &zero, K ? K : 1, nullptr, nullptr, 0, nullptr, nullptr, removed.data(),
+                  nullptr),
+            "eqf_edit_landmarks");
+        removed.resize(size_t(K));
+        return removed;
+    }
+    // New landmarks `ids` (strictly ascending) behind the ones the filter has, in the order given, where the CALLER measured them: p (3 per
+    // id) the camera-frame positions, P (3 x 3 per id, row-major, lower triangles read) the covariances of their errors (a range, a stereo
+    // triangulation); no cross-covariance with the rest of the state.  Returns one verdict per id: 1 done, 0 the id is already in the state, 2
+    // values rejected (not finite, p = 0, P not positive definite).  Throws std::runtime_error for ids that are not strictly ascending, or
+    // beyond the capacity.
+    std::vector<unsigned char> insertLandmarks(const std::vector<int>& ids, const double* p, const double* P) {
+        const int K = int(ids.size()), zero = 0;
+        std::vector<unsigned char> inserted(size_t(K ? K : 1), 0);
+        std::vector<double> pad(9, 0.0);  // (K = 0 hands over one unread entry)
+        check(eqf_edit_landmarks(handle_.get(), nullptr, nullptr, 0, &K, K ? ids.data() : &zero, K ? K : 1, K ? p : pad.data(), K ? P : pad.data(),
+                  nullptr, inserted.data()),
+            "eqf_edit_landmarks");
+        inserted.resize(size_t(K));
+        return inserted;
+    }
     int lastStatus() const { return lastStatus_; }  // EQF_SKIPPED_* where the reference returns early
     eqf_filter* handle() const { return handle_.get(); }
 

@@ -44,6 +44,8 @@
 #include "eqf_score_host.hpp"
 #include "eqf_lift.hpp"
 #include "eqf_lift_host.hpp"
+#include "eqf_mapedit.hpp"
+#include "eqf_mapedit_host.hpp"
 
 using namespace eqf;
 
@@ -327,6 +329,10 @@ struct eqf_filter {
     char* dScTab = nullptr;
     size_t scTabBytes = 0;
     bool scoreLdsSet = false;
+    // explicit landmark edits (eqf_mapedit.hpp; eqf_edit_landmarks), allocated by the first call from capacity and batch: the plan's image
+    // (mapedit::Image) as a pinned copy and its device copy, and evMapEdit: the last upload from the pinned image has been read.  (Last.)
+    char *hMapEdit = nullptr, *dMapEdit = nullptr;
+    hipEvent_t evMapEdit = nullptr;
 };
 
 namespace {
@@ -1671,6 +1677,9 @@ void freeAll(eqf_filter* f) {
     hipFree(f->dScWs);
     hipFree(f->dScTab);
     hipFree(f->dMixTab);
+    hipFree(f->dMapEdit);
+    if (f->hMapEdit) hipHostFree(f->hMapEdit);
+    if (f->evMapEdit) hipEventDestroy(f->evMapEdit);
     if (f->hMixTab) hipHostFree(f->hMixTab);
     if (f->evMix) hipEventDestroy(f->evMix);
     for (auto e : f->evPool) hipEventDestroy(e);
@@ -2747,6 +2756,87 @@ int eqf_copy_filters(eqf_filter* dst, eqf_filter* src, int n, const int* dst_idx
     dst->csValid = false;
     dst->permOnDevice.clear();
     dst->editOnDevice.clear();
+    return EQF_OK;
+}
+
+// ---- explicit landmark removal and insertion with priors (eqf_mapedit.hpp; the host's decisions: eqf_mapedit_host.hpp)
+static_assert(mapedit::kPrior == kMapPrior && mapedit::kOk == EQF_OK && mapedit::kInvalid == EQF_ERR_INVALID &&
+                  mapedit::kCapacity == EQF_ERR_CAPACITY && mapedit::kUnsorted == EQF_ERR_UNSORTED,
+    "eqf_mapedit_host.hpp repeats the layout constants and the error codes");
+namespace {
+// the plan's image, once per handle; a failure leaves the handle as it was
+int mapEditAlloc(eqf_filter* f) {
+    if (f->hMapEdit) return EQF_OK;
+    const size_t bytes = mapedit::imageCapacityBytes(f->B, f->cap);
+    void *h = nullptr, *d = nullptr;
+    hipEvent_t ev = nullptr;
+    if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess ||
+        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        if (h) hipHostFree(h);
+        if (d) hipFree(d);
+        return EQF_ERR_HIP;
+    }
+    f->hMapEdit = static_cast<char*>(h);
+    f->dMapEdit = static_cast<char*>(d);
+    f->evMapEdit = ev;
+    return EQF_OK;
+}
+}  // namespace
+
+int eqf_edit_landmarks(eqf_filter* f, const int* n_remove, const int* remove_ids, int rstride, const int* n_insert, const int* insert_ids,
+    int istride, const double* p, const double* P, unsigned char* removed, unsigned char* inserted) {
+    if (!f) return EQF_ERR_INVALID;
+    GATE(f);  // (queued IMU calls and a pending gate first: the gate may still change the landmark lists)
+    const int B = f->B, cap = f->cap;
+    const mapedit::Args ma{n_remove, remove_ids, rstride, n_insert, insert_ids, istride, p, P};
+    mapedit::Plan pl;
+    int rc = mapedit::plan(f->ids, cap, ma, pl);
+    if (rc) return rc;
+    const bool work = pl.anyRemoved || pl.anyInserted;
+    if (work) {
+        rc = mapEditAlloc(f);
+        if (rc) return rc;
+    }
+    if (removed) std::copy(pl.removed.begin(), pl.removed.end(), removed);
+    if (inserted) std::copy(pl.inserted.begin(), pl.inserted.end(), inserted);
+    if (!work) return EQF_OK;
+    const mapedit::Image im = mapedit::imageLayout(B, cap, pl);
+    HIPC(hipEventSynchronize(f->evMapEdit));
+    mapedit::fillImage(f->ids, ma, pl, im, f->hMapEdit);
+    HIPC(hipMemcpyAsync(f->dMapEdit, f->hMapEdit, im.bytes(), hipMemcpyHostToDevice, f->stream));
+    HIPC(hipEventRecord(f->evMapEdit, f->stream));
+    MapEditArgs a{};
+    a.g = f->g[f->pG];
+    a.prior = reinterpret_cast<const double*>(f->dMapEdit + im.offPrior());
+    a.cnt = reinterpret_cast<const int*>(f->dMapEdit + im.offCounts());
+    a.map = reinterpret_cast<const int*>(f->dMapEdit + im.offMap());
+    a.ns = int(im.ns); a.cap = cap;
+    a.p0 = f->p0; a.Q = f->Q[f->pG]; a.lmc = f->lmc; a.scratch = f->dScratch; a.errflag = f->errflag;
+    a.sigmaStride = f->sigmaStride; a.ld = f->ld;
+    if (pl.anyRemoved) {
+        a.Sin = f->Sigma[f->pS]; a.Sout = f->Sigma[f->pS ^ 1];
+        const int nvn = kLm0 + 3 * pl.maxN;
+        const dim3 grid((nvn + 255) / 256, (nvn + 3) / 4, B);
+        rc = profiled(f, EQF_PROF_CHURN, [&] {
+            withSigmaType(f, [&](auto t) { hipLaunchKernelGGL(k_mapedit_move<decltype(t)>, grid, dim3(256), 0, f->stream, a); });
+        });
+    } else {
+        a.Sin = nullptr; a.Sout = f->Sigma[f->pS];
+        const long long work1 = (long long)3 * pl.maxNew * (kLm0 + 3 * pl.maxN) * 2;
+        const dim3 grid(int(std::max<long long>(1, std::min<long long>(1024, (work1 + 255) / 256))), B);
+        rc = profiled(f, EQF_PROF_CHURN, [&] {
+            withSigmaType(f, [&](auto t) { hipLaunchKernelGGL(k_mapedit_append<decltype(t)>, grid, dim3(256), 0, f->stream, a); });
+        });
+    }
+    if (rc) return rc;
+    HIPC(hipGetLastError());
+    if (pl.anyRemoved) f->pS ^= 1;
+    f->ids = std::move(pl.newIds);
+    // what the host caches per landmark set starts over
+    f->csValid = false;
+    f->permOnDevice.clear();
+    f->editOnDevice.clear();
     return EQF_OK;
 }
 

@@ -213,6 +213,43 @@ int eqf_set_state(eqf_filter* f, int b, int N, const int* ids, const double* pos
  * allocated on first need, cannot be had).  The sticky error flag of either handle is neither copied nor cleared, and a copy does not
  * count as a restore towards the recovery from bit 128 (eqf_device_error). */
 int eqf_copy_filters(eqf_filter* dst, eqf_filter* src, int n, const int* dst_idx, const int* src_idx);
+/* Explicit landmark removal and insertion with priors (csrc/eqf_mapedit.hpp; the host's decisions: csrc/eqf_mapedit_host.hpp).  Per filter
+ * the removals come first, then the insertions are appended behind what is left, in the order given; an id named in both lists is REPLACED:
+ * it leaves its slot and comes back last with the new prior.  Both id lists of a filter are strictly ascending; a NULL count array means
+ * "none for any filter".
+ *   Removal is removeLandmarkAtIndex (VIOFilter.cpp:421-427) for every named id the state holds: its rows and columns of Sigma go, p0, Q, the
+ *   per-landmark constants and the ids are compacted, the order of the rest is kept.  removed[b][k] = 1 gone, 0 the id is not in the state
+ *   (no error, nothing changes on its account).
+ *   Insertion is addNewLandmarks (:345-391) with the caller's values in place of the median depth and initialPointVariance: the origin
+ *   landmark is p0 = p (a camera-frame position, as eqf_get_state_estimate reports it), Q the identity, every new row and column of Sigma zero
+ *   except the landmark's own 3 x 3 block, which is the LOWER triangle of P, mirrored (the upper triangle is never read) and rounded to the
+ *   handle's precision.  With Q = I the origin chart and the estimate's chart agree on that block: P is the covariance of the camera-frame
+ *   position error (eqf_get_marginals gives it back in either chart).  inserted[b][k] = 1 done; 0 the id is already in the state after the
+ *   removals (its values are not looked at); 2 values rejected: an entry of p or of P's lower triangle is not finite, p = 0, or P has a
+ *   pivot <= 0 in its 3 x 3 Cholesky factorisation (judged in double precision on the caller's numbers).
+ * All verdicts are decided on the host from the caller's arrays and the handle's id lists before anything is enqueued: removed / inserted
+ * (either may be NULL) are complete at return, and an entry that is not applied changes no bit.  A landmark that passes the host check but
+ * lies on the pole of the landmark chart raises bit 16 of eqf_device_error, like a new landmark of a vision frame.
+ * Nothing of a filter but its landmarks is touched: xi0's pose and velocity, X.A, X.w, the bias, the clock, the integrator, the base block and
+ * the kept blocks of Sigma, the sticky flag and the options keep every bit -- also in a filter with nothing to do, or all of whose entries
+ * got verdict 0 or 2.  The records of the last update (eqf_get_last_update, eqf_get_innovation_stats, eqf_get_gate_report,
+ * eqf_get_lift_report) are NOT re-ordered: they stay in the order of the landmark set they were taken on.
+ * Afterwards every getter answers bit for bit like a handle restored through eqf_set_state from this handle's getters with the same edit
+ * applied on the host (consistency.edit_landmarks_host), and every later call gives the bits it gives on that handle: eqf_copy_filters'
+ * contract.  The result is the same from run to run and for a filter alone in a handle or anywhere in a batch (no atomics on values).
+ * Settles what the handle has deferred first (queued IMU calls, speculative gate), then enqueues ONE launch and returns without waiting for
+ * the device.  When some filter loses a landmark, every filter's Sigma moves once into the other buffer (the ping-pong parity is shared by
+ * the batch); a call in which no filter loses anything writes only the new rows, columns and blocks in place, O(n * new).  Any capacity:
+ * no list is held in LDS.  A stream uploaded by eqf_stream_upload stays valid: the next eqf_stream_vision does its bookkeeping against the
+ * edited set.
+ * Before any effect: EQF_ERR_INVALID (NULL handle; a negative stride; a count outside [0, stride]; a count > 0 whose id list -- or p or P --
+ * is NULL), EQF_ERR_UNSORTED (an id list of a filter not strictly ascending), EQF_ERR_CAPACITY (a filter would hold more than its capacity
+ * after its ACCEPTED insertions), EQF_ERR_HIP (the plan's device image, allocated by the first call that has work, cannot be had).
+ * EQF_PRECISION_F32 handles are supported. */
+int eqf_edit_landmarks(eqf_filter* f, const int* n_remove /* [batch] or NULL */, const int* remove_ids /* [batch][rstride] */, int rstride,
+    const int* n_insert /* [batch] or NULL */, const int* insert_ids /* [batch][istride] */, int istride,
+    const double* p /* [batch][istride][3] */, const double* P /* [batch][istride][3][3] */,
+    unsigned char* removed /* [batch][rstride] or NULL */, unsigned char* inserted /* [batch][istride] or NULL */);
 /* xi0.cameraOffset = T_IC for the whole batch (VIOFilter::setAuxiliaryData, VIOFilter.cpp:74-82, overwrites the value
  * taken from the settings at construction, :68).  q must be a unit quaternion (w,x,y,z). */
 int eqf_set_camera_offset(eqf_filter* f, const double* q, const double* x);
