@@ -134,6 +134,7 @@ EXPORTED_SYMBOLS = [
     "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters", "eqf_update_linear", "eqf_update_landmarks",
     "eqf_get_mixture_moments", "eqf_merge_filters", "eqf_debug_mixture_launches", "eqf_debug_sigma_pad",
     "eqf_get_merge_costs", "eqf_score_vision", "eqf_get_lift_report", "eqf_edit_landmarks",
+    "eqf_update_linear_schmidt", "eqf_update_landmarks_schmidt",
     "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
     "eqf_set_sigma", "eqf_set_state", "eqf_copy_filters", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
@@ -207,6 +208,12 @@ def lib():
         if hasattr(L, "eqf_update_landmarks"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
             L.eqf_update_landmarks.argtypes = [vp, C.c_int, C.c_int, _ip, _ip, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double,
                                                C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), _dp, C.c_int, C.POINTER(LinearReport)]
+        if hasattr(L, "eqf_update_linear_schmidt"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
+            L.eqf_update_linear_schmidt.argtypes = [vp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double, C.POINTER(C.c_ubyte), _ip, _ip,
+                                                    C.c_int, _dp, C.c_int, C.POINTER(LinearReport)]
+            L.eqf_update_landmarks_schmidt.argtypes = [vp, C.c_int, C.c_int, _ip, _ip, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double,
+                                                       C.POINTER(C.c_ubyte), _ip, _ip, C.c_int, C.POINTER(C.c_ubyte), _dp, C.c_int,
+                                                       C.POINTER(LinearReport)]
         if hasattr(L, "eqf_merge_filters"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
             L.eqf_get_mixture_moments.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.POINTER(MixtureReport)]
             L.eqf_merge_filters.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, C.POINTER(MixtureReport)]
@@ -688,7 +695,25 @@ class FilterBatch:
         _check(lib().eqf_get_lift_report(self._h, int(b), C.byref(r)), "eqf_get_lift_report")
         return dict(kind=r.kind, info=r.info, DeltaU=np.array(r.DeltaU[:]), min_pivot=r.min_pivot, pivot_ratio=r.pivot_ratio)
 
-    def update_linear(self, H, resid, R, local=True, gate=float("inf"), mask=None, want_gamma=False, stats=True):
+    def _consider(self, consider, what):
+        """consider: one id list per filter, or an int array (B, K) (a single-filter handle also takes the list itself) -> (n_consider,
+        ids [B][cstride], cstride)"""
+        if self.B == 1 and not (len(consider) == 1 and np.ndim(consider[0]) == 1):
+            consider = [np.asarray(consider, dtype=np.int32).reshape(-1)]
+        if len(consider) != self.B:
+            raise ValueError(f"{what}: consider takes one id list per filter")
+        if isinstance(consider, np.ndarray) and consider.ndim == 2:  # (B, K): every filter names K ids, one conversion
+            cid = np.ascontiguousarray(consider, dtype=np.int32)
+            return np.full(self.B, cid.shape[1], dtype=np.int32), (cid if cid.shape[1] else np.zeros((self.B, 1), dtype=np.int32)), max(1, cid.shape[1])
+        cl = [np.asarray(x, dtype=np.int32).reshape(-1) for x in consider]
+        cstride = max(1, max(len(c) for c in cl))
+        nc = np.array([len(c) for c in cl], dtype=np.int32)
+        cid = np.zeros((self.B, cstride), dtype=np.int32)
+        for b, c in enumerate(cl):
+            cid[b, :len(c)] = c
+        return nc, cid, cstride
+
+    def update_linear(self, H, resid, R, local=True, gate=float("inf"), mask=None, want_gamma=False, stats=True, consider=None):
         """A measurement update with m <= 16 linear rows for EVERY filter of the handle in one call (include/eqf_vio_amd.h:
         eqf_update_linear): resid = H eps + noise, noise ~ N(0, R), eps "truth minus estimate" in the coordinates of sigma_local() (local)
         or of sigma().  H: one (m, n) array for a single-filter handle, an array (B, m, n_max) or a list of per-filter arrays (m, n_b) in the
@@ -696,7 +721,10 @@ class FilterBatch:
         R (m, m), broadcast to every filter, (B, m, m) or a list: only the lower triangle is read.  gate: chi-square threshold on the m-dof
         nis (consistency.chi2_gate_threshold(p, dof=m)); mask (B,): 0 leaves a filter alone.  A filter whose info is not 0 keeps every bit.
         With stats or want_gamma the call waits for the device and returns a dict: nis, logdet_S, loglik (B,), dof, info (B,) and, if
-        asked for, gamma (B, n_max) in the reference's index map (rows of untouched filters 0); otherwise it enqueues and returns None."""
+        asked for, gamma (B, n_max) in the reference's index map (rows of untouched filters 0); otherwise it enqueues and returns None.
+        consider: None, or one list of landmark ids per filter (strictly ascending): the Schmidt update (eqf_update_linear_schmidt) --
+        those landmarks keep their estimate and their covariance block, their cross-correlations still enter S and the gain; gamma comes
+        back with exact zeros there; an id the state does not hold is ignored.  consistency.schmidt_update_host is its numpy statement."""
         B = self.B
         if isinstance(H, np.ndarray) and H.ndim == 2:
             H = H[None]
@@ -710,9 +738,16 @@ class FilterBatch:
         ldg = max(ldh, 11 + 3 * max(self.num_landmarks(b) for b in range(B))) if want_gamma else 0
         G = np.zeros((B, ldg)) if want_gamma else None
         rep = (LinearReport * B)() if (stats or want_gamma) else None
-        _check(lib().eqf_update_linear(self._h, int(bool(local)), m, _p(Hs), ldh, _p(r), _p(Rs), float(gate),
-                                       None if mk is None else mk.ctypes.data_as(C.POINTER(C.c_ubyte)), None if G is None else _p(G), ldg, rep),
-               "eqf_update_linear")
+        mkp = None if mk is None else mk.ctypes.data_as(C.POINTER(C.c_ubyte))
+        if consider is None:
+            _check(lib().eqf_update_linear(self._h, int(bool(local)), m, _p(Hs), ldh, _p(r), _p(Rs), float(gate), mkp,
+                                           None if G is None else _p(G), ldg, rep),
+                   "eqf_update_linear")
+        else:
+            nc, cid, cstride = self._consider(consider, "update_linear")
+            _check(lib().eqf_update_linear_schmidt(self._h, int(bool(local)), m, _p(Hs), ldh, _p(r), _p(Rs), float(gate), mkp,
+                                                   nc.ctypes.data_as(_ip), cid.ctypes.data_as(_ip), cstride, None if G is None else _p(G), ldg, rep),
+                   "eqf_update_linear_schmidt")
         if rep is None:
             return None
         out = dict(nis=np.array([s.nis for s in rep]), logdet_S=np.array([s.logdet_S for s in rep]), loglik=np.array([s.loglik for s in rep]),
@@ -722,7 +757,7 @@ class FilterBatch:
         return out
 
     def update_landmarks(self, ids, H, resid, R, rows=None, local=True, gate=float("inf"), lm_gate=float("inf"), mask=None, wait=True,
-                         stride=None):
+                         stride=None, consider=None):
         """A measurement update from per-landmark blocks for EVERY filter of the handle in one call (include/eqf_vio_amd.h:
         eqf_update_landmarks): entry k of filter b measures the landmark ids[b][k] alone, resid_k = H_k eps_i + noise, noise ~ N(0, R_k),
         eps_i "truth minus estimate" of the landmark's 3-block in the coordinates of sigma_local() (local: the plain difference of
@@ -736,7 +771,9 @@ class FilterBatch:
         follow it.
         With wait the call waits for the device and returns a dict: nis, logdet_S, loglik, dof, info (B,), used (B, stride): 1 applied, 0 id
         not in the state, 2 gated, and gamma (B, n_max) in the reference's index map (rows of untouched filters 0); otherwise it enqueues
-        and returns None."""
+        and returns None.
+        consider: None, or one list of landmark ids per filter (strictly ascending): the Schmidt update (eqf_update_landmarks_schmidt),
+        as in update_linear -- the entries may measure consider landmarks."""
         B = self.B
         if B == 1 and not (isinstance(ids, (list, tuple)) and len(ids) == 1 and np.ndim(ids[0]) == 1):
             ids, H, resid, R = [ids], [H], [resid], [R]
@@ -772,10 +809,19 @@ class FilterBatch:
         G = np.zeros((B, ldg)) if wait else None
         used = np.zeros((B, stride), dtype=np.uint8) if wait else None
         rep = (LinearReport * B)() if wait else None
-        _check(lib().eqf_update_landmarks(self._h, int(bool(local)), rows, nk.ctypes.data_as(_ip), idm.ctypes.data_as(_ip), stride, _p(Hs), _p(rs),
-                                          _p(Rs), float(gate), float(lm_gate), None if mk is None else mk.ctypes.data_as(up),
-                                          None if used is None else used.ctypes.data_as(up), None if G is None else _p(G), ldg if wait else 0, rep),
-               "eqf_update_landmarks")
+        if consider is None:
+            _check(lib().eqf_update_landmarks(self._h, int(bool(local)), rows, nk.ctypes.data_as(_ip), idm.ctypes.data_as(_ip), stride, _p(Hs), _p(rs),
+                                              _p(Rs), float(gate), float(lm_gate), None if mk is None else mk.ctypes.data_as(up),
+                                              None if used is None else used.ctypes.data_as(up), None if G is None else _p(G), ldg if wait else 0, rep),
+                   "eqf_update_landmarks")
+        else:
+            nc, cid, cstride = self._consider(consider, "update_landmarks")
+            _check(lib().eqf_update_landmarks_schmidt(self._h, int(bool(local)), rows, nk.ctypes.data_as(_ip), idm.ctypes.data_as(_ip), stride,
+                                                      _p(Hs), _p(rs), _p(Rs), float(gate), float(lm_gate),
+                                                      None if mk is None else mk.ctypes.data_as(up), nc.ctypes.data_as(_ip),
+                                                      cid.ctypes.data_as(_ip), cstride, None if used is None else used.ctypes.data_as(up),
+                                                      None if G is None else _p(G), ldg if wait else 0, rep),
+                   "eqf_update_landmarks_schmidt")
         if not wait:
             return None
         return dict(nis=np.array([s.nis for s in rep]), logdet_S=np.array([s.logdet_S for s in rep]), loglik=np.array([s.loglik for s in rep]),

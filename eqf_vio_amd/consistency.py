@@ -19,6 +19,7 @@ to first order eps_loc = J eps with the block-diagonal J of local_jacobian_block
   linear_update_host(Sigma, H, resid, R) the numpy statement of that update (include/eqf_vio_amd.h: eqf_update_linear)
   stereo_rows / depth_rows / position_rows   per-landmark blocks (H_k, resid_k) for FilterBatch.update_landmarks(local=True)
   update_landmarks_host(Sigma, idx, H, resid, R, ...)  the dense numpy statement of that update (eqf_update_landmarks)
+  schmidt_update_host(Sigma, Ht, R, resid, consider_idx)  the numpy statement of the Schmidt (consider) variants of both updates
   mixture_weights(loglik)                log-likelihoods -> the normalised weights of a mixture (systematic_resample's)
   mixture_moments_host(members, w, centre, centred)   mean and covariance of a weighted batch in the chart of a centre state, the spread
                                          between the members included -- the numpy statement of FilterBatch.mixture_moments
@@ -389,6 +390,33 @@ def linear_update_host(Sigma, H, resid, R):
     logdet = 2.0 * float(np.sum(np.log(np.diag(L))))
     return dict(Sigma=Sg - Y.T @ Y, gamma=Y.T @ z, nis=nis, logdet_S=logdet, loglik=-0.5 * (nis + logdet + m * float(np.log(2.0 * np.pi))), dof=m,
                 Y=Y, L=L)
+
+
+def consider_indices(landmarks):
+    """The state indices c (reference index map: 11 + 3 i ..) of the landmark INDICES `landmarks`, ascending: what schmidt_update_host takes."""
+    return np.array([11 + 3 * int(i) + k for i in sorted(int(j) for j in landmarks) for k in range(3)], dtype=np.int64)
+
+
+def schmidt_update_host(Sigma, Ht, R, resid, consider_idx):
+    """The numpy statement of the Schmidt (consider) updates for one filter (include/eqf_vio_amd.h: eqf_update_linear_schmidt /
+    eqf_update_landmarks_schmidt; FilterBatch.update_linear / update_landmarks with consider=...).  Ht (m, n) already in Sigma's coordinates
+    (the dense rows: landmark_blocks_matrix(...) for per-landmark blocks), R (m, m: lower triangle read), consider_idx: the state indices
+    c that keep their estimate and their covariance block (consider_indices(...)).  With B, S = L L^T, Y, z of linear_update_host -- the full
+    update's, Ht may have columns in c -- the gain K = Y^T L^-1 has its rows c set to zero and the Joseph form
+    (I - K Ht) Sigma (I - K Ht)^T + K R K^T gives
+        gamma = Y^T z off c, +0.0 on c;    Sigma+ = Sigma - Y^T Y except on c x c, where Sigma+ = Sigma.
+    Returns dict(gamma, Sigma, nis, logdet_S, loglik, dof): nis, logdet_S, loglik, dof are the full update's.  With an empty set every value
+    is linear_update_host's.  Raises numpy.linalg.LinAlgError if S is not positive definite."""
+    Sg = np.asarray(Sigma, dtype=float)
+    c = np.asarray(consider_idx, dtype=np.int64).reshape(-1)
+    if len(c) and (c.min() < 0 or c.max() >= len(Sg) or len(np.unique(c)) != len(c)):
+        raise ValueError("consider_idx: distinct state indices")
+    r = linear_update_host(Sg, Ht, resid, R)
+    Sp, gamma = r["Sigma"].copy(), r["gamma"].copy()
+    if len(c):
+        Sp[np.ix_(c, c)] = Sg[np.ix_(c, c)]
+        gamma[c] = 0.0
+    return dict(gamma=gamma, Sigma=Sp, nis=r["nis"], logdet_S=r["logdet_S"], loglik=r["loglik"], dof=r["dof"])
 
 
 # ---- per-landmark blocks for FilterBatch.update_landmarks(local=True): entry k measures landmark i_k alone, resid_k = H_k eps_i + noise with

@@ -428,6 +428,31 @@ class VIOFilter {
             "eqf_update_landmarks");
         return rep;
     }
+    // The Schmidt (consider) variants of the two updates above (eqf_update_linear_schmidt / eqf_update_landmarks_schmidt): the landmarks
+    // considerIds (strictly ascending; one the state does not hold is ignored) keep their estimate and their covariance block, while their
+    // cross-correlations still enter S and the gain of everything else -- a large persistent map, a surveyed point.  The measurement may
+    // observe them.  The report is the full update's.
+    eqf_linear_report processLinearMeasurement(const double* H, int m, const double* resid, const double* R,
+        const std::vector<int>& considerIds, bool local = true, double gate = std::numeric_limits<double>::infinity()) {
+        eqf_linear_report rep;
+        const int n = 11 + 3 * eqf_num_landmarks(handle_.get(), 0), nc = int(considerIds.size());
+        check(eqf_update_linear_schmidt(handle_.get(), local ? 1 : 0, m, H, n, resid, R, gate, nullptr, &nc, considerIds.data(), nc, nullptr,
+                  0, &rep),
+            "eqf_update_linear_schmidt");
+        return rep;
+    }
+    eqf_linear_report processLandmarkMeasurements(const int* ids, int K, int rows, const double* H, const double* resid, const double* R,
+        const std::vector<int>& considerIds, bool local = true, double gate = std::numeric_limits<double>::infinity(),
+        double lm_gate = std::numeric_limits<double>::infinity(), unsigned char* used = nullptr) {
+        eqf_linear_report rep;
+        const int zero = 0, nc = int(considerIds.size());
+        std::vector<double> pad(9, 0.0);  // (stride is at least 1: K = 0 hands over one unread entry)
+        check(eqf_update_landmarks_schmidt(handle_.get(), local ? 1 : 0, rows, &K, K ? ids : &zero, K ? K : 1, K ? H : pad.data(),
+                  K ? resid : pad.data(), K ? R : pad.data(), gate, lm_gate, nullptr, &nc, considerIds.data(), nc, K ? used : nullptr, nullptr,
+                  0, &rep),
+            "eqf_update_landmarks_schmidt");
+        return rep;
+    }
     // How processLinearMeasurement, processLandmarkMeasurements, perturbState (and eqf_apply_increment) turn their increment into a group
     // step (eqf_set_option "innovation_lift"): false (default) the plain lift, which leaves the whole correction to the body-frame landmarks;
     // true the filter's own useInnovationLift / useDiscreteInnovationLift, as a vision frame does -- a stereo, range or zero-velocity update

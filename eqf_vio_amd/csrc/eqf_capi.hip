@@ -46,6 +46,8 @@
 #include "eqf_lift_host.hpp"
 #include "eqf_mapedit.hpp"
 #include "eqf_mapedit_host.hpp"
+#include "eqf_schmidt.hpp"
+#include "eqf_schmidt_host.hpp"
 
 using namespace eqf;
 
@@ -333,6 +335,13 @@ struct eqf_filter {
     // (mapedit::Image) as a pinned copy and its device copy, and evMapEdit: the last upload from the pinned image has been read.  (Last.)
     char *hMapEdit = nullptr, *dMapEdit = nullptr;
     hipEvent_t evMapEdit = nullptr;
+    // the Schmidt updates (eqf_schmidt.hpp; eqf_update_linear_schmidt / eqf_update_landmarks_schmidt), allocated by the first call from
+    // capacity and batch: the partition's image (schmidt::Image) as a pinned copy and its device copy, and evSch: the last upload from the
+    // pinned image has been read.  (Last.)
+    char *hSch = nullptr, *dSch = nullptr;
+    char* hSchDev = nullptr;  // device-side address of the pinned hSch (k_schmidt_gamma reads it)
+    hipEvent_t evSch = nullptr;
+    bool schLdsSet = false;
 };
 
 namespace {
@@ -1680,6 +1689,9 @@ void freeAll(eqf_filter* f) {
     hipFree(f->dMapEdit);
     if (f->hMapEdit) hipHostFree(f->hMapEdit);
     if (f->evMapEdit) hipEventDestroy(f->evMapEdit);
+    hipFree(f->dSch);
+    if (f->hSch) hipHostFree(f->hSch);
+    if (f->evSch) hipEventDestroy(f->evSch);
     if (f->hMixTab) hipHostFree(f->hMixTab);
     if (f->evMix) hipEventDestroy(f->evMix);
     for (auto e : f->evPool) hipEventDestroy(e);
@@ -3468,10 +3480,74 @@ int linAlloc(eqf_filter* f) {
     f->evLin = ev;
     return EQF_OK;
 }
-}  // namespace
 
-int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh, const double* resid, const double* R, double gate,
-    const unsigned char* mask, double* gamma, int ldg, eqf_linear_report* report) {
+// ---- the Schmidt (consider) variants (eqf_schmidt.hpp; the host's decisions: eqf_schmidt_host.hpp)
+static_assert(schmidt::kOk == EQF_OK && schmidt::kInvalid == EQF_ERR_INVALID && schmidt::kCapacity == EQF_ERR_CAPACITY &&
+                  schmidt::kUnsorted == EQF_ERR_UNSORTED && schmidt::kPadBase == kLm0 && schmidt::kTile == kSB,
+    "eqf_schmidt_host.hpp repeats the layout constants and the error codes");
+// the consider lists of a call as the C ABI has them
+struct SchCall {
+    const int* n;
+    const int* ids;
+    int cstride;
+};
+// the partition's image, once per handle; a failure leaves the handle as it was
+int schAlloc(eqf_filter* f) {
+    if (f->hSch) return EQF_OK;
+    const size_t bytes = schmidt::Image{size_t(f->B), size_t(f->ld)}.bytes();
+    void *h = nullptr, *d = nullptr, *hd = nullptr;
+    hipEvent_t ev = nullptr;
+    if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess || hipHostGetDevicePointer(&hd, h, 0) != hipSuccess ||
+        hipMalloc(&d, bytes) != hipSuccess || hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        if (h) hipHostFree(h);
+        if (d) hipFree(d);
+        return EQF_ERR_HIP;
+    }
+    f->hSch = static_cast<char*>(h);
+    f->hSchDev = static_cast<char*>(hd);
+    f->dSch = static_cast<char*>(d);
+    f->evSch = ev;
+    return EQF_OK;
+}
+// Builds every filter's partition from the handle's id mirror in the pinned image (schAlloc has run, the lists are checked); the launch of
+// k_schmidt_gamma brings it to the device.  sa: the arguments both kernels share, but for the verdict records and gamma; gridX: the
+// gathered downdate's.
+int schUpload(eqf_filter* f, const SchCall& sc, const int* N, SchArgs& sa, int& gridX) {
+    const int B = f->B;
+    const schmidt::Image im{size_t(B), size_t(f->ld)};
+    HIPC(hipEventSynchronize(f->evSch));
+    std::vector<int> act;
+    std::vector<unsigned char> fl;
+    int nAmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int nc = sc.n ? sc.n[b] : 0;
+        schmidt::buildActive(N[b], f->ids[b].data(), nc, nc ? sc.ids + size_t(b) * sc.cstride : nullptr, act, fl);
+        schmidt::fillFilter(im, size_t(b), act, fl, f->hSch);
+        nAmax = std::max(nAmax, int(act.size()));
+    }
+    const int nMax = schmidt::paddedOrder(maxN(f));
+    sa = SchArgs{};
+    sa.g = f->g[f->pG]; sa.Sigma = static_cast<double*>(f->Sigma[f->pS]); sa.ld = f->ld; sa.sigmaStride = f->sigmaStride;
+    sa.cnt = reinterpret_cast<const int*>(f->dSch + im.offCount()); sa.act = reinterpret_cast<const int*>(f->dSch + im.offActive());
+    sa.flag = reinterpret_cast<const unsigned char*>(f->dSch + im.offFlag()); sa.pitch = f->ld; sa.nJT = schmidt::colTiles(nMax);
+    sa.cntH = reinterpret_cast<const int*>(f->hSchDev + im.offCount()); sa.actH = reinterpret_cast<const int*>(f->hSchDev + im.offActive());
+    sa.flagH = reinterpret_cast<const unsigned char*>(f->hSchDev + im.offFlag());
+    sa.cntW = reinterpret_cast<int*>(f->dSch + im.offCount()); sa.actW = reinterpret_cast<int*>(f->dSch + im.offActive());
+    sa.flagW = reinterpret_cast<unsigned char*>(f->dSch + im.offFlag());
+    gridX = schmidt::gridX(nAmax, nMax);
+    return EQF_OK;
+}
+// (evSch: the pinned image has been read)
+int schGammaLaunch(eqf_filter* f, const SchArgs& sa) {
+    hipLaunchKernelGGL(k_schmidt_gamma, dim3((f->ld + 255) / 256, f->B), dim3(256), 0, f->stream, sa);
+    HIPC(hipEventRecord(f->evSch, f->stream));
+    return EQF_OK;
+}
+
+// eqf_update_linear (sc == nullptr: the launches it has always enqueued) and eqf_update_linear_schmidt
+int linUpdate(eqf_filter* f, int local, int m, const double* H, int ldh, const double* resid, const double* R, double gate,
+    const unsigned char* mask, const SchCall* sc, double* gamma, int ldg, eqf_linear_report* report) {
     if (!f || !linear::headArgsOk(local, m, H, resid, R, gate)) return EQF_ERR_INVALID;
     if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
     GATE(f);  // (queued IMU calls and a pending gate first: the gate may still change the landmark counts)
@@ -3479,7 +3555,12 @@ int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh,
     std::vector<int> N(B);
     for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
     if (!linear::argsOk(m, H, ldh, resid, R, mask, gamma, ldg, B, N.data())) return EQF_ERR_INVALID;
+    if (sc) {
+        const int bad = schmidt::checkLists(B, f->cap, sc->n, sc->ids, sc->cstride);
+        if (bad) return bad;
+    }
     int rc = linAlloc(f);
+    if (!rc && sc) rc = schAlloc(f);
     if (!rc) rc = liftAlloc(f, lift::callFactors(liftCallKind(f), maxN(f)));
     if (rc) return rc;
     if (local) {
@@ -3510,15 +3591,28 @@ int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh,
     rc = profiled(f, EQF_PROF_LIN_ROWS, [&] { hipLaunchKernelGGL(k_lin_rows, dim3(B), dim3(256), 0, f->stream, a); });
     if (!rc) rc = profiled(f, EQF_PROF_LIN_GAIN, [&] { hipLaunchKernelGGL(k_lin_gain, dim3(nt, B), dim3(256), kLinGainLdsBytes, f->stream, a); });
     if (!rc) rc = profiled(f, EQF_PROF_LIN_SOLVE, [&] { hipLaunchKernelGGL(k_lin_solve, dim3(B), dim3(256), 0, f->stream, a); });
+    SchArgs sa{};
+    int schGrid = 0;
+    if (!rc && sc) {
+        rc = schUpload(f, *sc, N.data(), sa, schGrid);
+        sa.out = f->dLinOut; sa.gamma = f->dLinWs + wl.offGamma(); sa.strideG = wl.stride();
+        if (!rc) rc = schGammaLaunch(f, sa);  // (in front of the lift and the group step: they see the masked gamma)
+    }
     // the group step, behind the solve's verdict (entry 3 of the record, where eqf_nees.hpp's info sits)
     IncArgs ia{};
     ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = f->dLinWs + wl.offGamma(); ia.strideG = wl.stride();
     ia.off = 0; ia.mask = nullptr; ia.info = f->dLinOut;
     // the lift reads the Sigma the call started from and may still refuse the filter: in front of the downdate
     if (!rc) rc = liftEnqueue(f, ia.gamma, ia.strideG, 0, nullptr, f->dLinOut, true, ia);
-    if (!rc)
+    if (!rc && sc) {
+        const SchLin lay{f->dLinWs + wl.offY(), wl.stride(), f->ld};
+        rc = profiled(f, EQF_PROF_LIN_DOWNDATE, [&] {
+            hipLaunchKernelGGL(k_schmidt_downdate<SchLin>, dim3(schGrid, B), dim3(256), schmidtLdsBytes<SchLin>(), f->stream, sa, lay);
+        });
+    } else if (!rc) {
         rc = profiled(f, EQF_PROF_LIN_DOWNDATE,
             [&] { hipLaunchKernelGGL(k_lin_downdate, dim3(linear::triTiles(nt), B), dim3(256), 0, f->stream, a); });
+    }
     if (rc) return rc;
     hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, ia);
     HIPC(hipGetLastError());
@@ -3547,6 +3641,18 @@ int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh,
         if (gamma) linear::unpackGamma(hG.data() + size_t(b) * f->ld, N[b], gamma + size_t(b) * ldg, info != 0);
     }
     return EQF_OK;
+}
+}  // namespace
+
+int eqf_update_linear(eqf_filter* f, int local, int m, const double* H, int ldh, const double* resid, const double* R, double gate,
+    const unsigned char* mask, double* gamma, int ldg, eqf_linear_report* report) {
+    return linUpdate(f, local, m, H, ldh, resid, R, gate, mask, nullptr, gamma, ldg, report);
+}
+int eqf_update_linear_schmidt(eqf_filter* f, int local, int m, const double* H, int ldh, const double* resid, const double* R, double gate,
+    const unsigned char* mask, const int* n_consider, const int* consider_ids, int cstride, double* gamma, int ldg,
+    eqf_linear_report* report) {
+    const SchCall sc{n_consider, consider_ids, cstride};
+    return linUpdate(f, local, m, H, ldh, resid, R, gate, mask, &sc, gamma, ldg, report);
 }
 
 // ---- the per-landmark block measurement update (eqf_blocks.hpp; per-entry arithmetic, index arithmetic and argument checks:
@@ -3603,10 +3709,10 @@ int blkAlloc(eqf_filter* f, const blocks::SmallLayout& sl, const blocks::WorkLay
     if (ev) f->evBlk = ev;
     return EQF_OK;
 }
-}  // namespace
 
-int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb, const double* resid,
-    const double* Rb, double gate, double lm_gate, const unsigned char* mask, unsigned char* used, double* gamma, int ldg,
+// eqf_update_landmarks (sc == nullptr: the launches it has always enqueued) and eqf_update_landmarks_schmidt
+int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb, const double* resid,
+    const double* Rb, double gate, double lm_gate, const unsigned char* mask, const SchCall* sc, unsigned char* used, double* gamma, int ldg,
     eqf_linear_report* report) {
     if (!f || !blocks::headArgsOk(local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate)) return EQF_ERR_INVALID;
     if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
@@ -3620,11 +3726,21 @@ int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, cons
         case 3: return EQF_ERR_CAPACITY;
         default: break;
     }
+    if (sc) {
+        const int bad = schmidt::checkLists(B, f->cap, sc->n, sc->ids, sc->cstride);
+        if (bad) return bad;
+    }
     const blocks::SmallLayout sl{B, stride, rows};
     const blocks::WorkLayout wl{f->ld, stride, rows, kDRec};
     int rc = blkAlloc(f, sl, wl);
     if (!rc) rc = liftAlloc(f, lift::callFactors(liftCallKind(f), maxN(f)));
+    if (!rc && sc) rc = schAlloc(f);
     if (rc) return rc;
+    if (sc && !f->schLdsSet) {  // (dynamic LDS beyond 64 KB, as k_blk_downdate's)
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schmidt_downdate<SchBlk>), hipFuncAttributeMaxDynamicSharedMemorySize,
+            schmidtLdsBytes<SchBlk>()));
+        f->schLdsSet = true;
+    }
     if (!f->blkLdsSet)  // (dynamic LDS beyond 64 KB: see allowUpdateLds; enqueueFactor sets its own kernels' and the flag)
         HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_blk_downdate), hipFuncAttributeMaxDynamicSharedMemorySize, kBlkDownLdsBytes));
     if (local) {
@@ -3665,6 +3781,15 @@ int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, cons
     if (rc) return rc;
     hipLaunchKernelGGL(k_blk_gamma, dim3(nt, B), dim3(64), 0, f->stream, a);
     hipLaunchKernelGGL(k_blk_tail, dim3(B), dim3(256), 0, f->stream, a);
+    SchArgs sa{};
+    int schGrid = 0;
+    if (sc) {
+        rc = schUpload(f, *sc, N.data(), sa, schGrid);
+        if (rc) return rc;
+        sa.out = f->dBlkOut; sa.gamma = f->dBlkWs + wl.offGamma(); sa.strideG = wl.strideD();
+        rc = schGammaLaunch(f, sa);  // (in front of the lift and the group step: they see the masked gamma)
+        if (rc) return rc;
+    }
     // the group step, behind the tail's verdict (entry 3 of the record, where eqf_nees.hpp's info sits)
     IncArgs ia{};
     ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = f->dBlkWs + wl.offGamma(); ia.strideG = wl.strideD();
@@ -3672,7 +3797,12 @@ int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, cons
     // the lift reads the Sigma the call started from and may still refuse the filter: in front of the downdate
     rc = liftEnqueue(f, ia.gamma, ia.strideG, 0, nullptr, f->dBlkOut, true, ia);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_blk_downdate, dim3(blocks::triTiles(nt), B), dim3(256), kBlkDownLdsBytes, f->stream, a);
+    if (sc) {
+        const SchBlk lay{f->dBlkWs, wl.strideD(), wl.mp(), rows, f->dBlkWi + wl.offCount(), wl.strideI()};
+        hipLaunchKernelGGL(k_schmidt_downdate<SchBlk>, dim3(schGrid, B), dim3(256), schmidtLdsBytes<SchBlk>(), f->stream, sa, lay);
+    } else {
+        hipLaunchKernelGGL(k_blk_downdate, dim3(blocks::triTiles(nt), B), dim3(256), kBlkDownLdsBytes, f->stream, a);
+    }
     hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, ia);
     HIPC(hipGetLastError());
     f->csValid = false;  // (C Sigma / S left by an earlier burst describe the old Sigma)
@@ -3705,6 +3835,19 @@ int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, cons
         if (gamma) blocks::unpackGamma(hG.data() + size_t(b) * f->ld, N[b], gamma + size_t(b) * ldg, word != 0);
     }
     return EQF_OK;
+}
+}  // namespace
+
+int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb, const double* resid,
+    const double* Rb, double gate, double lm_gate, const unsigned char* mask, unsigned char* used, double* gamma, int ldg,
+    eqf_linear_report* report) {
+    return blkUpdate(f, local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate, mask, nullptr, used, gamma, ldg, report);
+}
+int eqf_update_landmarks_schmidt(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb,
+    const double* resid, const double* Rb, double gate, double lm_gate, const unsigned char* mask, const int* n_consider,
+    const int* consider_ids, int cstride, unsigned char* used, double* gamma, int ldg, eqf_linear_report* report) {
+    const SchCall sc{n_consider, consider_ids, cstride};
+    return blkUpdate(f, local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate, mask, &sc, used, gamma, ldg, report);
 }
 
 static_assert(mixture::kRefBase == kBase && mixture::kPadBase == kLm0 && mixture::kRows == kMixRows && mixture::kLanes == kMixLanes &&

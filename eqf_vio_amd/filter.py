@@ -191,12 +191,14 @@ class VIOFilter:
                              scale=[scale], stats=True)
         return dict(logdet=float(r["logdet"][0]), min_pivot=float(r["min_pivot"][0]), dof=int(r["dof"][0]), info=int(r["info"][0]))
 
-    def process_linear_measurement(self, H, resid, R, local=True, gate=float("inf"), want_gamma=False):
+    def process_linear_measurement(self, H, resid, R, local=True, gate=float("inf"), want_gamma=False, consider=None):
         """A measurement update with m <= 16 linear rows: resid = H eps + noise, noise ~ N(0, R), eps "truth minus estimate" in the
         coordinates of stateCovarianceLocal() (local; consistency.velocity_rows / gravity_rows / landmark_rows write the usual rows) or of
         stateCovariance().  gate: chi-square threshold on the m-dof nis (consistency.chi2_gate_threshold(p, dof=m)).  Returns dict(nis,
-        logdet_S, loglik, dof, info[, gamma]); the filter is untouched when info != 0 (include/eqf_vio_amd.h: eqf_update_linear)."""
-        r = self._fb.update_linear(np.atleast_2d(np.asarray(H, dtype=float)), resid, R, local=local, gate=gate, want_gamma=want_gamma)
+        logdet_S, loglik, dof, info[, gamma]); the filter is untouched when info != 0 (include/eqf_vio_amd.h: eqf_update_linear).
+        consider: landmark ids (strictly ascending) that keep their estimate and covariance block (eqf_update_linear_schmidt)."""
+        r = self._fb.update_linear(np.atleast_2d(np.asarray(H, dtype=float)), resid, R, local=local, gate=gate, want_gamma=want_gamma,
+                                   consider=None if consider is None else [np.asarray(consider).reshape(-1)])
         out = dict(nis=float(r["nis"][0]), logdet_S=float(r["logdet_S"][0]), loglik=float(r["loglik"][0]), dof=int(r["dof"][0]),
                    info=int(r["info"][0]))
         if want_gamma:
@@ -205,13 +207,15 @@ class VIOFilter:
 
     processLinearMeasurement = process_linear_measurement
 
-    def process_landmark_measurements(self, ids, H, resid, R, rows=None, local=True, gate=float("inf"), lm_gate=float("inf")):
+    def process_landmark_measurements(self, ids, H, resid, R, rows=None, local=True, gate=float("inf"), lm_gate=float("inf"), consider=None):
         """A measurement update from per-landmark blocks: entry k measures the landmark ids[k] (strictly ascending) alone with H (K, rows, 3),
         resid (K, rows) and its own noise covariance R (K, rows, rows) or (rows, rows) -- the second camera of a stereo rig, a range, a
         surveyed position (consistency.stereo_rows / depth_rows / position_rows).  Returns dict(nis, logdet_S, loglik, dof, info, used (K,),
-        gamma); the filter is untouched when info != 0 (include/eqf_vio_amd.h: eqf_update_landmarks)."""
+        gamma); the filter is untouched when info != 0 (include/eqf_vio_amd.h: eqf_update_landmarks).
+        consider: landmark ids (strictly ascending) that keep their estimate and covariance block (eqf_update_landmarks_schmidt)."""
         K = len(np.asarray(ids).reshape(-1))
-        r = self._fb.update_landmarks([np.asarray(ids).reshape(-1)], [H], [resid], [R], rows=rows, local=local, gate=gate, lm_gate=lm_gate)
+        r = self._fb.update_landmarks([np.asarray(ids).reshape(-1)], [H], [resid], [R], rows=rows, local=local, gate=gate, lm_gate=lm_gate,
+                                      consider=None if consider is None else [np.asarray(consider).reshape(-1)])
         return dict(nis=float(r["nis"][0]), logdet_S=float(r["logdet_S"][0]), loglik=float(r["loglik"][0]), dof=int(r["dof"][0]),
                     info=int(r["info"][0]), used=r["used"][0, :K], gamma=r["gamma"][0])
 

@@ -526,6 +526,27 @@ int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk /* [b
     const double* Rb /* [batch][stride][rows][rows] */, double gate, double lm_gate, const unsigned char* mask /* [batch] or NULL */,
     unsigned char* used /* [batch][stride] or NULL */, double* gamma /* [batch][ldg] or NULL */, int ldg,
     eqf_linear_report* report /* [batch] or NULL */);
+/* The Schmidt-Kalman (consider) variants of the two updates above (csrc/eqf_schmidt.hpp): filter b names a CONSIDER set of
+ * n_consider[b] of its landmarks by id (consider_ids[b * cstride + k], strictly ascending; n_consider == NULL: empty sets); c are their
+ * state indices.  Those landmarks keep their estimate and their own covariance block -- a surveyed or long-converged map point is not
+ * dragged by one frame -- while their uncertainty and their cross-correlations still enter S and the gain of everything else.  The
+ * measurement may observe them: that is the point.  With B, S, L, Y, z as above (they, nis, logdet_S, loglik, dof, used, every gate and every
+ * verdict are those of the full update), the gain has its rows c set to zero and the Joseph form gives
+ *   gamma_i = (Y^T z)_i off c and +0.0 on c;   Sigma_ij <- Sigma_ij - (Y^T Y)_ij unless i and j are both in c: Sigma_cc keeps every bit.
+ * Every entry outside c x c, and gamma off c, has the bits of the full call with the same arguments; the returned gamma is the masked one.
+ * The downdate gathers the active rows, so its cost follows (n - |c|) n, not n^2.  An id the state does not hold is ignored (a map id
+ * may have left).  Before any effect, after the checks of the full call: EQF_ERR_INVALID (a negative n_consider[b] or cstride, a non-empty
+ * list with consider_ids NULL), EQF_ERR_CAPACITY (n_consider[b] beyond the handle's capacity or beyond cstride), EQF_ERR_UNSORTED;
+ * EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle.  Everything is decided on the host from the handle's ids before anything is
+ * enqueued; the call waits for the device only where the full call does.  Bit for bit the same from run to run and for a filter alone or
+ * anywhere in a batch.  Not covered: consider sets on the base states, a set stored in the handle, eqf_process_vision, the partitioned
+ * filter, fp32 handles. */
+int eqf_update_linear_schmidt(eqf_filter* f, int local, int m, const double* H, int ldh, const double* resid, const double* R, double gate,
+    const unsigned char* mask, const int* n_consider /* [batch] or NULL */, const int* consider_ids /* [batch][cstride] */, int cstride,
+    double* gamma, int ldg, eqf_linear_report* report);
+int eqf_update_landmarks_schmidt(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb,
+    const double* resid, const double* Rb, double gate, double lm_gate, const unsigned char* mask, const int* n_consider,
+    const int* consider_ids, int cstride, unsigned char* used, double* gamma, int ldg, eqf_linear_report* report);
 
 /* Moment matching over the filters of ONE handle, on the device (csrc/eqf_mixture.hpp): a weighted batch -- a Monte-Carlo study, a particle
  * set, a bank of hypotheses -- turned back into one mean and one covariance that includes the spread between its members, and several
