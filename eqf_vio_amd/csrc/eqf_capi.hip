@@ -44,6 +44,7 @@
 #include "eqf_score_host.hpp"
 #include "eqf_lift.hpp"
 #include "eqf_lift_host.hpp"
+#include "eqf_border_host.hpp"
 #include "eqf_mapedit.hpp"
 #include "eqf_mapedit_host.hpp"
 #include "eqf_schmidt.hpp"
@@ -300,6 +301,9 @@ struct eqf_filter {
     double *dGammaPart = nullptr, *dG11Part = nullptr;
     ResRole* dRoles = nullptr;
     int rolesN = -1, rolesCount = 0;  // chain shape (nbS, nbE, wtS) the role table was built for
+    unsigned long long rolesOmit = 0; // ... and the right-hand-side roles W(0, C) of the E-chain it leaves out (bit C; border rows)
+    int resBorder = 1;                // eqf_debug_option "res_border": the co-resident update launch carries the lift's regressors as border rows of the E-chain's last block row (eqf_border_host.hpp); 0: the right-hand-side roles of the E-chain as before
+    bool countsExact = true;          // the landmark counts the update will find on the device are the host's (false: a device-side outlier gate may lower them)
     int rolesFront = 0;               // roles in front of the prep roles (buildRoles' `front`)
     int dropRole[4] = {-1, 0, 0, 0};  // eqf_debug_drop_role: (kind, role, R, C) of the role whose workgroup leaves without publishing anything
     // profiling
@@ -812,10 +816,20 @@ UpdArgs makeUpdArgs(eqf_filter* f, const double* bearings, long long bearStride,
 // front (fold on a grid larger than the chip): the first diagonal blocks and the row heads / interior tiles of the E-chain's first `front`
 // dependency groups go in FRONT of the prep roles (ResArgs::nFront): they read Sigma only, wait for nothing the prep roles write, and the
 // E-chain -- the update's critical path -- starts at t = 0 instead of behind the prep workgroups of all filters.
-int buildRoles(eqf_filter* f, int Nmax, bool fold, int front = 0) {
+// border (the co-resident builds with eqf_debug_option "res_border" on): filters that carry the lift's regressors as border rows of the
+// E-chain's last block row need no right-hand-side role of that chain except the last one, which runs the lift.  The kernel decides filter
+// by filter (a role nobody needs returns at once); the table leaves out what NO filter of the batch needs (border::omitMask) -- only when the
+// device will find the host's landmark counts.
+int buildRoles(eqf_filter* f, int Nmax, bool fold, int front = 0, bool border = false) {
     const int nbS = roundUp(sDim(Nmax), kSB) / kSB, nbE = roundUp(eDim(Nmax), kSB) / kSB, wtS = roundUp(yCols(Nmax), kSB) / kSB;
     const int key = (fold ? 1 << 30 : 0) | (front << 27) | (nbS << 18) | (nbE << 9) | wtS;  // the table only changes when a chain crosses a 64-block boundary
-    if (f->rolesN == key) return EQF_OK;
+    unsigned long long omit = 0;
+    if (border && f->countsExact) {
+        std::vector<int> counts(f->B);
+        for (int b = 0; b < f->B; ++b) counts[b] = int(f->ids[b].size());
+        omit = border::omitMask(counts.data(), f->B, nbE);
+    }
+    if (f->rolesN == key && f->rolesOmit == omit) return EQF_OK;
     std::vector<ResRole> r;
     if (fold) {
         r.push_back({1, 6, 0, 0});
@@ -834,7 +848,8 @@ int buildRoles(eqf_filter* f, int Nmax, bool fold, int front = 0) {
             const bool moved = fold && kind == 1 && s < front;  // (its row head and interior tiles are in front; the right-hand-side tile waits for the prep roles)
             if (s + 1 < nb && !moved) r.push_back({kind, 0, s + 1, 0});
             for (int R = s + 2; R < nb && !moved; ++R) r.push_back({kind, 1, R, s});
-            for (int t = 0; t < wt; ++t) r.push_back({kind, 2, t, s});
+            for (int t = 0; t < wt; ++t)
+                if (!(kind == 1 && ((omit >> s) & 1ull))) r.push_back({kind, 2, t, s});
         }
     // fault injection (eqf_debug_drop_role): the matching role gets an index beyond every chain -- its workgroup returns at once (`R >= nb`)
     // and the flag it owes is never published: the hand-off time-out path of the kernel, on demand
@@ -848,6 +863,7 @@ int buildRoles(eqf_filter* f, int Nmax, bool fold, int front = 0) {
     if (rc) return rc;
     HIPC(hipMemcpy(f->dRoles, r.data(), sizeof(ResRole) * r.size(), hipMemcpyHostToDevice));
     f->rolesN = key;
+    f->rolesOmit = omit;
     f->rolesCount = int(r.size());
     return EQF_OK;
 }
@@ -1018,6 +1034,14 @@ int allowUpdateLds(eqf_filter* f) {
     return EQF_OK;
 }
 
+// Border rows (ResArgs::border): the co-resident builds of fp64 handles whose downdate runs inside the launch.  Not the fp32 mode and not
+// the downdate on the integer pipe: there existing checks hold one filter alone against the per-column launches (bit for bit) and against
+// a filter of a batch on a grid larger than the chip (1e-12 on Sigma behind the int8 split, which amplifies last-bit differences of the
+// state) -- shapes without the border.
+bool useBorder(const eqf_filter* f, const UpdateShape& s) {
+    return f->resBorder && s.resident && !s.pipeHeads && f->precision != EQF_PRECISION_F32 && !s.i8Slices;
+}
+
 // ONE launch for both chains: the roles of the table buildRoles left, the prep roles in front of them with `fold`, the downdate tiles
 // behind them unless the downdate runs on the integer pipe
 template <typename T>
@@ -1030,6 +1054,7 @@ int launchChainsResident(eqf_filter* f, const UpdateShape& s, const ChainArgs& c
     ra.nbCap = f->nbCap; ra.wtCap = f->wtCap;
     ra.stageFlags = f->dStageFlags;  // (row heads consume D[R-1] stage by stage)
     ra.eFromSigma = s.eFromSigma == 2 ? 1 : 0;
+    ra.border = useBorder(f, s) ? 1 : 0;  // (k_chol_resident decides filter by filter)
     if (s.fold) {
         ra.waitD0 = 3;
         ra.nPrep = s.lmBlocks + s.eBlocks;
@@ -1137,7 +1162,7 @@ int launchUpdateT(eqf_filter* f, const double* bearings, long long bearStride, c
     UpdateShape s{};
     int rc = allowUpdateLds(f);
     if (!rc) rc = updateShape(f, Nmax, s);
-    if (!rc && s.resident) rc = buildRoles(f, Nmax, s.fold, s.front);
+    if (!rc && s.resident) rc = buildRoles(f, Nmax, s.fold, s.front, useBorder(f, s));
     if (rc) return rc;
     a.pad = kSB; a.eFromSigma = s.eFromSigma;
     ChainArgs cS{}, cE{};
@@ -1420,7 +1445,10 @@ int visionOneLaunch(eqf_filter* f, const frame::Meas& m, const double* bearings,
         f->gate.nKept = plan.nKept;
     }
     if (!plan.anyWork) return EQF_OK;
-    return launchUpdate(f, bearings, bearStride, f->dPerm, plan.Nmax);
+    f->countsExact = !gateArmed;  // (an armed gate takes its outliers out on the device: the update may find fewer landmarks than the host counts)
+    rc = launchUpdate(f, bearings, bearStride, f->dPerm, plan.Nmax);
+    f->countsExact = true;
+    return rc;
 }
 
 // Speculative gate: the probe decides on the device, the frame's new landmarks and the update are enqueued without waiting for the
@@ -2968,6 +2996,11 @@ int eqf_debug_option(eqf_filter* f, const char* name, int value) {
         f->resTickets = value;
         return EQF_OK;
     }
+    if (!std::strcmp(name, "res_border")) {
+        if (value != 0 && value != 1) return EQF_ERR_INVALID;
+        f->resBorder = value;
+        return EQF_OK;
+    }
     if (!std::strcmp(name, "device_edit")) {
         f->deviceEdit = value ? 1 : 0;
         return EQF_OK;
@@ -3203,6 +3236,7 @@ static_assert(lift::kRefBase == kBase && lift::kPadBase == kLm0 && lift::kOff ==
               lift::kHead == kLiftHead && kLiftHead == kLinHead && lift::kWordFailed == kLiftWordFailed &&
               lift::kWordFailed != blocks::kInfoIdle && lift::kPadPos == kBase - kLiftOff,
     "eqf_lift_host.hpp repeats the layout constants");
+static_assert(border::kBlock == kSB && border::kStage == kQB && border::kRows == kBorderRows, "eqf_border_host.hpp repeats the layout constants");
 namespace {
 int liftCallKind(const eqf_filter* f) { return lift::callKind(f->liftOpt, f->prm.useInnovationLift, f->prm.useDiscreteInnovationLift); }
 // What a call needs before any effect: the records always, the factorisation's buffers where the call factors.  A failure frees what this

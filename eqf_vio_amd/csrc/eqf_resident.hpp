@@ -18,7 +18,9 @@
 //                       Y_Ct; S-chain tiles also carry the innovation column z along and leave their share of
 //                       gamma = Y^T z; the E-chain's leave their share of G11 = [Zt|Et]^T [Zt|Et].
 //   The last right-hand-side workgroup of the E-chain waits for every share, sums them IN BLOCK-ROW ORDER (deterministic)
-//   and runs the innovation lift.  The downdate tiles Sigma - Y^T Y are workgroups of their own BEHIND the roles in the grid: they
+//   and runs the innovation lift.  (Co-resident builds, filters with room in the E-chain's last block -- ResArgs::border: the lift's
+//   regressors ride along as border rows of that block row, G11 falls out of the last head's corner tile, and of the E-chain's W roles
+//   only the last one runs, for the lift alone.)  The downdate tiles Sigma - Y^T Y are workgroups of their own BEHIND the roles in the grid: they
 //   wait for the S-chain's last Y tile and overlap the tail of the (longer) E-chain.
 // Deadlock freedom: the roles are numbered in dependency order -- a workgroup only ever waits for LOWER numbers (roles: the groups before
 // theirs; downdate tiles: the S-chain's roles).  On a co-resident grid everything is resident.  On a grid larger than the chip the number
@@ -79,7 +81,20 @@ struct ResArgs {
     // and the arrival order scatters a filter's roles over the XCDs.)
     unsigned* ticket;
     unsigned ticketBase;
+    // Border rows (the co-resident builds, !PIPEH; eqf_border_host.hpp; eqf_debug_option "res_border"): a filter whose last E-chain block has a
+    // whole unpivoted 16-row stage carries the lift's eleven regressor columns [Z_P | E_top] along as ROWS of that stage.  The chain's generic
+    // tile code then leaves (L_e^-1 [Z_P | E_top])^T in them and -G11 in their 11 x 11 corner: the E-chain's right-hand-side roles, their running
+    // sums and the last hand-over + solve are not needed; the last row head finishes the corner and hands 121 doubles to the lift's workgroup.
+    int border;
 };
+
+// Border rows (ResArgs::border; the host's copy of this arithmetic: eqf_border_host.hpp): the stage of the E-chain's last block (order ne, nb
+// block columns) that carries them -- the first one behind the real columns -- or -1 when fewer than sixteen unpivoted rows are left.
+constexpr int kBorderRows = 11;
+EQF_DEV int borderStageOf(int ne, int nb) {
+    const int nst = realStages(ne, kSB * (nb - 1));
+    return nst <= 3 ? nst : -1;
+}
 
 // ---- 64x64 block <-> LDS through write-through / L1-bypassing 16-byte accesses.  Thread t handles row t / 4, 16 doubles
 // starting at column 16 (t % 4): one address register per block and immediate offsets (the asm operand limit).
@@ -630,6 +645,29 @@ __global__ __launch_bounds__(256, OCC2 ? 2 : 1) void k_chol_resident(ResArgs ra)
         return in ? v : (r == c ? 1.0 : 0.0);
     };
 
+    // Border rows (ResArgs::border): stage `bst` of the E-chain's last block row holds [Z_P | E_top]^T in its first eleven rows; -1: this filter
+    // (or this build) keeps the right-hand-side roles.  Decided per filter: a ragged batch mixes both.
+    const int bst = (!PIPEH && ra.border && nbE >= 2) ? borderStageOf(neE, nbE) : -1;
+    const bool borderRole = bst >= 0 && role.kind == 1;
+    // ... what a 16 x 16 tile (accumulator layout) of block (nbE - 1, C) holds there instead of the identity padding: tile row tr16 (of four) of
+    // the block, columns c0 .. c0 + 15 of it.  Entry (16 bst + q, c) = ZW[c][q] for a real column c (the pad column 5 and the columns past n_e,
+    // the 11 x 11 corner included: ZERO); rows 11 .. 15 of the stage stay identity rows.  The prep roles write ZW: waitPrep() comes first.
+    auto borderTile = [&](f64x4& v, int C, int tr16, int c0) __attribute__((always_inline)) {
+        if (tr16 != bst) return;
+        const double* Zw = ra.c1.W + (long long)b * ra.c1.strideW;
+        const int c = C * kSB + c0 + (lane & 15);
+        const bool in = c < neE && c != 5;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int rr = (lane >> 4) + 4 * q;
+            if (rr < kBorderRows) {
+                const double* p = Zw + (in ? (long long)c * ra.c1.ldW + rr : 0);
+                const double z = fold ? hoLoad8(p) : *p;
+                v[q] = in ? z : 0.0;
+            }
+        }
+    };
+
     // (fold) everything the prep roles of this launch write -- S, both chains' right-hand sides -- is there once all of them have published
     auto waitPrep = [&]() {
         if (!fold) return;
@@ -664,7 +702,9 @@ __global__ __launch_bounds__(256, OCC2 ? 2 : 1) void k_chol_resident(ResArgs ra)
         tr[1] = wv == 2 ? 1 : 2; tc[1] = 1;
         tr[2] = wv == 2 ? 3 : 2; tc[2] = wv == 2 ? 1 : 2;
         tr[3] = 3;               tc[3] = wv == 2 ? 2 : 3;
-        if (!srcSigma) waitPrep();
+        // (the chain's last head with the border rows: they come from ZW, which the prep roles write -- it is needed last of all heads)
+        const bool borderHead = borderRole && R == nb - 1;
+        if (!srcSigma || borderHead) waitPrep();
         f64x4 a1[4], a2[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -673,6 +713,13 @@ __global__ __launch_bounds__(256, OCC2 ? 2 : 1) void k_chol_resident(ResArgs ra)
                 a1[i][q] = tile0(R, R - 1, kQB * wv + (lane >> 4) + 4 * q, kQB * i + (lane & 15));
                 a2[i][q] = i < nt ? tile0(R, R, kQB * tr[i] + (lane >> 4) + 4 * q, kQB * tc[i] + (lane & 15)) : 0.0;
             }
+        if (borderHead) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                borderTile(a1[i], R - 1, wv, kQB * i);
+                if (i < nt) borderTile(a2[i], R, tr[i], kQB * tc[i]);
+            }
+        }
         EQF_HSTAMP(0);
         // (A dry run of the serial part during the idle time before the panels arrive -- to take the instruction-cache misses of
         // code a workgroup executes exactly once off the critical path -- was tried and measured: no gain.)
@@ -788,23 +835,53 @@ __global__ __launch_bounds__(256, OCC2 ? 2 : 1) void k_chol_resident(ResArgs ra)
             if (bad != 8) hoPublish(readyA + R * nbCap + (R - 1), epoch);
             EQF_HSTAMP(12);
         };
-        factor64<true>(s, tid, &bad, pre, D + (long long)R * kDRec, EQF_F64_ST(), realStages(ch.kind == 0 ? sDim(g.N) : eDim(g.N), kSB * R), mid,
-            stageOut, epoch);
+        // (the border head: nobody solves with D[nb-1] any more and nothing outside the launch reads an E-chain record -- it is not stored)
+        factor64<true>(s, tid, &bad, pre, borderHead ? nullptr : D + (long long)R * kDRec, EQF_F64_ST(),
+            realStages(ch.kind == 0 ? sDim(g.N) : eDim(g.N), kSB * R), mid, stageOut, epoch);
         EQF_HSTAMP(7);
-        hoDrain();
-        __syncthreads();
-        if (tid == 0 && bad != 8) hoPublish(ch.flags + (long long)b * ch.strideF + R, epoch);
-        EQF_HSTAMP(8);
+        if (borderHead) {
+            // ---- G11 from the corner tile (bst, bst) of the diagonal block.  factor64 never delivers or updates it (factorTiles skips the
+            // columns behind the real stages), so its slot of a2 still lacks two things: the product with this block row's own solved block
+            // L_{R,R-1} (what `pre` delivers from s.P for the other tiles) and the bst in-block products with the columns the pivot wave
+            // solved below the real rows (s.L, rows 16 bst .., columns 0 .. 16 bst - 1).  Fixed order of the sums: two runs give the same bits.
+            // The owning wave: 2 for bst = 1 (slot 1), 3 for bst = 2, 3 (slots 2, 3).
+            if (wv == (bst == 1 ? 2 : 3)) {
+                f64x4 t = bst == 1 ? a2[1] : (bst == 2 ? a2[2] : a2[3]);
+                t = mmTile<true, kSB>(t, &s.P[0][0], kSP, kQB * bst, &s.P[0][0], kSP, kQB * bst, lane, -1.0);
+                for (int j = 0; j < bst; ++j) t = mmTile<true, kQB>(t, &s.L[0][kQB * j], kSP, kQB * bst, &s.L[0][kQB * j], kSP, kQB * bst, lane, -1.0);
+                double* gOut = ra.g11Part + ((long long)b * nbCap + R) * 128;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int rr = (lane >> 4) + 4 * q, cc = lane & 15;
+                    if (rr < kBorderRows && cc < kBorderRows) hoStore8(gOut + rr * kBorderRows + cc, -t[q]);
+                }
+            }
+            hoDrain();
+            __syncthreads();
+            // (the flag of the right-hand-side tile this block row no longer has: the lift's workgroup waits for it)
+            if (tid == 0 && bad != 8) hoPublish(readyY + R * wtCap, epoch);
+            EQF_HSTAMP(8);
+        } else {
+            hoDrain();
+            __syncthreads();
+            if (tid == 0 && bad != 8) hoPublish(ch.flags + (long long)b * ch.strideF + R, epoch);
+            EQF_HSTAMP(8);
+        }
     } else if (role.role == 1) {
         // =========================================================================================== T(R, C)
         const int R = role.R, C = role.C;
         if (R >= nb) return;
-        if (!srcSigma) waitPrep();
+        const bool borderT = borderRole && R == nb - 1;  // (a tile of the block row that carries the border rows: see H)
+        if (!srcSigma || borderT) waitPrep();
         f64x4 acc[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc[i][q] = tile0(R, C, kQB * wv + (lane >> 4) + 4 * q, kQB * i + (lane & 15));
+        if (borderT) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) borderTile(acc[i], C, wv, kQB * i);
+        }
         if (C > 0) {
             // pipelined panel loop (panelIssue above): panel K+1 is fetched during the products of panel K whenever its two blocks are
             // already out (a look at the flags one iteration ahead, never a wait); at the frontier -- the newest panel not published
@@ -868,6 +945,8 @@ __global__ __launch_bounds__(256, OCC2 ? 2 : 1) void k_chol_resident(ResArgs ra)
         // =========================================================================================== W(t, C)
         const int t = role.R, C = role.C;
         if (t >= wt || C >= nb) return;
+        // (border rows: the E-chain has no right-hand-side tiles; the workgroup of its last block row stays, for the lift alone)
+        if (borderRole && C != nb - 1) return;
         const double* Tg = W + (long long)(C * kSB) * ldW + t * kSB;
         waitPrep();
         f64x4 acc[4];
@@ -876,7 +955,7 @@ __global__ __launch_bounds__(256, OCC2 ? 2 : 1) void k_chol_resident(ResArgs ra)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const double* p = Tg + (long long)(kQB * wv + (lane >> 4) + 4 * q) * ldW + kQB * i + (lane & 15);
-                acc[i][q] = fold ? hoLoad8(p) : *p;
+                acc[i][q] = borderRole ? 0.0 : (fold ? hoLoad8(p) : *p);  // (border rows: no right-hand-side tile, see below)
             }
         const bool isS = ch.kind == 0;
         double* zv = s.redL;  // [0, 64) the innovation column delta of this block row, [64, 128) z of block row K
@@ -918,6 +997,26 @@ __global__ __launch_bounds__(256, OCC2 ? 2 : 1) void k_chol_resident(ResArgs ra)
                 updateFinishBody(a, b, s.redL, 1);
             }
         };
+        if (borderRole) {
+            // ---- the lift's workgroup of a filter with border rows: the S-chain's sums and the part of the lift that needs gamma alone while
+            // the E-chain's last head is still factoring, then ONE flag and 121 doubles from that head (instead of D[nb-1], 40 KB, and a
+            // 64 x 64 strip solve for the last share of G11)
+            collect();
+            EQF_WSTAMP(0);
+            hoWait3(readyY + C * wtCap, nullptr, nullptr, epoch, tid, &bad, ra.errflag);
+            EQF_WSTAMP(1);
+            if (tid < 121) s.redL[8 + tid] = hoLoad8(ra.g11Part + ((long long)b * nbCap + C) * 128 + tid);
+            // (a wait that failed: no lift from stale sums -- thread 0 holds the verdict of both waits)
+            if (__syncthreads_or(tid == 0 && bad == 8)) {
+                if (ra.errflag && tid == 0) atomicOr(ra.errflag, kHoErrTimeout);
+                return;
+            }
+            EQF_WSTAMP(4);
+            updateFinishBody(a, b, s.redL, lastFast ? 2 : 0);
+            __syncthreads();
+            EQF_WSTAMP(5);
+            return;
+        }
         if (isS && tid < kSB) zv[tid] = fold ? hoLoad8(W + (long long)(C * kSB + tid) * ldW + 11) : W[(long long)(C * kSB + tid) * ldW + 11];
         if (C > 0) {
             // pipelined panel loop (see panelIssue): Q <- L_{C,K}, P <- Y_{K,t}; the S-chain also carries z_K along

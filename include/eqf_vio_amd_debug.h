@@ -41,6 +41,12 @@ int eqf_debug_drop_role(eqf_filter* f, int kind, int role, int R, int C);
  *                  on in-order dispatch, guarded by the time-outs).  0 (default): never.  1: on grids of at least six times the resident slots (16+
  *                  filters of N = 200, N >= ~700: +1-2 % per update there).  2: on every grid larger than the chip with a prep launch in front
  *                  (below six times the slots +3 .. 15 us per update).  Same results.
+ *   "res_border"   1 (default): in the co-resident builds of the update launch (one or two small filters; fp64 handles with the fp64 downdate
+ *                  inside the launch -- not the fp32 mode, not "downdate_slices") a filter whose last E-chain block has
+ *                  sixteen unpivoted rows carries the innovation lift's eleven regressor columns [Z_P | E_top] along as rows of that block: the
+ *                  chain's own tile updates leave G11 = [Z_P | E_top]^T Sigma_e^-1 [Z_P | E_top] in their corner, and the E-chain's right-hand-side
+ *                  roles with the last hand-over of a diagonal factor are not run.  0: those roles, as before.  Gamma and the state agree to
+ *                  rounding (another summation order of G11), Sigma bit for bit.
  *   "burst_fused_max_x10"    the one-launch IMU burst (k_burst_fused) is used up to value / 10 workgroups per CU (default: 1.25).
  *   "e_sigma_min_percu_x10"  the two-per-CU build of the update launch reads the E-chain's tiles in Sigma itself from value / 10 chain roles per
  *                  CU on (default 2.4: every such grid); below, the prep launch copies Sigma[6:, 6:].  Launch shapes only: same results. */
