@@ -49,6 +49,7 @@
 #include "eqf_mapedit_host.hpp"
 #include "eqf_schmidt.hpp"
 #include "eqf_schmidt_host.hpp"
+#include "eqf_workspace.hpp"
 
 using namespace eqf;
 
@@ -89,9 +90,107 @@ void launchI8Dd(int slices, const I8DdArgs& a, const UpdArgs* u, int nCt, hipStr
 // sources of new landmarks): the host never has to drain the stream before reusing a staging buffer.
 struct IntStage {
     static constexpr int kSlots = 8;
-    int* host[kSlots] = {};
-    hipEvent_t ev[kSlots] = {};
+    PinnedPtr<int> host[kSlots];
+    Event ev[kSlots];
     int next = 0;
+};
+
+// ---- What the optional routes keep on the handle: one sub-struct per route -- owners, capacities, the flag "dynamic-LDS attributes set"
+// and options --, all of them behind the members the per-step calls touch (see the end of eqf_filter).  A route states its sizes where it
+// reserves (reserveSlots); nothing here is freed by hand.
+// joint NEES / log det (eqf_nees.hpp; eqf_get_nees): error vectors -> z [B][kNeesRhs][ld], the record of the current diagonal block
+// [B][kDRec], the results [B][kNeesHead + kNeesRhs], and the pivot words [B]
+struct NeesRoute {
+    DevPtr<double> E, D, out;
+    DevPtr<int> bad;
+    bool ldsSet = false;
+};
+// draws from the covariance (eqf_sample.hpp; eqf_sample_sigma / eqf_apply_increment / eqf_perturb_filters): the samples and their images
+// [B][rows][ld] (cap: bytes of each); and the small operands of a call that does not wait for the device -- scale [B] | vectors
+// [B][kLm0 + 3 cap] (z of a perturbation or the increments) | mask [B] bytes -- as a staged image
+struct SampRoute {
+    DevPtr<double> Z, E;
+    size_t cap = 0;
+    StagedImage<> small;
+};
+// the low-rank linear measurement update (eqf_linear.hpp; eqf_update_linear): the operands of a call as a staged image
+// (linear::SmallLayout), the workspace [B][linear::WorkLayout::stride()] and the result records [B][kLinHead]
+struct LinRoute {
+    StagedImage<> small;
+    DevPtr<double> ws, out;
+};
+// the per-landmark block measurement update (eqf_blocks.hpp; eqf_update_landmarks), grown when a call's stride or rows ask for more: the
+// operands of a call as a staged image (blocks::SmallLayout), the workspace in doubles and in ints (blocks::WorkLayout; capacities in
+// bytes) and the records [B][kLinHead]
+struct BlkRoute {
+    StagedImage<> small;
+    DevPtr<double> ws, out;
+    DevPtr<int> wi;
+    size_t wsCap = 0, wiCap = 0;
+    bool ldsSet = false;
+};
+// the innovation lift of eqf_update_linear / eqf_update_landmarks / eqf_apply_increment / eqf_perturb_filters (eqf_lift.hpp;
+// eqf_set_option "innovation_lift"): the records [B][kLiftRec] of the last of these calls, and -- from the first call with the option on
+// -- the right-hand-side rows [B][kLiftRhs][ld], the record of the current diagonal block [B][kDRec] and the pivot words [B] (the image
+// that is factored is dSigmaLoc)
+struct LiftRoute {
+    int opt = 0;
+    bool called = false, ldsSet = false;
+    DevPtr<double> rec, E, D;
+    DevPtr<int> bad;
+};
+// eqf_copy_filters (eqf_clone.hpp): the pair table (pinned image + device copy, grown on demand; pairsCap in bytes), the small-state
+// staging image of the in-place case and two events -- evSrc orders a copy behind this handle's work when it is the source, evDone marks
+// the end of the last copy INTO this handle (its pair table may be reused, the source may go on)
+struct CloneRoute {
+    PinnedPtr<ClonePair> hPairs;
+    DevPtr<ClonePair> dPairs;
+    size_t pairsCap = 0;
+    DevPtr<char> small;
+    Event evSrc, evDone;
+};
+// moment matching over the handle's filters (eqf_mixture.hpp; eqf_get_mixture_moments / eqf_merge_filters): the workspace
+// (mixture::WorkLayout) and the member table of a call as a staged image, grown on demand (members, then the distinct filters)
+struct MixRoute {
+    DevPtr<double> ws;
+    StagedImage<> tab;
+    int launches = 0;  // kernel launches of the most recent mixture call, counted as they are made (eqf_debug_mixture_launches)
+};
+// the non-mutating forecast (eqf_forecast.hpp; eqf_forecast): the samples of a call as a pinned image and its device copy, the per-step
+// records the builder leaves for the landmark lanes, and the output records as a device image and its pinned copy
+// (forecast::imageCapacityDoubles / recDoubles / outStride).  The call synchronises before it returns, so the pinned images need no event.
+struct ForecastRoute {
+    PinnedPtr<ImuRec> hImu;
+    DevPtr<ImuRec> dImu;
+    DevPtr<double> rec, dOut;
+    PinnedPtr<double> hOut;
+};
+// pairwise merge costs (eqf_mergecost.hpp; eqf_get_merge_costs): one block for a chunk of images with their right-hand sides, records
+// and orders (grown when the option "merge_cost_chunk" asks for more), one for a call's items and records
+struct MergeCostRoute {
+    DevPtr<char> ws, items;
+    size_t wsBytes = 0, itemBytes = 0;
+    int chunkCap = 0, chunkOpt = 0;  // (what the blocks were carved for)
+    size_t itemCap = 0;
+};
+// scoring candidate frames (eqf_score.hpp; eqf_score_vision): one block for a chunk of images of order score::paddedOrder(capacity) with
+// their right-hand-side rows, diagonal-block records and pivot words (grown when the option "score_chunk" asks for more), one for a
+// call's items, matched slots, bearings, per-landmark statistics and records
+struct ScoreRoute {
+    DevPtr<char> ws, tab;
+    size_t wsBytes = 0, tabBytes = 0;
+    int chunkCap = 0, chunkOpt = 0;
+    bool ldsSet = false;
+};
+// explicit landmark edits (eqf_mapedit.hpp; eqf_edit_landmarks): the plan's image (mapedit::Image) as a staged image
+struct MapEditRoute {
+    StagedImage<> img;
+};
+// the Schmidt updates (eqf_schmidt.hpp; eqf_update_linear_schmidt / eqf_update_landmarks_schmidt): the partition's image
+// (schmidt::Image) as a staged image whose pinned side k_schmidt_gamma reads through its device-side address
+struct SchmidtRoute {
+    StagedImage<true> img;
+    bool ldsSet = false;
 };
 
 struct eqf_filter {
@@ -99,31 +198,33 @@ struct eqf_filter {
     size_t esz = 8;
     eqf_settings set{};
     Params prm{};
-    hipStream_t stream = nullptr;
+    Stream stream;  // (in front of every buffer and event: members go in reverse order, the stream last)
     int nTot = 0, ld = 0;
     long long sigmaStride = 0;
-    void* Sigma[2] = {nullptr, nullptr};
-    Glob* g[2] = {nullptr, nullptr};
-    double* p0 = nullptr;
-    double* lmc = nullptr;  // [B][15][cap] per-landmark constants (C0i, chart rotation)
-    double* Q[2] = {nullptr, nullptr};
+    DevPtr<void> Sigma[2];
+    DevPtr<Glob> g[2];
+    DevPtr<double> p0;
+    DevPtr<double> lmc;  // [B][15][cap] per-landmark constants (C0i, chart rotation)
+    DevPtr<double> Q[2];
     int pS = 0, pG = 0;
     // update chains
-    double *SA = nullptr, *SL = nullptr, *YW = nullptr, *YO = nullptr, *EA = nullptr, *EL = nullptr, *ZW = nullptr, *ZO = nullptr;
+    DevPtr<double> SA, SL, YW, YO, EA, EL, ZW, ZO;
     int ldS = 0, ldY = 0, ldE = 0, ldZ = kSB;
     long long strideDS = 0, strideDE = 0;  // diagonal-factor records of the two chains
     long long strideS = 0, strideY = 0, strideE = 0, strideZ = 0;
-    double *dbgDelta = nullptr, *dbgGamma = nullptr, *dbgGammaTot = nullptr, *red = nullptr;
-    int* errflag = nullptr;
+    DevPtr<double> dbgDelta, dbgGamma, dbgGammaTot, red;
+    DevPtr<int> errflag;
     // churn scratch
-    int *dMap = nullptr, *dNewN = nullptr, *dPerm = nullptr;  // (dNewN = dMap + B * cap)
+    DevPtr<int> dMap;
+    int* dNewN = nullptr;  // (= dMap + B * cap)
+    DevPtr<int> dPerm;
     std::vector<std::vector<int>> permOnDevice;  // what dPerm holds (uploadPerm): the same landmark set in the same order needs no new copy
-    double *dChord = nullptr, *dDepth2 = nullptr, *dScratch = nullptr, *dMeas = nullptr, *dOut = nullptr;
+    DevPtr<double> dChord, dDepth2, dScratch, dMeas, dOut;
     IntStage stMap, stPerm;  // pinned rings: [B*cap + B] (map + new counts), [B*cap]
     IntStage stEdit;         // pinned ring [2*B*cap + 4*B]: keep map | permutation | counts of a k_edit launch (one upload per frame)
-    int* dEdit = nullptr;    // its device image
+    DevPtr<int> dEdit;       // its device image
     std::vector<int> editOnDevice;  // ... as last uploaded
-    int* dEditBar = nullptr; // [B][4] k_edit's counters
+    DevPtr<int> dEditBar;    // [B][4] k_edit's counters
     int lastBurstShape[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // eqf_debug_launch_shape: the most recent IMU burst's launch shape
     std::vector<char> restoredMark; // [B] eqf_set_state since the last reset: once every filter has been restored a hand-off time-out (bit 128) is forgiven
     // OCC2 grids from this many roles per CU on read the E-chain's tiles in Sigma itself instead of a copy made by the prep launch
@@ -139,21 +240,21 @@ struct eqf_filter {
     // builders, two / four rows per wavefront) with the flag protocol: sized at 27 us of a 262 us frame at 8 filters, not built.
     double fusedMaxPerCU = 1.25;
     int deviceEdit = 1;      // landmark-set changes and the outlier gate of a frame in ONE launch, decided on the device (eqf_debug_option "device_edit")
-    double* dDepthSel = nullptr;    // [B] median scene depth selected on the device
-    double *hChord = nullptr, *hMeas = nullptr, *hOut = nullptr;
-    double* hChordDev = nullptr;  // device-side address of the pinned hChord
-    hipEvent_t evMeas = nullptr;
+    DevPtr<double> dDepthSel;    // [B] median scene depth selected on the device
+    PinnedPtr<double, true> hChord;  // (with its device-side address: hChord.dev)
+    PinnedPtr<double> hMeas, hOut;
+    Event evMeas;
     bool measPending = false;    // eqf_process_vision: the bearings sit in hMeas, their copy is visionCore's to enqueue (with k_edit's image behind them)
     // input ring for per-call records (batch > 1)
-    ImuRec* dRing = nullptr;
-    ImuRec* hRing = nullptr;
-    hipEvent_t evRing[kRing] = {};
+    DevPtr<ImuRec> dRing;
+    PinnedPtr<ImuRec> hRing;
+    Event evRing[kRing];
     bool ringUsed[kRing] = {};
     long long ringCount = 0;
     // stream mode
-    ImuRec* sImu = nullptr;   // [K][B]
-    ImuRec* sVis = nullptr;   // [F][B] (stamp only)
-    double* sBear = nullptr;  // [F][B][nb][3]
+    DevPtr<ImuRec> sImu;   // [K][B]
+    DevPtr<ImuRec> sVis;   // [F][B] (stamp only)
+    DevPtr<double> sBear;  // [F][B][nb][3]
     int sK = 0, sF = 0, sNb = 0;
     std::vector<int> sIds;
     std::vector<double> hImuStamp, hVisStamp;  // host mirrors of the stamps
@@ -163,9 +264,9 @@ struct eqf_filter {
     std::vector<char> init;
     std::vector<char> devInit;  // the filter's lazy initialisation has been LAUNCHED (init is set when the call is queued)
     int densePropagate = 0;
-    void *dF = nullptr, *dG = nullptr, *dBn = nullptr;  // dense backend: F, G = F Sigma, Bn (n x 6)
-    void* dBlk = nullptr;          // split propagate path: per-landmark records [B][cap][kBlkRec] (T)
-    CommonLds* dBlkCommon = nullptr;
+    DevPtr<void> dF, dG, dBn;  // dense backend: F, G = F Sigma, Bn (n x 6)
+    DevPtr<void> dBlk;         // split propagate path: per-landmark records [B][cap][kBlkRec] (T)
+    DevPtr<CommonLds> dBlkCommon;
     int splitPropagate = -1;       // -1 heuristic, 0 never, 1 always (EQF_SPLIT_PROPAGATE)
     bool ldsAttrSet = false;       // hipFuncAttributeMaxDynamicSharedMemorySize applied on this handle's device (allowUpdateLds)
     // speculative outlier gate: the frame whose gate answer the host has not looked at yet
@@ -180,11 +281,10 @@ struct eqf_filter {
         bool onDevice = false;              // k_edit removed the outliers itself: only the host's id lists are left to bring up to date
         std::vector<int> nKept;             // ... kept landmarks per filter (the chords in hChord are in that order)
     } gate;
-    int* hGate = nullptr;        // pinned [B]: raised by k_probe
-    int* hGateDev = nullptr;     // device-side address of hGate
-    int* dMask = nullptr;        // [B]
-    hipEvent_t evGate = nullptr;
-    hipEvent_t evMask = nullptr;   // k_set_update_ok has read hGate (resolveGate's redo): recorded before the host may clear it again
+    PinnedPtr<int, true> hGate;  // pinned [B]: raised by k_probe (with its device-side address: hGate.dev)
+    DevPtr<int> dMask;           // [B]
+    Event evGate;
+    Event evMask;                  // k_set_update_ok has read hGate (resolveGate's redo): recorded before the host may clear it again
     bool maskPending = false;
     int csInBurst = 1;           // bursts closed by a vision step also leave C Sigma' and S (BurstArgs::csOut; eqf_debug_option "cs_in_burst")
     bool csValid = false;        // ... and they are still what the update would compute (nothing moved a landmark since)
@@ -213,100 +313,52 @@ struct eqf_filter {
         int k0 = 0, cnt = 0;
         ImuRec inl[kBurstMax];
     } burst;
-    void *dColRec = nullptr, *dRowRec = nullptr;  // per step and landmark records of k_burst_build
-    BurstStep* dSteps = nullptr;
+    DevPtr<void> dColRec, dRowRec;  // per step and landmark records of k_burst_build
+    DevPtr<BurstStep> dSteps;
     int cholSplit = -1;            // -1 heuristic, 0 fused chain launches, 1 panel + update launches (EQF_CHOL_SPLIT)
-    int* dFlags = nullptr;         // [B][2][flagStride]: epoch flags of the in-launch hand-off of the diagonal-factor records
+    DevPtr<int> dFlags;            // [B][2][flagStride]: epoch flags of the in-launch hand-off of the diagonal-factor records
     int flagStride = 0;
     int updateEpoch = 0;           // one per launchUpdate
     // k_chol_resident (one launch per update while the grid fits the chip): EQF_CHOL_RESIDENT = 0 switches it off
     int cholResident = 1;
     int resFoldPrep = 1;           // co-resident grid: the prep work as roles of the SAME launch (EQF_RES_FOLD_PREP = 0: k_update_prep64 launched first)
-    int* dPrepFlags = nullptr;     // [B][nPrepCap]
+    DevPtr<int> dPrepFlags;        // [B][nPrepCap]
     int nPrepCap = 0;
     int burstFused = 1;            // latency case: builder and block workgroups of a burst in ONE launch (EQF_BURST_FUSED = 0: two launches)
-    int* dBuildFlags = nullptr;    // [B][nBuildCap]: steps each builder workgroup has published, + 32 * burstEpoch
+    DevPtr<int> dBuildFlags;       // [B][nBuildCap]: steps each builder workgroup has published, + 32 * burstEpoch
     int nBuildCap = 0, burstEpoch = 0;
     int residentPerCU = -1;        // hipOccupancyMaxActiveBlocksPerMultiprocessor of k_chol_resident on this device (lazily queried)
     int numCUs = 0;
     int nbCap = 0, wtCap = 0;
-    int *dReadyA = nullptr, *dReadyY = nullptr, *dResCounters = nullptr, *dStageFlags = nullptr;
-    unsigned* dTicket = nullptr;  // k_chol_resident on a grid larger than the chip: arrival tickets, [B][32] (ResArgs::ticket); ticketBase = tickets drawn per filter by earlier launches
+    DevPtr<int> dReadyA, dReadyY, dResCounters, dStageFlags;
+    DevPtr<unsigned> dTicket;     // k_chol_resident on a grid larger than the chip: arrival tickets, [B][32] (ResArgs::ticket); ticketBase = tickets drawn per filter by earlier launches
     unsigned ticketBase = 0;
     // the covariance downdate on the integer matrix pipe (eqf_i8.hpp; eqf_set_option "downdate_slices"): slices (0 = fp64), and the
-    // workspace of the split -- slices for i8Slices, i8WsStride bytes per filter, and the columns' exponent words
+    // workspace of the split -- slices for i8Slices, i8WsStride bytes per filter (i8WsBytes in all), and the columns' exponent words
     int ddSlices = 0, i8Slices = 0;
-    signed char* dI8Ws = nullptr;
-    int* dI8Expo = nullptr;
+    DevPtr<signed char> dI8Ws;
+    DevPtr<int> dI8Expo;
     long long i8WsStride = 0;
+    size_t i8WsBytes = 0;
     // covariance in the coordinates of the estimate (eqf_local.hpp): the J blocks [B][kJacHead + 9 cap] and an image of Sigma's size, both
-    // allocated by the first getter that needs them
-    double *dJac = nullptr, *dSigmaLoc = nullptr;
-    // joint NEES / log det (eqf_nees.hpp; eqf_get_nees), allocated by its first call: error vectors -> z [B][kNeesRhs][ld], the record of
-    // the current diagonal block [B][kDRec], the results [B][kNeesHead + kNeesRhs], and the pivot words [B]
-    double *dNeesE = nullptr, *dNeesD = nullptr, *dNeesOut = nullptr;
-    int* dNeesBad = nullptr;
-    bool neesLdsSet = false;
-    // draws from the covariance (eqf_sample.hpp; eqf_sample_sigma / eqf_apply_increment / eqf_perturb_filters), allocated on first need: the
-    // samples and their images [B][sampRows][ld]; and the small operands of a call that does not wait for the device -- scale [B] | vectors
-    // [B][kLm0 + 3 cap] (z of a perturbation or the increments) | mask [B] bytes -- as a pinned image and its device copy (evSamp: the last
-    // upload from the pinned image has been read)
-    double *dSampZ = nullptr, *dSampE = nullptr;
-    int sampRows = 0;
-    char *hSampSmall = nullptr, *dSampSmall = nullptr;
-    hipEvent_t evSamp = nullptr;
-    // the low-rank linear measurement update (eqf_linear.hpp; eqf_update_linear), allocated by its first call: the operands of a call as a
-    // pinned image and its device copy (linear::SmallLayout; evLin: the last upload from the pinned image has been read), the workspace
-    // [B][linear::WorkLayout::stride()] and the result records [B][kLinHead]
-    char *hLinSmall = nullptr, *dLinSmall = nullptr;
-    double *dLinWs = nullptr, *dLinOut = nullptr;
-    hipEvent_t evLin = nullptr;
-    // the per-landmark block measurement update (eqf_blocks.hpp; eqf_update_landmarks), allocated on first need and grown when a call's
-    // stride or rows ask for more: the operands of a call as a pinned image and its device copy (blocks::SmallLayout; evBlk: the last
-    // upload from the pinned image has been read), the workspace in doubles and in ints (blocks::WorkLayout) and the records [B][kLinHead]
-    char *hBlkSmall = nullptr, *dBlkSmall = nullptr;
-    size_t blkSmallBytes = 0, blkWsDoubles = 0, blkWiInts = 0;
-    double *dBlkWs = nullptr, *dBlkOut = nullptr;
-    int* dBlkWi = nullptr;
-    hipEvent_t evBlk = nullptr;
-    bool blkLdsSet = false;
-    // the innovation lift of eqf_update_linear / eqf_update_landmarks / eqf_apply_increment / eqf_perturb_filters (eqf_lift.hpp;
-    // eqf_set_option "innovation_lift"): the records [B][kLiftRec] of the last of these calls, allocated by the first of them, and -- by
-    // the first call with the option on -- the right-hand-side rows [B][kLiftRhs][ld], the record of the current diagonal block
-    // [B][kDRec] and the pivot words [B] (the image that is factored is dSigmaLoc)
-    int liftOpt = 0;
-    bool liftCalled = false, liftLdsSet = false;
-    double *dLiftRec = nullptr, *dLiftE = nullptr, *dLiftD = nullptr;
-    int* dLiftBad = nullptr;
-    // eqf_copy_filters (eqf_clone.hpp): the pair table (pinned image + device copy, grown on demand), the small-state staging image of the
-    // in-place case (allocated on first need) and two events -- evCloneSrc orders a copy behind this handle's work when it is the source,
-    // evCloneDone marks the end of the last copy INTO this handle (its pair table may be reused, the source may go on)
-    ClonePair *hClonePairs = nullptr, *dClonePairs = nullptr;
-    int clonePairsCap = 0;
-    char* dCloneSmall = nullptr;
-    hipEvent_t evCloneSrc = nullptr, evCloneDone = nullptr;
-    // moment matching over the handle's filters (eqf_mixture.hpp; eqf_get_mixture_moments / eqf_merge_filters), allocated on first need
-    // from capacity and batch: the workspace (mixture::WorkLayout), the member table of a call (pinned image + device copy, grown on
-    // demand: members, then the distinct filters) and evMix: the last upload from the pinned image has been read
-    double* dMixWs = nullptr;
-    char *hMixTab = nullptr, *dMixTab = nullptr;
-    size_t mixTabBytes = 0;
-    int mixLaunches = 0;  // kernel launches of the most recent mixture call, counted as they are made (eqf_debug_mixture_launches)
-    hipEvent_t evMix = nullptr;
+    // allocated by the first call that needs them.  dSigmaLoc is ONE slot that the getters, NEES and the draws, the lift, the mixture
+    // routes and the in-place copy all name (sigmaLocWant)
+    DevPtr<double> dJac, dSigmaLoc;
     // innovation statistics of every update (eqf_innov.hpp; eqf_set_option "innovation_stats"): the tail launch k_innov_stats and its
     // records [B][kInnovHead + cap], allocated when the option is first switched on
     int innovStats = 0;
-    double* dInnov = nullptr;
+    DevPtr<double> dInnov;
     int resTickets = 0;           // eqf_debug_option "res_tickets": 0 (default) the block index (rounds 3-5), 1 tickets on grids >= 6 x the resident slots, 2 on every grid larger than the chip (non-FOLD)
-    double *dGammaPart = nullptr, *dG11Part = nullptr;
-    ResRole* dRoles = nullptr;
+    DevPtr<double> dGammaPart, dG11Part;
+    DevPtr<ResRole> dRoles;
+    size_t rolesBytes = 0;            // (capacity of dRoles)
     int rolesN = -1, rolesCount = 0;  // chain shape (nbS, nbE, wtS) the role table was built for
     unsigned long long rolesOmit = 0; // ... and the right-hand-side roles W(0, C) of the E-chain it leaves out (bit C; border rows)
     int resBorder = 1;                // eqf_debug_option "res_border": the co-resident update launch carries the lift's regressors as border rows of the E-chain's last block row (eqf_border_host.hpp); 0: the right-hand-side roles of the E-chain as before
     bool countsExact = true;          // the landmark counts the update will find on the device are the host's (false: a device-side outlier gate may lower them)
     int rolesFront = 0;               // roles in front of the prep roles (buildRoles' `front`)
     int dropRole[4] = {-1, 0, 0, 0};  // eqf_debug_drop_role: (kind, role, R, C) of the role whose workgroup leaves without publishing anything
-    // profiling
+    // profiling (the event pool is the one place that creates and destroys events by hand)
     bool prof = false;
     std::vector<ProfPair> profPairs;
     std::vector<hipEvent_t> evPool;
@@ -314,38 +366,28 @@ struct eqf_filter {
     double profMs[EQF_PROF_CLASSES] = {};
     std::vector<ProfSample> profSamples[EQF_PROF_CLASSES];  // per-bracket times with their launch shape
     double profOverheadMs = 0.0;  // elapsed time of an EMPTY event bracket (calibrated when profiling is switched on)
-    // the non-mutating forecast (eqf_forecast.hpp; eqf_forecast), allocated by its first call from capacity and batch: the samples of a call
-    // as a pinned image and its device copy, the per-step records the builder leaves for the landmark lanes, and the output records as a
-    // device image and its pinned copy (forecast::imageCapacityDoubles / recDoubles / outStride).  The call synchronises before it returns,
-    // so the pinned images need no event.  (Last in the handle: what the per-step calls touch keeps its place.)
-    ImuRec *hFcImu = nullptr, *dFcImu = nullptr;
-    double *dFcRec = nullptr, *dFcOut = nullptr, *hFcOut = nullptr;
-    // pairwise merge costs (eqf_mergecost.hpp; eqf_get_merge_costs), allocated on first need: one block for a chunk of images with their
-    // right-hand sides, records and orders (grown when the option "merge_cost_chunk" asks for more), one for a call's items and records.
-    // (Behind everything else, for the same reason.)
-    char* dMcWs = nullptr;
-    int mcChunkCap = 0, mcChunkOpt = 0;
-    char* dMcItems = nullptr;
-    size_t mcItemCap = 0;
-    // scoring candidate frames (eqf_score.hpp; eqf_score_vision), allocated on first need: one block for a chunk of images of order
-    // score::paddedOrder(capacity) with their right-hand-side rows, diagonal-block records and pivot words (grown when the option
-    // "score_chunk" asks for more), one for a call's items, matched slots, bearings, per-landmark statistics and records.  (Last, again.)
-    char* dScWs = nullptr;
-    int scChunkCap = 0, scChunkOpt = 0;
-    char* dScTab = nullptr;
-    size_t scTabBytes = 0;
-    bool scoreLdsSet = false;
-    // explicit landmark edits (eqf_mapedit.hpp; eqf_edit_landmarks), allocated by the first call from capacity and batch: the plan's image
-    // (mapedit::Image) as a pinned copy and its device copy, and evMapEdit: the last upload from the pinned image has been read.  (Last.)
-    char *hMapEdit = nullptr, *dMapEdit = nullptr;
-    hipEvent_t evMapEdit = nullptr;
-    // the Schmidt updates (eqf_schmidt.hpp; eqf_update_linear_schmidt / eqf_update_landmarks_schmidt), allocated by the first call from
-    // capacity and batch: the partition's image (schmidt::Image) as a pinned copy and its device copy, and evSch: the last upload from the
-    // pinned image has been read.  (Last.)
-    char *hSch = nullptr, *dSch = nullptr;
-    char* hSchDev = nullptr;  // device-side address of the pinned hSch (k_schmidt_gamma reads it)
-    hipEvent_t evSch = nullptr;
-    bool schLdsSet = false;
+    // ---- the optional routes, behind everything the per-step calls touch (R21.1: a route's pointers in the middle of the handle cost
+    // 0.6 % of the benchmark).  A new route adds a sub-struct here and names its slots where it reserves.
+    NeesRoute nees;
+    SampRoute samp;
+    LinRoute lin;
+    BlkRoute blk;
+    LiftRoute lift;
+    CloneRoute clone;
+    MixRoute mix;
+    ForecastRoute fc;
+    MergeCostRoute mc;
+    ScoreRoute sc;
+    MapEditRoute medit;
+    SchmidtRoute sch;
+
+    ~eqf_filter() {
+        for (auto e : evPool) (void)hipEventDestroy(e);
+        for (auto& p : profPairs) {
+            (void)hipEventDestroy(p.a);
+            (void)hipEventDestroy(p.b);
+        }
+    }
 };
 
 namespace {
@@ -387,30 +429,82 @@ int profDrain(eqf_filter* f) {
     return EQF_OK;
 }
 
+// `count` elements (of `esz` bytes where the owner is untyped) into an owner; what it held is freed first
 template <typename T>
-int dmalloc(T** p, size_t count) {
-    HIPC(hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T)));
+int dmalloc(DevPtr<T>& p, size_t count, size_t esz = sizeof(std::conditional_t<std::is_void<T>::value, char, T>)) {
+    p.reset();
+    HIPC(hipMalloc(p.slot(), std::max<size_t>(count, 1) * esz));
     return EQF_OK;
 }
-template <typename T>
-int hmalloc(T** p, size_t count) {
-    HIPC(hipHostMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
+template <typename T, bool M>
+int hmalloc(PinnedPtr<T, M>& p, size_t count) {
+    p.reset();
+    HIPC(hipHostMalloc(p.slot(), std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
+    if constexpr (M) HIPC(hipHostGetDevicePointer(p.mapped(), p.get(), 0));
     return EQF_OK;
 }
 
-int stageInit(IntStage& s, size_t count) {
+// ---- the HIP side of the allocation transaction (eqf_workspace_host.hpp)
+struct HipBackend {
+    hipStream_t stream;
+    void* allocDevice(size_t bytes) {
+        void* p = nullptr;
+        return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr;
+    }
+    void* allocPinned(size_t bytes, void** mapped) {
+        void* p = nullptr;
+        if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
+        if (mapped && hipHostGetDevicePointer(mapped, p, 0) != hipSuccess) {
+            (void)hipHostFree(p);
+            return nullptr;
+        }
+        return p;
+    }
+    void* allocEvent() {
+        hipEvent_t e = nullptr;
+        return hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess ? e : nullptr;
+    }
+    void freeDevice(void* p) { (void)hipFree(p); }
+    void freePinned(void* p) { (void)hipHostFree(p); }
+    void freeEvent(void* p) { (void)hipEventDestroy(static_cast<hipEvent_t>(p)); }
+    bool drain() { return hipStreamSynchronize(stream) == hipSuccess; }
+    void clearError() { (void)hipGetLastError(); }  // (a failed allocation must not fail the next launch through the sticky last error)
+};
+// the wants of the owners
+template <class T>
+workspace::Want want(DevPtr<T>& p, size_t bytes, size_t* cap = nullptr) { return workspace::device(p.slot(), bytes, cap); }
+template <class T>
+workspace::Want want(PinnedPtr<T, false>& p, size_t bytes, size_t* cap = nullptr) { return workspace::pinned(p.slot(), bytes, cap); }
+template <class T>
+workspace::Want want(PinnedPtr<T, true>& p, size_t bytes, size_t* cap = nullptr) { return workspace::pinned(p.slot(), bytes, cap, p.mapped()); }
+inline workspace::Want want(Event& e) { return workspace::event(e.slot()); }
+// (a staged image is three wants: WANT_STAGED(image, bytes) inside a list)
+#define WANT_STAGED(im, bytes) want((im).host, (bytes), &(im).cap), want((im).dev, (bytes), &(im).cap), want((im).read)
+// Everything a call needs, all or nothing (workspace::reserve): EQF_ERR_HIP leaves the handle exactly as it was.  `installed`: which
+// wants this call allocated.
+template <int N>
+int reserveSlots(eqf_filter* f, const workspace::Want (&w)[N], workspace::Result* installed = nullptr) {
+    HipBackend be{f->stream};
+    const workspace::Result r = workspace::reserve(be, w);
+    if (installed) *installed = r;
+    return r.ok ? EQF_OK : EQF_ERR_HIP;
+}
+// the image of Sigma's size that several routes share: one slot
+workspace::Want sigmaLocWant(eqf_filter* f, bool wanted = true) {
+    return want(f->dSigmaLoc, wanted ? sizeof(double) * size_t(f->sigmaStride) * f->B : 0);
+}
+
+int eventInit(eqf_filter* f, Event& e) {
+    const workspace::Want w[] = {want(e)};
+    return reserveSlots(f, w);
+}
+int stageInit(eqf_filter* f, IntStage& s, size_t count) {
     for (int i = 0; i < IntStage::kSlots; ++i) {
-        int rc = hmalloc(&s.host[i], count);
+        int rc = hmalloc(s.host[i], count);
+        if (!rc) rc = eventInit(f, s.ev[i]);
         if (rc) return rc;
-        HIPC(hipEventCreateWithFlags(&s.ev[i], hipEventDisableTiming));
     }
     return EQF_OK;
-}
-void stageFree(IntStage& s) {
-    for (int i = 0; i < IntStage::kSlots; ++i) {
-        if (s.host[i]) hipHostFree(s.host[i]);
-        if (s.ev[i]) hipEventDestroy(s.ev[i]);
-    }
 }
 // next free staging buffer (waits only if its previous upload, 8 uploads ago, is still in flight)
 int stageAcquire(IntStage& s, int** host, int* slot) {
@@ -856,10 +950,9 @@ int buildRoles(eqf_filter* f, int Nmax, bool fold, int front = 0, bool border = 
     if (f->dropRole[0] >= 0)
         for (auto& q : r)
             if (q.kind == f->dropRole[0] && q.role == f->dropRole[1] && q.R == f->dropRole[2] && q.C == f->dropRole[3]) q.R = 1 << 20;
-    HIPC(hipStreamSynchronize(f->stream));
-    hipFree(f->dRoles);
-    f->dRoles = nullptr;
-    int rc = dmalloc(&f->dRoles, r.size());
+    HIPC(hipStreamSynchronize(f->stream));  // (the last update may still read the table)
+    const workspace::Want w[] = {want(f->dRoles, sizeof(ResRole) * std::max<size_t>(r.size(), 1), &f->rolesBytes)};
+    int rc = reserveSlots(f, w);
     if (rc) return rc;
     HIPC(hipMemcpy(f->dRoles, r.data(), sizeof(ResRole) * r.size(), hipMemcpyHostToDevice));
     f->rolesN = key;
@@ -1294,16 +1387,16 @@ int probe(eqf_filter* f, const double* bearings, long long bearStride, bool with
     const int B = f->B, cap = f->cap;
     const int nmax = std::max(1, maxN(f));
     // with readback the kernel writes the chords straight into pinned host memory (no copy command behind it)
-    double* chordDst = (readback || speculative) ? f->hChordDev : f->dChord;  // (speculative: resolveGate reads them if the gate tripped)
+    double* chordDst = (readback || speculative) ? f->hChord.dev : f->dChord;  // (speculative: resolveGate reads them if the gate tripped)
     // (the Mahalanobis statistic only where a gate looks at it: the depth-only probe of addNewAndUpdate stays k_probe)
     const bool maha = f->gateKind == EQF_GATE_MAHALANOBIS && bearings && (readback || speculative);
     int rc = profiled(f, EQF_PROF_CHURN, [&] {
         if (maha)
             hipLaunchKernelGGL(k_probe_maha, dim3((nmax + 127) / 128, B), dim3(128), 0, f->stream, f->g[f->pG], f->p0, f->Q[f->pG], cap, bearings,
-                bearStride, withPerm ? f->dPerm : nullptr, chordDst, f->dDepth2, f->gateThr, speculative ? f->hGateDev : nullptr, mahaArgs(f));
+                bearStride, withPerm ? f->dPerm : nullptr, chordDst, f->dDepth2, f->gateThr, speculative ? f->hGate.dev : nullptr, mahaArgs(f));
         else
             hipLaunchKernelGGL(k_probe, dim3((nmax + 127) / 128, B), dim3(128), 0, f->stream, f->g[f->pG], f->p0, f->Q[f->pG], cap, bearings,
-                bearStride, withPerm ? f->dPerm : nullptr, chordDst, f->dDepth2, f->gateThr, speculative ? f->hGateDev : nullptr);
+                bearStride, withPerm ? f->dPerm : nullptr, chordDst, f->dDepth2, f->gateThr, speculative ? f->hGate.dev : nullptr);
     });
     if (rc) return rc;
     if (readback) HIPC(hipStreamSynchronize(f->stream));
@@ -1326,7 +1419,7 @@ int awaitMaskAndClearFlags(eqf_filter* f) {
         HIPC(hipEventSynchronize(f->evMask));
         f->maskPending = false;
     }
-    std::fill(f->hGate, f->hGate + f->B, 0);
+    std::fill(f->hGate.get(), f->hGate + f->B, 0);
     return EQF_OK;
 }
 
@@ -1343,7 +1436,7 @@ int armGate(eqf_filter* f, bool onDevice, const frame::Meas& m, const double* be
 
 // resolveGate's redo: the update of the filters hGate marks runs after all
 int launchSetUpdateOk(eqf_filter* f) {
-    hipLaunchKernelGGL(k_set_update_ok, dim3((f->B + 63) / 64), dim3(64), 0, f->stream, f->g[f->pG], f->hGateDev, f->B);
+    hipLaunchKernelGGL(k_set_update_ok, dim3((f->B + 63) / 64), dim3(64), 0, f->stream, f->g[f->pG], f->hGate.dev, f->B);
     HIPC(hipEventRecord(f->evMask, f->stream));
     f->maskPending = true;
     return EQF_OK;
@@ -1412,8 +1505,8 @@ int visionOneLaunch(eqf_filter* f, const frame::Meas& m, const double* bearings,
     ea.bearings = bearings; ea.bearStride = bearStride;
     ea.gateThr = f->gateThr;
     ea.measVar = f->set.measurementVariance;
-    ea.gateFlag = gateArmed ? f->hGateDev : nullptr;
-    ea.chordOut = gateArmed ? f->hChordDev : nullptr;
+    ea.gateFlag = gateArmed ? f->hGate.dev : nullptr;
+    ea.chordOut = gateArmed ? f->hChord.dev : nullptr;
     ea.depthDefault = f->set.initialSceneDepth; ea.pointVar = f->set.initialPointVariance;
     ea.p0 = f->p0; ea.Q = f->Q[f->pG]; ea.lmc = f->lmc;
     ea.errflag = f->errflag;
@@ -1652,85 +1745,6 @@ int resolveGate(eqf_filter* f) {
     return visionCore(f, mids, f->gate.nb, f->gate.bearings, f->gate.bearStride, act, nullptr, &gated);
 }
 
-void freeAll(eqf_filter* f) {
-    if (!f) return;
-    for (int p = 0; p < 2; ++p) {
-        hipFree(f->Sigma[p]);
-        hipFree(f->g[p]);
-        hipFree(f->Q[p]);
-    }
-    for (void* p : {(void*)f->p0, (void*)f->lmc, (void*)f->SA, (void*)f->SL, (void*)f->YW, (void*)f->YO, (void*)f->EA, (void*)f->EL, (void*)f->ZW,
-             (void*)f->ZO, (void*)f->dbgDelta, (void*)f->dbgGamma, (void*)f->dbgGammaTot, (void*)f->red, (void*)f->errflag, (void*)f->dMap,
-             (void*)f->dPerm, (void*)f->dChord, (void*)f->dDepth2, (void*)f->dDepthSel, (void*)f->dScratch, (void*)f->dMeas,
-             (void*)f->dOut, (void*)f->dRing, (void*)f->sImu, (void*)f->sVis, (void*)f->sBear, f->dF, f->dG, f->dBn, f->dBlk, (void*)f->dBlkCommon, f->dColRec, f->dRowRec, (void*)f->dSteps, (void*)f->dFlags, (void*)f->dReadyA, (void*)f->dReadyY, (void*)f->dResCounters, (void*)f->dTicket, (void*)f->dStageFlags, (void*)f->dPrepFlags, (void*)f->dBuildFlags, (void*)f->dGammaPart,
-             (void*)f->dG11Part, (void*)f->dRoles, (void*)f->dI8Ws, (void*)f->dI8Expo, (void*)f->dJac, (void*)f->dSigmaLoc, (void*)f->dInnov,
-             (void*)f->dNeesE, (void*)f->dNeesD, (void*)f->dNeesOut, (void*)f->dNeesBad, (void*)f->dSampZ, (void*)f->dSampE, (void*)f->dSampSmall})
-        hipFree(p);
-    if (f->hSampSmall) hipHostFree(f->hSampSmall);
-    if (f->evSamp) hipEventDestroy(f->evSamp);
-    hipFree(f->dLinSmall);
-    hipFree(f->dLinWs);
-    hipFree(f->dLinOut);
-    if (f->hLinSmall) hipHostFree(f->hLinSmall);
-    if (f->evLin) hipEventDestroy(f->evLin);
-    hipFree(f->dBlkSmall);
-    hipFree(f->dBlkWs);
-    hipFree(f->dBlkWi);
-    hipFree(f->dBlkOut);
-    hipFree(f->dLiftRec);
-    hipFree(f->dLiftE);
-    hipFree(f->dLiftD);
-    hipFree(f->dLiftBad);
-    if (f->hBlkSmall) hipHostFree(f->hBlkSmall);
-    if (f->evBlk) hipEventDestroy(f->evBlk);
-    if (f->hGate) hipHostFree(f->hGate);
-    if (f->dMask) hipFree(f->dMask);
-    if (f->evGate) hipEventDestroy(f->evGate);
-    if (f->evMask) hipEventDestroy(f->evMask);
-    stageFree(f->stMap);
-    stageFree(f->stPerm);
-    stageFree(f->stEdit);
-    hipFree(f->dEdit);
-    hipFree(f->dEditBar);
-    for (void* p : {(void*)f->hChord, (void*)f->hMeas,
-             (void*)f->hOut, (void*)f->hRing})
-        if (p) hipHostFree(p);
-    for (auto& e : f->evRing)
-        if (e) hipEventDestroy(e);
-    if (f->evMeas) hipEventDestroy(f->evMeas);
-    hipFree(f->dClonePairs);
-    hipFree(f->dCloneSmall);
-    if (f->hClonePairs) hipHostFree(f->hClonePairs);
-    if (f->evCloneSrc) hipEventDestroy(f->evCloneSrc);
-    if (f->evCloneDone) hipEventDestroy(f->evCloneDone);
-    hipFree(f->dFcImu);
-    hipFree(f->dFcRec);
-    hipFree(f->dFcOut);
-    if (f->hFcImu) hipHostFree(f->hFcImu);
-    if (f->hFcOut) hipHostFree(f->hFcOut);
-    hipFree(f->dMixWs);
-    hipFree(f->dMcWs);
-    hipFree(f->dMcItems);
-    hipFree(f->dScWs);
-    hipFree(f->dScTab);
-    hipFree(f->dMixTab);
-    hipFree(f->dMapEdit);
-    if (f->hMapEdit) hipHostFree(f->hMapEdit);
-    if (f->evMapEdit) hipEventDestroy(f->evMapEdit);
-    hipFree(f->dSch);
-    if (f->hSch) hipHostFree(f->hSch);
-    if (f->evSch) hipEventDestroy(f->evSch);
-    if (f->hMixTab) hipHostFree(f->hMixTab);
-    if (f->evMix) hipEventDestroy(f->evMix);
-    for (auto e : f->evPool) hipEventDestroy(e);
-    for (auto& p : f->profPairs) {
-        hipEventDestroy(p.a);
-        hipEventDestroy(p.b);
-    }
-    if (f->stream) hipStreamDestroy(f->stream);
-    delete f;
-}
-
 // ---- the blocked factorisation (eqf_factor.hpp): the one launch loop of every route that factors
 // Enqueues A = L L^T of `images` images (grid.y) of order at most mMax each (nb block columns: the one place on the host where an order
 // becomes a block-column count for a launch of these kernels), with rhsRows block rows of right-hand side carried along: diag(0) always (it clears the pivot word, also for an empty matrix), then per block column the diagonal block, the panel if a
@@ -1895,37 +1909,37 @@ int eqf_create(const eqf_settings* settings, int capacity_landmarks, int batch, 
     f->strideE = (long long)nepC * nepC; f->strideZ = (long long)nepC * kSB;
     int rc = EQF_OK;
     auto chk = [&](int r) { if (r && !rc) rc = r; };
-    if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess) rc = EQF_ERR_HIP;
+    if (hipStreamCreateWithFlags(f->stream.put(), hipStreamNonBlocking) != hipSuccess) rc = EQF_ERR_HIP;
     for (int q = 0; q < 2 && !rc; ++q) {
-        if (hipMalloc(&f->Sigma[q], f->esz * f->sigmaStride * B) != hipSuccess) rc = EQF_ERR_HIP;
-        chk(dmalloc(&f->g[q], B));
-        chk(dmalloc(&f->Q[q], (size_t)5 * cap * B));
+        chk(dmalloc(f->Sigma[q], (size_t)f->sigmaStride * B, f->esz));
+        chk(dmalloc(f->g[q], B));
+        chk(dmalloc(f->Q[q], (size_t)5 * cap * B));
     }
-    chk(dmalloc(&f->p0, (size_t)3 * cap * B));
-    chk(dmalloc(&f->lmc, (size_t)15 * cap * B));
+    chk(dmalloc(f->p0, (size_t)3 * cap * B));
+    chk(dmalloc(f->lmc, (size_t)15 * cap * B));
     f->strideDS = std::max<long long>(f->strideS, (long long)(mpC / kSB) * kDRec);
     f->strideDE = std::max<long long>(f->strideE, (long long)(nepC / kSB) * kDRec);
-    chk(dmalloc(&f->SA, f->strideS * B)); chk(dmalloc(&f->SL, f->strideDS * B));
-    chk(dmalloc(&f->YW, f->strideY * B)); chk(dmalloc(&f->YO, f->strideY * B));
-    chk(dmalloc(&f->EA, f->strideE * B)); chk(dmalloc(&f->EL, f->strideDE * B));
-    chk(dmalloc(&f->ZW, f->strideZ * B)); chk(dmalloc(&f->ZO, f->strideZ * B));
-    chk(dmalloc(&f->dbgDelta, (size_t)2 * cap * B));
-    chk(dmalloc(&f->dbgGamma, (size_t)(kLm0 + 3 * cap) * B));
-    chk(dmalloc(&f->dbgGammaTot, (size_t)(9 + 3 * cap) * B));
-    chk(dmalloc(&f->red, (size_t)256 * B));
-    chk(dmalloc(&f->errflag, 1));
-    chk(dmalloc(&f->dMap, (size_t)cap * B + B)); if (!rc) f->dNewN = f->dMap + (size_t)cap * B;  /* (one copy brings both) */ chk(dmalloc(&f->dPerm, (size_t)cap * B));
-    chk(dmalloc(&f->dChord, (size_t)cap * B)); chk(dmalloc(&f->dDepth2, (size_t)cap * B));
-    chk(dmalloc(&f->dScratch, (size_t)kLmRec * cap * B)); chk(dmalloc(&f->dMeas, (size_t)3 * cap * B + ((size_t)2 * cap * B + 4 * B + 1) / 2));  /* (+ k_edit's image behind the bearings: one copy brings both) */
-    chk(dmalloc(&f->dOut, (size_t)f->nTot * f->nTot + 16));
-    chk(dmalloc(&f->dRing, (size_t)kRing * B));
-    if (!rc && hipMalloc(&f->dBlk, f->esz * (size_t)kBlkRec * cap * B) != hipSuccess) rc = EQF_ERR_HIP;
-    chk(dmalloc(&f->dBlkCommon, B));
-    if (!rc && hipMalloc(&f->dColRec, f->esz * (size_t)kBurstMax * burstRecStep((long long)kColRec * cap) * B) != hipSuccess) rc = EQF_ERR_HIP;
-    if (!rc && hipMalloc(&f->dRowRec, f->esz * (size_t)kBurstMax * burstRecStep((long long)kBlkRec * cap) * B) != hipSuccess) rc = EQF_ERR_HIP;
-    chk(dmalloc(&f->dSteps, (size_t)kBurstMax * B));
+    chk(dmalloc(f->SA, f->strideS * B)); chk(dmalloc(f->SL, f->strideDS * B));
+    chk(dmalloc(f->YW, f->strideY * B)); chk(dmalloc(f->YO, f->strideY * B));
+    chk(dmalloc(f->EA, f->strideE * B)); chk(dmalloc(f->EL, f->strideDE * B));
+    chk(dmalloc(f->ZW, f->strideZ * B)); chk(dmalloc(f->ZO, f->strideZ * B));
+    chk(dmalloc(f->dbgDelta, (size_t)2 * cap * B));
+    chk(dmalloc(f->dbgGamma, (size_t)(kLm0 + 3 * cap) * B));
+    chk(dmalloc(f->dbgGammaTot, (size_t)(9 + 3 * cap) * B));
+    chk(dmalloc(f->red, (size_t)256 * B));
+    chk(dmalloc(f->errflag, 1));
+    chk(dmalloc(f->dMap, (size_t)cap * B + B)); if (!rc) f->dNewN = f->dMap + (size_t)cap * B;  /* (one copy brings both) */ chk(dmalloc(f->dPerm, (size_t)cap * B));
+    chk(dmalloc(f->dChord, (size_t)cap * B)); chk(dmalloc(f->dDepth2, (size_t)cap * B));
+    chk(dmalloc(f->dScratch, (size_t)kLmRec * cap * B)); chk(dmalloc(f->dMeas, (size_t)3 * cap * B + ((size_t)2 * cap * B + 4 * B + 1) / 2));  /* (+ k_edit's image behind the bearings: one copy brings both) */
+    chk(dmalloc(f->dOut, (size_t)f->nTot * f->nTot + 16));
+    chk(dmalloc(f->dRing, (size_t)kRing * B));
+    chk(dmalloc(f->dBlk, (size_t)kBlkRec * cap * B, f->esz));
+    chk(dmalloc(f->dBlkCommon, B));
+    chk(dmalloc(f->dColRec, (size_t)kBurstMax * burstRecStep((long long)kColRec * cap) * B, f->esz));
+    chk(dmalloc(f->dRowRec, (size_t)kBurstMax * burstRecStep((long long)kBlkRec * cap) * B, f->esz));
+    chk(dmalloc(f->dSteps, (size_t)kBurstMax * B));
     f->nBuildCap = ((cap + 3) / 4 + 63) / 64 * 64 + 1088;  // stride of a replica: > 4 KB, not a multiple of it
-    chk(dmalloc(&f->dBuildFlags, (size_t)f->nBuildCap * kFlagReplicas * B));
+    chk(dmalloc(f->dBuildFlags, (size_t)f->nBuildCap * kFlagReplicas * B));
     if (!rc && hipMemset(f->dBuildFlags, 0, sizeof(int) * f->nBuildCap * kFlagReplicas * B) != hipSuccess) rc = EQF_ERR_HIP;
     if (const char* e = std::getenv("EQF_BURST_ROWS")) f->burstRows = (std::atoi(e) == 1 || std::atoi(e) == 2 || std::atoi(e) == 4) ? std::atoi(e) : 0;
     if (const char* e = std::getenv("EQF_IMU_BURST")) f->burstMax = std::max(0, std::min(kBurstMax, std::atoi(e)));
@@ -1944,18 +1958,18 @@ int eqf_create(const eqf_settings* settings, int capacity_landmarks, int batch, 
         // roles in the batch (one filter of N = 4000: 71 k), beyond that the per-column launches run
         const long long maxRoles = (long long)(f->nbCap + 1) * f->nbCap + (long long)f->wtCap * f->nbCap;
         if (!rc && maxRoles * B <= 200000) {  // (N = 4000: 71 k roles)
-            chk(dmalloc(&f->dReadyA, (size_t)2 * f->nbCap * f->nbCap * B));
-            chk(dmalloc(&f->dReadyY, (size_t)2 * f->nbCap * f->wtCap * B));
-            chk(dmalloc(&f->dResCounters, (size_t)4 * B));
-            chk(dmalloc(&f->dTicket, (size_t)32 * B));  // (one counter per filter, a 128-byte line each)
+            chk(dmalloc(f->dReadyA, (size_t)2 * f->nbCap * f->nbCap * B));
+            chk(dmalloc(f->dReadyY, (size_t)2 * f->nbCap * f->wtCap * B));
+            chk(dmalloc(f->dResCounters, (size_t)4 * B));
+            chk(dmalloc(f->dTicket, (size_t)32 * B));  // (one counter per filter, a 128-byte line each)
             if (!rc && hipMemset(f->dTicket, 0, sizeof(unsigned) * 32 * B) != hipSuccess) rc = EQF_ERR_HIP;
-            chk(dmalloc(&f->dStageFlags, (size_t)2 * f->nbCap * 4 * B));
+            chk(dmalloc(f->dStageFlags, (size_t)2 * f->nbCap * 4 * B));
             if (!rc && hipMemset(f->dStageFlags, 0, sizeof(int) * 2 * f->nbCap * 4 * B) != hipSuccess) rc = EQF_ERR_HIP;
             f->nPrepCap = (mpC / 2 + 3) / 1 + nepC / kNB + 8;  // (landmark workgroups carry >= 1 wave each; Z-row workgroups of kNB rows)
-            chk(dmalloc(&f->dPrepFlags, (size_t)f->nPrepCap * B));
+            chk(dmalloc(f->dPrepFlags, (size_t)f->nPrepCap * B));
             if (!rc && hipMemset(f->dPrepFlags, 0, sizeof(int) * f->nPrepCap * B) != hipSuccess) rc = EQF_ERR_HIP;
-            chk(dmalloc(&f->dGammaPart, (size_t)f->nbCap * ycC * B));
-            chk(dmalloc(&f->dG11Part, (size_t)f->nbCap * 128 * B));
+            chk(dmalloc(f->dGammaPart, (size_t)f->nbCap * ycC * B));
+            chk(dmalloc(f->dG11Part, (size_t)f->nbCap * 128 * B));
             if (!rc && (hipMemset(f->dReadyA, 0, sizeof(int) * 2 * f->nbCap * f->nbCap * B) != hipSuccess ||
                         hipMemset(f->dReadyY, 0, sizeof(int) * 2 * f->nbCap * f->wtCap * B) != hipSuccess ||
                         hipMemset(f->dResCounters, 0, sizeof(int) * 4 * B) != hipSuccess))
@@ -1963,28 +1977,21 @@ int eqf_create(const eqf_settings* settings, int capacity_landmarks, int batch, 
         }
     }
     f->flagStride = std::max(mpC, nepC) / kSB + 1;
-    chk(dmalloc(&f->dFlags, (size_t)2 * f->flagStride * B));
+    chk(dmalloc(f->dFlags, (size_t)2 * f->flagStride * B));
     if (!rc && hipMemset(f->dFlags, 0, sizeof(int) * 2 * f->flagStride * B) != hipSuccess) rc = EQF_ERR_HIP;
     if (const char* e = std::getenv("EQF_GATE_SPECULATIVE")) f->gateSpeculative = std::atoi(e);
-    chk(stageInit(f->stMap, (size_t)cap * B + B)); chk(stageInit(f->stPerm, (size_t)cap * B));
-    chk(stageInit(f->stEdit, (size_t)2 * cap * B + 4 * B)); chk(dmalloc(&f->dEdit, (size_t)2 * cap * B + 4 * B)); chk(dmalloc(&f->dEditBar, (size_t)4 * B));
+    chk(stageInit(f, f->stMap, (size_t)cap * B + B)); chk(stageInit(f, f->stPerm, (size_t)cap * B));
+    chk(stageInit(f, f->stEdit, (size_t)2 * cap * B + 4 * B)); chk(dmalloc(f->dEdit, (size_t)2 * cap * B + 4 * B)); chk(dmalloc(f->dEditBar, (size_t)4 * B));
     if (!rc && hipMemset(f->dEditBar, 0, sizeof(int) * 4 * B) != hipSuccess) rc = EQF_ERR_HIP;
-    chk(hmalloc(&f->hChord, (size_t)cap * B)); chk(dmalloc(&f->dDepthSel, B));
-    chk(hmalloc(&f->hGate, B)); chk(dmalloc(&f->dMask, B));
-    if (!rc && hipHostGetDevicePointer(reinterpret_cast<void**>(&f->hGateDev), f->hGate, 0) != hipSuccess) rc = EQF_ERR_HIP;
-    if (!rc && hipEventCreateWithFlags(&f->evGate, hipEventDisableTiming) != hipSuccess) rc = EQF_ERR_HIP;
-    if (!rc && hipEventCreateWithFlags(&f->evMask, hipEventDisableTiming) != hipSuccess) rc = EQF_ERR_HIP;
-    if (!rc && hipHostGetDevicePointer(reinterpret_cast<void**>(&f->hChordDev), f->hChord, 0) != hipSuccess) rc = EQF_ERR_HIP;
-    chk(hmalloc(&f->hMeas, (size_t)3 * cap * B + ((size_t)2 * cap * B + 4 * B + 1) / 2)); chk(hmalloc(&f->hOut, (size_t)f->nTot * f->nTot + 16));
-    chk(hmalloc(&f->hRing, (size_t)kRing * B));
-    if (!rc) {
-        for (auto& e : f->evRing)
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = EQF_ERR_HIP;
-        if (hipEventCreateWithFlags(&f->evMeas, hipEventDisableTiming) != hipSuccess) rc = EQF_ERR_HIP;
-    }
+    chk(hmalloc(f->hChord, (size_t)cap * B)); chk(dmalloc(f->dDepthSel, B));
+    chk(hmalloc(f->hGate, B)); chk(dmalloc(f->dMask, B));
+    chk(eventInit(f, f->evGate)); chk(eventInit(f, f->evMask)); chk(eventInit(f, f->evMeas));
+    chk(hmalloc(f->hMeas, (size_t)3 * cap * B + ((size_t)2 * cap * B + 4 * B + 1) / 2)); chk(hmalloc(f->hOut, (size_t)f->nTot * f->nTot + 16));
+    chk(hmalloc(f->hRing, (size_t)kRing * B));
+    for (auto& e : f->evRing) chk(eventInit(f, e));
     if (!rc) rc = initState(f);
     if (rc) {
-        freeAll(f);
+        delete f;  // (the device is current: every owner frees what it got, the stream last)
         return rc;
     }
     *out = f;
@@ -1995,7 +2002,7 @@ void eqf_destroy(eqf_filter* f) {
     if (!f) return;
     hipSetDevice(f->device);
     if (f->stream) hipStreamSynchronize(f->stream);
-    freeAll(f);
+    delete f;
 }
 
 int eqf_reset(eqf_filter* f) {
@@ -2121,8 +2128,7 @@ int eqf_stream_upload(eqf_filter* f, int K, const double* imu, int F, const doub
     const int B = f->B;
     for (int k = 1; k < nbear; ++k)
         if (ids[k] <= ids[k - 1]) return EQF_ERR_UNSORTED;  // strictly ascending, as in eqf_process_vision
-    hipFree(f->sImu); hipFree(f->sVis); hipFree(f->sBear);
-    f->sImu = nullptr; f->sVis = nullptr; f->sBear = nullptr;
+    f->sImu.reset(); f->sVis.reset(); f->sBear.reset();
     std::vector<ImuRec> ri((size_t)K * B), rv((size_t)F * B);
     f->hImuStamp.resize((size_t)K * B);
     f->hVisStamp.resize((size_t)F * B);
@@ -2141,9 +2147,9 @@ int eqf_stream_upload(eqf_filter* f, int K, const double* imu, int F, const doub
         rv[e].stamp = vstamps[e];
         f->hVisStamp[e] = vstamps[e];
     }
-    int rc = dmalloc(&f->sImu, ri.size());
-    if (!rc) rc = dmalloc(&f->sVis, rv.size());
-    if (!rc) rc = dmalloc(&f->sBear, (size_t)F * B * nbear * 3);
+    int rc = dmalloc(f->sImu, ri.size());
+    if (!rc) rc = dmalloc(f->sVis, rv.size());
+    if (!rc) rc = dmalloc(f->sBear, (size_t)F * B * nbear * 3);
     if (rc) return rc;
     HIPC(hipMemcpy(f->sImu, ri.data(), sizeof(ImuRec) * ri.size(), hipMemcpyHostToDevice));
     HIPC(hipMemcpy(f->sVis, rv.data(), sizeof(ImuRec) * rv.size(), hipMemcpyHostToDevice));
@@ -2226,7 +2232,7 @@ int eqf_get_state_estimate(eqf_filter* f, int b, double* pose_q, double* pose_x,
     hipLaunchKernelGGL(k_state_estimate, dim3((N + 255) / 256 + 1), dim3(256), 0, f->stream, f->g[f->pG], b, f->p0, f->Q[f->pG], f->cap, f->dOut);
     HIPC(hipMemcpyAsync(f->hOut, f->dOut, sizeof(double) * (10 + 3 * N), hipMemcpyDeviceToHost, f->stream));
     HIPC(hipStreamSynchronize(f->stream));
-    if (pose_q) std::copy(f->hOut, f->hOut + 4, pose_q);
+    if (pose_q) std::copy(f->hOut.get(), f->hOut + 4, pose_q);
     if (pose_x) std::copy(f->hOut + 4, f->hOut + 7, pose_x);
     if (velocity) std::copy(f->hOut + 7, f->hOut + 10, velocity);
     if (p) std::copy(f->hOut + 10, f->hOut + 10 + 3 * N, p);
@@ -2314,19 +2320,10 @@ int eqf_get_sigma(eqf_filter* f, int b, double* dst, int ld) {
 // coordinates of the estimate as well (k_sigma_local).  The buffers are allocated on first use: a failed allocation is EQF_ERR_HIP and
 // leaves the handle as it was.
 static int launchLocal(eqf_filter* f, int b0, int count, bool sigmaToo) {
-    if (!f->dJac) {
-        if (hipMalloc(reinterpret_cast<void**>(&f->dJac), sizeof(double) * size_t(jacStride(f->cap)) * f->B) != hipSuccess) {
-            (void)hipGetLastError();
-            f->dJac = nullptr;
-            return EQF_ERR_HIP;
-        }
-    }
-    if (sigmaToo && !f->dSigmaLoc) {
-        if (hipMalloc(reinterpret_cast<void**>(&f->dSigmaLoc), sizeof(double) * size_t(f->sigmaStride) * f->B) != hipSuccess) {
-            (void)hipGetLastError();
-            f->dSigmaLoc = nullptr;
-            return EQF_ERR_HIP;
-        }
+    {
+        const workspace::Want w[] = {want(f->dJac, sizeof(double) * size_t(jacStride(f->cap)) * f->B), sigmaLocWant(f, sigmaToo)};
+        const int rc = reserveSlots(f, w);
+        if (rc) return rc;
     }
     int nMax = 0;
     for (int b = b0; b < b0 + count; ++b) nMax = std::max(nMax, int(f->ids[b].size()));
@@ -2380,7 +2377,7 @@ int eqf_get_marginals(eqf_filter* f, int b, int local, double* base, double* lm)
     HIPC(hipMemcpyAsync(head, f->dJac + (long long)b * jacStride(f->cap), sizeof(head), hipMemcpyDeviceToHost, f->stream));
     HIPC(hipStreamSynchronize(f->stream));
     if (local && head[13] != 0.0) return EQF_ERR_NUMERIC;
-    std::copy(f->hOut, f->hOut + 121, base);
+    std::copy(f->hOut.get(), f->hOut + 121, base);
     if (N > 0) std::copy(f->hOut + 121, f->hOut + 121 + (size_t)9 * N, lm);
     return EQF_OK;
 }
@@ -2397,36 +2394,18 @@ int eqf_get_local_jacobian(eqf_filter* f, int b, double* G, double* RAt, double*
         f->stream));
     HIPC(hipStreamSynchronize(f->stream));
     if (f->hOut[13] != 0.0) return EQF_ERR_NUMERIC;
-    std::copy(f->hOut, f->hOut + 4, G);
+    std::copy(f->hOut.get(), f->hOut + 4, G);
     std::copy(f->hOut + 4, f->hOut + 13, RAt);
     if (N > 0) std::copy(f->hOut + kJacHead, f->hOut + kJacHead + (size_t)9 * N, lmJ);
     return EQF_OK;
 }
 
-// eqf_forecast's workspace, all or nothing: a failed allocation leaves the handle as it was
+// eqf_forecast's workspace, from capacity and batch
 static int forecastWorkspace(eqf_filter* f) {
-    if (f->dFcOut) return EQF_OK;
     const size_t nImg = sizeof(double) * forecast::imageCapacityDoubles(f->B), nRec = sizeof(double) * forecast::recDoubles(f->B),
                  nOut = sizeof(double) * forecast::outStride(f->cap) * f->B;
-    void *hImu = nullptr, *dImu = nullptr, *dRec = nullptr, *dOut = nullptr, *hOut = nullptr;
-    const bool ok = hipHostMalloc(&hImu, nImg, hipHostMallocDefault) == hipSuccess && hipMalloc(&dImu, nImg) == hipSuccess &&
-                    hipMalloc(&dRec, nRec) == hipSuccess && hipMalloc(&dOut, nOut) == hipSuccess &&
-                    hipHostMalloc(&hOut, nOut, hipHostMallocDefault) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        if (hImu) hipHostFree(hImu);
-        if (hOut) hipHostFree(hOut);
-        hipFree(dImu);
-        hipFree(dRec);
-        hipFree(dOut);
-        return EQF_ERR_HIP;
-    }
-    f->hFcImu = static_cast<ImuRec*>(hImu);
-    f->dFcImu = static_cast<ImuRec*>(dImu);
-    f->dFcRec = static_cast<double*>(dRec);
-    f->dFcOut = static_cast<double*>(dOut);
-    f->hFcOut = static_cast<double*>(hOut);
-    return EQF_OK;
+    const workspace::Want w[] = {want(f->fc.hImu, nImg), want(f->fc.dImu, nImg), want(f->fc.rec, nRec), want(f->fc.dOut, nOut), want(f->fc.hOut, nOut)};
+    return reserveSlots(f, w);
 }
 
 int eqf_forecast(eqf_filter* f, int K, const double* imu, const double* t1, int local, int stride, const eqf_forecast_out* out, int* status) {
@@ -2443,17 +2422,17 @@ int eqf_forecast(eqf_filter* f, int K, const double* imu, const double* t1, int 
     int rc = forecastWorkspace(f);
     if (rc) return rc;
     const int nSteps = fc::steps(K, t1 != nullptr);
-    double* img = reinterpret_cast<double*>(f->hFcImu);
+    double* img = reinterpret_cast<double*>(f->fc.hImu.get());
     for (int k = 0; k < K; ++k)
         for (int b = 0; b < B; ++b) fc::packSample(imu + ((size_t)k * B + b) * 7, img + fc::imageIndex(k, b, B));
     if (t1)
         for (int b = 0; b < B; ++b) fc::packStamp(t1[b], img + fc::imageIndex(K, b, B));
     if (nSteps > 0)
-        HIPC(hipMemcpyAsync(f->dFcImu, f->hFcImu, sizeof(double) * fc::imageDoubles(K, t1 != nullptr, B), hipMemcpyHostToDevice, f->stream));
+        HIPC(hipMemcpyAsync(f->fc.dImu, f->fc.hImu, sizeof(double) * fc::imageDoubles(K, t1 != nullptr, B), hipMemcpyHostToDevice, f->stream));
     FcArgs a{};
     a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.lmc = f->lmc;
     a.Sin = static_cast<const double*>(f->Sigma[f->pS]); a.sigmaStride = f->sigmaStride; a.cap = cap; a.ld = f->ld; a.B = B;
-    a.K = K; a.nSteps = nSteps; a.local = local; a.imu = f->dFcImu; a.rec = f->dFcRec; a.out = f->dFcOut;
+    a.K = K; a.nSteps = nSteps; a.local = local; a.imu = f->fc.dImu; a.rec = f->fc.rec; a.out = f->fc.dOut;
     a.outStride = (long long)fc::outStride(cap); a.prm = f->prm;
     const fc::Grid gb = fc::buildGrid(B), gl = fc::lmGrid(maxN(f), B);
     hipLaunchKernelGGL(k_forecast_build, dim3(gb.x, gb.y), dim3(gb.threads), 0, f->stream, a);
@@ -2473,23 +2452,23 @@ int eqf_forecast(eqf_filter* f, int K, const double* imu, const double* t1, int 
     }
     // one copy for the whole batch while the span is not mostly unused capacity (a copy costs microseconds before its first byte), one per filter otherwise
     if (used && end - first <= 4 * used) {
-        HIPC(hipMemcpyAsync(f->hFcOut + first, f->dFcOut + first, sizeof(double) * (end - first), hipMemcpyDeviceToHost, f->stream));
+        HIPC(hipMemcpyAsync(f->fc.hOut + first, f->fc.dOut + first, sizeof(double) * (end - first), hipMemcpyDeviceToHost, f->stream));
     } else {
         for (int b = 0; b < B; ++b)
             if (st[b] == EQF_OK)
-                HIPC(hipMemcpyAsync(f->hFcOut + fc::outStride(cap) * b, f->dFcOut + fc::outStride(cap) * b, sizeof(double) * fc::outUsed(N[b]),
+                HIPC(hipMemcpyAsync(f->fc.hOut + fc::outStride(cap) * b, f->fc.dOut + fc::outStride(cap) * b, sizeof(double) * fc::outUsed(N[b]),
                     hipMemcpyDeviceToHost, f->stream));
     }
     HIPC(hipStreamSynchronize(f->stream));
     const double nan = std::nan("");
     for (int b = 0; b < B; ++b) {
-        const double* h = f->hFcOut + fc::outStride(cap) * b;
-        const double* hb = f->hFcOut + fc::outBase(cap, b);
+        const double* h = f->fc.hOut + fc::outStride(cap) * b;
+        const double* hb = f->fc.hOut + fc::outBase(cap, b);
         const bool skipped = st[b] != EQF_OK;
         bool numeric = false;
         if (!skipped) {
             numeric = h[fc::kHeadFlag] != 0.0;
-            for (int i = 0; i < N[b] && !numeric; ++i) numeric = f->hFcOut[fc::outLm(cap, b, i) + fc::kLmFlag] != 0.0;
+            for (int i = 0; i < N[b] && !numeric; ++i) numeric = f->fc.hOut[fc::outLm(cap, b, i) + fc::kLmFlag] != 0.0;
             if (numeric) st[b] = EQF_ERR_NUMERIC;
             else if (nSteps > 0 && h[fc::kHeadSteps] == 0.0) st[b] = EQF_SKIPPED_NONPOSITIVE_DT;
         }
@@ -2506,7 +2485,7 @@ int eqf_forecast(eqf_filter* f, int K, const double* imu, const double* t1, int 
         for (int i = 0; i < (wants.perLandmark() ? stride : 0); ++i) {
             const bool live = i < N[b] && !skipped;
             static const double zeros[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-            const double* l = live ? f->hFcOut + fc::outLm(cap, b, i) : nullptr;
+            const double* l = live ? f->fc.hOut + fc::outLm(cap, b, i) : nullptr;
             const size_t row = (size_t)b * stride + i;
             // (rows behind a filter's landmarks are written as zero)
             auto putLm = [&](double* dst, int off, int n) {
@@ -2654,7 +2633,7 @@ static size_t cloneSmallBytes(const eqf_filter* f) {
 static CloneSide cloneStageSide(eqf_filter* f) {
     const size_t cap = f->cap, B = f->B;
     CloneSide s{};
-    char* p = f->dCloneSmall;
+    char* p = f->clone.small;
     s.g = reinterpret_cast<Glob*>(p); p += sizeof(Glob) * B;
     s.p0 = reinterpret_cast<double*>(p); p += sizeof(double) * 3 * cap * B;
     s.Q = reinterpret_cast<double*>(p); p += sizeof(double) * 5 * cap * B;
@@ -2716,60 +2695,38 @@ int eqf_copy_filters(eqf_filter* dst, eqf_filter* src, int n, const int* dst_idx
     if (pairs.empty()) return EQF_OK;
     // everything that can fail is had before anything is written
     const int nTab = int(pairs.size() + stagePairs.size());
-    if (!dst->evCloneDone) {
-        if (hipEventCreateWithFlags(&dst->evCloneDone, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); dst->evCloneDone = nullptr; return EQF_ERR_HIP; }
+    {
+        const bool stages = !stagePairs.empty();
+        const workspace::Want wd[] = {want(dst->clone.evDone), want(dst->clone.hPairs, sizeof(ClonePair) * nTab, &dst->clone.pairsCap),
+            want(dst->clone.dPairs, sizeof(ClonePair) * nTab, &dst->clone.pairsCap), sigmaLocWant(dst, stages),
+            want(dst->clone.small, stages ? cloneSmallBytes(dst) : 0)};
+        const workspace::Want ws[] = {want(src->clone.evSrc)};
+        int rc = reserveSlots(dst, wd);
+        if (!rc) rc = reserveSlots(src, ws);
+        if (rc) return rc;
     }
-    if (!src->evCloneSrc) {
-        if (hipEventCreateWithFlags(&src->evCloneSrc, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); src->evCloneSrc = nullptr; return EQF_ERR_HIP; }
-    }
-    HIPC(hipEventSynchronize(dst->evCloneDone));  // (the previous copy into this handle has read its pair table)
-    if (nTab > dst->clonePairsCap) {
-        ClonePair *h = nullptr, *d = nullptr;
-        if (hipHostMalloc(reinterpret_cast<void**>(&h), sizeof(ClonePair) * nTab, hipHostMallocDefault) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&d), sizeof(ClonePair) * nTab) != hipSuccess) {
-            (void)hipGetLastError();
-            if (h) hipHostFree(h);
-            return EQF_ERR_HIP;
-        }
-        if (dst->hClonePairs) hipHostFree(dst->hClonePairs);
-        hipFree(dst->dClonePairs);
-        dst->hClonePairs = h;
-        dst->dClonePairs = d;
-        dst->clonePairsCap = nTab;
-    }
-    if (!stagePairs.empty()) {
-        if (!dst->dSigmaLoc && hipMalloc(reinterpret_cast<void**>(&dst->dSigmaLoc), sizeof(double) * size_t(dst->sigmaStride) * dst->B) != hipSuccess) {
-            (void)hipGetLastError();
-            dst->dSigmaLoc = nullptr;
-            return EQF_ERR_HIP;
-        }
-        if (!dst->dCloneSmall && hipMalloc(reinterpret_cast<void**>(&dst->dCloneSmall), cloneSmallBytes(dst)) != hipSuccess) {
-            (void)hipGetLastError();
-            dst->dCloneSmall = nullptr;
-            return EQF_ERR_HIP;
-        }
-    }
+    HIPC(hipEventSynchronize(dst->clone.evDone));  // (the previous copy into this handle has read its pair table)
     hipStream_t st = dst->stream;
     if (!inPlace) {  // the copy sees what the source has enqueued
-        HIPC(hipEventRecord(src->evCloneSrc, src->stream));
-        HIPC(hipStreamWaitEvent(st, src->evCloneSrc, 0));
+        HIPC(hipEventRecord(src->clone.evSrc, src->stream));
+        HIPC(hipStreamWaitEvent(st, src->clone.evSrc, 0));
     }
-    std::copy(pairs.begin(), pairs.end(), dst->hClonePairs);
-    std::copy(stagePairs.begin(), stagePairs.end(), dst->hClonePairs + pairs.size());
-    HIPC(hipMemcpyAsync(dst->dClonePairs, dst->hClonePairs, sizeof(ClonePair) * nTab, hipMemcpyHostToDevice, st));
+    std::copy(pairs.begin(), pairs.end(), dst->clone.hPairs.get());
+    std::copy(stagePairs.begin(), stagePairs.end(), dst->clone.hPairs + pairs.size());
+    HIPC(hipMemcpyAsync(dst->clone.dPairs, dst->clone.hPairs, sizeof(ClonePair) * nTab, hipMemcpyHostToDevice, st));
     CloneSigmaArgs sa{};
     sa.src = src->Sigma[src->pS]; sa.stage = dst->dSigmaLoc; sa.dst = dst->Sigma[dst->pS];
     sa.ldSrc = src->ld; sa.ldDst = dst->ld; sa.strideSrc = src->sigmaStride; sa.strideDst = dst->sigmaStride;
-    sa.pairs = dst->dClonePairs; sa.nPairs = int(pairs.size());
+    sa.pairs = dst->clone.dPairs; sa.nPairs = int(pairs.size());
     CloneSmallArgs ma{};
     ma.src = cloneSide(src); ma.dst = cloneSide(dst); ma.restore = 1;
-    ma.pairs = dst->dClonePairs; ma.nPairs = int(pairs.size());
+    ma.pairs = dst->clone.dPairs; ma.nPairs = int(pairs.size());
     if (!stagePairs.empty()) {
         int nStageN = 0;
         for (auto& p : stagePairs) nStageN = std::max(nStageN, p.N);
         CloneSigmaArgs ss = sa;
         ss.dst = dst->dSigmaLoc;
-        ss.pairs = dst->dClonePairs + pairs.size(); ss.nPairs = int(stagePairs.size());
+        ss.pairs = dst->clone.dPairs + pairs.size(); ss.nPairs = int(stagePairs.size());
         CloneSmallArgs ms = ma;
         ms.dst = cloneStageSide(dst); ms.restore = 0;
         ms.pairs = ss.pairs; ms.nPairs = ss.nPairs;
@@ -2778,8 +2735,8 @@ int eqf_copy_filters(eqf_filter* dst, eqf_filter* src, int n, const int* dst_idx
     }
     launchClone(dst, st, sa, ma, nMaxN);
     HIPC(hipGetLastError());
-    HIPC(hipEventRecord(dst->evCloneDone, st));
-    if (!inPlace) HIPC(hipStreamWaitEvent(src->stream, dst->evCloneDone, 0));  // (the source's later work flips its buffers: not before the copy has read them)
+    HIPC(hipEventRecord(dst->clone.evDone, st));
+    if (!inPlace) HIPC(hipStreamWaitEvent(src->stream, dst->clone.evDone, 0));  // (the source's later work flips its buffers: not before the copy has read them)
     // host mirrors (read first: in place a destination may be a source); the caches that describe the device's landmark sets start over
     std::vector<std::vector<int>> ids(pairs.size());
     std::vector<double> t(pairs.size());
@@ -2804,23 +2761,10 @@ static_assert(mapedit::kPrior == kMapPrior && mapedit::kOk == EQF_OK && mapedit:
                   mapedit::kCapacity == EQF_ERR_CAPACITY && mapedit::kUnsorted == EQF_ERR_UNSORTED,
     "eqf_mapedit_host.hpp repeats the layout constants and the error codes");
 namespace {
-// the plan's image, once per handle; a failure leaves the handle as it was
-int mapEditAlloc(eqf_filter* f) {
-    if (f->hMapEdit) return EQF_OK;
-    const size_t bytes = mapedit::imageCapacityBytes(f->B, f->cap);
-    void *h = nullptr, *d = nullptr;
-    hipEvent_t ev = nullptr;
-    if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess ||
-        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        if (h) hipHostFree(h);
-        if (d) hipFree(d);
-        return EQF_ERR_HIP;
-    }
-    f->hMapEdit = static_cast<char*>(h);
-    f->dMapEdit = static_cast<char*>(d);
-    f->evMapEdit = ev;
-    return EQF_OK;
+// the plan's image, from capacity and batch
+int mapEditReserve(eqf_filter* f) {
+    const workspace::Want w[] = {WANT_STAGED(f->medit.img, mapedit::imageCapacityBytes(f->B, f->cap))};
+    return reserveSlots(f, w);
 }
 }  // namespace
 
@@ -2835,22 +2779,21 @@ int eqf_edit_landmarks(eqf_filter* f, const int* n_remove, const int* remove_ids
     if (rc) return rc;
     const bool work = pl.anyRemoved || pl.anyInserted;
     if (work) {
-        rc = mapEditAlloc(f);
+        rc = mapEditReserve(f);
         if (rc) return rc;
     }
     if (removed) std::copy(pl.removed.begin(), pl.removed.end(), removed);
     if (inserted) std::copy(pl.inserted.begin(), pl.inserted.end(), inserted);
     if (!work) return EQF_OK;
     const mapedit::Image im = mapedit::imageLayout(B, cap, pl);
-    HIPC(hipEventSynchronize(f->evMapEdit));
-    mapedit::fillImage(f->ids, ma, pl, im, f->hMapEdit);
-    HIPC(hipMemcpyAsync(f->dMapEdit, f->hMapEdit, im.bytes(), hipMemcpyHostToDevice, f->stream));
-    HIPC(hipEventRecord(f->evMapEdit, f->stream));
+    HIPC(f->medit.img.wait());
+    mapedit::fillImage(f->ids, ma, pl, im, f->medit.img.host);
+    HIPC(f->medit.img.upload(im.bytes(), f->stream));
     MapEditArgs a{};
     a.g = f->g[f->pG];
-    a.prior = reinterpret_cast<const double*>(f->dMapEdit + im.offPrior());
-    a.cnt = reinterpret_cast<const int*>(f->dMapEdit + im.offCounts());
-    a.map = reinterpret_cast<const int*>(f->dMapEdit + im.offMap());
+    a.prior = reinterpret_cast<const double*>(f->medit.img.dev + im.offPrior());
+    a.cnt = reinterpret_cast<const int*>(f->medit.img.dev + im.offCounts());
+    a.map = reinterpret_cast<const int*>(f->medit.img.dev + im.offMap());
     a.ns = int(im.ns); a.cap = cap;
     a.p0 = f->p0; a.Q = f->Q[f->pG]; a.lmc = f->lmc; a.scratch = f->dScratch; a.errflag = f->errflag;
     a.sigmaStride = f->sigmaStride; a.ld = f->ld;
@@ -3023,23 +2966,11 @@ int eqf_set_option(eqf_filter* f, const char* name, int value) {
             // workspace from the capacity: the slices of every filter's Y (mp x nv at most) and one exponent word per column
             const int nvCap = kLm0 + 3 * f->cap, mpCap = roundUp(sDim(f->cap), kSB);
             if (!i8Exact(mpCap, value)) return EQF_ERR_CAPACITY;  // (int32 accumulation would no longer be exact: capacity > ~37 000)
-            HIPC(hipStreamSynchronize(f->stream));
-            hipFree(f->dI8Ws);
-            hipFree(f->dI8Expo);
-            f->dI8Ws = nullptr;
-            f->dI8Expo = nullptr;
-            f->i8Slices = 0;
-            f->ddSlices = 0;
             const long long stride = i8SliceBytes(mpCap, nvCap, value);
-            if (hipMalloc(&f->dI8Ws, size_t(stride) * f->B) != hipSuccess ||
-                hipMalloc(&f->dI8Expo, sizeof(int) * size_t(i8ddExpoWords(nvCap)) * f->B) != hipSuccess) {
-                (void)hipGetLastError();  // (a failed allocation must not fail the next update through the sticky last error)
-                hipFree(f->dI8Ws);
-                hipFree(f->dI8Expo);
-                f->dI8Ws = nullptr;
-                f->dI8Expo = nullptr;
-                return EQF_ERR_HIP;
-            }
+            const workspace::Want w[] = {want(f->dI8Ws, size_t(stride) * f->B, &f->i8WsBytes),
+                want(f->dI8Expo, sizeof(int) * size_t(i8ddExpoWords(nvCap)) * f->B)};
+            const int rc = reserveSlots(f, w);
+            if (rc) return rc;
             f->i8WsStride = stride;
             f->i8Slices = value;
         }
@@ -3057,11 +2988,9 @@ int eqf_set_option(eqf_filter* f, const char* name, int value) {
         if (value && f->precision == EQF_PRECISION_F32) return EQF_ERR_UNSUPPORTED;
         GATE(f);
         if (value && !f->dInnov) {
-            if (hipMalloc(reinterpret_cast<void**>(&f->dInnov), sizeof(double) * (size_t)(kInnovHead + f->cap) * f->B) != hipSuccess) {
-                (void)hipGetLastError();
-                f->dInnov = nullptr;
-                return EQF_ERR_HIP;
-            }
+            const workspace::Want w[] = {want(f->dInnov, sizeof(double) * (size_t)(kInnovHead + f->cap) * f->B)};
+            const int rc = reserveSlots(f, w);
+            if (rc) return rc;
         }
         // (switching the option, either way, forgets the last update's statistics)
         if (f->dInnov) HIPC(hipMemsetAsync(f->dInnov, 0, sizeof(double) * (size_t)(kInnovHead + f->cap) * f->B, f->stream));
@@ -3071,17 +3000,17 @@ int eqf_set_option(eqf_filter* f, const char* name, int value) {
     if (!std::strcmp(name, "innovation_lift")) {  // eqf_lift.hpp: 0 the plain lift, 1 the handle's useInnovationLift / useDiscreteInnovationLift
         if (!lift::optionOk(value)) return EQF_ERR_INVALID;
         if (f->precision == EQF_PRECISION_F32) return EQF_ERR_UNSUPPORTED;
-        f->liftOpt = value;
+        f->lift.opt = value;
         return EQF_OK;
     }
     if (!std::strcmp(name, "merge_cost_chunk")) {  // images per round of eqf_get_merge_costs (0: as many as the handle has filters)
         if (value != 0 && !mergecost::chunkOptionOk(value)) return EQF_ERR_INVALID;
-        f->mcChunkOpt = value;
+        f->mc.chunkOpt = value;
         return EQF_OK;
     }
     if (!std::strcmp(name, "score_chunk")) {  // images per round of eqf_score_vision (0: as many as the handle has filters)
         if (value != 0 && !score::chunkOptionOk(value)) return EQF_ERR_INVALID;
-        f->scChunkOpt = value;
+        f->sc.chunkOpt = value;
         return EQF_OK;
     }
     return EQF_ERR_INVALID;
@@ -3135,37 +3064,17 @@ int eqf_get_innovation_stats(eqf_filter* f, int b, eqf_innovation_stats* out, do
     return EQF_OK;
 }
 
-// One device allocation of eqf_get_nees's buffers; a failure frees what this call got and leaves the handle as it was.
-static int neesAlloc(eqf_filter* f) {
-    if (f->dNeesE && f->dSigmaLoc) return EQF_OK;
-    void *e = nullptr, *d = nullptr, *o = nullptr, *w = nullptr, *s = nullptr;
-    bool ok = true;
-    if (!f->dNeesE) {
-        ok = hipMalloc(&e, sizeof(double) * size_t(kNeesRhs) * f->ld * f->B) == hipSuccess &&
-             hipMalloc(&d, sizeof(double) * size_t(kDRec) * f->B) == hipSuccess &&
-             hipMalloc(&o, sizeof(double) * size_t(kNeesHead + kNeesRhs) * f->B) == hipSuccess &&
-             hipMalloc(&w, sizeof(int) * size_t(f->B)) == hipSuccess;
-    }
-    if (ok && !f->dSigmaLoc) ok = hipMalloc(&s, sizeof(double) * size_t(f->sigmaStride) * f->B) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        for (void* p : {e, d, o, w, s})
-            if (p) hipFree(p);
-        return EQF_ERR_HIP;
-    }
-    if (e) {
-        f->dNeesE = static_cast<double*>(e);
-        f->dNeesD = static_cast<double*>(d);
-        f->dNeesOut = static_cast<double*>(o);
-        f->dNeesBad = static_cast<int*>(w);
-    }
-    if (s) f->dSigmaLoc = static_cast<double*>(s);
-    return EQF_OK;
+// the buffers of eqf_get_nees and of the draws' factorisation, from capacity and batch
+static int neesReserve(eqf_filter* f) {
+    const size_t B = size_t(f->B);
+    const workspace::Want w[] = {want(f->nees.E, sizeof(double) * size_t(kNeesRhs) * f->ld * B), want(f->nees.D, sizeof(double) * size_t(kDRec) * B),
+        want(f->nees.out, sizeof(double) * size_t(kNeesHead + kNeesRhs) * B), want(f->nees.bad, sizeof(int) * B), sigmaLocWant(f)};
+    return reserveSlots(f, w);
 }
 
 // A = L L^T of every filter's submatrix from internal index off, in place in the scratch image -- Sigma_loc (k_sigma_local) or a copy of
-// Sigma --, the nrhs error vectors that lie in dNeesE carried along, and k_nees_tail's report in dNeesOut: what eqf_get_nees and the draws
-// (nrhs = 0) share.  Enqueues; the buffers are there (neesAlloc).
+// Sigma --, the nrhs error vectors that lie in nees.E carried along, and k_nees_tail's report in nees.out: what eqf_get_nees and the draws
+// (nrhs = 0) share.  Enqueues; the buffers are there (neesReserve).
 static int neesFactor(eqf_filter* f, int local, int off, int nrhs) {
     const int B = f->B, mMax = kLm0 + 3 * maxN(f) - off;
     int rc = EQF_OK;
@@ -3176,9 +3085,9 @@ static int neesFactor(eqf_filter* f, int local, int off, int nrhs) {
         HIPC(hipMemcpyAsync(f->dSigmaLoc, f->Sigma[f->pS], sizeof(double) * size_t(f->sigmaStride) * B, hipMemcpyDeviceToDevice, f->stream));
     }
     NeesArgs a{};
-    a.g = f->g[f->pG]; a.A = f->dSigmaLoc; a.ld = f->ld; a.strideA = f->sigmaStride; a.E = f->dNeesE; a.ldE = std::max(mMax, 1); a.D = f->dNeesD;
-    a.bad = f->dNeesBad; a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.off = off; a.nrhs = nrhs; a.out = f->dNeesOut;
-    rc = enqueueFactor(f->stream, f->neesLdsSet, a, B, mMax, nrhs > 0 ? 1 : 0);
+    a.g = f->g[f->pG]; a.A = f->dSigmaLoc; a.ld = f->ld; a.strideA = f->sigmaStride; a.E = f->nees.E; a.ldE = std::max(mMax, 1); a.D = f->nees.D;
+    a.bad = f->nees.bad; a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.off = off; a.nrhs = nrhs; a.out = f->nees.out;
+    rc = enqueueFactor(f->stream, f->nees.ldsSet, a, B, mMax, nrhs > 0 ? 1 : 0);
     if (rc) return rc;
     hipLaunchKernelGGL(k_nees_tail, dim3(B), dim3(256), 0, f->stream, a);
     HIPC(hipGetLastError());
@@ -3203,7 +3112,7 @@ int eqf_get_nees(eqf_filter* f, int local, int first, int nrhs, const double* er
     GATE(f);  // (a pending outlier gate may still change the landmark counts: settle them before they are looked at)
     const int B = f->B, nMax = maxN(f);
     if (nrhs > 0 && lde < kBase + 3 * nMax) return EQF_ERR_INVALID;
-    int rc = neesAlloc(f);
+    int rc = neesReserve(f);
     if (rc) return rc;
     const int off = first == kBase ? kLm0 : first, ldE = std::max(kLm0 + 3 * nMax - off, 1);
     // the error vectors in the submatrix' own (padded) index map: entry i of the reference -> column (i < 11 ? i : i + 1) - off
@@ -3218,12 +3127,12 @@ int eqf_get_nees(eqf_filter* f, int local, int first, int nrhs, const double* er
                 for (int i = first; i < n; ++i) dst[(i < kBase ? i : i + 1) - off] = src[i];
             }
         }
-        HIPC(hipMemcpyAsync(f->dNeesE, hE.data(), sizeof(double) * hE.size(), hipMemcpyHostToDevice, f->stream));
+        HIPC(hipMemcpyAsync(f->nees.E, hE.data(), sizeof(double) * hE.size(), hipMemcpyHostToDevice, f->stream));
     }
     rc = neesFactor(f, local, off, nrhs);
     if (rc) return rc;
     std::vector<double> hO(size_t(B) * (kNeesHead + kNeesRhs));
-    HIPC(hipMemcpyAsync(hO.data(), f->dNeesOut, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipMemcpyAsync(hO.data(), f->nees.out, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
     HIPC(hipStreamSynchronize(f->stream));
     neesStats(hO.data(), B, stats);
     for (int b = 0; b < B; ++b)
@@ -3238,63 +3147,46 @@ static_assert(lift::kRefBase == kBase && lift::kPadBase == kLm0 && lift::kOff ==
     "eqf_lift_host.hpp repeats the layout constants");
 static_assert(border::kBlock == kSB && border::kStage == kQB && border::kRows == kBorderRows, "eqf_border_host.hpp repeats the layout constants");
 namespace {
-int liftCallKind(const eqf_filter* f) { return lift::callKind(f->liftOpt, f->prm.useInnovationLift, f->prm.useDiscreteInnovationLift); }
-// What a call needs before any effect: the records always, the factorisation's buffers where the call factors.  A failure frees what this
-// call got and leaves the handle as it was.
-int liftAlloc(eqf_filter* f, bool factors) {
-    void *r = nullptr, *e = nullptr, *d = nullptr, *w = nullptr, *s = nullptr;
-    bool ok = true;
-    if (!f->dLiftRec) ok = hipMalloc(&r, sizeof(double) * size_t(kLiftRec) * f->B) == hipSuccess;
-    if (ok && factors && !f->dLiftE)
-        ok = hipMalloc(&e, sizeof(double) * lift::rhsDoubles(f->ld) * f->B) == hipSuccess &&
-             hipMalloc(&d, sizeof(double) * size_t(kDRec) * f->B) == hipSuccess && hipMalloc(&w, sizeof(int) * size_t(f->B)) == hipSuccess;
-    if (ok && factors && !f->dSigmaLoc) ok = hipMalloc(&s, sizeof(double) * size_t(f->sigmaStride) * f->B) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        for (void* p : {r, e, d, w, s})
-            if (p) hipFree(p);
-        return EQF_ERR_HIP;
-    }
-    if (r) f->dLiftRec = static_cast<double*>(r);
-    if (e) {
-        f->dLiftE = static_cast<double*>(e);
-        f->dLiftD = static_cast<double*>(d);
-        f->dLiftBad = static_cast<int*>(w);
-    }
-    if (s) f->dSigmaLoc = static_cast<double*>(s);
-    return EQF_OK;
+int liftCallKind(const eqf_filter* f) { return lift::callKind(f->lift.opt, f->prm.useInnovationLift, f->prm.useDiscreteInnovationLift); }
+// What a call needs before any effect: the records always, the factorisation's buffers where the call factors.
+int liftReserve(eqf_filter* f, bool factors) {
+    const size_t B = size_t(f->B);
+    const workspace::Want w[] = {want(f->lift.rec, sizeof(double) * size_t(kLiftRec) * B),
+        want(f->lift.E, factors ? sizeof(double) * lift::rhsDoubles(f->ld) * B : 0), want(f->lift.D, factors ? sizeof(double) * size_t(kDRec) * B : 0),
+        want(f->lift.bad, factors ? sizeof(int) * B : 0), sigmaLocWant(f, factors)};
+    return reserveSlots(f, w);
 }
 // Enqueues the lift of a call behind the launches that left its increment (filter b: gamma[b * strideG + j], internal index offG + j) and,
 // for an update, its verdict (records [B][kLinHead], entry 3) -- and in front of whatever changes Sigma: a device copy of Sigma, the
 // right-hand side, the factorisation and the tail where some filter takes a bundleLift, the tail alone (the records) otherwise.  The
-// filters the tail has not dealt with are k_apply_increment's: its IncArgs get the records.  (liftAlloc has run.)
+// filters the tail has not dealt with are k_apply_increment's: its IncArgs get the records.  (liftReserve has run.)
 int liftEnqueue(eqf_filter* f, const double* gamma, long long strideG, int offG, const unsigned char* dMask, double* verdict, bool writesVerdict,
     IncArgs& ia) {
     const int B = f->B, nMax = maxN(f), kind = liftCallKind(f);
     LiftArgs a{};
     a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.cap = f->cap; a.A = f->dSigmaLoc; a.ld = f->ld; a.strideA = f->sigmaStride;
-    a.E = f->dLiftE; a.ldE = lift::rhsPitch(nMax); a.D = f->dLiftD; a.bad = f->dLiftBad; a.gamma = gamma; a.strideG = strideG; a.offG = offG;
+    a.E = f->lift.E; a.ldE = lift::rhsPitch(nMax); a.D = f->lift.D; a.bad = f->lift.bad; a.gamma = gamma; a.strideG = strideG; a.offG = offG;
     a.mask = dMask; a.verdict = verdict; a.fail = writesVerdict ? verdict : nullptr; a.kind = lift::callFactors(kind, nMax) ? kind : 0;
-    a.rec = f->dLiftRec; a.prm = f->prm;
+    a.rec = f->lift.rec; a.prm = f->prm;
     if (a.kind) {
         HIPC(hipMemcpyAsync(f->dSigmaLoc, f->Sigma[f->pS], sizeof(double) * size_t(f->sigmaStride) * B, hipMemcpyDeviceToDevice, f->stream));
         hipLaunchKernelGGL(k_lift_rhs, dim3(lift::rhsGroups(nMax), B), dim3(256), 0, f->stream, a);
-        const int rc = enqueueFactor(f->stream, f->liftLdsSet, a, B, lift::order(nMax), 1);
+        const int rc = enqueueFactor(f->stream, f->lift.ldsSet, a, B, lift::order(nMax), 1);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(k_lift_tail, dim3(B), dim3(256), 0, f->stream, a);
     HIPC(hipGetLastError());
-    f->liftCalled = true;
-    ia.lift = f->dLiftRec;
+    f->lift.called = true;
+    ia.lift = f->lift.rec;
     ia.liftStride = kLiftRec;
     return EQF_OK;
 }
 }  // namespace
 
 int eqf_get_lift_report(eqf_filter* f, int b, eqf_lift_report* out) {
-    if (!f || !out || b < 0 || b >= f->B || !f->liftCalled) return EQF_ERR_INVALID;
+    if (!f || !out || b < 0 || b >= f->B || !f->lift.called) return EQF_ERR_INVALID;
     double rec[kLiftRec];
-    HIPC(hipMemcpyAsync(rec, f->dLiftRec + size_t(b) * kLiftRec, sizeof(rec), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipMemcpyAsync(rec, f->lift.rec + size_t(b) * kLiftRec, sizeof(rec), hipMemcpyDeviceToHost, f->stream));
     HIPC(hipStreamSynchronize(f->stream));
     lift::Report r;
     lift::unpackReport(rec, &r);
@@ -3318,47 +3210,23 @@ SampSmall sampCarve(const eqf_filter* f, char* p) {
     double* d = reinterpret_cast<double*>(p);
     return SampSmall{d, d + f->B, reinterpret_cast<unsigned char*>(d + f->B * (1 + sampVecLen(f)))};
 }
-// the small operands' two images and their event; a failure leaves the handle as it was
-int sampSmallAlloc(eqf_filter* f) {
-    if (f->dSampSmall) return EQF_OK;
-    void *h = nullptr, *d = nullptr;
-    hipEvent_t ev = nullptr;
-    if (hipHostMalloc(&h, sampSmallBytes(f), hipHostMallocDefault) != hipSuccess || hipMalloc(&d, sampSmallBytes(f)) != hipSuccess ||
-        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        if (h) hipHostFree(h);
-        if (d) hipFree(d);
-        return EQF_ERR_HIP;
-    }
-    f->hSampSmall = static_cast<char*>(h);
-    f->dSampSmall = static_cast<char*>(d);
-    f->evSamp = ev;
-    return EQF_OK;
+// the small operands as a staged image
+int sampSmallReserve(eqf_filter* f) {
+    const workspace::Want w[] = {WANT_STAGED(f->samp.small, sampSmallBytes(f))};
+    return reserveSlots(f, w);
 }
 // room for `rows` samples per filter
-int sampRowsAlloc(eqf_filter* f, int rows) {
-    if (rows <= f->sampRows) return EQF_OK;
-    void *z = nullptr, *e = nullptr;
+int sampRowsReserve(eqf_filter* f, int rows) {
     const size_t bytes = sizeof(double) * size_t(rows) * f->ld * f->B;
-    if (hipMalloc(&z, bytes) != hipSuccess || hipMalloc(&e, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        if (z) hipFree(z);
-        return EQF_ERR_HIP;
-    }
-    HIPC(hipStreamSynchronize(f->stream));  // (an earlier call's launches may still read the old ones)
-    hipFree(f->dSampZ);
-    hipFree(f->dSampE);
-    f->dSampZ = static_cast<double*>(z);
-    f->dSampE = static_cast<double*>(e);
-    f->sampRows = rows;
-    return EQF_OK;
+    const workspace::Want w[] = {want(f->samp.Z, bytes, &f->samp.cap), want(f->samp.E, bytes, &f->samp.cap)};
+    return reserveSlots(f, w);
 }
-// E = scale Z L^T behind neesFactor (nsamp >= 1 rows per filter in dSampZ -> dSampE, row pitch ldE)
+// E = scale Z L^T behind neesFactor (nsamp >= 1 rows per filter in samp.Z -> samp.E, row pitch ldE)
 void sampTrmm(eqf_filter* f, int off, int nsamp, int ldE, const double* dScale) {
     const int mMax = sample::paddedOrder(maxN(f), off);
     if (mMax <= 0) return;
     SampleArgs s{};
-    s.g = f->g[f->pG]; s.A = f->dSigmaLoc; s.ld = f->ld; s.strideA = f->sigmaStride; s.Z = f->dSampZ; s.E = f->dSampE; s.ldE = ldE;
+    s.g = f->g[f->pG]; s.A = f->dSigmaLoc; s.ld = f->ld; s.strideA = f->sigmaStride; s.Z = f->samp.Z; s.E = f->samp.E; s.ldE = ldE;
     s.nsamp = nsamp; s.scale = dScale; s.off = off;
     hipLaunchKernelGGL(k_sample_trmm, dim3(sample::blockColumns(mMax), sample::rowTiles(nsamp), f->B), dim3(256), kSampleLdsBytes, f->stream, s);
 }
@@ -3373,9 +3241,9 @@ int eqf_sample_sigma(eqf_filter* f, int local, int first, int nsamp, const doubl
     GATE(f);
     const int B = f->B, nMax = maxN(f);
     if (!sample::drawArgsOk(local, first, nsamp, z, ldz, eps, lde, stats, nMax)) return EQF_ERR_INVALID;
-    int rc = neesAlloc(f);
-    if (!rc && nsamp > 0) rc = sampRowsAlloc(f, nsamp);
-    if (!rc && scale) rc = sampSmallAlloc(f);
+    int rc = neesReserve(f);
+    if (!rc && nsamp > 0) rc = sampRowsReserve(f, nsamp);
+    if (!rc && scale) rc = sampSmallReserve(f);
     if (rc) return rc;
     const int off = sample::cutOffset(first), ldE = std::max(sample::paddedOrder(nMax, off), 1);
     rc = neesFactor(f, local, off, 0);
@@ -3386,21 +3254,21 @@ int eqf_sample_sigma(eqf_filter* f, int local, int first, int nsamp, const doubl
         for (int b = 0; b < B; ++b)
             for (int k = 0; k < nsamp; ++k)
                 sample::packRow(z + (size_t(b) * nsamp + k) * ldz, first, int(f->ids[b].size()), hZ.data() + (size_t(b) * nsamp + k) * ldE, ldE);
-        HIPC(hipMemcpyAsync(f->dSampZ, hZ.data(), sizeof(double) * hZ.size(), hipMemcpyHostToDevice, f->stream));
+        HIPC(hipMemcpyAsync(f->samp.Z, hZ.data(), sizeof(double) * hZ.size(), hipMemcpyHostToDevice, f->stream));
         const double* dScale = nullptr;
         if (scale) {
-            HIPC(hipEventSynchronize(f->evSamp));
-            SampSmall h = sampCarve(f, f->hSampSmall), d = sampCarve(f, f->dSampSmall);
+            HIPC(f->samp.small.wait());
+            SampSmall h = sampCarve(f, f->samp.small.host), d = sampCarve(f, f->samp.small.dev);
             std::copy(scale, scale + B, h.scale);
-            HIPC(hipMemcpyAsync(d.scale, h.scale, sizeof(double) * B, hipMemcpyHostToDevice, f->stream));
+            HIPC(f->samp.small.upload(sizeof(double) * B, f->stream));  // (the scales lie in front)
             dScale = d.scale;
         }
         sampTrmm(f, off, nsamp, ldE, dScale);
         HIPC(hipGetLastError());
-        HIPC(hipMemcpyAsync(hZ.data(), f->dSampE, sizeof(double) * hZ.size(), hipMemcpyDeviceToHost, f->stream));
+        HIPC(hipMemcpyAsync(hZ.data(), f->samp.E, sizeof(double) * hZ.size(), hipMemcpyDeviceToHost, f->stream));
     }
     std::vector<double> hO(size_t(B) * (kNeesHead + kNeesRhs));
-    HIPC(hipMemcpyAsync(hO.data(), f->dNeesOut, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipMemcpyAsync(hO.data(), f->nees.out, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
     HIPC(hipStreamSynchronize(f->stream));
     if (stats) neesStats(hO.data(), B, stats);
     const double nan = std::nan("");
@@ -3420,18 +3288,17 @@ int eqf_apply_increment(eqf_filter* f, const double* gamma, int ldg, const unsig
     std::vector<int> N(B);
     for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
     if (!sample::incrementArgsOk(gamma, ldg, mask, B, N.data())) return EQF_ERR_INVALID;
-    int rc = sampSmallAlloc(f);
-    if (!rc) rc = liftAlloc(f, lift::callFactors(liftCallKind(f), maxN(f)));
+    int rc = sampSmallReserve(f);
+    if (!rc) rc = liftReserve(f, lift::callFactors(liftCallKind(f), maxN(f)));
     if (rc) return rc;
-    HIPC(hipEventSynchronize(f->evSamp));
-    SampSmall h = sampCarve(f, f->hSampSmall), d = sampCarve(f, f->dSampSmall);
+    HIPC(f->samp.small.wait());
+    SampSmall h = sampCarve(f, f->samp.small.host), d = sampCarve(f, f->samp.small.dev);
     const int len = int(sampVecLen(f));
     for (int b = 0; b < B; ++b) {
         sample::packRow(gamma + size_t(b) * ldg, 0, N[b], h.vec + size_t(b) * len, kLm0 + 3 * N[b]);
         h.mask[b] = mask ? mask[b] : 1;
     }
-    HIPC(hipMemcpyAsync(d.vec, h.vec, sizeof(double) * size_t(B) * len + size_t(B), hipMemcpyHostToDevice, f->stream));  // (the mask lies behind)
-    HIPC(hipEventRecord(f->evSamp, f->stream));
+    HIPC(f->samp.small.upload(sizeof(double) * size_t(B) * len + size_t(B), f->stream, sizeof(double) * size_t(B)));  // (the vectors; the mask lies behind)
     IncArgs a{};
     a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.cap = f->cap; a.gamma = d.vec; a.strideG = len; a.off = 0; a.mask = d.mask;
     rc = liftEnqueue(f, d.vec, len, 0, d.mask, nullptr, false, a);
@@ -3448,16 +3315,16 @@ int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, cons
     GATE(f);
     const int B = f->B, nMax = maxN(f);
     if (!sample::perturbArgsOk(first, z, ldz, scale, B, nMax)) return EQF_ERR_INVALID;
-    int rc = neesAlloc(f);
-    if (!rc) rc = sampRowsAlloc(f, 1);
-    if (!rc) rc = sampSmallAlloc(f);
-    if (!rc) rc = liftAlloc(f, lift::callFactors(liftCallKind(f), nMax));
+    int rc = neesReserve(f);
+    if (!rc) rc = sampRowsReserve(f, 1);
+    if (!rc) rc = sampSmallReserve(f);
+    if (!rc) rc = liftReserve(f, lift::callFactors(liftCallKind(f), nMax));
     if (rc) return rc;
     const int off = sample::cutOffset(first), ldE = std::max(sample::paddedOrder(nMax, off), 1);
     rc = neesFactor(f, 0, off, 0);
     if (rc) return rc;
-    HIPC(hipEventSynchronize(f->evSamp));
-    SampSmall h = sampCarve(f, f->hSampSmall), d = sampCarve(f, f->dSampSmall);
+    HIPC(f->samp.small.wait());
+    SampSmall h = sampCarve(f, f->samp.small.host), d = sampCarve(f, f->samp.small.dev);
     for (int b = 0; b < B; ++b) {
         h.scale[b] = scale ? scale[b] : 1.0;
         h.mask[b] = h.scale[b] != 0.0;
@@ -3465,22 +3332,22 @@ int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, cons
     }
     HIPC(hipMemcpyAsync(d.scale, h.scale, sizeof(double) * B, hipMemcpyHostToDevice, f->stream));
     HIPC(hipMemcpyAsync(d.mask, h.mask, size_t(B), hipMemcpyHostToDevice, f->stream));
-    HIPC(hipMemcpyAsync(f->dSampZ, h.vec, sizeof(double) * size_t(B) * ldE, hipMemcpyHostToDevice, f->stream));
-    HIPC(hipEventRecord(f->evSamp, f->stream));
+    HIPC(hipMemcpyAsync(f->samp.Z, h.vec, sizeof(double) * size_t(B) * ldE, hipMemcpyHostToDevice, f->stream));
+    HIPC(f->samp.small.record(f->stream));
     // (a submatrix of order 0 -- first = 11, no landmarks anywhere -- has no sample: k_apply_increment then reads no entry of the image)
     sampTrmm(f, off, 1, ldE, d.scale);
     IncArgs a{};
-    a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.cap = f->cap; a.gamma = f->dSampE; a.strideG = ldE; a.off = off; a.mask = d.mask;
-    a.info = f->dNeesOut;
+    a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.cap = f->cap; a.gamma = f->samp.E; a.strideG = ldE; a.off = off; a.mask = d.mask;
+    a.info = f->nees.out;
     // (the lift factors Sigma[6:, 6:] in the scratch image: the draw's factor has been consumed by sampTrmm)
-    rc = liftEnqueue(f, f->dSampE, ldE, off, d.mask, f->dNeesOut, false, a);
+    rc = liftEnqueue(f, f->samp.E, ldE, off, d.mask, f->nees.out, false, a);
     if (rc) return rc;
     hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, a);
     HIPC(hipGetLastError());
     f->csValid = false;
     if (!stats) return EQF_OK;
     std::vector<double> hO(size_t(B) * (kNeesHead + kNeesRhs));
-    HIPC(hipMemcpyAsync(hO.data(), f->dNeesOut, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipMemcpyAsync(hO.data(), f->nees.out, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
     HIPC(hipStreamSynchronize(f->stream));
     neesStats(hO.data(), B, stats);
     return EQF_OK;
@@ -3490,29 +3357,13 @@ int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, cons
 static_assert(linear::kRefBase == kBase && linear::kPadBase == kLm0 && linear::kRows == kLinRows && linear::kTile == kSB &&
               linear::kHead == kLinHead, "eqf_linear_host.hpp repeats the layout constants");
 namespace {
-// every buffer of eqf_update_linear in one go; a failure frees what this call got and leaves the handle as it was
-int linAlloc(eqf_filter* f) {
-    if (f->dLinWs) return EQF_OK;
+// every buffer of eqf_update_linear, from capacity and batch
+int linReserve(eqf_filter* f) {
     const linear::SmallLayout sl{f->B, linear::refOrder(f->cap)};
     const linear::WorkLayout wl{f->ld};
-    void *h = nullptr, *d = nullptr, *w = nullptr, *o = nullptr;
-    hipEvent_t ev = nullptr;
-    if (hipHostMalloc(&h, sl.bytes(), hipHostMallocDefault) != hipSuccess || hipMalloc(&d, sl.bytes()) != hipSuccess ||
-        hipMalloc(&w, sizeof(double) * size_t(wl.stride()) * f->B) != hipSuccess ||
-        hipMalloc(&o, sizeof(double) * size_t(kLinHead) * f->B) != hipSuccess ||
-        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        if (h) hipHostFree(h);
-        for (void* p : {d, w, o})
-            if (p) hipFree(p);
-        return EQF_ERR_HIP;
-    }
-    f->hLinSmall = static_cast<char*>(h);
-    f->dLinSmall = static_cast<char*>(d);
-    f->dLinWs = static_cast<double*>(w);
-    f->dLinOut = static_cast<double*>(o);
-    f->evLin = ev;
-    return EQF_OK;
+    const workspace::Want w[] = {WANT_STAGED(f->lin.small, sl.bytes()), want(f->lin.ws, sizeof(double) * size_t(wl.stride()) * f->B),
+        want(f->lin.out, sizeof(double) * size_t(kLinHead) * f->B)};
+    return reserveSlots(f, w);
 }
 
 // ---- the Schmidt (consider) variants (eqf_schmidt.hpp; the host's decisions: eqf_schmidt_host.hpp)
@@ -3525,57 +3376,43 @@ struct SchCall {
     const int* ids;
     int cstride;
 };
-// the partition's image, once per handle; a failure leaves the handle as it was
-int schAlloc(eqf_filter* f) {
-    if (f->hSch) return EQF_OK;
-    const size_t bytes = schmidt::Image{size_t(f->B), size_t(f->ld)}.bytes();
-    void *h = nullptr, *d = nullptr, *hd = nullptr;
-    hipEvent_t ev = nullptr;
-    if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess || hipHostGetDevicePointer(&hd, h, 0) != hipSuccess ||
-        hipMalloc(&d, bytes) != hipSuccess || hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        if (h) hipHostFree(h);
-        if (d) hipFree(d);
-        return EQF_ERR_HIP;
-    }
-    f->hSch = static_cast<char*>(h);
-    f->hSchDev = static_cast<char*>(hd);
-    f->dSch = static_cast<char*>(d);
-    f->evSch = ev;
-    return EQF_OK;
+// the partition's image, from capacity and batch
+int schReserve(eqf_filter* f) {
+    const workspace::Want w[] = {WANT_STAGED(f->sch.img, (schmidt::Image{size_t(f->B), size_t(f->ld)}.bytes()))};
+    return reserveSlots(f, w);
 }
-// Builds every filter's partition from the handle's id mirror in the pinned image (schAlloc has run, the lists are checked); the launch of
+// Builds every filter's partition from the handle's id mirror in the pinned image (schReserve has run, the lists are checked); the launch of
 // k_schmidt_gamma brings it to the device.  sa: the arguments both kernels share, but for the verdict records and gamma; gridX: the
 // gathered downdate's.
 int schUpload(eqf_filter* f, const SchCall& sc, const int* N, SchArgs& sa, int& gridX) {
     const int B = f->B;
     const schmidt::Image im{size_t(B), size_t(f->ld)};
-    HIPC(hipEventSynchronize(f->evSch));
+    HIPC(f->sch.img.wait());
     std::vector<int> act;
     std::vector<unsigned char> fl;
     int nAmax = 0;
     for (int b = 0; b < B; ++b) {
         const int nc = sc.n ? sc.n[b] : 0;
         schmidt::buildActive(N[b], f->ids[b].data(), nc, nc ? sc.ids + size_t(b) * sc.cstride : nullptr, act, fl);
-        schmidt::fillFilter(im, size_t(b), act, fl, f->hSch);
+        schmidt::fillFilter(im, size_t(b), act, fl, f->sch.img.host);
         nAmax = std::max(nAmax, int(act.size()));
     }
     const int nMax = schmidt::paddedOrder(maxN(f));
     sa = SchArgs{};
     sa.g = f->g[f->pG]; sa.Sigma = static_cast<double*>(f->Sigma[f->pS]); sa.ld = f->ld; sa.sigmaStride = f->sigmaStride;
-    sa.cnt = reinterpret_cast<const int*>(f->dSch + im.offCount()); sa.act = reinterpret_cast<const int*>(f->dSch + im.offActive());
-    sa.flag = reinterpret_cast<const unsigned char*>(f->dSch + im.offFlag()); sa.pitch = f->ld; sa.nJT = schmidt::colTiles(nMax);
-    sa.cntH = reinterpret_cast<const int*>(f->hSchDev + im.offCount()); sa.actH = reinterpret_cast<const int*>(f->hSchDev + im.offActive());
-    sa.flagH = reinterpret_cast<const unsigned char*>(f->hSchDev + im.offFlag());
-    sa.cntW = reinterpret_cast<int*>(f->dSch + im.offCount()); sa.actW = reinterpret_cast<int*>(f->dSch + im.offActive());
-    sa.flagW = reinterpret_cast<unsigned char*>(f->dSch + im.offFlag());
+    sa.cnt = reinterpret_cast<const int*>(f->sch.img.dev + im.offCount()); sa.act = reinterpret_cast<const int*>(f->sch.img.dev + im.offActive());
+    sa.flag = reinterpret_cast<const unsigned char*>(f->sch.img.dev + im.offFlag()); sa.pitch = f->ld; sa.nJT = schmidt::colTiles(nMax);
+    sa.cntH = reinterpret_cast<const int*>(f->sch.img.host.dev + im.offCount()); sa.actH = reinterpret_cast<const int*>(f->sch.img.host.dev + im.offActive());
+    sa.flagH = reinterpret_cast<const unsigned char*>(f->sch.img.host.dev + im.offFlag());
+    sa.cntW = reinterpret_cast<int*>(f->sch.img.dev + im.offCount()); sa.actW = reinterpret_cast<int*>(f->sch.img.dev + im.offActive());
+    sa.flagW = reinterpret_cast<unsigned char*>(f->sch.img.dev + im.offFlag());
     gridX = schmidt::gridX(nAmax, nMax);
     return EQF_OK;
 }
-// (evSch: the pinned image has been read)
+// (sch.img's event: the pinned image has been read)
 int schGammaLaunch(eqf_filter* f, const SchArgs& sa) {
     hipLaunchKernelGGL(k_schmidt_gamma, dim3((f->ld + 255) / 256, f->B), dim3(256), 0, f->stream, sa);
-    HIPC(hipEventRecord(f->evSch, f->stream));
+    HIPC(f->sch.img.record(f->stream));
     return EQF_OK;
 }
 
@@ -3593,9 +3430,9 @@ int linUpdate(eqf_filter* f, int local, int m, const double* H, int ldh, const d
         const int bad = schmidt::checkLists(B, f->cap, sc->n, sc->ids, sc->cstride);
         if (bad) return bad;
     }
-    int rc = linAlloc(f);
-    if (!rc && sc) rc = schAlloc(f);
-    if (!rc) rc = liftAlloc(f, lift::callFactors(liftCallKind(f), maxN(f)));
+    int rc = linReserve(f);
+    if (!rc && sc) rc = schReserve(f);
+    if (!rc) rc = liftReserve(f, lift::callFactors(liftCallKind(f), maxN(f)));
     if (rc) return rc;
     if (local) {
         rc = launchLocal(f, 0, B, false);  // (only writes the J records)
@@ -3603,9 +3440,9 @@ int linUpdate(eqf_filter* f, int local, int m, const double* H, int ldh, const d
     }
     const linear::SmallLayout sl{B, linear::refOrder(f->cap)};
     const linear::WorkLayout wl{f->ld};
-    HIPC(hipEventSynchronize(f->evLin));
-    double* hs = reinterpret_cast<double*>(f->hLinSmall);
-    double* ds = reinterpret_cast<double*>(f->dLinSmall);
+    HIPC(f->lin.small.wait());
+    double* hs = reinterpret_cast<double*>(f->lin.small.host.get());
+    double* ds = reinterpret_cast<double*>(f->lin.small.dev.get());
     unsigned char* hm = reinterpret_cast<unsigned char*>(hs + sl.offMask());
     for (int b = 0; b < B; ++b) {
         linear::packFilter(m, N[b], H + size_t(b) * m * ldh, ldh, resid + size_t(b) * m, R + size_t(b) * m * m,
@@ -3613,15 +3450,14 @@ int linUpdate(eqf_filter* f, int local, int m, const double* H, int ldh, const d
             hs + sl.offR() + size_t(b) * kLinRows * kLinRows);
         hm[b] = mask ? (mask[b] ? 1 : 0) : 1;
     }
-    HIPC(hipMemcpyAsync(f->dLinSmall, f->hLinSmall, sl.bytes(), hipMemcpyHostToDevice, f->stream));
-    HIPC(hipEventRecord(f->evLin, f->stream));
+    HIPC(f->lin.small.upload(sl.bytes(), f->stream));
     const int nMax = maxN(f), nt = linear::rowTiles(nMax);
     LinArgs a{};
     a.g = f->g[f->pG]; a.Sigma = static_cast<double*>(f->Sigma[f->pS]); a.ld = f->ld; a.sigmaStride = f->sigmaStride;
     a.H = ds + sl.offH(); a.ldr = sl.ldr; a.resid = ds + sl.offResid(); a.R = ds + sl.offR();
     a.mask = reinterpret_cast<const unsigned char*>(ds + sl.offMask());
     a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.m = m; a.gate = gate;
-    a.ws = f->dLinWs; a.wsStride = wl.stride(); a.out = f->dLinOut;
+    a.ws = f->lin.ws; a.wsStride = wl.stride(); a.out = f->lin.out;
     rc = profiled(f, EQF_PROF_LIN_ROWS, [&] { hipLaunchKernelGGL(k_lin_rows, dim3(B), dim3(256), 0, f->stream, a); });
     if (!rc) rc = profiled(f, EQF_PROF_LIN_GAIN, [&] { hipLaunchKernelGGL(k_lin_gain, dim3(nt, B), dim3(256), kLinGainLdsBytes, f->stream, a); });
     if (!rc) rc = profiled(f, EQF_PROF_LIN_SOLVE, [&] { hipLaunchKernelGGL(k_lin_solve, dim3(B), dim3(256), 0, f->stream, a); });
@@ -3629,17 +3465,17 @@ int linUpdate(eqf_filter* f, int local, int m, const double* H, int ldh, const d
     int schGrid = 0;
     if (!rc && sc) {
         rc = schUpload(f, *sc, N.data(), sa, schGrid);
-        sa.out = f->dLinOut; sa.gamma = f->dLinWs + wl.offGamma(); sa.strideG = wl.stride();
+        sa.out = f->lin.out; sa.gamma = f->lin.ws + wl.offGamma(); sa.strideG = wl.stride();
         if (!rc) rc = schGammaLaunch(f, sa);  // (in front of the lift and the group step: they see the masked gamma)
     }
     // the group step, behind the solve's verdict (entry 3 of the record, where eqf_nees.hpp's info sits)
     IncArgs ia{};
-    ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = f->dLinWs + wl.offGamma(); ia.strideG = wl.stride();
-    ia.off = 0; ia.mask = nullptr; ia.info = f->dLinOut;
+    ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = f->lin.ws + wl.offGamma(); ia.strideG = wl.stride();
+    ia.off = 0; ia.mask = nullptr; ia.info = f->lin.out;
     // the lift reads the Sigma the call started from and may still refuse the filter: in front of the downdate
-    if (!rc) rc = liftEnqueue(f, ia.gamma, ia.strideG, 0, nullptr, f->dLinOut, true, ia);
+    if (!rc) rc = liftEnqueue(f, ia.gamma, ia.strideG, 0, nullptr, f->lin.out, true, ia);
     if (!rc && sc) {
-        const SchLin lay{f->dLinWs + wl.offY(), wl.stride(), f->ld};
+        const SchLin lay{f->lin.ws + wl.offY(), wl.stride(), f->ld};
         rc = profiled(f, EQF_PROF_LIN_DOWNDATE, [&] {
             hipLaunchKernelGGL(k_schmidt_downdate<SchLin>, dim3(schGrid, B), dim3(256), schmidtLdsBytes<SchLin>(), f->stream, sa, lay);
         });
@@ -3653,10 +3489,10 @@ int linUpdate(eqf_filter* f, int local, int m, const double* H, int ldh, const d
     f->csValid = false;  // (C Sigma / S left by an earlier burst describe the old Sigma and the old landmarks)
     if (!gamma && !report) return EQF_OK;
     std::vector<double> hO(size_t(B) * kLinHead), hG;
-    HIPC(hipMemcpyAsync(hO.data(), f->dLinOut, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipMemcpyAsync(hO.data(), f->lin.out, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
     if (gamma) {
         hG.resize(size_t(B) * f->ld);
-        HIPC(hipMemcpy2DAsync(hG.data(), sizeof(double) * f->ld, f->dLinWs + wl.offGamma(), sizeof(double) * wl.stride(),
+        HIPC(hipMemcpy2DAsync(hG.data(), sizeof(double) * f->ld, f->lin.ws + wl.offGamma(), sizeof(double) * wl.stride(),
             sizeof(double) * f->ld, B, hipMemcpyDeviceToHost, f->stream));
     }
     HIPC(hipStreamSynchronize(f->stream));
@@ -3694,54 +3530,11 @@ int eqf_update_linear_schmidt(eqf_filter* f, int local, int m, const double* H, 
 static_assert(blocks::kRefBase == kBase && blocks::kPadBase == kLm0 && blocks::kTile == kSB && blocks::kHead == kLinHead,
     "eqf_blocks_host.hpp repeats the layout constants");
 namespace {
-// The buffers of eqf_update_landmarks for this call's shape; what is there and large enough is kept.  A failure frees what this call got
-// and leaves the handle as it was.
-int blkAlloc(eqf_filter* f, const blocks::SmallLayout& sl, const blocks::WorkLayout& wl) {
-    const size_t needS = sl.bytes(), needW = size_t(wl.strideD()) * f->B, needI = size_t(wl.strideI()) * f->B;
-    void *h = nullptr, *d = nullptr, *w = nullptr, *wi = nullptr, *o = nullptr;
-    hipEvent_t ev = nullptr;
-    bool ok = true;
-    if (needS > f->blkSmallBytes) ok = ok && hipHostMalloc(&h, needS, hipHostMallocDefault) == hipSuccess && hipMalloc(&d, needS) == hipSuccess;
-    if (ok && needW > f->blkWsDoubles) ok = hipMalloc(&w, sizeof(double) * needW) == hipSuccess;
-    if (ok && needI > f->blkWiInts) ok = hipMalloc(&wi, sizeof(int) * needI) == hipSuccess;
-    if (ok && !f->dBlkOut) ok = hipMalloc(&o, sizeof(double) * size_t(kLinHead) * f->B) == hipSuccess;
-    if (ok && !f->evBlk) ok = hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        if (h) hipHostFree(h);
-        for (void* p : {d, w, wi, o})
-            if (p) hipFree(p);
-        return EQF_ERR_HIP;
-    }
-    // (what is replaced may still be in use by an earlier call that did not wait: the stream is drained first)
-    if ((h || w || wi) && (f->hBlkSmall || f->dBlkWs || f->dBlkWi) && hipStreamSynchronize(f->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        if (h) hipHostFree(h);
-        for (void* p : {d, w, wi, o})
-            if (p) hipFree(p);
-        if (ev) hipEventDestroy(ev);
-        return EQF_ERR_HIP;
-    }
-    if (h) {
-        if (f->hBlkSmall) hipHostFree(f->hBlkSmall);
-        hipFree(f->dBlkSmall);
-        f->hBlkSmall = static_cast<char*>(h);
-        f->dBlkSmall = static_cast<char*>(d);
-        f->blkSmallBytes = needS;
-    }
-    if (w) {
-        hipFree(f->dBlkWs);
-        f->dBlkWs = static_cast<double*>(w);
-        f->blkWsDoubles = needW;
-    }
-    if (wi) {
-        hipFree(f->dBlkWi);
-        f->dBlkWi = static_cast<int*>(wi);
-        f->blkWiInts = needI;
-    }
-    if (o) f->dBlkOut = static_cast<double*>(o);
-    if (ev) f->evBlk = ev;
-    return EQF_OK;
+// The buffers of eqf_update_landmarks for this call's shape; what is there and large enough is kept.
+int blkReserve(eqf_filter* f, const blocks::SmallLayout& sl, const blocks::WorkLayout& wl) {
+    const workspace::Want w[] = {WANT_STAGED(f->blk.small, sl.bytes()), want(f->blk.ws, sizeof(double) * size_t(wl.strideD()) * f->B, &f->blk.wsCap),
+        want(f->blk.wi, sizeof(int) * size_t(wl.strideI()) * f->B, &f->blk.wiCap), want(f->blk.out, sizeof(double) * size_t(kLinHead) * f->B)};
+    return reserveSlots(f, w);
 }
 
 // eqf_update_landmarks (sc == nullptr: the launches it has always enqueued) and eqf_update_landmarks_schmidt
@@ -3766,23 +3559,23 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
     }
     const blocks::SmallLayout sl{B, stride, rows};
     const blocks::WorkLayout wl{f->ld, stride, rows, kDRec};
-    int rc = blkAlloc(f, sl, wl);
-    if (!rc) rc = liftAlloc(f, lift::callFactors(liftCallKind(f), maxN(f)));
-    if (!rc && sc) rc = schAlloc(f);
+    int rc = blkReserve(f, sl, wl);
+    if (!rc) rc = liftReserve(f, lift::callFactors(liftCallKind(f), maxN(f)));
+    if (!rc && sc) rc = schReserve(f);
     if (rc) return rc;
-    if (sc && !f->schLdsSet) {  // (dynamic LDS beyond 64 KB, as k_blk_downdate's)
+    if (sc && !f->sch.ldsSet) {  // (dynamic LDS beyond 64 KB, as k_blk_downdate's)
         HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schmidt_downdate<SchBlk>), hipFuncAttributeMaxDynamicSharedMemorySize,
             schmidtLdsBytes<SchBlk>()));
-        f->schLdsSet = true;
+        f->sch.ldsSet = true;
     }
-    if (!f->blkLdsSet)  // (dynamic LDS beyond 64 KB: see allowUpdateLds; enqueueFactor sets its own kernels' and the flag)
+    if (!f->blk.ldsSet)  // (dynamic LDS beyond 64 KB: see allowUpdateLds; enqueueFactor sets its own kernels' and the flag)
         HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_blk_downdate), hipFuncAttributeMaxDynamicSharedMemorySize, kBlkDownLdsBytes));
     if (local) {
         rc = launchLocal(f, 0, B, false);  // (only writes the J records)
         if (rc) return rc;
     }
-    HIPC(hipEventSynchronize(f->evBlk));
-    char* hs = f->hBlkSmall;
+    HIPC(f->blk.small.wait());
+    char* hs = f->blk.small.host;
     const size_t ne = sl.entries();
     std::memcpy(hs + sl.offH(), Hb, sizeof(double) * ne * rows * 3);
     std::memcpy(hs + sl.offResid(), resid, sizeof(double) * ne * rows);
@@ -3796,22 +3589,21 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
         for (int k = 0; k < stride; ++k)
             hIdx[size_t(b) * stride + k] = (hm[b] && k < nk[b]) ? blocks::findId(f->ids[b].data(), N[b], ids[size_t(b) * stride + k]) : -1;
     }
-    HIPC(hipMemcpyAsync(f->dBlkSmall, f->hBlkSmall, sl.bytes(), hipMemcpyHostToDevice, f->stream));
-    HIPC(hipEventRecord(f->evBlk, f->stream));
+    HIPC(f->blk.small.upload(sl.bytes(), f->stream));
     const int nMax = maxN(f), nt = blocks::rowTiles(nMax);
     const int nPT = blocks::pairTiles(stride);
     BlkArgs a{};
     a.g = f->g[f->pG]; a.Sigma = static_cast<double*>(f->Sigma[f->pS]); a.ld = f->ld; a.sigmaStride = f->sigmaStride;
-    a.Hb = reinterpret_cast<const double*>(f->dBlkSmall + sl.offH()); a.resid = reinterpret_cast<const double*>(f->dBlkSmall + sl.offResid());
-    a.Rb = reinterpret_cast<const double*>(f->dBlkSmall + sl.offR()); a.idx = reinterpret_cast<const int*>(f->dBlkSmall + sl.offIdx());
-    a.nk = reinterpret_cast<const int*>(f->dBlkSmall + sl.offNk()); a.mask = reinterpret_cast<const unsigned char*>(f->dBlkSmall + sl.offMask());
+    a.Hb = reinterpret_cast<const double*>(f->blk.small.dev + sl.offH()); a.resid = reinterpret_cast<const double*>(f->blk.small.dev + sl.offResid());
+    a.Rb = reinterpret_cast<const double*>(f->blk.small.dev + sl.offR()); a.idx = reinterpret_cast<const int*>(f->blk.small.dev + sl.offIdx());
+    a.nk = reinterpret_cast<const int*>(f->blk.small.dev + sl.offNk()); a.mask = reinterpret_cast<const unsigned char*>(f->blk.small.dev + sl.offMask());
     a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.rows = rows; a.stride = stride; a.mp = wl.mp(); a.nb = wl.nb();
     a.gate = gate; a.lmGate = lm_gate;
-    a.ws = f->dBlkWs; a.wsStride = wl.strideD(); a.offHt = wl.offHt(); a.offGamma = wl.offGamma(); a.offD = wl.offD();
-    a.wi = f->dBlkWi; a.wiStride = wl.strideI(); a.out = f->dBlkOut;
+    a.ws = f->blk.ws; a.wsStride = wl.strideD(); a.offHt = wl.offHt(); a.offGamma = wl.offGamma(); a.offD = wl.offD();
+    a.wi = f->blk.wi; a.wiStride = wl.strideI(); a.out = f->blk.out;
     hipLaunchKernelGGL(k_blk_rows, dim3(B), dim3(256), 0, f->stream, a);
     hipLaunchKernelGGL(k_blk_gain, dim3(nt + nPT * nPT, B), dim3(256), 0, f->stream, a, nt, nPT);
-    rc = enqueueFactor(f->stream, f->blkLdsSet, a, B, wl.mp(), blocks::rhsBlocks(blocks::paddedOrder(nMax)));
+    rc = enqueueFactor(f->stream, f->blk.ldsSet, a, B, wl.mp(), blocks::rhsBlocks(blocks::paddedOrder(nMax)));
     if (rc) return rc;
     hipLaunchKernelGGL(k_blk_gamma, dim3(nt, B), dim3(64), 0, f->stream, a);
     hipLaunchKernelGGL(k_blk_tail, dim3(B), dim3(256), 0, f->stream, a);
@@ -3820,19 +3612,19 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
     if (sc) {
         rc = schUpload(f, *sc, N.data(), sa, schGrid);
         if (rc) return rc;
-        sa.out = f->dBlkOut; sa.gamma = f->dBlkWs + wl.offGamma(); sa.strideG = wl.strideD();
+        sa.out = f->blk.out; sa.gamma = f->blk.ws + wl.offGamma(); sa.strideG = wl.strideD();
         rc = schGammaLaunch(f, sa);  // (in front of the lift and the group step: they see the masked gamma)
         if (rc) return rc;
     }
     // the group step, behind the tail's verdict (entry 3 of the record, where eqf_nees.hpp's info sits)
     IncArgs ia{};
-    ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = f->dBlkWs + wl.offGamma(); ia.strideG = wl.strideD();
-    ia.off = 0; ia.mask = nullptr; ia.info = f->dBlkOut;
+    ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = f->blk.ws + wl.offGamma(); ia.strideG = wl.strideD();
+    ia.off = 0; ia.mask = nullptr; ia.info = f->blk.out;
     // the lift reads the Sigma the call started from and may still refuse the filter: in front of the downdate
-    rc = liftEnqueue(f, ia.gamma, ia.strideG, 0, nullptr, f->dBlkOut, true, ia);
+    rc = liftEnqueue(f, ia.gamma, ia.strideG, 0, nullptr, f->blk.out, true, ia);
     if (rc) return rc;
     if (sc) {
-        const SchBlk lay{f->dBlkWs, wl.strideD(), wl.mp(), rows, f->dBlkWi + wl.offCount(), wl.strideI()};
+        const SchBlk lay{f->blk.ws, wl.strideD(), wl.mp(), rows, f->blk.wi + wl.offCount(), wl.strideI()};
         hipLaunchKernelGGL(k_schmidt_downdate<SchBlk>, dim3(schGrid, B), dim3(256), schmidtLdsBytes<SchBlk>(), f->stream, sa, lay);
     } else {
         hipLaunchKernelGGL(k_blk_downdate, dim3(blocks::triTiles(nt), B), dim3(256), kBlkDownLdsBytes, f->stream, a);
@@ -3843,11 +3635,11 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
     if (!used && !gamma && !report) return EQF_OK;
     std::vector<double> hO(size_t(B) * kLinHead), hG;
     std::vector<int> hU(size_t(B) * wl.strideI());
-    HIPC(hipMemcpyAsync(hO.data(), f->dBlkOut, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
-    HIPC(hipMemcpyAsync(hU.data(), f->dBlkWi, sizeof(int) * hU.size(), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipMemcpyAsync(hO.data(), f->blk.out, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipMemcpyAsync(hU.data(), f->blk.wi, sizeof(int) * hU.size(), hipMemcpyDeviceToHost, f->stream));
     if (gamma) {
         hG.resize(size_t(B) * f->ld);
-        HIPC(hipMemcpy2DAsync(hG.data(), sizeof(double) * f->ld, f->dBlkWs + wl.offGamma(), sizeof(double) * wl.strideD(),
+        HIPC(hipMemcpy2DAsync(hG.data(), sizeof(double) * f->ld, f->blk.ws + wl.offGamma(), sizeof(double) * wl.strideD(),
             sizeof(double) * f->ld, B, hipMemcpyDeviceToHost, f->stream));
     }
     HIPC(hipStreamSynchronize(f->stream));
@@ -3892,7 +3684,7 @@ namespace {
 #define MIX_LAUNCH(f, ...)                  \
     do {                                    \
         hipLaunchKernelGGL(__VA_ARGS__);    \
-        ++(f)->mixLaunches;                 \
+        ++(f)->mix.launches;                 \
     } while (0)
 constexpr int kMixGlobWords = int(sizeof(Glob) / 8);
 // What both entry points check and build before any effect: the arguments, the members' landmark lists against the reference's, the
@@ -3917,65 +3709,32 @@ int mixCheck(eqf_filter* f, int n, const int* idx, const double* w, int ref, boo
     c.N = int(rid.size());
     return EQF_OK;  // (headArgsOk: the weight sum is positive, so at least one member is walked)
 }
-// every buffer a call needs; a failure leaves the handle as it was
-int mixAlloc(eqf_filter* f, size_t tabBytes) {
+// every buffer a call needs: the workspace from capacity and batch, the table for this call's members
+int mixReserve(eqf_filter* f, size_t tabBytes) {
     const mixture::WorkLayout wl{f->B, f->cap, f->ld, kMixGlobWords};
-    if (!f->dMixWs) {
-        void* w = nullptr;
-        hipEvent_t ev = nullptr;
-        if (hipMalloc(&w, sizeof(double) * wl.doubles()) != hipSuccess || hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            if (w) hipFree(w);
-            return EQF_ERR_HIP;
-        }
-        f->dMixWs = static_cast<double*>(w);
-        f->evMix = ev;
-    }
-    if (tabBytes > f->mixTabBytes) {
-        HIPC(hipEventSynchronize(f->evMix));  // (the old image may still be read; nothing is held yet that a failure here would leak)
-        HIPC(hipStreamSynchronize(f->stream));
-        void *h = nullptr, *d = nullptr;
-        if (hipHostMalloc(&h, tabBytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&d, tabBytes) != hipSuccess) {
-            (void)hipGetLastError();
-            if (h) hipHostFree(h);
-            return EQF_ERR_HIP;
-        }
-        if (f->hMixTab) hipHostFree(f->hMixTab);
-        hipFree(f->dMixTab);
-        f->hMixTab = static_cast<char*>(h);
-        f->dMixTab = static_cast<char*>(d);
-        f->mixTabBytes = tabBytes;
-    }
-    if (!f->dSigmaLoc) {
-        if (hipMalloc(reinterpret_cast<void**>(&f->dSigmaLoc), sizeof(double) * size_t(f->sigmaStride) * f->B) != hipSuccess) {
-            (void)hipGetLastError();
-            f->dSigmaLoc = nullptr;
-            return EQF_ERR_HIP;
-        }
-    }
-    return EQF_OK;
+    const workspace::Want w[] = {want(f->mix.ws, sizeof(double) * wl.doubles()), WANT_STAGED(f->mix.tab, tabBytes), sigmaLocWant(f)};
+    return reserveSlots(f, w);
 }
 // The tables' upload and the arguments of every kernel of a call; P goes to slot `slot` of the scratch image.
 int mixPrepare(eqf_filter* f, const MixCall& c, int ref, int dst, int slot, MixArgs& a) {
     const size_t nm = c.members.size(), nu = c.uniq.size();
     const size_t tabBytes = sizeof(MixMember) * nm + sizeof(int) * nu;
-    int rc = mixAlloc(f, tabBytes);
+    int rc = mixReserve(f, tabBytes);
     if (rc) return rc;
     rc = launchLocal(f, 0, f->B, false);  // (only writes the J records)
     if (rc) return rc;
-    f->mixLaunches = 1;  // (k_local_jacobian)
-    HIPC(hipEventSynchronize(f->evMix));
-    std::memcpy(f->hMixTab, c.members.data(), sizeof(MixMember) * nm);
-    std::memcpy(f->hMixTab + sizeof(MixMember) * nm, c.uniq.data(), sizeof(int) * nu);
-    HIPC(hipMemcpyAsync(f->dMixTab, f->hMixTab, tabBytes, hipMemcpyHostToDevice, f->stream));
-    HIPC(hipEventRecord(f->evMix, f->stream));
+    f->mix.launches = 1;  // (k_local_jacobian)
+    HIPC(f->mix.tab.wait());
+    std::memcpy(f->mix.tab.host, c.members.data(), sizeof(MixMember) * nm);
+    std::memcpy(f->mix.tab.host + sizeof(MixMember) * nm, c.uniq.data(), sizeof(int) * nu);
+    HIPC(f->mix.tab.upload(tabBytes, f->stream));
     const mixture::WorkLayout wl{f->B, f->cap, f->ld, kMixGlobWords};
-    double* ws = f->dMixWs;
+    double* ws = f->mix.ws;
     a = MixArgs{};
     a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.cap = f->cap; a.B = f->B;
     a.jac = f->dJac; a.jacT = ws + wl.offJac(); a.est = ws + wl.offEst(); a.err = ws + wl.offErr(); a.mean = ws + wl.offMean();
-    a.mem = reinterpret_cast<const MixMember*>(f->dMixTab); a.n = int(nm);
-    a.uniq = reinterpret_cast<const int*>(f->dMixTab + sizeof(MixMember) * nm); a.nUniq = int(nu);
+    a.mem = reinterpret_cast<const MixMember*>(f->mix.tab.dev.get()); a.n = int(nm);
+    a.uniq = reinterpret_cast<const int*>(f->mix.tab.dev + sizeof(MixMember) * nm); a.nUniq = int(nu);
     a.N = c.N; a.ref = ref; a.dst = dst;
     a.Sigma = static_cast<double*>(f->Sigma[f->pS]); a.ld = f->ld; a.sigmaStride = f->sigmaStride;
     a.P = f->dSigmaLoc + (long long)slot * f->sigmaStride;
@@ -4119,29 +3878,19 @@ McWs mcCarve(const eqf_filter* f, char* p, int C) {
     w.bad = reinterpret_cast<int*>(w.g + C);
     return w;
 }
-// both blocks of a call; a failure frees what this call got and leaves the handle as it was
-int mcAlloc(eqf_filter* f, int chunk, size_t nItems) {
-    void *w = nullptr, *t = nullptr;
-    const size_t itemBytes = nItems * (sizeof(PairItem) + sizeof(double) * kPairRec);
-    const bool needW = chunk > f->mcChunkCap, needT = nItems > f->mcItemCap;
-    if (!needW && !needT) return EQF_OK;
-    if ((needW && hipMalloc(&w, sizeof(double) * mcWsDoubles(f, chunk)) != hipSuccess) || (needT && hipMalloc(&t, itemBytes) != hipSuccess)) {
-        (void)hipGetLastError();
-        if (w) hipFree(w);
-        return EQF_ERR_HIP;
+// both blocks of a call; a block this call installed is zero-filled where its unused parts are read
+int mcReserve(eqf_filter* f, int chunk, size_t nItems) {
+    const size_t wsBytes = sizeof(double) * mcWsDoubles(f, chunk);
+    const workspace::Want w[] = {want(f->mc.ws, wsBytes, &f->mc.wsBytes),
+        want(f->mc.items, nItems * (sizeof(PairItem) + sizeof(double) * kPairRec), &f->mc.itemBytes)};
+    workspace::Result got;
+    const int rc = reserveSlots(f, w, &got);
+    if (rc) return rc;
+    if (got.has(0)) {
+        f->mc.chunkCap = chunk;
+        HIPC(hipMemsetAsync(f->mc.ws, 0, wsBytes, f->stream));  // (upper triangles and the Globs are read, never used)
     }
-    HIPC(hipStreamSynchronize(f->stream));
-    if (needW) {
-        hipFree(f->dMcWs);
-        f->dMcWs = static_cast<char*>(w);
-        f->mcChunkCap = chunk;
-        HIPC(hipMemsetAsync(w, 0, sizeof(double) * mcWsDoubles(f, chunk), f->stream));  // (upper triangles and the Globs are read, never used)
-    }
-    if (needT) {
-        hipFree(f->dMcItems);
-        f->dMcItems = static_cast<char*>(t);
-        f->mcItemCap = nItems;
-    }
+    if (got.has(1)) f->mc.itemCap = nItems;
     return EQF_OK;
 }
 }  // namespace
@@ -4158,14 +3907,14 @@ int eqf_get_merge_costs(eqf_filter* f, int n, const int* idx, const double* w, i
     mergecost::distinct(n, idx, f->B, c.uniq);  // (every member's image is needed, a member of weight 0 too)
     std::vector<mergecost::Item> items;
     mergecost::buildItems(n, idx, c.wt.data(), kind, npairs, pairs, items);
-    const int chunk = mergecost::chunkSize(f->mcChunkOpt, f->B);
-    rc = mcAlloc(f, chunk, items.size());
+    const int chunk = mergecost::chunkSize(f->mc.chunkOpt, f->B);
+    rc = mcReserve(f, chunk, items.size());
     if (rc) return rc;
     // e_b, J'_b and Sigma'_b of every distinct member about c = xHat_ref
-    const int launchesBefore = f->mixLaunches;  // (eqf_debug_mixture_launches keeps answering for the most recent MIXTURE call)
+    const int launchesBefore = f->mix.launches;  // (eqf_debug_mixture_launches keeps answering for the most recent MIXTURE call)
     MixArgs a;
     rc = mixPrepare(f, c, ref, ref, ref, a);
-    f->mixLaunches = launchesBefore;
+    f->mix.launches = launchesBefore;
     if (rc) return rc;
     a.centre = ref; a.centreFilter = ref; a.centred = 0;
     const int N = c.N, strips = std::max(1, (N + 255) / 256);
@@ -4178,9 +3927,9 @@ int eqf_get_merge_costs(eqf_filter* f, int n, const int* idx, const double* w, i
     }
     HIPC(hipGetLastError());
     const int off = mergecost::offsetOf(first), m = mergecost::paddedOrder(N, off);
-    const McWs ws = mcCarve(f, f->dMcWs, f->mcChunkCap);
-    PairItem* dItems = reinterpret_cast<PairItem*>(f->dMcItems);
-    double* dRec = reinterpret_cast<double*>(f->dMcItems + sizeof(PairItem) * f->mcItemCap);
+    const McWs ws = mcCarve(f, f->mc.ws, f->mc.chunkCap);
+    PairItem* dItems = reinterpret_cast<PairItem*>(f->mc.items.get());
+    double* dRec = reinterpret_cast<double*>(f->mc.items + sizeof(PairItem) * f->mc.itemCap);
     HIPC(hipMemcpyAsync(dItems, items.data(), sizeof(PairItem) * items.size(), hipMemcpyHostToDevice, f->stream));
     PairArgs pa{};
     pa.items = dItems; pa.S = f->dSigmaLoc; pa.ld = f->ld; pa.strideS = f->sigmaStride; pa.err = a.err; pa.jacT = a.jacT; pa.cap = f->cap;
@@ -4196,7 +3945,7 @@ int eqf_get_merge_costs(eqf_filter* f, int n, const int* idx, const double* w, i
             pa.item0 = int(seg0[s] + (long long)ch * chunk);
             pa.count = cnt;
             hipLaunchKernelGGL(k_pair_form, dim3(kLm0 + 3 * N + 1, cnt), dim3(256), 0, f->stream, pa);
-            rc = enqueueFactor(f->stream, f->neesLdsSet, na, cnt, m, 1);
+            rc = enqueueFactor(f->stream, f->nees.ldsSet, na, cnt, m, 1);
             if (rc) return rc;
             hipLaunchKernelGGL(k_nees_tail, dim3(cnt), dim3(256), 0, f->stream, na);
             hipLaunchKernelGGL(k_pair_tail, dim3((cnt + 255) / 256), dim3(256), 0, f->stream, pa);
@@ -4260,27 +4009,16 @@ ScTab scTabLayout(size_t nItems, size_t nMatched) {
     t.bytes = t.slots + sizeof(int) * nMatched;
     return t;
 }
-// both blocks of a call; a failure frees what this call got and leaves the handle as it was
-int scAlloc(eqf_filter* f, int chunk, size_t tabBytes) {
-    void *w = nullptr, *t = nullptr;
-    const bool needW = chunk > f->scChunkCap, needT = tabBytes > f->scTabBytes;
-    if (!needW && !needT) return EQF_OK;
-    if ((needW && hipMalloc(&w, sizeof(double) * scWsDoubles(f, chunk)) != hipSuccess) || (needT && hipMalloc(&t, tabBytes) != hipSuccess)) {
-        (void)hipGetLastError();
-        if (w) hipFree(w);
-        return EQF_ERR_HIP;
-    }
-    HIPC(hipStreamSynchronize(f->stream));
-    if (needW) {
-        hipFree(f->dScWs);
-        f->dScWs = static_cast<char*>(w);
-        f->scChunkCap = chunk;
-        HIPC(hipMemsetAsync(w, 0, sizeof(double) * scWsDoubles(f, chunk), f->stream));  // (upper triangles of diagonal tiles are read, never used)
-    }
-    if (needT) {
-        hipFree(f->dScTab);
-        f->dScTab = static_cast<char*>(t);
-        f->scTabBytes = tabBytes;
+// both blocks of a call; a workspace this call installed is zero-filled
+int scReserve(eqf_filter* f, int chunk, size_t tabBytes) {
+    const size_t wsBytes = sizeof(double) * scWsDoubles(f, chunk);
+    const workspace::Want w[] = {want(f->sc.ws, wsBytes, &f->sc.wsBytes), want(f->sc.tab, tabBytes, &f->sc.tabBytes)};
+    workspace::Result got;
+    const int rc = reserveSlots(f, w, &got);
+    if (rc) return rc;
+    if (got.has(0)) {
+        f->sc.chunkCap = chunk;
+        HIPC(hipMemsetAsync(f->sc.ws, 0, wsBytes, f->stream));  // (upper triangles of diagonal tiles are read, never used)
     }
     return EQF_OK;
 }
@@ -4319,35 +4057,35 @@ int eqf_score_vision(eqf_filter* f, int ncand, const int* nb, const int* ids, co
             std::memcpy(&y[3 * (size_t(items[it].first) + k)], bearings + (it * stride + size_t(pos[size_t(items[it].first) + k])) * 3, sizeof(double) * 3);
     std::vector<double> hRec(nItems * score::kRec, 0.0), hLm(nMatched, 0.0);
     if (nMatched > 0) {
-        const int chunk = score::chunkSize(f->scChunkOpt, B);
+        const int chunk = score::chunkSize(f->sc.chunkOpt, B);
         const ScTab tab = scTabLayout(nItems, nMatched);
-        int rc = scAlloc(f, chunk, tab.bytes);
+        int rc = scReserve(f, chunk, tab.bytes);
         if (rc) return rc;
-        const ScWs ws = scCarve(f, f->dScWs, f->scChunkCap);
+        const ScWs ws = scCarve(f, f->sc.ws, f->sc.chunkCap);
         ScoreArgs a{};
-        a.items = reinterpret_cast<const ScoreItem*>(f->dScTab + tab.items);
-        a.slots = reinterpret_cast<const int*>(f->dScTab + tab.slots);
-        a.y = reinterpret_cast<const double*>(f->dScTab + tab.y);
-        a.nisLm = reinterpret_cast<double*>(f->dScTab + tab.nisLm);
-        a.rec = reinterpret_cast<double*>(f->dScTab + tab.rec);
+        a.items = reinterpret_cast<const ScoreItem*>(f->sc.tab + tab.items);
+        a.slots = reinterpret_cast<const int*>(f->sc.tab + tab.slots);
+        a.y = reinterpret_cast<const double*>(f->sc.tab + tab.y);
+        a.nisLm = reinterpret_cast<double*>(f->sc.tab + tab.nisLm);
+        a.rec = reinterpret_cast<double*>(f->sc.tab + tab.rec);
         a.Q = f->Q[f->pG]; a.lmc = f->lmc; a.S = static_cast<const double*>(f->Sigma[f->pS]); a.sigmaStride = f->sigmaStride; a.ld = f->ld;
         a.cap = cap; a.measVar = f->set.measurementVariance;
         a.ldW = score::paddedOrder(cap); a.strideW = (long long)a.ldW * a.ldW; a.W = ws.W; a.E = ws.E; a.D = ws.D; a.bad = ws.bad;
-        HIPC(hipMemcpyAsync(f->dScTab + tab.items, items.data(), sizeof(ScoreItem) * nItems, hipMemcpyHostToDevice, f->stream));
-        HIPC(hipMemcpyAsync(f->dScTab + tab.slots, slots.data(), sizeof(int) * nMatched, hipMemcpyHostToDevice, f->stream));
-        HIPC(hipMemcpyAsync(f->dScTab + tab.y, y.data(), sizeof(double) * 3 * nMatched, hipMemcpyHostToDevice, f->stream));
+        HIPC(hipMemcpyAsync(f->sc.tab + tab.items, items.data(), sizeof(ScoreItem) * nItems, hipMemcpyHostToDevice, f->stream));
+        HIPC(hipMemcpyAsync(f->sc.tab + tab.slots, slots.data(), sizeof(int) * nMatched, hipMemcpyHostToDevice, f->stream));
+        HIPC(hipMemcpyAsync(f->sc.tab + tab.y, y.data(), sizeof(double) * 3 * nMatched, hipMemcpyHostToDevice, f->stream));
         for (int ch = 0; ch < score::numChunks((long long)nItems, chunk); ++ch) {
             const int cnt = score::chunkCount((long long)nItems, chunk, ch);
             a.item0 = ch * chunk;
             a.count = cnt;
             hipLaunchKernelGGL(k_score_form, dim3((mLm + 3) / 4 + 1, cnt), dim3(256), 0, f->stream, a);
-            rc = enqueueFactor(f->stream, f->scoreLdsSet, a, cnt, 2 * mLm, 1);
+            rc = enqueueFactor(f->stream, f->sc.ldsSet, a, cnt, 2 * mLm, 1);
             if (rc) return rc;
             hipLaunchKernelGGL(k_score_tail, dim3(cnt), dim3(256), 0, f->stream, a);
         }
         HIPC(hipGetLastError());
-        HIPC(hipMemcpyAsync(hRec.data(), f->dScTab + tab.rec, sizeof(double) * hRec.size(), hipMemcpyDeviceToHost, f->stream));
-        HIPC(hipMemcpyAsync(hLm.data(), f->dScTab + tab.nisLm, sizeof(double) * nMatched, hipMemcpyDeviceToHost, f->stream));
+        HIPC(hipMemcpyAsync(hRec.data(), f->sc.tab + tab.rec, sizeof(double) * hRec.size(), hipMemcpyDeviceToHost, f->stream));
+        HIPC(hipMemcpyAsync(hLm.data(), f->sc.tab + tab.nisLm, sizeof(double) * nMatched, hipMemcpyDeviceToHost, f->stream));
     }
     HIPC(hipStreamSynchronize(f->stream));
     if (nis_lm) std::fill(nis_lm, nis_lm + nItems * stride, 0.0);
@@ -4377,7 +4115,7 @@ int eqf_score_vision(eqf_filter* f, int ncand, const int* nb, const int* ids, co
     return EQF_OK;
 }
 
-int eqf_debug_mixture_launches(eqf_filter* f) { return f ? f->mixLaunches : EQF_ERR_INVALID; }
+int eqf_debug_mixture_launches(eqf_filter* f) { return f ? f->mix.launches : EQF_ERR_INVALID; }
 
 int eqf_debug_sigma_pad(eqf_filter* f, int b, int image, double* max_abs) {
     if (!f || b < 0 || b >= f->B || (image != 0 && image != 1) || !max_abs) return EQF_ERR_INVALID;
@@ -4462,9 +4200,9 @@ int eqf_set_dense_propagate(eqf_filter* f, int on) {
     HIPC(hipSetDevice(f->device));
     if (on && !f->dF) {
         const size_t bytes = f->esz * f->sigmaStride * f->B;
-        HIPC(hipMalloc(&f->dF, bytes));
-        HIPC(hipMalloc(&f->dG, bytes));
-        HIPC(hipMalloc(&f->dBn, f->esz * (size_t)f->nTot * 6 * f->B));
+        const workspace::Want w[] = {want(f->dF, bytes), want(f->dG, bytes), want(f->dBn, f->esz * (size_t)f->nTot * 6 * f->B)};
+        const int rc = reserveSlots(f, w);
+        if (rc) return rc;
         HIPC(hipMemset(f->dF, 0, bytes));
         HIPC(hipMemset(f->dG, 0, bytes));
     }
