@@ -17,6 +17,8 @@ SKIPPED_BEFORE_FIRST_IMU = 1
 SKIPPED_NONPOSITIVE_DT = 2
 SKIPPED_NOT_INITIALISED = 3
 SKIPPED_NO_BEARINGS = 4
+OBS_BEARING, OBS_RANGE, OBS_POSITION = 0, 1, 2  # EQF_OBS_*: the kinds of observe_landmarks
+OBS_ROWS = {OBS_BEARING: 2, OBS_RANGE: 1, OBS_POSITION: 3}
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_UNSORTED, ERR_NUMERIC, ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6, -7
 PRECISION_F64, PRECISION_F32 = 0, 1
 GATE_CHORD, GATE_MAHALANOBIS = 0, 1
@@ -134,7 +136,7 @@ EXPORTED_SYMBOLS = [
     "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters", "eqf_update_linear", "eqf_update_landmarks",
     "eqf_get_mixture_moments", "eqf_merge_filters", "eqf_debug_mixture_launches", "eqf_debug_sigma_pad",
     "eqf_get_merge_costs", "eqf_score_vision", "eqf_get_lift_report", "eqf_edit_landmarks",
-    "eqf_update_linear_schmidt", "eqf_update_landmarks_schmidt",
+    "eqf_update_linear_schmidt", "eqf_update_landmarks_schmidt", "eqf_observe_landmarks",
     "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
     "eqf_set_sigma", "eqf_set_state", "eqf_copy_filters", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
@@ -214,6 +216,10 @@ def lib():
             L.eqf_update_landmarks_schmidt.argtypes = [vp, C.c_int, C.c_int, _ip, _ip, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double,
                                                        C.POINTER(C.c_ubyte), _ip, _ip, C.c_int, C.POINTER(C.c_ubyte), _dp, C.c_int,
                                                        C.POINTER(LinearReport)]
+        if hasattr(L, "eqf_observe_landmarks"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
+            L.eqf_observe_landmarks.argtypes = [vp, C.c_int, _dp, C.c_int, _ip, _ip, C.c_int, _dp, _dp, C.c_double, C.c_double,
+                                                C.POINTER(C.c_ubyte), _ip, _ip, C.c_int, C.POINTER(C.c_ubyte), _dp, _dp, _dp, C.c_int,
+                                                C.POINTER(LinearReport)]
         if hasattr(L, "eqf_merge_filters"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
             L.eqf_get_mixture_moments.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.POINTER(MixtureReport)]
             L.eqf_merge_filters.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, C.POINTER(MixtureReport)]
@@ -826,6 +832,80 @@ class FilterBatch:
             return None
         return dict(nis=np.array([s.nis for s in rep]), logdet_S=np.array([s.logdet_S for s in rep]), loglik=np.array([s.loglik for s in rep]),
                     dof=np.array([s.dof for s in rep], dtype=np.int32), info=np.array([s.info for s in rep], dtype=np.int32), used=used, gamma=G)
+
+    def observe_landmarks(self, kind, ids, meas, R, cam=None, gate=float("inf"), lm_gate=float("inf"), mask=None, consider=None, wait=True,
+                          want_rows=False, stride=None):
+        """update_landmarks with the rows formed ON THE DEVICE at each filter's own estimate (include/eqf_vio_amd.h:
+        eqf_observe_landmarks): no dump_state, no state_estimate, no rows in numpy.  kind: OBS_BEARING (2 rows; meas a bearing in the
+        measuring camera's frame), OBS_RANGE (1 row; meas the distance from that camera's centre) or OBS_POSITION (3 rows; meas a position
+        in that camera's frame).  ids, meas, R: lists with one item per filter -- ids (K_b,) strictly ascending, meas (K_b, 3) ((K_b,)
+        or (K_b, 1) for a range), R (K_b, rows, rows: lower triangles read), (rows, rows) or a scalar variance, broadcast to every entry;
+        a single-filter handle also takes the arrays themselves.  cam: None (the primary camera), (q_c, t_c) -- the measuring camera's
+        pose in the primary camera's frame, quaternion (w, x, y, z) -- for the call, or a list of B such pairs, one per filter.
+        gate, lm_gate, mask, consider, stride: as in update_landmarks.  consistency.observe_rows_host is the numpy statement of the rows.
+        With wait or want_rows the call waits for the device and returns update_landmarks' dict -- used has one more value, 3 not
+        observable -- and, with want_rows, Ht (B, stride, rows, 3) and resid (B, stride, rows) as the device formed them (zeros where an
+        entry is absent or not observable); otherwise it enqueues and returns None."""
+        B = self.B
+        kind = int(kind)
+        if kind not in OBS_ROWS:
+            raise ValueError("observe_landmarks: kind is OBS_BEARING, OBS_RANGE or OBS_POSITION")
+        rows = OBS_ROWS[kind]
+        if B == 1 and not (isinstance(ids, (list, tuple)) and len(ids) == 1 and np.ndim(ids[0]) == 1):
+            ids, meas, R = [ids], [meas], [R]
+        if not isinstance(R, (list, tuple)):
+            R = [R] * B
+        if not (len(ids) == len(meas) == len(R) == B):
+            raise ValueError("observe_landmarks: one item per filter")
+        idl = [np.asarray(x, dtype=np.int32).reshape(-1) for x in ids]
+        longest = max(1, max(len(i) for i in idl))
+        stride = longest if stride is None else int(stride)
+        if stride < longest:
+            raise ValueError("observe_landmarks: stride is shorter than the longest list")
+        nk = np.array([len(i) for i in idl], dtype=np.int32)
+        idm = np.zeros((B, stride), dtype=np.int32)
+        ms = np.zeros((B, stride, 3))
+        Rs = np.zeros((B, stride, rows, rows))
+        for b in range(B):
+            k = int(nk[b])
+            if k == 0:
+                continue
+            idm[b, :k] = idl[b]
+            m = np.asarray(meas[b], dtype=np.float64).reshape(k, -1)
+            ms[b, :k, :m.shape[1]] = m
+            Rb = np.asarray(R[b], dtype=np.float64)
+            Rs[b, :k] = np.broadcast_to(Rb * np.eye(rows) if Rb.ndim == 0 else Rb, (k, rows, rows))
+        camp, per = None, 0
+        if cam is not None:
+            per = int(not (len(cam) == 2 and np.ndim(cam[0][0]) == 0))  # (a pair's first item is q, its first item a number)
+            pairs = cam if per else [cam]
+            if per and len(pairs) != B:
+                raise ValueError("observe_landmarks: one camera offset, or one per filter")
+            camp = np.ascontiguousarray([np.concatenate([np.asarray(q, dtype=np.float64).reshape(4), np.asarray(t, dtype=np.float64).reshape(3)])
+                                         for q, t in pairs])
+        mk = None if mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mask), (B,)) != 0, dtype=np.uint8)
+        up = C.POINTER(C.c_ubyte)
+        out = bool(wait or want_rows)
+        ldg = 11 + 3 * max(self.num_landmarks(b) for b in range(B))
+        G = np.zeros((B, ldg)) if out else None
+        used = np.zeros((B, stride), dtype=np.uint8) if out else None
+        rep = (LinearReport * B)() if out else None
+        Ht = np.zeros((B, stride, rows, 3)) if want_rows else None
+        rs = np.zeros((B, stride, rows)) if want_rows else None
+        nc, cid, cstride = (None, None, 0) if consider is None else self._consider(consider, "observe_landmarks")
+        _check(lib().eqf_observe_landmarks(self._h, kind, None if camp is None else _p(camp), per, nk.ctypes.data_as(_ip), idm.ctypes.data_as(_ip),
+                                           stride, _p(ms), _p(Rs), float(gate), float(lm_gate), None if mk is None else mk.ctypes.data_as(up),
+                                           None if nc is None else nc.ctypes.data_as(_ip), None if cid is None else cid.ctypes.data_as(_ip),
+                                           cstride, None if used is None else used.ctypes.data_as(up), None if Ht is None else _p(Ht),
+                                           None if rs is None else _p(rs), None if G is None else _p(G), ldg if out else 0, rep),
+               "eqf_observe_landmarks")
+        if not out:
+            return None
+        res = dict(nis=np.array([s.nis for s in rep]), logdet_S=np.array([s.logdet_S for s in rep]), loglik=np.array([s.loglik for s in rep]),
+                   dof=np.array([s.dof for s in rep], dtype=np.int32), info=np.array([s.info for s in rep], dtype=np.int32), used=used, gamma=G)
+        if want_rows:
+            res.update(Ht=Ht, resid=rs)
+        return res
 
     @staticmethod
     def _members(idx, w):

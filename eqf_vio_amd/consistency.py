@@ -138,12 +138,17 @@ def local_jacobian_blocks(origin, group):
     eta0 = gravity_dir(origin["q"])
     etaHat = _quat_rotate(_quat_inverse(Aq), eta0)
     G = stereo_sphere_chart_diff(etaHat, etaHat) @ RAt @ stereo_sphere_chart_inv_diff_at_zero(eta0)
+    return dict(G=G, RAt=RAt, lm=landmark_jacobian_blocks(group))
+
+
+def landmark_jacobian_blocks(group):
+    """The landmark blocks of local_jacobian_blocks alone, (N, 3, 3): a_i^-1 R(q_i)^T.  They do not depend on the gravity chart."""
     Qq = np.asarray(group["Qq"], dtype=float).reshape(-1, 4)
     Qa = np.asarray(group["Qa"], dtype=float).reshape(-1)
     lm = np.zeros((len(Qa), 3, 3))
     for i in range(len(Qa)):
         lm[i] = quat_to_matrix(Qq[i]).T / Qa[i]
-    return dict(G=G, RAt=RAt, lm=lm)
+    return lm
 
 
 def jacobian_matrix(blocks):
@@ -444,6 +449,60 @@ def depth_rows(p_hat, rng):
 def position_rows(p_hat, p_meas):
     """A surveyed position of landmark p_hat in the camera frame (relocalisation).  Returns (H = I (3, 3), resid = p_meas - p_hat)."""
     return np.eye(3), np.asarray(p_meas, dtype=float) - np.asarray(p_hat, dtype=float)
+
+
+OBS_BEARING, OBS_RANGE, OBS_POSITION = 0, 1, 2
+OBS_ROWS = {OBS_BEARING: 2, OBS_RANGE: 1, OBS_POSITION: 3}
+
+
+def observe_rows_host(kind, state, ids, meas, cam=None):
+    """What FilterBatch.observe_landmarks forms for ONE filter, in numpy: the three row functions above at the estimate of a dump_state
+    dictionary `state`, followed by local_jacobian_blocks' landmark blocks
+    (landmark_jacobian_blocks: the gravity chart plays no part).  kind: OBS_BEARING / OBS_RANGE / OBS_POSITION; ids (K,) landmark ids; meas (K, 3):
+    a bearing y, (rho, -, -) or a position m in the measuring camera's frame; cam: None (the primary camera) or (q_c (w, x, y, z), t_c), the
+    measuring camera's pose in the primary camera's frame -- q_c is normalised.  Per entry whose id the state holds: p_hat = J_i p0_i,
+    p_c = R_c^T (p_hat - t_c), the kind's (H, resid) at p_c with H taken back to the primary frame by R_c^T, and Ht = H J_i.
+    Returns (Ht (K, rows, 3), resid (K, rows), used (K,)): used 1 formed, 0 id not in the state, 3 not observable (|p_c| zero or not
+    finite, a singular chart, a chart value that is not finite); rows of entries that are not formed are zeros."""
+    rows = OBS_ROWS[kind]
+    sid = [int(i) for i in state["ids"]]
+    ids = np.asarray(ids, dtype=int).reshape(-1)
+    meas = np.asarray(meas, dtype=float).reshape(len(ids), 3)
+    J = landmark_jacobian_blocks(state["group"])
+    p0 = np.asarray(state["origin"]["p"], dtype=float).reshape(-1, 3)
+    q_c, t_c = np.array([1.0, 0.0, 0.0, 0.0]), np.zeros(3)
+    if cam is not None:
+        q_c, t_c = np.asarray(cam[0], dtype=float), np.asarray(cam[1], dtype=float)
+        q_c = q_c / np.sqrt(float(q_c @ q_c))
+    Rc = quat_to_matrix(q_c)
+    Ht, resid, used = np.zeros((len(ids), rows, 3)), np.zeros((len(ids), rows)), np.zeros(len(ids), dtype=np.uint8)
+    for k, lid in enumerate(ids):
+        if int(lid) not in sid:
+            continue
+        i = sid.index(int(lid))
+        with np.errstate(all="ignore"):
+            p_hat = J[i] @ p0[i]
+            p_c = Rc.T @ (p_hat - t_c)
+            d = float(np.linalg.norm(p_c))
+        used[k] = 3
+        if not (d > 0.0 and np.isfinite(d)):
+            continue
+        if kind == OBS_BEARING:
+            try:
+                with np.errstate(all="ignore"):
+                    H, r = stereo_rows(p_hat, q_c, t_c, meas[k])
+            except ValueError:
+                continue
+            if not np.all(np.isfinite(r)):
+                continue
+        elif kind == OBS_RANGE:
+            H, r = depth_rows(p_c, meas[k, 0])
+            H = H @ Rc.T
+        else:
+            H, r = position_rows(p_c, meas[k])
+            H = H @ Rc.T
+        Ht[k], resid[k], used[k] = H @ J[i], r, 1
+    return Ht, resid, used
 
 
 # ---- explicit landmark edits (FilterBatch.edit_landmarks): the host statement of the edit and the usual priors

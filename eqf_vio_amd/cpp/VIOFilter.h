@@ -453,6 +453,21 @@ class VIOFilter {
             "eqf_update_landmarks_schmidt");
         return rep;
     }
+    // processLandmarkMeasurements with the rows formed on the device at the filter's own estimate (eqf_observe_landmarks): kind
+    // EQF_OBS_BEARING / _RANGE / _POSITION, meas [K][3] (a bearing, a range in meas[3 k], a position in the measuring camera's frame), R
+    // [K][rows][rows] (lower triangles), cam NULL (this camera) or [7] = (q_c: w, x, y, z; t_c), the measuring camera's pose in this
+    // camera's frame.  used [K]: 1 applied, 0 id not in the state, 2 gated, 3 not observable; Ht [K][rows][3] and resid [K][rows], where
+    // given, receive the rows the device formed.  The overload with considerIds is the Schmidt variant.
+    eqf_linear_report processLandmarkObservations(int kind, const int* ids, int K, const double* meas, const double* R, const double* cam = nullptr,
+        double gate = std::numeric_limits<double>::infinity(), double lm_gate = std::numeric_limits<double>::infinity(),
+        unsigned char* used = nullptr, double* Ht = nullptr, double* resid = nullptr) {
+        return observeLandmarks(kind, ids, K, meas, R, cam, nullptr, gate, lm_gate, used, Ht, resid);
+    }
+    eqf_linear_report processLandmarkObservations(int kind, const int* ids, int K, const double* meas, const double* R, const double* cam,
+        const std::vector<int>& considerIds, double gate = std::numeric_limits<double>::infinity(),
+        double lm_gate = std::numeric_limits<double>::infinity(), unsigned char* used = nullptr, double* Ht = nullptr, double* resid = nullptr) {
+        return observeLandmarks(kind, ids, K, meas, R, cam, &considerIds, gate, lm_gate, used, Ht, resid);
+    }
     // How processLinearMeasurement, processLandmarkMeasurements, perturbState (and eqf_apply_increment) turn their increment into a group
     // step (eqf_set_option "innovation_lift"): false (default) the plain lift, which leaves the whole correction to the body-frame landmarks;
     // true the filter's own useInnovationLift / useDiscreteInnovationLift, as a vision frame does -- a stereo, range or zero-velocity update
@@ -623,6 +638,17 @@ class VIOFilter {
     static void check(int rc, const char* what) {
         if (rc == EQF_ERR_NUMERIC) throw std::domain_error("The vectors cannot be exactly opposing.");  // SO3.cpp:160-161
         if (rc < 0) throw std::runtime_error(std::string(what) + " failed with status " + std::to_string(rc));
+    }
+    eqf_linear_report observeLandmarks(int kind, const int* ids, int K, const double* meas, const double* R, const double* cam,
+        const std::vector<int>* considerIds, double gate, double lm_gate, unsigned char* used, double* Ht, double* resid) {
+        eqf_linear_report rep;
+        const int zero = 0, nc = considerIds ? int(considerIds->size()) : 0;
+        std::vector<double> pad(9, 0.0);  // (stride is at least 1: K = 0 hands over one unread entry)
+        check(eqf_observe_landmarks(handle_.get(), kind, cam, 0, &K, K ? ids : &zero, K ? K : 1, K ? meas : pad.data(), K ? R : pad.data(), gate,
+                  lm_gate, nullptr, considerIds ? &nc : nullptr, considerIds ? considerIds->data() : nullptr, nc, K ? used : nullptr,
+                  K ? Ht : nullptr, K ? resid : nullptr, nullptr, 0, &rep),
+            "eqf_observe_landmarks");
+        return rep;
     }
     std::unique_ptr<eqf_filter, Deleter> handle_;
     std::vector<int> ids_;

@@ -87,66 +87,84 @@ EQF_DI FactorView factorView(const BlkArgs& a, int b) {
 // Sigma(r, c) by the lower triangle
 EQF_DI double blkSym(const double* S, int ld, int r, int c) { return r >= c ? S[(long long)r * ld + c] : S[(long long)c * ld + r]; }
 
-// grid = B, block = 256
-__global__ __launch_bounds__(256) void k_blk_rows(BlkArgs a) {
-    __shared__ int sInfo;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int N = a.g[b].N, n = kLm0 + 3 * N, rows = a.rows;
-    const double* jac = a.jac ? a.jac + b * jacStride(a.cap) : nullptr;
+// The three steps of a rows kernel (k_blk_rows here, k_obs_rows of eqf_observe.hpp), so that both leave the same workspace.
+// Thread 0 opens the filter's record with the verdict word `info` and zeroes the words of the later kernels.
+__device__ __forceinline__ void blkRowsOpen(const BlkArgs& a, int b, int info) {
     double* out = a.out + (long long)b * kLinHead;
-    int* used = blkUsed(a, b);
-    if (tid == 0) {
-        int info = 0;
-        if (!a.mask[b]) info = 3;
-        else if (jac && jac[13] != 0.0) info = -1;
-        out[0] = 0.0;
-        out[1] = 0.0;
-        out[2] = 0.0;
-        out[3] = (double)info;
-        blkCount(a, b)[0] = 0;
-        blkCount(a, b)[1] = 0;  // (the pivot word of k_factor_diag)
-        blkCount(a, b)[2] = 0;  // (the non-finite word of k_blk_gamma)
-        sInfo = info;
-    }
-    __syncthreads();
-    if (sInfo == 3) return;  // (the operands of a filter that is masked out are never read)
-    const int nkb = min(max(a.nk[b], 0), a.stride);
-    const double* S = a.Sigma + (long long)b * a.sigmaStride;
+    out[0] = 0.0;
+    out[1] = 0.0;
+    out[2] = 0.0;
+    out[3] = (double)info;
+    blkCount(a, b)[0] = 0;
+    blkCount(a, b)[1] = 0;  // (the pivot word of k_factor_diag)
+    blkCount(a, b)[2] = 0;  // (the non-finite word of k_blk_gamma)
+}
+// Entry k of filter b on landmark i (in the state) with rows H (times J unless it is nullptr) and residual resid: Ht into the workspace,
+// S_kk from Sigma_ii, d2_k; returns the verdict.  S: the filter's Sigma.
+__device__ __forceinline__ int blkRowsEntry(const BlkArgs& a, int b, int k, int i, const double* S, const double* H, const double* J,
+    const double* R, const double* resid) {
+    const int rows = a.rows;
+    double Ht[9], Sii[9], Skk[9];
+    blocks::formRows(rows, H, J, Ht);
+    const int l = kLm0 + 3 * i;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Sii[3 * r + c] = c <= r ? S[(long long)(l + r) * a.ld + l + c] : 0.0;
+    blocks::entryS(rows, Ht, Sii, R, Skk);
     double* HtAll = blkHt(a, b);
-    for (int k = tid; k < nkb; k += 256) {
-        const long long e = (long long)b * a.stride + k;
-        const int i = a.idx[e];
-        int verdict = blocks::kAbsent;
-        if (i >= 0 && i < N) {
-            double Ht[9], Sii[9], Skk[9];
-            blocks::formRows(rows, a.Hb + e * rows * 3, jac ? jac + kJacHead + 9LL * i : nullptr, Ht);
-            const int l = kLm0 + 3 * i;
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) Sii[3 * r + c] = c <= r ? S[(long long)(l + r) * a.ld + l + c] : 0.0;
-            blocks::entryS(rows, Ht, Sii, a.Rb + e * rows * rows, Skk);
-            verdict = blocks::entryVerdict(i, blocks::entryD2(rows, Skk, a.resid + e * rows), a.lmGate);
-            for (int q = 0; q < 9; ++q) HtAll[9LL * k + q] = q < 3 * rows ? Ht[q] : 0.0;
-        }
-        used[k] = verdict;
-    }
+    for (int q = 0; q < 9; ++q) HtAll[9LL * k + q] = q < 3 * rows ? Ht[q] : 0.0;
+    return blocks::entryVerdict(i, blocks::entryD2(rows, Skk, resid), a.lmGate);
+}
+// Behind the entries (the whole workgroup, used[] written): the compaction, and the residual of the entries that take part as the last
+// row of the tall matrix.  resid: [B][stride][rows].
+__device__ __forceinline__ void blkRowsClose(const BlkArgs& a, int b, int nkb, int n, int info, const double* resid) {
+    const int tid = threadIdx.x, rows = a.rows;
     __syncthreads();
     if (tid == 0) {
-        const int cnt = blocks::compact(nkb, used, blkPos(a, b), blkEnt(a, b));
+        const int cnt = blocks::compact(nkb, blkUsed(a, b), blkPos(a, b), blkEnt(a, b));
         blkCount(a, b)[0] = cnt;
-        if (cnt == 0 && sInfo == 0) out[3] = (double)blocks::kInfoIdle;
+        if (cnt == 0 && info == 0) a.out[(long long)b * kLinHead + 3] = (double)blocks::kInfoIdle;
     }
     __syncthreads();
-    // the residual of the entries that take part: the last row of the tall matrix
     const int* pos = blkPos(a, b);
     double* Mz = blkM(a, b) + (long long)(a.mp + n) * a.mp;
     for (int k = tid; k < nkb; k += 256) {
         const int p = pos[k];
         if (p < 0) continue;
         const long long e = (long long)b * a.stride + k;
-        for (int r = 0; r < rows; ++r) Mz[rows * p + r] = a.resid[e * rows + r];
+        for (int r = 0; r < rows; ++r) Mz[rows * p + r] = resid[e * rows + r];
     }
+}
+
+// grid = B, block = 256
+__global__ __launch_bounds__(256) void k_blk_rows(BlkArgs a) {
+    __shared__ int sInfo;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int N = a.g[b].N, n = kLm0 + 3 * N, rows = a.rows;
+    const double* jac = a.jac ? a.jac + b * jacStride(a.cap) : nullptr;
+    int* used = blkUsed(a, b);
+    if (tid == 0) {
+        int info = 0;
+        if (!a.mask[b]) info = 3;
+        else if (jac && jac[13] != 0.0) info = -1;
+        blkRowsOpen(a, b, info);
+        sInfo = info;
+    }
+    __syncthreads();
+    if (sInfo == 3) return;  // (the operands of a filter that is masked out are never read)
+    const int nkb = min(max(a.nk[b], 0), a.stride);
+    const double* S = a.Sigma + (long long)b * a.sigmaStride;
+    for (int k = tid; k < nkb; k += 256) {
+        const long long e = (long long)b * a.stride + k;
+        const int i = a.idx[e];
+        int verdict = blocks::kAbsent;
+        if (i >= 0 && i < N)
+            verdict = blkRowsEntry(a, b, k, i, S, a.Hb + e * rows * 3, jac ? jac + kJacHead + 9LL * i : nullptr, a.Rb + e * rows * rows,
+                a.resid + e * rows);
+        used[k] = verdict;
+    }
+    blkRowsClose(a, b, nkb, n, sInfo, a.resid);
 }
 
 // grid = (nIB + nPT^2, B) with nIB = 64-row tiles of the largest filter, nPT = blocks::pairTiles(stride); block = 256

@@ -47,6 +47,7 @@
 #include "eqf_border_host.hpp"
 #include "eqf_mapedit.hpp"
 #include "eqf_mapedit_host.hpp"
+#include "eqf_observe.hpp"
 #include "eqf_schmidt.hpp"
 #include "eqf_schmidt_host.hpp"
 #include "eqf_workspace.hpp"
@@ -121,12 +122,13 @@ struct LinRoute {
 };
 // the per-landmark block measurement update (eqf_blocks.hpp; eqf_update_landmarks), grown when a call's stride or rows ask for more: the
 // operands of a call as a staged image (blocks::SmallLayout), the workspace in doubles and in ints (blocks::WorkLayout; capacities in
-// bytes) and the records [B][kLinHead]
+// bytes), the records [B][kLinHead] and, from the first eqf_observe_landmarks, the rows that call forms (observe::RowsLayout; capacity in
+// bytes)
 struct BlkRoute {
     StagedImage<> small;
-    DevPtr<double> ws, out;
+    DevPtr<double> ws, out, obs;
     DevPtr<int> wi;
-    size_t wsCap = 0, wiCap = 0;
+    size_t wsCap = 0, wiCap = 0, obsCap = 0;
     bool ldsSet = false;
 };
 // the innovation lift of eqf_update_linear / eqf_update_landmarks / eqf_apply_increment / eqf_perturb_filters (eqf_lift.hpp;
@@ -3530,24 +3532,40 @@ int eqf_update_linear_schmidt(eqf_filter* f, int local, int m, const double* H, 
 static_assert(blocks::kRefBase == kBase && blocks::kPadBase == kLm0 && blocks::kTile == kSB && blocks::kHead == kLinHead,
     "eqf_blocks_host.hpp repeats the layout constants");
 namespace {
-// The buffers of eqf_update_landmarks for this call's shape; what is there and large enough is kept.
-int blkReserve(eqf_filter* f, const blocks::SmallLayout& sl, const blocks::WorkLayout& wl) {
-    const workspace::Want w[] = {WANT_STAGED(f->blk.small, sl.bytes()), want(f->blk.ws, sizeof(double) * size_t(wl.strideD()) * f->B, &f->blk.wsCap),
-        want(f->blk.wi, sizeof(int) * size_t(wl.strideI()) * f->B, &f->blk.wiCap), want(f->blk.out, sizeof(double) * size_t(kLinHead) * f->B)};
+// The buffers of eqf_update_landmarks for this call's shape; what is there and large enough is kept.  obsBytes: the rows array of
+// eqf_observe_landmarks (0: not this call's).
+int blkReserve(eqf_filter* f, size_t smallBytes, const blocks::WorkLayout& wl, size_t obsBytes) {
+    const workspace::Want w[] = {WANT_STAGED(f->blk.small, smallBytes), want(f->blk.ws, sizeof(double) * size_t(wl.strideD()) * f->B, &f->blk.wsCap),
+        want(f->blk.wi, sizeof(int) * size_t(wl.strideI()) * f->B, &f->blk.wiCap), want(f->blk.out, sizeof(double) * size_t(kLinHead) * f->B),
+        want(f->blk.obs, obsBytes, &f->blk.obsCap)};
     return reserveSlots(f, w);
 }
+// what eqf_observe_landmarks hands blkUpdate in place of rows
+struct ObsCall {
+    int kind;
+    const double* cam;
+    int camPerFilter;
+    const double* meas;
+    double* HtOut;
+    double* residOut;
+};
 
-// eqf_update_landmarks (sc == nullptr: the launches it has always enqueued) and eqf_update_landmarks_schmidt
+// eqf_update_landmarks (sc == nullptr: the launches it has always enqueued), eqf_update_landmarks_schmidt and, with oc,
+// eqf_observe_landmarks: local = 0, Hb and resid nullptr -- k_obs_rows forms the rows on the device in k_blk_rows's place
 int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb, const double* resid,
-    const double* Rb, double gate, double lm_gate, const unsigned char* mask, const SchCall* sc, unsigned char* used, double* gamma, int ldg,
-    eqf_linear_report* report) {
-    if (!f || !blocks::headArgsOk(local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate)) return EQF_ERR_INVALID;
+    const double* Rb, double gate, double lm_gate, const unsigned char* mask, const SchCall* sc, const ObsCall* oc, unsigned char* used,
+    double* gamma, int ldg, eqf_linear_report* report) {
+    if (!f) return EQF_ERR_INVALID;
+    if (oc ? !observe::headArgsOk(oc->kind, oc->camPerFilter, nk, ids, stride, oc->meas, Rb, gate, lm_gate)
+           : !blocks::headArgsOk(local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate))
+        return EQF_ERR_INVALID;
     if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
     GATE(f);  // (queued IMU calls and a pending gate first: the gate may still change the landmark lists)
     const int B = f->B;
     std::vector<int> N(B);
     for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
-    switch (blocks::argsCheck(rows, nk, ids, stride, Hb, resid, Rb, mask, gamma, ldg, B, N.data(), f->cap)) {
+    switch (oc ? observe::argsCheck(oc->kind, oc->cam, oc->camPerFilter, nk, ids, stride, oc->meas, Rb, mask, gamma, ldg, B, N.data(), f->cap)
+               : blocks::argsCheck(rows, nk, ids, stride, Hb, resid, Rb, mask, gamma, ldg, B, N.data(), f->cap)) {
         case 1: return EQF_ERR_INVALID;
         case 2: return EQF_ERR_UNSORTED;
         case 3: return EQF_ERR_CAPACITY;
@@ -3558,8 +3576,12 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
         if (bad) return bad;
     }
     const blocks::SmallLayout sl{B, stride, rows};
+    const observe::SmallLayout ol{B, stride, rows};
+    const observe::RowsLayout orl{B, stride, rows};
     const blocks::WorkLayout wl{f->ld, stride, rows, kDRec};
-    int rc = blkReserve(f, sl, wl);
+    const size_t smallBytes = oc ? ol.bytes() : sl.bytes(), offR = oc ? ol.offR() : sl.offR(), offIdx = oc ? ol.offIdx() : sl.offIdx(),
+                 offNk = oc ? ol.offNk() : sl.offNk(), offMask = oc ? ol.offMask() : sl.offMask();
+    int rc = blkReserve(f, smallBytes, wl, oc ? sizeof(double) * orl.doubles() : 0);
     if (!rc) rc = liftReserve(f, lift::callFactors(liftCallKind(f), maxN(f)));
     if (!rc && sc) rc = schReserve(f);
     if (rc) return rc;
@@ -3577,31 +3599,52 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
     HIPC(f->blk.small.wait());
     char* hs = f->blk.small.host;
     const size_t ne = sl.entries();
-    std::memcpy(hs + sl.offH(), Hb, sizeof(double) * ne * rows * 3);
-    std::memcpy(hs + sl.offResid(), resid, sizeof(double) * ne * rows);
-    std::memcpy(hs + sl.offR(), Rb, sizeof(double) * ne * rows * rows);
-    int* hIdx = reinterpret_cast<int*>(hs + sl.offIdx());
-    int* hNk = reinterpret_cast<int*>(hs + sl.offNk());
-    unsigned char* hm = reinterpret_cast<unsigned char*>(hs + sl.offMask());
+    if (oc) {
+        double* hCam = reinterpret_cast<double*>(hs + ol.offCam());
+        for (int b = 0; b < B; ++b) {
+            const bool read = oc->cam && (!oc->camPerFilter || !mask || mask[b]);  // (a masked filter's own offset is never read)
+            observe::unitCam(read ? oc->cam + (oc->camPerFilter ? size_t(b) * observe::kCam : 0) : nullptr, hCam + size_t(b) * observe::kCam);
+        }
+        std::memcpy(hs + ol.offMeas(), oc->meas, sizeof(double) * ne * 3);
+    } else {
+        std::memcpy(hs + sl.offH(), Hb, sizeof(double) * ne * rows * 3);
+        std::memcpy(hs + sl.offResid(), resid, sizeof(double) * ne * rows);
+    }
+    std::memcpy(hs + offR, Rb, sizeof(double) * ne * rows * rows);
+    int* hIdx = reinterpret_cast<int*>(hs + offIdx);
+    int* hNk = reinterpret_cast<int*>(hs + offNk);
+    unsigned char* hm = reinterpret_cast<unsigned char*>(hs + offMask);
     for (int b = 0; b < B; ++b) {
         hNk[b] = nk[b];
         hm[b] = mask ? (mask[b] ? 1 : 0) : 1;
         for (int k = 0; k < stride; ++k)
             hIdx[size_t(b) * stride + k] = (hm[b] && k < nk[b]) ? blocks::findId(f->ids[b].data(), N[b], ids[size_t(b) * stride + k]) : -1;
     }
-    HIPC(f->blk.small.upload(sl.bytes(), f->stream));
+    HIPC(f->blk.small.upload(smallBytes, f->stream));
     const int nMax = maxN(f), nt = blocks::rowTiles(nMax);
     const int nPT = blocks::pairTiles(stride);
     BlkArgs a{};
     a.g = f->g[f->pG]; a.Sigma = static_cast<double*>(f->Sigma[f->pS]); a.ld = f->ld; a.sigmaStride = f->sigmaStride;
-    a.Hb = reinterpret_cast<const double*>(f->blk.small.dev + sl.offH()); a.resid = reinterpret_cast<const double*>(f->blk.small.dev + sl.offResid());
-    a.Rb = reinterpret_cast<const double*>(f->blk.small.dev + sl.offR()); a.idx = reinterpret_cast<const int*>(f->blk.small.dev + sl.offIdx());
-    a.nk = reinterpret_cast<const int*>(f->blk.small.dev + sl.offNk()); a.mask = reinterpret_cast<const unsigned char*>(f->blk.small.dev + sl.offMask());
+    if (oc) {
+        a.Hb = f->blk.obs + orl.offHt(); a.resid = f->blk.obs + orl.offResid();
+    } else {
+        a.Hb = reinterpret_cast<const double*>(f->blk.small.dev + sl.offH()); a.resid = reinterpret_cast<const double*>(f->blk.small.dev + sl.offResid());
+    }
+    a.Rb = reinterpret_cast<const double*>(f->blk.small.dev + offR); a.idx = reinterpret_cast<const int*>(f->blk.small.dev + offIdx);
+    a.nk = reinterpret_cast<const int*>(f->blk.small.dev + offNk); a.mask = reinterpret_cast<const unsigned char*>(f->blk.small.dev + offMask);
     a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.rows = rows; a.stride = stride; a.mp = wl.mp(); a.nb = wl.nb();
     a.gate = gate; a.lmGate = lm_gate;
     a.ws = f->blk.ws; a.wsStride = wl.strideD(); a.offHt = wl.offHt(); a.offGamma = wl.offGamma(); a.offD = wl.offD();
     a.wi = f->blk.wi; a.wiStride = wl.strideI(); a.out = f->blk.out;
-    hipLaunchKernelGGL(k_blk_rows, dim3(B), dim3(256), 0, f->stream, a);
+    if (oc) {
+        ObsArgs o{};
+        o.a = a; o.kind = oc->kind; o.cam = reinterpret_cast<const double*>(f->blk.small.dev + ol.offCam());
+        o.meas = reinterpret_cast<const double*>(f->blk.small.dev + ol.offMeas()); o.p0 = f->p0; o.Q = f->Q[f->pG];
+        o.Ht = f->blk.obs + orl.offHt(); o.resid = f->blk.obs + orl.offResid();
+        hipLaunchKernelGGL(k_obs_rows, dim3(B), dim3(256), 0, f->stream, o);
+    } else {
+        hipLaunchKernelGGL(k_blk_rows, dim3(B), dim3(256), 0, f->stream, a);
+    }
     hipLaunchKernelGGL(k_blk_gain, dim3(nt + nPT * nPT, B), dim3(256), 0, f->stream, a, nt, nPT);
     rc = enqueueFactor(f->stream, f->blk.ldsSet, a, B, wl.mp(), blocks::rhsBlocks(blocks::paddedOrder(nMax)));
     if (rc) return rc;
@@ -3632,9 +3675,13 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
     hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, ia);
     HIPC(hipGetLastError());
     f->csValid = false;  // (C Sigma / S left by an earlier burst describe the old Sigma)
-    if (!used && !gamma && !report) return EQF_OK;
-    std::vector<double> hO(size_t(B) * kLinHead), hG;
+    if (!used && !gamma && !report && !(oc && (oc->HtOut || oc->residOut))) return EQF_OK;
+    std::vector<double> hO(size_t(B) * kLinHead), hG, hRows;
     std::vector<int> hU(size_t(B) * wl.strideI());
+    if (oc && (oc->HtOut || oc->residOut)) {
+        hRows.resize(orl.doubles());
+        HIPC(hipMemcpyAsync(hRows.data(), f->blk.obs, sizeof(double) * hRows.size(), hipMemcpyDeviceToHost, f->stream));
+    }
     HIPC(hipMemcpyAsync(hO.data(), f->blk.out, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
     HIPC(hipMemcpyAsync(hU.data(), f->blk.wi, sizeof(int) * hU.size(), hipMemcpyDeviceToHost, f->stream));
     if (gamma) {
@@ -3659,6 +3706,12 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
         if (used)
             for (int k = 0; k < stride; ++k) used[size_t(b) * stride + k] = (word != 3 && k < nk[b]) ? (unsigned char)u[wl.offUsed() + k] : 0;
         if (gamma) blocks::unpackGamma(hG.data() + size_t(b) * f->ld, N[b], gamma + size_t(b) * ldg, word != 0);
+        for (int k = 0; oc && k < stride; ++k) {  // (the kernel stores zeros for an entry that is absent or not observable)
+            const size_t e = size_t(b) * stride + k;
+            const bool formed = word != 3 && k < nk[b];
+            for (int q = 0; oc->HtOut && q < 3 * rows; ++q) oc->HtOut[e * rows * 3 + q] = formed ? hRows[orl.offHt() + e * rows * 3 + q] : 0.0;
+            for (int q = 0; oc->residOut && q < rows; ++q) oc->residOut[e * rows + q] = formed ? hRows[orl.offResid() + e * rows + q] : 0.0;
+        }
     }
     return EQF_OK;
 }
@@ -3667,13 +3720,25 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
 int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb, const double* resid,
     const double* Rb, double gate, double lm_gate, const unsigned char* mask, unsigned char* used, double* gamma, int ldg,
     eqf_linear_report* report) {
-    return blkUpdate(f, local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate, mask, nullptr, used, gamma, ldg, report);
+    return blkUpdate(f, local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate, mask, nullptr, nullptr, used, gamma, ldg, report);
 }
 int eqf_update_landmarks_schmidt(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb,
     const double* resid, const double* Rb, double gate, double lm_gate, const unsigned char* mask, const int* n_consider,
     const int* consider_ids, int cstride, unsigned char* used, double* gamma, int ldg, eqf_linear_report* report) {
     const SchCall sc{n_consider, consider_ids, cstride};
-    return blkUpdate(f, local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate, mask, &sc, used, gamma, ldg, report);
+    return blkUpdate(f, local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate, mask, &sc, nullptr, used, gamma, ldg, report);
+}
+// the rows formed on the device (eqf_observe.hpp; per-entry arithmetic, layouts and argument checks: eqf_observe_host.hpp)
+static_assert(observe::kBearing == EQF_OBS_BEARING && observe::kRange == EQF_OBS_RANGE && observe::kPosition == EQF_OBS_POSITION,
+    "eqf_observe_host.hpp repeats the kinds");
+int eqf_observe_landmarks(eqf_filter* f, int kind, const double* cam, int cam_per_filter, const int* nk, const int* ids, int stride,
+    const double* meas, const double* Rb, double gate, double lm_gate, const unsigned char* mask, const int* n_consider,
+    const int* consider_ids, int cstride, unsigned char* used, double* Ht_out, double* resid_out, double* gamma, int ldg,
+    eqf_linear_report* report) {
+    const ObsCall oc{kind, cam, cam_per_filter, meas, Ht_out, resid_out};
+    const SchCall sc{n_consider, consider_ids, cstride};
+    return blkUpdate(f, 0, observe::rowsOf(kind), nk, ids, stride, nullptr, nullptr, Rb, gate, lm_gate, mask, n_consider ? &sc : nullptr, &oc,
+        used, gamma, ldg, report);
 }
 
 static_assert(mixture::kRefBase == kBase && mixture::kPadBase == kLm0 && mixture::kRows == kMixRows && mixture::kLanes == kMixLanes &&

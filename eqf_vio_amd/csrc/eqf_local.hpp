@@ -21,6 +21,7 @@
 #pragma once
 #include "eqf_device.hpp"
 #include "eqf_math.hpp"
+#include "eqf_observe_host.hpp"
 
 namespace eqf {
 
@@ -114,13 +115,7 @@ __global__ __launch_bounds__(256) void k_local_jacobian(LocalArgs a) {
     }
     if (i < s.N) {
         const double* q = a.Q + (long long)b * 5 * cap;
-        const m33 R = q2m(quat{q[i], q[cap + i], q[2 * cap + i], q[3 * cap + i]});
-        const double ia = 1.0 / q[4 * cap + i];
-        double* o = jac + kJacHead + 9LL * i;
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[3 * r + c] = ia * R.a[3 * c + r];
+        observe::landmarkJ(quat{q[i], q[cap + i], q[2 * cap + i], q[3 * cap + i]}, q[4 * cap + i], jac + kJacHead + 9LL * i);
     }
 }
 

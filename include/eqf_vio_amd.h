@@ -547,6 +547,45 @@ int eqf_update_linear_schmidt(eqf_filter* f, int local, int m, const double* H, 
 int eqf_update_landmarks_schmidt(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb,
     const double* resid, const double* Rb, double gate, double lm_gate, const unsigned char* mask, const int* n_consider,
     const int* consider_ids, int cstride, unsigned char* used, double* gamma, int ldg, eqf_linear_report* report);
+/* eqf_update_landmarks with the rows FORMED ON THE DEVICE, at the handle's own estimate (csrc/eqf_observe.hpp): a second
+ * camera's bearings, a depth sensor's ranges or surveyed positions go in as they were measured, nothing of the state is read back, and a
+ * call with every output NULL enqueues and returns.  `kind` sets the rows and what meas[(b * stride + k) * 3 + ..] holds: */
+#define EQF_OBS_BEARING 0  /* 2 rows; meas = y, a bearing in the measuring camera's frame, taken as given (as eqf_process_vision's) */
+#define EQF_OBS_RANGE 1    /* 1 row;  meas[0] = rho, the distance from that camera's centre */
+#define EQF_OBS_POSITION 2 /* 3 rows; meas = m, a position in that camera's frame */
+/* cam = (q_c: w, x, y, z; t_c): the pose of the measuring camera in the primary camera's frame, the frame the landmarks live in; q_c is
+ * normalised by the library.  NULL: the identity (a bearing is then the primary camera's own); cam_per_filter = 0: one offset [7] for the
+ * call; cam_per_filter = 1: one per filter [batch][7], a bank of extrinsic hypotheses.  Per entry whose id the state holds, with i its
+ * landmark, J_i = a_i^-1 R(q_i)^T (eqf_get_local_jacobian's block), p_hat = J_i p0_i and R_c = R(q_c):
+ *   p_c = R_c^T (p_hat - t_c),  d = |p_c|,  y_hat = p_c / d
+ *   BEARING   H = stereoSphereChartDiff(y_hat, y_hat) (I - y_hat y_hat^T) R_c^T / d     resid = stereoSphereChart(y, pole y_hat)
+ *   RANGE     H = y_hat^T R_c^T                                                         resid = rho - d
+ *   POSITION  H = R_c^T                                                                 resid = m - p_c
+ *   Ht = H J_i, the rows in eqf_get_sigma's coordinates
+ * -- consistency.stereo_rows / depth_rows / position_rows at the device's estimate (consistency.observe_rows_host is the numpy
+ * statement).  From there on the call IS eqf_update_landmarks(local = 0) with (Ht, resid, Rb) at the same stride and rows, bit for bit
+ * and launch for launch (one rows kernel in the other's place): each entry's d2 and lm_gate, S, the factorisation, gamma, gate, mask, the
+ * report and its info codes, the option "innovation_lift", the in-place downdate and the group step; a non-NULL n_consider makes it
+ * eqf_update_landmarks_schmidt.  The gravity chart plays no part: info -1 never occurs.
+ * used has one more value, 3 NOT OBSERVABLE: d is zero or not finite, or, for a bearing, the chart is singular (y_hat at the chart's own
+ * pole e3, where the chart functions raise their flag, or y at the antipode of y_hat, where the chart's value is not finite).  Such an
+ * entry is a decoupled block that is never formed, like an absent or a gated one: the result is bit for bit the call's without it.
+ * Ht_out [batch][stride][rows][3] / resid_out [batch][stride][rows] return what the device formed -- every entry's Jacobian and
+ * innovation, for a tracker or a log; zeros for an entry that is absent or not observable, of a masked filter or beyond nk[b].
+ * With used, Ht_out, resid_out, gamma and report all NULL the call enqueues and returns; otherwise it synchronises and copies out.  The
+ * errors are eqf_update_landmarks's (and eqf_update_landmarks_schmidt's), before any effect; in addition EQF_ERR_INVALID for an unknown
+ * kind, a cam_per_filter that is not 0 or 1, a zero quaternion, or a value of cam or meas that is not finite where it is read (k < nk[b]
+ * of a filter that is not masked out; meas[1], meas[2] of a range are not read; the single offset of a call is always read).
+ * EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle.
+ * Not covered: the partitioned filter; an iterated (re-linearised) update; a camera offset carried in the state; a dry run that only
+ * predicts the rows. */
+int eqf_observe_landmarks(eqf_filter* f, int kind, const double* cam /* NULL | [7] | [batch][7] */, int cam_per_filter,
+    const int* nk /* [batch] */, const int* ids /* [batch][stride] */, int stride, const double* meas /* [batch][stride][3] */,
+    const double* Rb /* [batch][stride][rows][rows], lower triangles */, double gate, double lm_gate,
+    const unsigned char* mask /* [batch] or NULL */, const int* n_consider /* [batch] or NULL */,
+    const int* consider_ids /* [batch][cstride] */, int cstride, unsigned char* used /* [batch][stride] or NULL */,
+    double* Ht_out /* [batch][stride][rows][3] or NULL */, double* resid_out /* [batch][stride][rows] or NULL */,
+    double* gamma /* [batch][ldg] or NULL */, int ldg, eqf_linear_report* report /* [batch] or NULL */);
 
 /* Moment matching over the filters of ONE handle, on the device (csrc/eqf_mixture.hpp): a weighted batch -- a Monte-Carlo study, a particle
  * set, a bank of hypotheses -- turned back into one mean and one covariance that includes the spread between its members, and several
