@@ -96,6 +96,12 @@ class MixtureReport(C.Structure):
     _fields_ = [("n_eff", C.c_double), ("spread_trace", C.c_double), ("total_trace", C.c_double), ("n", C.c_int), ("info", C.c_int)]
 
 
+class SplitReport(C.Structure):
+    """eqf_split_report (include/eqf_vio_amd.h)."""
+
+    _fields_ = [("S", C.c_double), ("info", C.c_int)]
+
+
 class PairCost(C.Structure):
     """eqf_pair_cost (include/eqf_vio_amd.h)."""
 
@@ -134,7 +140,7 @@ EXPORTED_SYMBOLS = [
     "eqf_get_ids", "eqf_get_state_estimate", "eqf_get_origin", "eqf_get_group", "eqf_get_bias", "eqf_get_sigma",
     "eqf_get_sigma_local", "eqf_get_marginals", "eqf_get_local_jacobian", "eqf_forecast", "eqf_debug_sigma_local_all", "eqf_get_innovation_stats", "eqf_get_nees",
     "eqf_sample_sigma", "eqf_apply_increment", "eqf_perturb_filters", "eqf_update_linear", "eqf_update_landmarks",
-    "eqf_get_mixture_moments", "eqf_merge_filters", "eqf_debug_mixture_launches", "eqf_debug_sigma_pad",
+    "eqf_get_mixture_moments", "eqf_merge_filters", "eqf_split_filters", "eqf_debug_mixture_launches", "eqf_debug_sigma_pad",
     "eqf_get_merge_costs", "eqf_score_vision", "eqf_get_lift_report", "eqf_edit_landmarks",
     "eqf_update_linear_schmidt", "eqf_update_landmarks_schmidt", "eqf_observe_landmarks",
     "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
@@ -225,6 +231,8 @@ def lib():
             L.eqf_merge_filters.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, C.POINTER(MixtureReport)]
             L.eqf_debug_mixture_launches.argtypes = [vp]
             L.eqf_debug_sigma_pad.argtypes = [vp, C.c_int, C.c_int, _dp]
+        if hasattr(L, "eqf_split_filters"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
+            L.eqf_split_filters.argtypes = [vp, C.c_int, _dp, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, C.c_int, C.POINTER(SplitReport)]
         if hasattr(L, "eqf_get_merge_costs"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
             L.eqf_get_merge_costs.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.POINTER(PairCost),
                                               C.POINTER(SigmaStats)]
@@ -941,6 +949,54 @@ class FilterBatch:
         _check(lib().eqf_merge_filters(self._h, len(ii), ii.ctypes.data_as(_ip), _p(ww), int(ref), int(dst), C.byref(rep) if report else None),
                "eqf_merge_filters")
         return self._mixture_report(rep) if report else None
+
+    def split_filters(self, a, dst_idx, src_idx, shift, shrink, local=True, want_gamma=False, report=True):
+        """The deterministic split on the device (include/eqf_vio_amd.h: eqf_split_filters; consistency.split_host is its numpy statement):
+        child k makes filter dst_idx[k] what copy_filters(src_idx[k] -> dst_idx[k]) leaves, with Sigma - shrink[k] u u^T and the state
+        moved by shift[k] u, u = Sigma Ht^T / sqrt(Ht Sigma Ht^T) of the source.  a: array (B, >= n_max), row b the functional of filter b
+        (rows of filters that are no child's source are not read), or a list of per-filter rows (None for the others); local: the rows are
+        written against sigma_local()'s error around the estimate (a J is formed on the device), else against sigma()'s.  dst == src is the
+        child that stays in place; a filter named as a dst may be a source only of itself.  consistency.split_components gives
+        moment-matched (weights, shift, shrink).  Returns None (want_gamma and report both false: enqueues and returns, unless a dst's
+        ids, clock or flags change) or a dict with S (n,), info (n,) per child -- info != 0: nothing of that source's children was written --
+        and, with want_gamma, gamma (n, n_max), child k's increment in the reference index map."""
+        B = self.B
+        di = np.ascontiguousarray(np.atleast_1d(dst_idx), dtype=np.int32)
+        si = np.ascontiguousarray(np.atleast_1d(src_idx), dtype=np.int32)
+        n = int(di.size)
+        if si.size != n:
+            raise ValueError("split_filters: dst_idx and src_idx differ in length")
+        sh = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, dtype=np.float64), (n,)))
+        sk = np.ascontiguousarray(np.broadcast_to(np.asarray(shrink, dtype=np.float64), (n,)))
+        if n == 0:  # (an empty numpy array may have no address: the C ABI wants its arrays also for n = 0)
+            di = si = np.zeros(1, dtype=np.int32)
+            sh = sk = np.zeros(1)
+        nmax = 11 + 3 * max([self.num_landmarks(b) for b in range(B)] + [0])
+        if isinstance(a, np.ndarray) and a.ndim == 2:
+            A = np.ascontiguousarray(a, dtype=np.float64)
+            if A.shape[0] != B:
+                raise ValueError("split_filters: one row per filter of the handle")
+        else:
+            A = np.zeros((B, nmax))
+            for b, row in enumerate(a):
+                if row is not None:
+                    r = np.asarray(row, dtype=np.float64).ravel()
+                    if r.size > nmax:
+                        raise ValueError("split_filters: a row longer than the largest filter's order")
+                    A[b, :r.size] = r
+        G = np.zeros((n, nmax)) if want_gamma else None
+        rep = (SplitReport * max(n, 1))() if report else None
+        _check(lib().eqf_split_filters(self._h, int(bool(local)), _p(A), int(A.shape[1]), n, di.ctypes.data_as(_ip), si.ctypes.data_as(_ip),
+                                       _p(sh), _p(sk), None if G is None else _p(G), nmax, rep), "eqf_split_filters")
+        if not want_gamma and not report:
+            return None
+        out = {}
+        if report:
+            out["S"] = np.array([rep[k].S for k in range(n)])
+            out["info"] = np.array([rep[k].info for k in range(n)], dtype=np.int32)
+        if want_gamma:
+            out["gamma"] = G
+        return out
 
     def merge_costs(self, idx, w, ref=None, kind="runnalls", first=0, pairs=None):
         """Pairwise merge costs of the weighted members idx of this handle, on the device (include/eqf_vio_amd.h: eqf_get_merge_costs;

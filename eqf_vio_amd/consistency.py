@@ -424,6 +424,65 @@ def schmidt_update_host(Sigma, Ht, R, resid, consider_idx):
     return dict(gamma=gamma, Sigma=Sp, nis=r["nis"], logdet_S=r["logdet_S"], loglik=r["loglik"], dof=r["dof"])
 
 
+# ---- the deterministic split (FilterBatch.split_filters; include/eqf_vio_amd.h: eqf_split_filters)
+def split_host(Sigma, Ht, shift, shrink):
+    """The numpy statement of FilterBatch.split_filters' arithmetic for one source: Ht (n,) already in Sigma's coordinates (for a local row
+    pass a @ jacobian_matrix(blocks)), shift and shrink (K,).
+        B = Sigma Ht^T, S = Ht B, u = B / sqrt(S);   Sigma_k = Sigma - shrink_k u u^T,   gamma_k = shift_k u.
+    Returns dict(S, u, Sigma (K, n, n), gamma (K, n)).  Raises numpy.linalg.LinAlgError if S is not positive."""
+    Sg = np.asarray(Sigma, dtype=float)
+    h = np.asarray(Ht, dtype=float).reshape(-1)
+    sh = np.atleast_1d(np.asarray(shift, dtype=float))
+    sk = np.atleast_1d(np.asarray(shrink, dtype=float))
+    B = Sg @ h
+    S = float(h @ B)
+    if not (S > 0.0 and np.isfinite(S)):
+        raise np.linalg.LinAlgError("split_host: the functional's variance is not positive")
+    u = B / np.sqrt(S)
+    uu = np.outer(u, u)
+    return dict(S=S, u=u, Sigma=np.stack([Sg - k * uu for k in sk]), gamma=np.stack([s * u for s in sh]))
+
+
+def split_components(K, spread, outer_weight=None):
+    """Moment-matched components of a split along one functional: (weights, shift, shrink), each (K,), with sum w = 1, sum w shift = 0 and
+    sum w (shift^2 - shrink) = 0, so that the children of FilterBatch.split_filters carry the parent's first two moments.  spread: the
+    outer components sit at -+spread standard deviations of the functional.
+        K = 2: weights (1/2, 1/2), shift (-spread, spread), shrink spread^2.
+        K = 3: weights (q, 1 - 2 q, q) with q = outer_weight (default 1/4), shift (-spread, 0, spread), common shrink 2 q spread^2.
+    Parameters that would give a shrink outside [0, 1] (or a weight outside (0, 1)) are refused."""
+    s = float(spread)
+    if not np.isfinite(s) or s < 0.0:
+        raise ValueError("split_components: spread must be finite and >= 0")
+    if int(K) == 2:
+        if outer_weight is not None and float(outer_weight) != 0.5:
+            raise ValueError("split_components: two components weigh 1/2 each")
+        w, shift, k = np.array([0.5, 0.5]), np.array([-s, s]), s * s
+    elif int(K) == 3:
+        q = 0.25 if outer_weight is None else float(outer_weight)
+        if not 0.0 < q < 0.5:
+            raise ValueError("split_components: outer_weight must lie in (0, 1/2)")
+        w, shift, k = np.array([q, 1.0 - 2.0 * q, q]), np.array([-s, 0.0, s]), 2.0 * q * s * s
+    else:
+        raise ValueError("split_components: K is 2 or 3")
+    if not 0.0 <= k <= 1.0:
+        raise ValueError("split_components: these parameters give a shrink outside [0, 1]")
+    return w, shift, np.full(len(w), k)
+
+
+def depth_axis_row(p_hat, i, n):
+    """(n,) the LOCAL row (sigma_local()'s coordinates, split_filters(local=True)) that measures landmark i's camera-frame position along
+    its own bearing p_hat / |p_hat|: the depth of the landmark.  n = 11 + 3 N.  The depth-hypothesis split: K children along this row,
+    weighted afterwards by score_vision or an innovation log-likelihood and reduced with reduce_mixture."""
+    p = np.asarray(p_hat, dtype=float).reshape(3)
+    d = float(np.linalg.norm(p))
+    n, i = int(n), int(i)
+    if i < 0 or 11 + 3 * i + 3 > n or not d > 0.0:
+        raise ValueError("depth_axis_row: no such landmark")
+    row = np.zeros(n)
+    row[11 + 3 * i:14 + 3 * i] = p / d
+    return row
+
+
 # ---- per-landmark blocks for FilterBatch.update_landmarks(local=True): entry k measures landmark i_k alone, resid_k = H_k eps_i + noise with
 # eps_i = p_true - p_hat, the plain difference of camera-frame positions (the landmark block of the estimate's chart)
 def stereo_rows(p_hat, q_21, t_21, y2):

@@ -50,6 +50,8 @@
 #include "eqf_observe.hpp"
 #include "eqf_schmidt.hpp"
 #include "eqf_schmidt_host.hpp"
+#include "eqf_split.hpp"
+#include "eqf_split_host.hpp"
 #include "eqf_workspace.hpp"
 
 using namespace eqf;
@@ -193,6 +195,12 @@ struct MapEditRoute {
 struct SchmidtRoute {
     StagedImage<true> img;
     bool ldsSet = false;
+};
+// eqf_split_filters (eqf_split.hpp): the plan's image (split::Image: rows, shifts, shrinks, the source, child and pair tables) as a
+// staged image, and the workspace (split::Work: Ht, B, u, the increments, the verdict records and the increment step's mask)
+struct SplitRoute {
+    StagedImage<> img;
+    DevPtr<char> ws;
 };
 
 struct eqf_filter {
@@ -382,6 +390,7 @@ struct eqf_filter {
     ScoreRoute sc;
     MapEditRoute medit;
     SchmidtRoute sch;
+    SplitRoute split;
 
     ~eqf_filter() {
         for (auto e : evPool) (void)hipEventDestroy(e);
@@ -3916,6 +3925,111 @@ int eqf_merge_filters(eqf_filter* f, int n, const int* idx, const double* w, int
         f->csValid = false;
         f->permOnDevice.clear();
         f->editOnDevice.clear();
+    }
+    return EQF_OK;
+}
+
+// ---- splitting filters into mixture components (eqf_split.hpp; the host's decisions: eqf_split_host.hpp)
+static_assert(split::kRefBase == kBase && split::kPadBase == kLm0 && split::kOk == EQF_OK && split::kInvalid == EQF_ERR_INVALID &&
+                  sizeof(split::Source) == sizeof(SplitSource) && sizeof(split::Child) == sizeof(SplitChild) &&
+                  sizeof(split::Pair) == sizeof(ClonePair) && offsetof(split::Pair, N) == offsetof(ClonePair, N) &&
+                  split::kAxisRows == kSplitAxisRows && split::kTileRows == kSplitTileRows && split::kTileCols == kSplitTileCols,
+    "eqf_split_host.hpp repeats the layout constants, the tables and the error codes");
+
+int eqf_split_filters(eqf_filter* f, int local, const double* a, int lda, int n, const int* dst_idx, const int* src_idx, const double* shift,
+    const double* shrink, double* gamma, int ldg, eqf_split_report* report) {
+    if (!f) return EQF_ERR_INVALID;
+    int rc = split::headCheck(f->B, local, a, n, dst_idx, src_idx, shift, shrink);
+    if (rc) return rc;
+    if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
+    if (n == 0) return EQF_OK;
+    GATE(f);  // (queued IMU calls and a pending gate first: the gate may still change the landmark counts)
+    const int B = f->B;
+    std::vector<int> N(B);
+    for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
+    rc = split::rowCheck(a, lda, n, src_idx, gamma ? ldg : -1, N.data());
+    if (rc) return rc;
+    split::Plan pl;
+    split::group(B, n, dst_idx, src_idx, N.data(), pl);
+    const split::Image im{size_t(B), size_t(f->cap)};
+    const split::Work wk{size_t(B), size_t(f->ld)};
+    {
+        const workspace::Want w[] = {WANT_STAGED(f->split.img, im.bytes()), want(f->split.ws, wk.bytes())};
+        rc = reserveSlots(f, w);
+        if (rc) return rc;
+    }
+    if (local) {
+        rc = launchLocal(f, 0, B, false);  // (only writes the J records)
+        if (rc) return rc;
+    }
+    HIPC(f->split.img.wait());
+    split::fillImage(im, pl, a, lda, shift, shrink, f->split.img.host);
+    HIPC(f->split.img.upload(im.bytes(), f->stream));
+    const int ns = int(pl.sources.size()), np = int(pl.pairs.size());
+    char* di = f->split.img.dev;
+    double* ws = reinterpret_cast<double*>(f->split.ws.get());
+    SplitArgs sa{};
+    sa.Sigma = static_cast<const double*>(f->Sigma[f->pS]); sa.SigmaW = static_cast<double*>(f->Sigma[f->pS]); sa.ld = f->ld;
+    sa.sigmaStride = f->sigmaStride;
+    sa.rows = reinterpret_cast<const double*>(di + im.offRows()); sa.ldr = int(im.ldr());
+    sa.shift = reinterpret_cast<const double*>(di + im.offShift()); sa.shrink = reinterpret_cast<const double*>(di + im.offShrink());
+    sa.sources = reinterpret_cast<const SplitSource*>(di + im.offSources()); sa.ns = ns;
+    sa.children = reinterpret_cast<const SplitChild*>(di + im.offChildren());
+    sa.pairs = reinterpret_cast<ClonePair*>(di + im.offPairs());
+    sa.jac = local ? f->dJac.get() : nullptr; sa.cap = f->cap;
+    sa.Ht = ws + wk.offHt(); sa.Bv = ws + wk.offB(); sa.U = ws + wk.offU(); sa.G = ws + wk.offG(); sa.rec = ws + wk.offRec();
+    sa.mask = reinterpret_cast<unsigned char*>(ws + wk.offMask());
+    hipStream_t st = f->stream;
+    HIPC(hipMemsetAsync(sa.mask, 0, size_t(B), st));  // (filters that are no child's dst are not moved)
+    hipLaunchKernelGGL(k_split_row, dim3(ns), dim3(256), 0, st, sa);
+    hipLaunchKernelGGL(k_split_axis, dim3(split::axisBlocks(pl.maxN), ns), dim3(256), 0, st, sa);
+    hipLaunchKernelGGL(k_split_verdict, dim3(ns), dim3(256), 0, st, sa);
+    hipLaunchKernelGGL(k_split_sigma, dim3(split::tileColBlocks(pl.maxN), split::tileRowBlocks(pl.maxN), std::min(ns, 65535)), dim3(256), 0, st, sa);
+    // everything that is not Sigma: the clone route's kernels over the pairs the verdicts have left, then the plain group step
+    if (np > 0) {
+        CloneSmallArgs ma{};
+        ma.src = cloneSide(f); ma.dst = cloneSide(f); ma.restore = 1;
+        ma.pairs = sa.pairs; ma.nPairs = np;
+        hipLaunchKernelGGL(k_clone_small, dim3(std::max(1, (f->cap + 255) / 256), std::min(np, 65535)), dim3(256), 0, st, ma);
+        hipLaunchKernelGGL(k_clone_restore, dim3(std::max(1, (pl.maxN + 127) / 128), std::min(np, 65535)), dim3(128), 0, st, f->g[f->pG].get(),
+            f->p0.get(), f->lmc.get(), f->cap, f->errflag.get(), sa.pairs, np);
+    }
+    IncArgs ia{};
+    ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = sa.G; ia.strideG = f->ld; ia.off = 0; ia.mask = sa.mask;
+    hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, st, ia);  // (always the plain lift: ia.lift stays NULL)
+    HIPC(hipGetLastError());
+    f->csValid = false;  // (the caches that describe the device's Sigma and landmark sets start over, as behind eqf_copy_filters)
+    f->permOnDevice.clear();
+    f->editOnDevice.clear();
+    // The host's bookkeeping of a dst follows eqf_copy_filters(src -> dst) -- if the device wrote.  Where no dst's bookkeeping would change
+    // (eqf_merge_filters' rule) the verdicts are not waited for.
+    bool same = true;
+    for (const auto& c : pl.children) {
+        const int d = c.dst, s = pl.sources[c.source].src;
+        if (d != s && !(f->ids[d] == f->ids[s] && f->curTime[d] == f->curTime[s] && f->init[d] == f->init[s] && f->devInit[d] == f->devInit[s] &&
+                          f->report[d].ids.empty()))
+            same = false;
+    }
+    if (!gamma && !report && same) return EQF_OK;
+    std::vector<double> hRec(size_t(2) * ns), hG;
+    HIPC(hipMemcpyAsync(hRec.data(), sa.rec, sizeof(double) * hRec.size(), hipMemcpyDeviceToHost, st));
+    if (gamma) {
+        hG.resize(size_t(B) * f->ld);
+        HIPC(hipMemcpyAsync(hG.data(), sa.G, sizeof(double) * hG.size(), hipMemcpyDeviceToHost, st));
+    }
+    HIPC(hipStreamSynchronize(st));
+    // (read first: the mirrors of the sources are not among the destinations that change, by the dst/src rule)
+    for (const auto& c : pl.children) {
+        const int d = c.dst, s = pl.sources[c.source].src, info = int(hRec[size_t(2) * c.source + 1]);
+        if (report) {
+            report[c.call].S = hRec[size_t(2) * c.source];
+            report[c.call].info = info;
+        }
+        if (gamma) linear::unpackGamma(hG.data() + size_t(d) * f->ld, N[s], gamma + size_t(c.call) * ldg, info != 0);
+        if (info == 0 && d != s) {
+            f->ids[d] = f->ids[s]; f->curTime[d] = f->curTime[s]; f->init[d] = f->init[s]; f->devInit[d] = f->devInit[s];
+            f->report[d] = {};  // (the gate and its threshold are settings: they stay)
+        }
     }
     return EQF_OK;
 }

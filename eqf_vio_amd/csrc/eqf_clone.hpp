@@ -29,7 +29,8 @@ namespace eqf {
 constexpr int kCloneRows = 8;  // rows per workgroup = 16-byte loads in flight per lane
 
 struct ClonePair {
-    int dst, src;
+    int dst, src;   // dst < 0: a pair the device has withdrawn (a split whose source failed); k_clone_small and k_clone_restore pass over it.
+                    // k_clone_sigma does NOT: it is never handed such a table (eqf_split.hpp moves Sigma itself)
     int N;          // landmarks of the source filter: the extent moved is kLm0 + 3 N
     int fromStage;  // read the staging image instead of the source handle
 };
@@ -111,6 +112,7 @@ __global__ __launch_bounds__(256) void k_clone_small(CloneSmallArgs a) {
     const int cd = a.dst.cap;
     for (int k = blockIdx.y; k < a.nPairs; k += gridDim.y) {
         const ClonePair p = a.pairs[k];
+        if (p.dst < 0) continue;  // (withdrawn on the device: eqf_split.hpp)
         const bool st = p.fromStage != 0;
         const CloneSide* sd = st ? &a.stage : &a.src;  // (uniform: scalar loads from the kernel arguments)
         const int N = p.N, cs = sd->cap;
@@ -162,6 +164,7 @@ __global__ __launch_bounds__(128) void k_clone_restore(Glob* g, const double* p0
     const int tid = blockIdx.x * 128 + threadIdx.x;
     for (int k = blockIdx.y; k < nPairs; k += gridDim.y) {
         const int b = pairs[k].dst, N = pairs[k].N;
+        if (b < 0) continue;
         Glob& s = g[b];
         int bad = 0;
         for (int i = tid; i < N; i += gridDim.x * 128) {

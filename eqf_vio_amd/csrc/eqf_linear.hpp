@@ -58,6 +58,36 @@ EQF_DI double* linBt(const LinArgs& a, int b) { return a.ws + b * a.wsStride + (
 EQF_DI double* linY(const LinArgs& a, int b) { return a.ws + b * a.wsStride + 2LL * kLinRows * a.ld; }
 EQF_DI double* linGamma(const LinArgs& a, int b) { return a.ws + b * a.wsStride + 3LL * kLinRows * a.ld; }
 
+// One row's base block: h (reference map, 11 entries) -> o (padded map, 12 entries, the pad 0), times J's base blocks (G at jac, R_A^T at
+// jac + 4) from the right when jac is given.  Shared with eqf_split.hpp's k_split_row.
+EQF_DI void linRowBase(const double* h, const double* jac, double* o) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) o[c] = h[c];
+    if (jac) {
+        const double* G = jac;
+        const double* RAt = jac + 4;
+        o[6] = fma(h[7], G[2], h[6] * G[0]);
+        o[7] = fma(h[7], G[3], h[6] * G[1]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[8 + c] = dot3(h[8], RAt[c], h[9], RAt[3 + c], h[10], RAt[6 + c]);
+    } else {
+#pragma unroll
+        for (int c = 6; c < kBase; ++c) o[c] = h[c];
+    }
+    o[kBase] = 0.0;
+}
+// ... and landmark i's block: hh = h + kBase + 3 i -> oo = o + kLm0 + 3 i, times J_i (jac + kJacHead + 9 i) when jac is given
+EQF_DI void linRowLandmark(const double* hh, const double* jac, int i, double* oo) {
+    if (jac) {
+        const double* J = jac + kJacHead + 9LL * i;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) oo[c] = dot3(hh[0], J[c], hh[1], J[3 + c], hh[2], J[6 + c]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) oo[c] = hh[c];
+    }
+}
+
 // grid = B, block = 256
 __global__ __launch_bounds__(256) void k_lin_rows(LinArgs a) {
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -81,32 +111,10 @@ __global__ __launch_bounds__(256) void k_lin_rows(LinArgs a) {
         const double* h = H + (long long)k * a.ldr;
         double* o = Ht + (long long)k * ld;
         if (blk == 0) {
-#pragma unroll
-            for (int c = 0; c < 6; ++c) o[c] = h[c];
-            if (jac) {
-                const double* G = jac;
-                const double* RAt = jac + 4;
-                o[6] = fma(h[7], G[2], h[6] * G[0]);
-                o[7] = fma(h[7], G[3], h[6] * G[1]);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) o[8 + c] = dot3(h[8], RAt[c], h[9], RAt[3 + c], h[10], RAt[6 + c]);
-            } else {
-#pragma unroll
-                for (int c = 6; c < kBase; ++c) o[c] = h[c];
-            }
-            o[kBase] = 0.0;
+            linRowBase(h, jac, o);
         } else {
             const int i = blk - 1;
-            const double* hh = h + kBase + 3 * i;
-            double* oo = o + kLm0 + 3 * i;
-            if (jac) {
-                const double* J = jac + kJacHead + 9LL * i;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) oo[c] = dot3(hh[0], J[c], hh[1], J[3 + c], hh[2], J[6 + c]);
-            } else {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) oo[c] = hh[c];
-            }
+            linRowLandmark(h + kBase + 3 * i, jac, i, o + kLm0 + 3 * i);
         }
     }
 }

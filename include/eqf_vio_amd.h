@@ -632,6 +632,52 @@ int eqf_get_mixture_moments(eqf_filter* f, int n, const int* idx, const double* 
     double* mean /* [11 + 3 N] or NULL */, double* P, int ld, eqf_mixture_report* report /* or NULL */);
 int eqf_merge_filters(eqf_filter* f, int n, const int* idx, const double* w, int ref, int dst, eqf_mixture_report* report /* or NULL */);
 
+/* The deterministic split: filters become mixture components placed along one functional, on the device (csrc/eqf_split.hpp; the host's
+ * decisions: csrc/eqf_split_host.hpp).  Everything is fp64 in the origin chart and the reference index map -- the coordinates of
+ * eqf_get_sigma and eqf_apply_increment.  Per source filter s (order 11 + 3 N_s, covariance Sigma) with its row a + s * lda:
+ *   Ht = a (local = 0) or a J_s (local = 1: the row is written against eqf_get_sigma_local's error around the estimate; a J is formed on
+ *   the device by the code that forms H J for eqf_update_linear(local = 1));  B = Sigma Ht^T,  S = Ht B (the variance of the functional),
+ *   u = B / sqrt(S), so that u u^T <= Sigma and Ht u = sqrt(S).
+ * Child k is the record (dst_idx[k], src_idx[k], shift[k], shrink[k]).  Afterwards filter dst is what eqf_copy_filters(src -> dst) would
+ * leave, except that Sigma_dst = Sigma_src - shrink u u^T (product u_i u_j first, then one fused multiply-add: bit-for-bit symmetric when
+ * Sigma_src was) and that the state is moved by gamma = shift u with eqf_apply_increment's step, bias += gamma[0:6],
+ * X <- VIOExp(liftInnovation(gamma[6:], xi0)) X -- ALWAYS the plain lift, whatever the option "innovation_lift" says: the moment identity
+ * below holds in this chart for the plain step only.  The functional moves by shift sqrt(S) and keeps the variance (1 - shrink) S;
+ * shrink = 1 leaves Sigma singular along u.  With weights w~_k of the caller's (the handle holds none, as for eqf_merge_filters),
+ * sum w~_k = 1, sum w~_k shift_k = 0 and sum w~_k (shift_k^2 - shrink_k) = 0, the children of a source satisfy
+ * sum_k w~_k (Sigma_k + gamma_k gamma_k^T) = Sigma exactly (consistency.split_components gives such triples).
+ * Gather semantics, eqf_copy_filters': every source is read as it was before the call; src_idx may repeat (fan-out), dst_idx may not;
+ * dst == src is the child that stays in the parent's slot, written in place.  A filter named as a dst may be a source only of ITSELF --
+ * one that a child of another source overwrites may be nobody's source: no swaps, no permutations through other sources (EQF_ERR_INVALID) --,
+ * so that one pass reads a tile of a source once and writes all its children without staging.  Rows of a that
+ * belong to no child's source are never read.  Filters that are not named keep every bit.
+ * The verdict is per SOURCE and decided on the device: info 0 done; 1 S is not positive or a value is not finite; -1 local = 1 and the
+ * source's gravity chart is singular.  A source with info != 0 writes none of its children -- every such dst keeps every bit, the one in
+ * place included --, their gamma rows are 0 and their S is NaN; the call returns EQF_OK and eqf_device_error is never touched.
+ * Exactness: a child with shrink == 0 has the source's Sigma bit for bit (signs of zeros included), a child with shift == 0 the source's
+ * state bit for bit, with both it is eqf_copy_filters' result; a child with shift != 0 has the state eqf_apply_increment (option
+ * "innovation_lift" off) leaves on a fork when given the returned gamma row.  gamma (or NULL): row k, leading dimension ldg, is child k's
+ * increment; report (or NULL): entry k is child k's source's verdict.
+ * Settles what the handle has deferred, then enqueues a fixed number of launches whatever n and the fan-out are; with gamma == NULL and
+ * report == NULL it returns without waiting -- unless a dst's host bookkeeping (ids, clock, flags, gate report) differs from what the copy
+ * leaves, where the verdicts are waited for so that it changes only if the device wrote (eqf_merge_filters' rule).  Bit for bit the same
+ * from run to run and for a filter alone in a handle or anywhere in a batch (no atomics, one fixed summation order).
+ * n = 0 does nothing at all (nothing is settled either).  Before any effect other than settling what was deferred (the checks that need
+ * the landmark counts come behind it, as in the sibling calls): EQF_ERR_INVALID for a NULL f, or with n > 0 a NULL a, index array, shift or shrink; n < 0 (n = 0 is EQF_OK); local not
+ * 0 or 1; an index out of range; a dst named twice; a dst with another source that is itself some child's source; lda -- or ldg with gamma given -- smaller than
+ * 11 + 3 N of a named source; a shift that is not finite; a shrink that is not finite or outside [0, 1]; an entry of the read part of a
+ * named source's row that is not finite.  EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle.  EQF_ERR_HIP if the workspace, allocated on
+ * first need from capacity and batch, cannot be had (the handle stays as it was).
+ * Not covered: the partitioned filter (eqf_tf_*, eqf_tiled_*), fp32 handles, sources and destinations in different handles, the C++ facade
+ * VIOFilter.h (one filter per handle). */
+typedef struct eqf_split_report {
+    double S;   /* variance of the functional in the source; NaN when info != 0 */
+    int info;   /* 0 done; 1 S not positive or a value not finite; -1 local = 1 and the gravity chart singular */
+} eqf_split_report;
+int eqf_split_filters(eqf_filter* f, int local, const double* a /* [batch][lda] */, int lda, int n, const int* dst_idx, const int* src_idx,
+    const double* shift /* [n] */, const double* shrink /* [n] */, double* gamma /* [n][ldg] or NULL */, int ldg,
+    eqf_split_report* report /* [n] or NULL */);
+
 /* WHICH members to merge: the pairwise merge costs of the members of a mixture, on the device (csrc/eqf_mergecost.hpp).  Members, weights,
  * ref, the normalisation of w and the checks on ids are eqf_get_mixture_moments'; first is eqf_get_nees's (0 | 6 | 11: the trailing
  * principal submatrix from that reference index).  Everything is taken in the ONE chart chi_c, c = xHat_ref: e_b and J'_b as above,
