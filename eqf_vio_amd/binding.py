@@ -72,6 +72,12 @@ class LinearReport(C.Structure):
     _fields_ = [("nis", C.c_double), ("logdet_S", C.c_double), ("loglik", C.c_double), ("dof", C.c_int), ("info", C.c_int)]
 
 
+class IterReport(C.Structure):
+    """eqf_iter_report (include/eqf_vio_amd.h)."""
+
+    _fields_ = [("n_lin", C.c_int), ("status", C.c_int), ("last_step", C.c_double)]
+
+
 class LiftReport(C.Structure):
     """eqf_lift_report (include/eqf_vio_amd.h)."""
 
@@ -143,6 +149,7 @@ EXPORTED_SYMBOLS = [
     "eqf_get_mixture_moments", "eqf_merge_filters", "eqf_split_filters", "eqf_debug_mixture_launches", "eqf_debug_sigma_pad",
     "eqf_get_merge_costs", "eqf_score_vision", "eqf_get_lift_report", "eqf_edit_landmarks",
     "eqf_update_linear_schmidt", "eqf_update_landmarks_schmidt", "eqf_observe_landmarks",
+    "eqf_observe_landmarks_iterated", "eqf_debug_iterate_launches",
     "eqf_set_outlier_gate", "eqf_get_outlier_gate", "eqf_get_gate_report",
     "eqf_set_sigma", "eqf_set_state", "eqf_copy_filters", "eqf_set_camera_offset", "eqf_get_integrator", "eqf_get_last_update", "eqf_debug_get_blocks", "eqf_device_error", "eqf_debug_drop_role", "eqf_debug_option", "eqf_debug_launch_shape", "eqf_set_dense_propagate", "eqf_set_imu_burst", "eqf_set_option", "eqf_profile_enable",
     "eqf_profile_get", "eqf_profile_class_name", "eqf_version", "eqf_build_info", "eqf_tile_propagate", "eqf_tile_downdate", "eqf_tile_potrf", "eqf_tile_trsm", "eqf_tile_gemm_tn", "eqf_tile_mirror", "eqf_tile_downdate_i8", "eqf_tile_gemm_tn_i8", "eqf_tile_i8_workspace_bytes", "eqf_tile_syrk_i8", "eqf_tile_syrk_i8_workspace_bytes", "eqf_stream_create_masked", "eqf_stream_destroy",
@@ -226,6 +233,11 @@ def lib():
             L.eqf_observe_landmarks.argtypes = [vp, C.c_int, _dp, C.c_int, _ip, _ip, C.c_int, _dp, _dp, C.c_double, C.c_double,
                                                 C.POINTER(C.c_ubyte), _ip, _ip, C.c_int, C.POINTER(C.c_ubyte), _dp, _dp, _dp, C.c_int,
                                                 C.POINTER(LinearReport)]
+        if hasattr(L, "eqf_observe_landmarks_iterated"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate it)
+            L.eqf_observe_landmarks_iterated.argtypes = [vp, C.c_int, _dp, C.c_int, _ip, _ip, C.c_int, _dp, _dp, C.c_double, C.c_double,
+                                                         C.POINTER(C.c_ubyte), _ip, _ip, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_ubyte),
+                                                         _dp, _dp, _dp, C.c_int, C.POINTER(LinearReport), _dp, C.POINTER(IterReport)]
+            L.eqf_debug_iterate_launches.argtypes = [vp]
         if hasattr(L, "eqf_merge_filters"):  # (an older build loaded through EQF_VIO_AMD_LIB for an A/B run may predate them)
             L.eqf_get_mixture_moments.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.POINTER(MixtureReport)]
             L.eqf_merge_filters.argtypes = [vp, C.c_int, _ip, _dp, C.c_int, C.c_int, C.POINTER(MixtureReport)]
@@ -842,7 +854,7 @@ class FilterBatch:
                     dof=np.array([s.dof for s in rep], dtype=np.int32), info=np.array([s.info for s in rep], dtype=np.int32), used=used, gamma=G)
 
     def observe_landmarks(self, kind, ids, meas, R, cam=None, gate=float("inf"), lm_gate=float("inf"), mask=None, consider=None, wait=True,
-                          want_rows=False, stride=None):
+                          want_rows=False, stride=None, max_lin=1, tol=0.0, want_trace=False):
         """update_landmarks with the rows formed ON THE DEVICE at each filter's own estimate (include/eqf_vio_amd.h:
         eqf_observe_landmarks): no dump_state, no state_estimate, no rows in numpy.  kind: OBS_BEARING (2 rows; meas a bearing in the
         measuring camera's frame), OBS_RANGE (1 row; meas the distance from that camera's centre) or OBS_POSITION (3 rows; meas a position
@@ -853,9 +865,17 @@ class FilterBatch:
         gate, lm_gate, mask, consider, stride: as in update_landmarks.  consistency.observe_rows_host is the numpy statement of the rows.
         With wait or want_rows the call waits for the device and returns update_landmarks' dict -- used has one more value, 3 not
         observable -- and, with want_rows, Ht (B, stride, rows, 3) and resid (B, stride, rows) as the device formed them (zeros where an
-        entry is absent or not observable); otherwise it enqueues and returns None."""
+        entry is absent or not observable); otherwise it enqueues and returns None.
+        max_lin > 1 makes it the ITERATED update (eqf_observe_landmarks_iterated): the rows are re-formed at the estimate the update would
+        give, at most max_lin linearisations, until the largest change of the increment on the named landmarks is <= tol (chart units;
+        0: never stop early), and only the last linearisation is applied; resid is then r~ = resid + Ht g.  With max_lin > 1 or
+        want_trace the dict also holds n_lin, status (0 converged, 1 ran out of linearisations, 2 stalled, 3 an intermediate solve
+        failed, 4 masked out) and last_step, each (B,), and with want_trace g_trace (max_lin, B, stride, 3): the increment on each
+        entry's landmark at which linearisation k was taken.  consistency.observe_iterated_host is the numpy statement."""
         B = self.B
         kind = int(kind)
+        max_lin = int(max_lin)
+        iterated = max_lin > 1 or bool(want_trace)
         if kind not in OBS_ROWS:
             raise ValueError("observe_landmarks: kind is OBS_BEARING, OBS_RANGE or OBS_POSITION")
         rows = OBS_ROWS[kind]
@@ -893,7 +913,7 @@ class FilterBatch:
                                          for q, t in pairs])
         mk = None if mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mask), (B,)) != 0, dtype=np.uint8)
         up = C.POINTER(C.c_ubyte)
-        out = bool(wait or want_rows)
+        out = bool(wait or want_rows or want_trace)
         ldg = 11 + 3 * max(self.num_landmarks(b) for b in range(B))
         G = np.zeros((B, ldg)) if out else None
         used = np.zeros((B, stride), dtype=np.uint8) if out else None
@@ -901,6 +921,26 @@ class FilterBatch:
         Ht = np.zeros((B, stride, rows, 3)) if want_rows else None
         rs = np.zeros((B, stride, rows)) if want_rows else None
         nc, cid, cstride = (None, None, 0) if consider is None else self._consider(consider, "observe_landmarks")
+        if iterated:
+            irep = (IterReport * B)() if out else None
+            trace = np.zeros((max(max_lin, 1), B, stride, 3)) if want_trace else None
+            _check(lib().eqf_observe_landmarks_iterated(
+                self._h, kind, None if camp is None else _p(camp), per, nk.ctypes.data_as(_ip), idm.ctypes.data_as(_ip), stride, _p(ms), _p(Rs),
+                float(gate), float(lm_gate), None if mk is None else mk.ctypes.data_as(up), None if nc is None else nc.ctypes.data_as(_ip),
+                None if cid is None else cid.ctypes.data_as(_ip), cstride, max_lin, float(tol), None if used is None else used.ctypes.data_as(up),
+                None if Ht is None else _p(Ht), None if rs is None else _p(rs), None if G is None else _p(G), ldg if out else 0, rep,
+                None if trace is None else _p(trace), irep), "eqf_observe_landmarks_iterated")
+            if not out:
+                return None
+            res = dict(nis=np.array([s.nis for s in rep]), logdet_S=np.array([s.logdet_S for s in rep]), loglik=np.array([s.loglik for s in rep]),
+                       dof=np.array([s.dof for s in rep], dtype=np.int32), info=np.array([s.info for s in rep], dtype=np.int32), used=used,
+                       gamma=G, n_lin=np.array([s.n_lin for s in irep], dtype=np.int32), status=np.array([s.status for s in irep], dtype=np.int32),
+                       last_step=np.array([s.last_step for s in irep]))
+            if want_rows:
+                res.update(Ht=Ht, resid=rs)
+            if want_trace:
+                res.update(g_trace=trace)
+            return res
         _check(lib().eqf_observe_landmarks(self._h, kind, None if camp is None else _p(camp), per, nk.ctypes.data_as(_ip), idm.ctypes.data_as(_ip),
                                            stride, _p(ms), _p(Rs), float(gate), float(lm_gate), None if mk is None else mk.ctypes.data_as(up),
                                            None if nc is None else nc.ctypes.data_as(_ip), None if cid is None else cid.ctypes.data_as(_ip),
@@ -1133,6 +1173,10 @@ class FilterBatch:
     def debug_mixture_launches(self):
         """Kernel launches of the most recent merge() (include/eqf_vio_amd_debug.h)."""
         return _check(lib().eqf_debug_mixture_launches(self._h), "eqf_debug_mixture_launches")
+
+    def debug_iterate_launches(self):
+        """Kernel launches the most recent iterated observe_landmarks added to the one-shot call's (include/eqf_vio_amd_debug.h)."""
+        return _check(lib().eqf_debug_iterate_launches(self._h), "eqf_debug_iterate_launches")
 
     def debug_sigma_pad(self, b=0, image=0):
         """Largest |entry| of the pad row and column of filter b's internal covariance (image 0) or of slot b of the scratch image, where

@@ -564,6 +564,166 @@ def observe_rows_host(kind, state, ids, meas, cam=None):
     return Ht, resid, used
 
 
+# ---- the iterated (re-linearised) observation update (FilterBatch.observe_landmarks(max_lin > 1); eqf_observe_landmarks_iterated)
+ITER_CONVERGED, ITER_EXHAUSTED, ITER_STALLED, ITER_SOLVE_FAILED, ITER_MASKED = 0, 1, 2, 3, 4
+
+
+def landmark_step_state(state, ids, g):
+    """A copy of the dump_state dictionary `state` whose landmarks ids[k] (those the state holds) took the plain group step
+    Q_i <- Delta_i(g[k], p0_i) Q_i of eqf_apply_increment: q <- exp(-(p0 x g) / |p0|^2) q, a <- exp(-p0 . g / |p0|^2) a.  Everything else is
+    shared with `state`.  The trial point of a linearisation."""
+    sid = [int(i) for i in state["ids"]]
+    p0 = np.asarray(state["origin"]["p"], dtype=float).reshape(-1, 3)
+    Qq = np.array(state["group"]["Qq"], dtype=float).reshape(-1, 4)
+    Qa = np.array(state["group"]["Qa"], dtype=float).reshape(-1)
+    g = np.asarray(g, dtype=float).reshape(-1, 3)
+    for k, lid in enumerate(np.asarray(ids, dtype=int).reshape(-1)):
+        if int(lid) not in sid:
+            continue
+        i = sid.index(int(lid))
+        n2 = float(p0[i] @ p0[i])
+        with np.errstate(all="ignore"):
+            Qq[i] = _quat_mul(_quat_from_matrix(_so3_exp_matrix(-np.cross(p0[i], g[k]) / n2)), Qq[i])
+            Qa[i] = np.exp(-float(p0[i] @ g[k]) / n2) * Qa[i]
+    return dict(state, group=dict(state["group"], Qq=Qq, Qa=Qa))
+
+
+def _iter_blocks(Sigma, state, ids, on, Ht, R):
+    """(idx of the entries `on`, the dense rows over their landmark blocks M only (m, 3 |on|), Sigma_MM, blockdiag(R))"""
+    sid = [int(i) for i in state["ids"]]
+    rows = Ht.shape[1]
+    idx = [sid.index(int(ids[k])) for k in on]
+    M = np.array([11 + 3 * i + c for i in idx for c in range(3)], dtype=np.int64)
+    Hd = np.zeros((rows * len(on), 3 * len(on)))
+    Rd = np.zeros((rows * len(on), rows * len(on)))
+    for p, k in enumerate(on):
+        Hd[rows * p:rows * (p + 1), 3 * p:3 * (p + 1)] = Ht[k]
+        Rd[rows * p:rows * (p + 1), rows * p:rows * (p + 1)] = np.tril(R[k]) + np.tril(R[k], -1).T
+    Sg = np.tril(Sigma) + np.tril(Sigma, -1).T
+    return idx, Hd, Sg[np.ix_(M, M)], Rd
+
+
+def observe_iterated_step(kind, Sigma, state, ids, meas, R, g, on, cam=None, consider=None):
+    """ONE step of the iteration for one filter: the rows at the trial point g (K, 3) -- increments on each entry's landmark block, from the
+    UNCHANGED state --, r~ = resid + Ht g, and g_next = Sigma_MM Ht^T (Ht Sigma_MM Ht^T + R)^-1 r~ over the entries `on`, zero on an entry
+    whose landmark id is in `consider`.  Returns (Ht (K, rows, 3), rt (K, rows), g_next (K, 3), stalled).  Raises numpy.linalg.LinAlgError
+    when S is not positive definite."""
+    ids = np.asarray(ids, dtype=int).reshape(-1)
+    g = np.asarray(g, dtype=float).reshape(len(ids), 3)
+    R = np.asarray(R, dtype=float)
+    with np.errstate(all="ignore"):  # (a trial point that is not finite is a verdict, not a warning)
+        Ht, resid, u = observe_rows_host(kind, landmark_step_state(state, ids, g), ids, meas, cam)
+    stalled = any(u[k] != 1 for k in on)
+    rt = resid + np.einsum("krc,kc->kr", Ht, g)
+    g_next = np.zeros_like(g)
+    if stalled or not len(on):
+        return Ht, rt, g_next, stalled
+    _, Hd, Smm, Rd = _iter_blocks(np.asarray(Sigma, dtype=float), state, ids, on, Ht, R)
+    T = Smm @ Hd.T
+    L = np.linalg.cholesky(Hd @ T + Rd)
+    w = np.linalg.solve(L.T, np.linalg.solve(L, rt[on].reshape(-1)))
+    g_next[on] = (T @ w).reshape(len(on), 3)
+    for k in on:
+        if consider is not None and int(ids[k]) in [int(c) for c in consider]:
+            g_next[k] = 0.0
+    return Ht, rt, g_next, stalled
+
+
+def observe_iterated_host(kind, Sigma, state, ids, meas, R, cam=None, max_lin=1, tol=0.0, consider=None, gate=np.inf, lm_gate=np.inf):
+    """The numpy statement of FilterBatch.observe_landmarks(max_lin=..., tol=...) for ONE filter (include/eqf_vio_amd.h:
+    eqf_observe_landmarks_iterated).  Sigma (n, n), state: a dump_state dictionary, ids (K,), meas (K, 3), R (K, rows, rows), cam as
+    observe_rows_host's, consider: landmark IDS that keep estimate and covariance.  Linearisation 0 at the state decides and freezes used
+    (update_landmarks_host's verdicts with lm_gate; 3 not observable); then g_{k+1}, last_step = max |g_{k+1} - g_k| and the stop rule
+    (last_step <= tol with tol > 0: converged) as observe_iterated_step states them, and the commit: update_landmarks_host -- or, with
+    consider, schmidt_update_host -- with the committed rows (Ht_K, r~_K) on the prior Sigma.
+    Returns dict(Ht, resid (= r~_K), used, g_trace (max_lin, K, 3), n_lin, status, last_step, gamma, Sigma, nis, info)."""
+    Sg = np.asarray(Sigma, dtype=float)
+    ids = np.asarray(ids, dtype=int).reshape(-1)
+    K, rows = len(ids), OBS_ROWS[kind]
+    R = np.broadcast_to(np.asarray(R, dtype=float), (K, rows, rows)) if np.ndim(R) >= 2 else np.broadcast_to(float(R) * np.eye(rows), (K, rows, rows))
+    sid = [int(i) for i in state["ids"]]
+    idx = np.array([sid.index(int(i)) if int(i) in sid else -1 for i in ids])
+    Ht, rt, used3 = observe_rows_host(kind, state, ids, meas, cam)
+    first = update_landmarks_host(Sg, np.where(used3 == 1, idx, -1), Ht, rt, R, lm_gate=lm_gate)
+    used = np.where(used3 == 3, 3, first["used"]).astype(np.uint8)
+    on = [int(k) for k in np.flatnonzero(used == 1)]
+    g = np.zeros((K, 3))
+    trace = np.zeros((int(max_lin), K, 3))
+    n_lin, status, last_step = int(max_lin), ITER_EXHAUSTED, 0.0
+    for k in range(int(max_lin) - 1):
+        try:
+            _, Hd, Smm, Rd = _iter_blocks(Sg, state, ids, on, Ht, R)
+            T = Smm @ Hd.T
+            L = np.linalg.cholesky(Hd @ T + Rd)
+            w = np.linalg.solve(L.T, np.linalg.solve(L, rt[on].reshape(-1)))
+            gn = np.zeros((K, 3))
+            gn[on] = (T @ w).reshape(len(on), 3)
+            for e in on:
+                if consider is not None and int(ids[e]) in [int(c) for c in consider]:
+                    gn[e] = 0.0
+            step = float(np.max(np.abs(gn - g))) if K else 0.0
+            if not np.isfinite(step):
+                raise np.linalg.LinAlgError("not finite")
+        except np.linalg.LinAlgError:
+            n_lin, status, last_step = k + 1, ITER_SOLVE_FAILED, np.nan
+            break
+        last_step = step
+        if tol > 0.0 and step <= tol:
+            n_lin, status = k + 1, ITER_CONVERGED
+            break
+        with np.errstate(all="ignore"):  # (a trial point that is not finite is a verdict, not a warning)
+            Hn, rn, u = observe_rows_host(kind, landmark_step_state(state, ids, gn), ids, meas, cam)
+        if any(u[e] != 1 for e in on):
+            n_lin, status = k + 1, ITER_STALLED
+            break
+        for e in on:
+            Ht[e], rt[e] = Hn[e], rn[e] + Hn[e] @ gn[e]
+        g = gn
+        trace[k + 1] = g
+    cidx = consider_indices([sid.index(int(c)) for c in (consider if consider is not None else []) if int(c) in sid])
+    fin = update_landmarks_host(Sg, np.where(used == 1, idx, -1), Ht, rt, R, gate=gate)
+    gamma, Sp = fin["gamma"], fin["Sigma"]
+    if fin["info"] == 0 and len(cidx) and len(on):
+        N = (len(Sg) - 11) // 3
+        Rd = np.zeros((rows * len(on), rows * len(on)))
+        for p, e in enumerate(on):
+            Rd[rows * p:rows * (p + 1), rows * p:rows * (p + 1)] = np.tril(R[e]) + np.tril(R[e], -1).T
+        s = schmidt_update_host(np.tril(Sg) + np.tril(Sg, -1).T, landmark_blocks_matrix(N, idx[on], Ht[on]), Rd, rt[on].reshape(-1), cidx)
+        gamma, Sp = s["gamma"], s["Sigma"]
+    return dict(Ht=Ht, resid=rt, used=used, g_trace=trace, n_lin=n_lin, status=status, last_step=last_step, gamma=gamma, Sigma=Sp,
+                nis=fin["nis"], info=fin["info"])
+
+
+def map_cost(kind, Sigma, state, ids, meas, R, gamma, used, cam=None, gradient=False):
+    """The iteration's own objective at an increment gamma (n,) of the prior estimate, over the entries with used == 1:
+        1/2 gamma^T Sigma^-1 gamma + 1/2 r(gamma)^T R^-1 r(gamma),
+    r(gamma) the kind's residual at the state whose landmarks took the plain step with their blocks of gamma (landmark_step_state).
+    gradient=True returns (cost, Sigma^-1 gamma - Ht(gamma)^T R^-1 r(gamma)) -- a moved estimate lowers the residual by Ht times the
+    move -- whose norm an iterated update drives towards zero."""
+    Sg = np.asarray(Sigma, dtype=float)
+    Sg = np.tril(Sg) + np.tril(Sg, -1).T
+    ids = np.asarray(ids, dtype=int).reshape(-1)
+    K, rows = len(ids), OBS_ROWS[kind]
+    R = np.broadcast_to(np.asarray(R, dtype=float), (K, rows, rows)) if np.ndim(R) >= 2 else np.broadcast_to(float(R) * np.eye(rows), (K, rows, rows))
+    sid = [int(i) for i in state["ids"]]
+    gamma = np.asarray(gamma, dtype=float).reshape(-1)
+    g = np.zeros((K, 3))
+    for k in range(K):
+        if int(ids[k]) in sid:
+            i = sid.index(int(ids[k]))
+            g[k] = gamma[11 + 3 * i:14 + 3 * i]
+    Ht, r, _ = observe_rows_host(kind, landmark_step_state(state, ids, g), ids, meas, cam)
+    a = np.linalg.solve(Sg, gamma)
+    cost, grad = 0.5 * float(gamma @ a), a.copy()
+    for k in np.flatnonzero(np.asarray(used) == 1):
+        Rl = np.tril(R[k]) + np.tril(R[k], -1).T
+        v = np.linalg.solve(Rl, r[k])
+        cost += 0.5 * float(r[k] @ v)
+        i = sid.index(int(ids[k]))
+        grad[11 + 3 * i:14 + 3 * i] -= Ht[k].T @ v
+    return (cost, grad) if gradient else cost
+
+
 # ---- explicit landmark edits (FilterBatch.edit_landmarks): the host statement of the edit and the usual priors
 def edit_landmarks_host(state_dump, remove_ids, insert_ids, p, P):
     """What FilterBatch.edit_landmarks does to ONE filter, on a dump_state dictionary, in numpy: a new dictionary with ids, origin p, group

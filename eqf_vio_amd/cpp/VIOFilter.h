@@ -468,6 +468,27 @@ class VIOFilter {
         double lm_gate = std::numeric_limits<double>::infinity(), unsigned char* used = nullptr, double* Ht = nullptr, double* resid = nullptr) {
         return observeLandmarks(kind, ids, K, meas, R, cam, &considerIds, gate, lm_gate, used, Ht, resid);
     }
+    // ... ITERATED (eqf_observe_landmarks_iterated): the rows are re-formed at the estimate the update would give, at most max_lin (1 ..
+    // EQF_ITER_MAX_LIN) linearisations, until the increment on the named landmarks changes by no more than tol (chart units; 0: never stop
+    // early), and only the last linearisation is applied.  Returns the iteration report {n_lin, status, last_step}: status 0 converged, 1 ran
+    // out of linearisations, 2 stalled at a trial point that was not observable, 3 an intermediate solve failed; report, where given,
+    // receives the update's own report.  considerIds: NULL, or the Schmidt variant's list.  resid receives r~ = resid + Ht g of the
+    // committed linearisation.
+    eqf_iter_report processLandmarkObservations(int kind, const int* ids, int K, const double* meas, const double* R, const double* cam,
+        int max_lin, double tol, eqf_linear_report* report = nullptr, const std::vector<int>* considerIds = nullptr,
+        double gate = std::numeric_limits<double>::infinity(), double lm_gate = std::numeric_limits<double>::infinity(),
+        unsigned char* used = nullptr, double* Ht = nullptr, double* resid = nullptr) {
+        eqf_linear_report rep;
+        eqf_iter_report iter;
+        const int zero = 0, nc = considerIds ? int(considerIds->size()) : 0;
+        std::vector<double> pad(9, 0.0);  // (stride is at least 1: K = 0 hands over one unread entry)
+        check(eqf_observe_landmarks_iterated(handle_.get(), kind, cam, 0, &K, K ? ids : &zero, K ? K : 1, K ? meas : pad.data(),
+                  K ? R : pad.data(), gate, lm_gate, nullptr, considerIds ? &nc : nullptr, considerIds ? considerIds->data() : nullptr, nc,
+                  max_lin, tol, K ? used : nullptr, K ? Ht : nullptr, K ? resid : nullptr, nullptr, 0, &rep, nullptr, &iter),
+            "eqf_observe_landmarks_iterated");
+        if (report) *report = rep;
+        return iter;
+    }
     // How processLinearMeasurement, processLandmarkMeasurements, perturbState (and eqf_apply_increment) turn their increment into a group
     // step (eqf_set_option "innovation_lift"): false (default) the plain lift, which leaves the whole correction to the body-frame landmarks;
     // true the filter's own useInnovationLift / useDiscreteInnovationLift, as a vision frame does -- a stereo, range or zero-velocity update

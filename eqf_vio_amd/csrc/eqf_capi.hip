@@ -47,6 +47,7 @@
 #include "eqf_border_host.hpp"
 #include "eqf_mapedit.hpp"
 #include "eqf_mapedit_host.hpp"
+#include "eqf_iterate.hpp"
 #include "eqf_observe.hpp"
 #include "eqf_schmidt.hpp"
 #include "eqf_schmidt_host.hpp"
@@ -201,6 +202,17 @@ struct SchmidtRoute {
 struct SplitRoute {
     StagedImage<> img;
     DevPtr<char> ws;
+};
+// the iterated landmark observation update (eqf_iterate.hpp; eqf_observe_landmarks_iterated), grown when a call asks for more: the
+// workspace in doubles [B][iterate::WorkLayout::strideD()] and in ints [B][kInts], g_trace on the device (iterate::traceDoubles); capacities
+// in bytes.  The two row buffers are BlkRoute::obs at twice its size.  launches: the kernel launches the most recent such call added to
+// eqf_observe_landmarks's own, counted as they were made (eqf_debug_iterate_launches).
+struct IterRoute {
+    DevPtr<double> ws, trace;
+    DevPtr<int> wi;
+    size_t wsCap = 0, traceCap = 0, wiCap = 0;
+    bool ldsSet = false;
+    int launches = 0;
 };
 
 struct eqf_filter {
@@ -391,6 +403,7 @@ struct eqf_filter {
     MapEditRoute medit;
     SchmidtRoute sch;
     SplitRoute split;
+    IterRoute iter;
 
     ~eqf_filter() {
         for (auto e : evPool) (void)hipEventDestroy(e);
@@ -1762,20 +1775,23 @@ int resolveGate(eqf_filter* f) {
 // block row lies below and the trailing tiles if a block column lies behind.  ldsSet: the handle's flag for the dynamic-LDS attributes
 // of this instantiation.
 template <class Args>
-int enqueueFactor(hipStream_t stream, bool& ldsSet, const Args& a, int images, int mMax, int rhsRows) {
+int enqueueFactor(hipStream_t stream, bool& ldsSet, const Args& a, int images, int mMax, int rhsRows, int* launches = nullptr) {
     const int nb = mMax <= 0 ? 0 : (mMax + kSB - 1) / kSB;
     if (!ldsSet) {  // (dynamic LDS beyond 64 KB: see allowUpdateLds)
         HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_factor_panel<Args>), hipFuncAttributeMaxDynamicSharedMemorySize, kFactorPanelLdsBytes));
         HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_factor_trail<Args>), hipFuncAttributeMaxDynamicSharedMemorySize, kFactorTrailLdsBytes));
         ldsSet = true;
     }
+    int made = 1;
     hipLaunchKernelGGL(k_factor_diag<Args>, dim3(1, images), dim3(256), kLdsFactorBytes, stream, a, 0);
     for (int K = 0; K < nb; ++K) {
         const int t = nb - K - 1;
+        made += (K > 0) + (t + rhsRows > 0) + (t > 0);
         if (K > 0) hipLaunchKernelGGL(k_factor_diag<Args>, dim3(1, images), dim3(256), kLdsFactorBytes, stream, a, K);
         if (t + rhsRows > 0) hipLaunchKernelGGL(k_factor_panel<Args>, dim3(t + rhsRows, images), dim3(256), kFactorPanelLdsBytes, stream, a, K, t);
         if (t > 0) hipLaunchKernelGGL(k_factor_trail<Args>, dim3(t * (t + 1) / 2 + rhsRows * t, images), dim3(256), kFactorTrailLdsBytes, stream, a, K, t);
     }
+    if (launches) *launches += made;
     return EQF_OK;
 }
 
@@ -3558,13 +3574,30 @@ struct ObsCall {
     double* HtOut;
     double* residOut;
 };
+// what eqf_observe_landmarks_iterated adds to that
+struct IterCall {
+    int maxLin;
+    double tol;
+    double* gTrace;
+    eqf_iter_report* rep;
+};
+// the buffers of the intermediate linearisations; what is there and large enough is kept
+int iterReserve(eqf_filter* f, const iterate::WorkLayout& il, int maxLin, int stride) {
+    const workspace::Want w[] = {want(f->iter.ws, sizeof(double) * size_t(il.strideD()) * f->B, &f->iter.wsCap),
+        want(f->iter.wi, sizeof(int) * size_t(iterate::WorkLayout::kInts) * f->B, &f->iter.wiCap),
+        want(f->iter.trace, sizeof(double) * iterate::traceDoubles(maxLin, f->B, stride), &f->iter.traceCap)};
+    return reserveSlots(f, w);
+}
 
 // eqf_update_landmarks (sc == nullptr: the launches it has always enqueued), eqf_update_landmarks_schmidt and, with oc,
-// eqf_observe_landmarks: local = 0, Hb and resid nullptr -- k_obs_rows forms the rows on the device in k_blk_rows's place
+// eqf_observe_landmarks: local = 0, Hb and resid nullptr -- k_obs_rows forms the rows on the device in k_blk_rows's place; with ic (and
+// more than one linearisation) the kernels of eqf_iterate.hpp run between k_obs_rows and k_blk_gain and leave the committed rows where
+// k_obs_rows left its own
 int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb, const double* resid,
     const double* Rb, double gate, double lm_gate, const unsigned char* mask, const SchCall* sc, const ObsCall* oc, unsigned char* used,
-    double* gamma, int ldg, eqf_linear_report* report) {
+    double* gamma, int ldg, eqf_linear_report* report, const IterCall* ic = nullptr) {
     if (!f) return EQF_ERR_INVALID;
+    if (ic && !iterate::argsOk(ic->maxLin, ic->tol)) return EQF_ERR_INVALID;
     if (oc ? !observe::headArgsOk(oc->kind, oc->camPerFilter, nk, ids, stride, oc->meas, Rb, gate, lm_gate)
            : !blocks::headArgsOk(local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate))
         return EQF_ERR_INVALID;
@@ -3588,9 +3621,12 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
     const observe::SmallLayout ol{B, stride, rows};
     const observe::RowsLayout orl{B, stride, rows};
     const blocks::WorkLayout wl{f->ld, stride, rows, kDRec};
-    const size_t smallBytes = oc ? ol.bytes() : sl.bytes(), offR = oc ? ol.offR() : sl.offR(), offIdx = oc ? ol.offIdx() : sl.offIdx(),
+    const iterate::WorkLayout il{stride, rows, kDRec};
+    const bool iterating = ic && ic->maxLin > 1;
+    const size_t smallBytes = iterating ? iterate::smallBytes(ol) : (oc ? ol.bytes() : sl.bytes()), offR = oc ? ol.offR() : sl.offR(), offIdx = oc ? ol.offIdx() : sl.offIdx(),
                  offNk = oc ? ol.offNk() : sl.offNk(), offMask = oc ? ol.offMask() : sl.offMask();
-    int rc = blkReserve(f, smallBytes, wl, oc ? sizeof(double) * orl.doubles() : 0);
+    int rc = blkReserve(f, smallBytes, wl, oc ? sizeof(double) * orl.doubles() * (iterating ? 2 : 1) : 0);
+    if (!rc && iterating) rc = iterReserve(f, il, ic->maxLin, stride);
     if (!rc) rc = liftReserve(f, lift::callFactors(liftCallKind(f), maxN(f)));
     if (!rc && sc) rc = schReserve(f);
     if (rc) return rc;
@@ -3628,6 +3664,9 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
         hm[b] = mask ? (mask[b] ? 1 : 0) : 1;
         for (int k = 0; k < stride; ++k)
             hIdx[size_t(b) * stride + k] = (hm[b] && k < nk[b]) ? blocks::findId(f->ids[b].data(), N[b], ids[size_t(b) * stride + k]) : -1;
+        for (int k = 0; iterating && k < stride; ++k)
+            hs[iterate::offConsider(ol) + size_t(b) * stride + k] = (sc && sc->n && hm[b] && k < nk[b] &&
+                iterate::considered(sc->ids + size_t(b) * sc->cstride, sc->n[b], ids[size_t(b) * stride + k])) ? 1 : 0;
     }
     HIPC(f->blk.small.upload(smallBytes, f->stream));
     const int nMax = maxN(f), nt = blocks::rowTiles(nMax);
@@ -3651,6 +3690,31 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
         o.meas = reinterpret_cast<const double*>(f->blk.small.dev + ol.offMeas()); o.p0 = f->p0; o.Q = f->Q[f->pG];
         o.Ht = f->blk.obs + orl.offHt(); o.resid = f->blk.obs + orl.offResid();
         hipLaunchKernelGGL(k_obs_rows, dim3(B), dim3(256), 0, f->stream, o);
+        if (ic) f->iter.launches = 0;
+        if (iterating) {
+            IterArgs t{};
+            t.a = a; t.kind = o.kind; t.cam = o.cam; t.meas = o.meas; t.p0 = o.p0; t.Q = o.Q;
+            t.consider = reinterpret_cast<const unsigned char*>(f->blk.small.dev + iterate::offConsider(ol));
+            t.rowsBuf = f->blk.obs; t.bufStride = (long long)orl.doubles(); t.offResid = (long long)orl.offResid();
+            t.ws = f->iter.ws; t.wsStride = il.strideD(); t.offT = il.offT(); t.offW = il.offW(); t.offG = il.offG(); t.offGn = il.offGn();
+            t.offD = il.offD(); t.offStep = il.offStep(); t.wi = f->iter.wi; t.trace = f->iter.trace; t.maxLin = ic->maxLin; t.B = B;
+            t.tol = ic->tol;
+            // the progress words, g, gNext and lastStep of every filter and the whole trace start as zeros
+            HIPC(hipMemsetAsync(f->iter.wi, 0, sizeof(int) * size_t(iterate::WorkLayout::kInts) * B, f->stream));
+            HIPC(hipMemset2DAsync(f->iter.ws + il.offG(), sizeof(double) * il.strideD(), 0, sizeof(double) * (il.strideD() - il.offG()), B,
+                f->stream));
+            HIPC(hipMemsetAsync(f->iter.trace, 0, sizeof(double) * iterate::traceDoubles(ic->maxLin, B, stride), f->stream));
+            for (int k = 0; k + 1 < ic->maxLin; ++k) {
+                hipLaunchKernelGGL(k_iter_form, dim3(nPT * nPT, B), dim3(256), 0, f->stream, t, nPT);
+                rc = enqueueFactor(f->stream, f->iter.ldsSet, t, B, il.mp(), 1, &f->iter.launches);
+                if (rc) return rc;
+                hipLaunchKernelGGL(k_iter_step, dim3(B), dim3(256), 0, f->stream, t, k);
+                hipLaunchKernelGGL(k_iter_rows, dim3(B), dim3(256), 0, f->stream, t, k);
+                f->iter.launches += 3;
+            }
+            hipLaunchKernelGGL(k_iter_commit, dim3(B), dim3(256), 0, f->stream, t);
+            ++f->iter.launches;
+        }
     } else {
         hipLaunchKernelGGL(k_blk_rows, dim3(B), dim3(256), 0, f->stream, a);
     }
@@ -3684,9 +3748,19 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
     hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, ia);
     HIPC(hipGetLastError());
     f->csValid = false;  // (C Sigma / S left by an earlier burst describe the old Sigma)
-    if (!used && !gamma && !report && !(oc && (oc->HtOut || oc->residOut))) return EQF_OK;
-    std::vector<double> hO(size_t(B) * kLinHead), hG, hRows;
-    std::vector<int> hU(size_t(B) * wl.strideI());
+    if (!used && !gamma && !report && !(oc && (oc->HtOut || oc->residOut)) && !(ic && (ic->gTrace || ic->rep))) return EQF_OK;
+    std::vector<double> hO(size_t(B) * kLinHead), hG, hRows, hStep;
+    std::vector<int> hU(size_t(B) * wl.strideI()), hIt;
+    if (iterating && ic->rep) {
+        hStep.resize(B);
+        hIt.resize(size_t(B) * iterate::WorkLayout::kInts);
+        HIPC(hipMemcpyAsync(hIt.data(), f->iter.wi, sizeof(int) * hIt.size(), hipMemcpyDeviceToHost, f->stream));
+        HIPC(hipMemcpy2DAsync(hStep.data(), sizeof(double), f->iter.ws + il.offStep(), sizeof(double) * il.strideD(), sizeof(double), B,
+            hipMemcpyDeviceToHost, f->stream));
+    }
+    if (iterating && ic->gTrace)
+        HIPC(hipMemcpyAsync(ic->gTrace, f->iter.trace, sizeof(double) * iterate::traceDoubles(ic->maxLin, B, stride), hipMemcpyDeviceToHost,
+            f->stream));
     if (oc && (oc->HtOut || oc->residOut)) {
         hRows.resize(orl.doubles());
         HIPC(hipMemcpyAsync(hRows.data(), f->blk.obs, sizeof(double) * hRows.size(), hipMemcpyDeviceToHost, f->stream));
@@ -3699,6 +3773,7 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
             sizeof(double) * f->ld, B, hipMemcpyDeviceToHost, f->stream));
     }
     HIPC(hipStreamSynchronize(f->stream));
+    if (ic && ic->gTrace && !iterating) std::fill(ic->gTrace, ic->gTrace + iterate::traceDoubles(1, B, stride), 0.0);
     for (int b = 0; b < B; ++b) {
         const double* o = hO.data() + size_t(b) * kLinHead;
         const int* u = hU.data() + size_t(b) * wl.strideI();
@@ -3715,6 +3790,13 @@ int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids,
         if (used)
             for (int k = 0; k < stride; ++k) used[size_t(b) * stride + k] = (word != 3 && k < nk[b]) ? (unsigned char)u[wl.offUsed() + k] : 0;
         if (gamma) blocks::unpackGamma(hG.data() + size_t(b) * f->ld, N[b], gamma + size_t(b) * ldg, word != 0);
+        if (ic && ic->rep) {
+            const int* w = iterating ? hIt.data() + size_t(b) * iterate::WorkLayout::kInts : nullptr;
+            // (one linearisation: nothing was solved on the way)
+            ic->rep[b].n_lin = w ? w[iterate::WorkLayout::kNLin] : (word == 3 ? 0 : 1);
+            ic->rep[b].status = w ? w[iterate::WorkLayout::kStatus] : (word == 3 ? iterate::kMasked : iterate::kExhausted);
+            ic->rep[b].last_step = w ? hStep[b] : 0.0;
+        }
         for (int k = 0; oc && k < stride; ++k) {  // (the kernel stores zeros for an entry that is absent or not observable)
             const size_t e = size_t(b) * stride + k;
             const bool formed = word != 3 && k < nk[b];
@@ -3748,6 +3830,18 @@ int eqf_observe_landmarks(eqf_filter* f, int kind, const double* cam, int cam_pe
     const SchCall sc{n_consider, consider_ids, cstride};
     return blkUpdate(f, 0, observe::rowsOf(kind), nk, ids, stride, nullptr, nullptr, Rb, gate, lm_gate, mask, n_consider ? &sc : nullptr, &oc,
         used, gamma, ldg, report);
+}
+// ... and re-formed at the moved estimate until the increment settles (eqf_iterate.hpp; eqf_iterate_host.hpp)
+static_assert(iterate::kMaxLin == EQF_ITER_MAX_LIN, "eqf_iterate_host.hpp repeats the limit");
+int eqf_observe_landmarks_iterated(eqf_filter* f, int kind, const double* cam, int cam_per_filter, const int* nk, const int* ids, int stride,
+    const double* meas, const double* Rb, double gate, double lm_gate, const unsigned char* mask, const int* n_consider,
+    const int* consider_ids, int cstride, int max_lin, double tol, unsigned char* used, double* Ht_out, double* resid_out, double* gamma,
+    int ldg, eqf_linear_report* report, double* g_trace, eqf_iter_report* iter_report) {
+    const ObsCall oc{kind, cam, cam_per_filter, meas, Ht_out, resid_out};
+    const SchCall sc{n_consider, consider_ids, cstride};
+    const IterCall ic{max_lin, tol, g_trace, iter_report};
+    return blkUpdate(f, 0, observe::rowsOf(kind), nk, ids, stride, nullptr, nullptr, Rb, gate, lm_gate, mask, n_consider ? &sc : nullptr, &oc,
+        used, gamma, ldg, report, &ic);
 }
 
 static_assert(mixture::kRefBase == kBase && mixture::kPadBase == kLm0 && mixture::kRows == kMixRows && mixture::kLanes == kMixLanes &&
@@ -4295,6 +4389,7 @@ int eqf_score_vision(eqf_filter* f, int ncand, const int* nb, const int* ids, co
 }
 
 int eqf_debug_mixture_launches(eqf_filter* f) { return f ? f->mix.launches : EQF_ERR_INVALID; }
+int eqf_debug_iterate_launches(eqf_filter* f) { return f ? f->iter.launches : EQF_ERR_INVALID; }
 
 int eqf_debug_sigma_pad(eqf_filter* f, int b, int image, double* max_abs) {
     if (!f || b < 0 || b >= f->B || (image != 0 && image != 1) || !max_abs) return EQF_ERR_INVALID;

@@ -193,6 +193,18 @@ EQF_DI quat so3Exp(d3 w) {  // SO3.cpp:122-140
     return m2q(add33(eye3(), add33(scl33(A, wx), scl33(B, mul33(wx, wx)))));
 }
 
+// One landmark's part of the plain group step: Q_i <- Delta_i(gq, p0_i) Q_i with Q_i = (q, a), p0 the landmark's origin and gq its
+// 3-block of the increment (EqFMatrices.cpp:54-63, SOT3Exp, VIOGroup.cpp:105-107).  k_apply_increment's expression, also what
+// eqf_iterate_host.hpp takes a trial point with.
+EQF_DI void landmarkStep(d3 qi, d3 gq, const double* Q, int cap, int i, quat* Qn, double* an) {
+    const double n2 = dot3(qi, qi);
+    const quat dq = so3Exp(scl(-1.0 / n2, crs(qi, gq)));
+    const double da = exp(-dot3(qi, gq) / n2);
+    const quat Qq = quat{Q[i], Q[cap + i], Q[2 * cap + i], Q[3 * cap + i]};
+    *Qn = qmul(dq, Qq);
+    *an = da * Q[4 * cap + i];
+}
+
 struct se3 {
     quat q;
     d3 x;

@@ -137,13 +137,11 @@ __global__ __launch_bounds__(256) void k_apply_increment(IncArgs a) {
         for (int i = tid - 64; i < N; i += 192) {
             const d3 qi = mk3(p0[i], p0[cap + i], p0[2 * cap + i]);
             const d3 gq = mk3(gam(kLm0 + 3 * i), gam(kLm0 + 3 * i + 1), gam(kLm0 + 3 * i + 2));
-            const double n2 = dot3(qi, qi);
-            const quat dq = so3Exp(scl(-1.0 / n2, crs(qi, gq)));
-            const double da = exp(-dot3(qi, gq) / n2);
-            const quat Qq = quat{Q[i], Q[cap + i], Q[2 * cap + i], Q[3 * cap + i]};
-            const quat Qn = qmul(dq, Qq);
+            quat Qn;
+            double an;
+            landmarkStep(qi, gq, Q, cap, i, &Qn, &an);
             Q[i] = Qn.w; Q[cap + i] = Qn.x; Q[2 * cap + i] = Qn.y; Q[3 * cap + i] = Qn.z;
-            Q[4 * cap + i] = da * Q[4 * cap + i];
+            Q[4 * cap + i] = an;
         }
     }
 }

@@ -222,18 +222,23 @@ class VIOFilter:
     processLandmarkMeasurements = process_landmark_measurements
 
     def process_landmark_observations(self, kind, ids, meas, R, cam=None, gate=float("inf"), lm_gate=float("inf"), consider=None,
-                                      want_rows=False):
+                                      want_rows=False, max_lin=1, tol=0.0):
         """process_landmark_measurements with the rows formed on the device at the filter's own estimate (include/eqf_vio_amd.h:
         eqf_observe_landmarks): kind binding.OBS_BEARING / OBS_RANGE / OBS_POSITION, entry k the measurement meas[k] (a bearing, a range,
         a position in the measuring camera's frame) of the landmark ids[k] (strictly ascending) with noise covariance R (K, rows, rows),
         (rows, rows) or a scalar variance; cam: None (this camera) or (q_c, t_c), the measuring camera's pose in this camera's frame.
         Returns dict(nis, logdet_S, loglik, dof, info, used (K,): 1 applied, 0 id not in the state, 2 gated, 3 not observable; gamma) and,
-        with want_rows, Ht (K, rows, 3) and resid (K, rows) as the device formed them."""
+        with want_rows, Ht (K, rows, 3) and resid (K, rows) as the device formed them.  max_lin > 1: the iterated update
+        (eqf_observe_landmarks_iterated) with at most max_lin linearisations and the step tolerance tol; the dict then also holds n_lin,
+        status and last_step."""
         K = len(np.asarray(ids).reshape(-1))
         r = self._fb.observe_landmarks(kind, [np.asarray(ids).reshape(-1)], [meas], [R], cam=cam, gate=gate, lm_gate=lm_gate,
-                                       consider=None if consider is None else [np.asarray(consider).reshape(-1)], want_rows=want_rows)
+                                       consider=None if consider is None else [np.asarray(consider).reshape(-1)], want_rows=want_rows,
+                                       max_lin=max_lin, tol=tol)
         out = dict(nis=float(r["nis"][0]), logdet_S=float(r["logdet_S"][0]), loglik=float(r["loglik"][0]), dof=int(r["dof"][0]),
                    info=int(r["info"][0]), used=r["used"][0, :K], gamma=r["gamma"][0])
+        if "n_lin" in r:
+            out.update(n_lin=int(r["n_lin"][0]), status=int(r["status"][0]), last_step=float(r["last_step"][0]))
         if want_rows:
             out.update(Ht=r["Ht"][0, :K], resid=r["resid"][0, :K])
         return out

@@ -577,8 +577,7 @@ int eqf_update_landmarks_schmidt(eqf_filter* f, int local, int rows, const int* 
  * kind, a cam_per_filter that is not 0 or 1, a zero quaternion, or a value of cam or meas that is not finite where it is read (k < nk[b]
  * of a filter that is not masked out; meas[1], meas[2] of a range are not read; the single offset of a call is always read).
  * EQF_ERR_UNSUPPORTED on an EQF_PRECISION_F32 handle.
- * Not covered: the partitioned filter; an iterated (re-linearised) update; a camera offset carried in the state; a dry run that only
- * predicts the rows. */
+ * Not covered: the partitioned filter; a camera offset carried in the state; a dry run that only predicts the rows. */
 int eqf_observe_landmarks(eqf_filter* f, int kind, const double* cam /* NULL | [7] | [batch][7] */, int cam_per_filter,
     const int* nk /* [batch] */, const int* ids /* [batch][stride] */, int stride, const double* meas /* [batch][stride][3] */,
     const double* Rb /* [batch][stride][rows][rows], lower triangles */, double gate, double lm_gate,
@@ -586,6 +585,56 @@ int eqf_observe_landmarks(eqf_filter* f, int kind, const double* cam /* NULL | [
     const int* consider_ids /* [batch][cstride] */, int cstride, unsigned char* used /* [batch][stride] or NULL */,
     double* Ht_out /* [batch][stride][rows][3] or NULL */, double* resid_out /* [batch][stride][rows] or NULL */,
     double* gamma /* [batch][ldg] or NULL */, int ldg, eqf_linear_report* report /* [batch] or NULL */);
+/* eqf_observe_landmarks ITERATED: the rows are re-formed at the estimate the update would give until the increment settles -- the
+ * iterated Kalman update, Gauss-Newton on the MAP cost -- and only the last linearisation is applied (csrc/eqf_iterate.hpp; DESIGN
+ * 4.5q).  For a measurement whose one linearisation at the prior is poor: a second camera's bearing or a range on a landmark that entered
+ * at the median depth, a surveyed position after drift.  Every argument of eqf_observe_landmarks has its meaning, its checks and its
+ * errors here; max_lin (1 .. EQF_ITER_MAX_LIN) is the largest number of linearisations and tol (absolute, in chart units, >= 0 and
+ * finite; 0: never stop early) the step below which a filter stops; EQF_ERR_INVALID otherwise.  Everything is fp64, per filter, and
+ * neither Sigma nor the state is written before the commit:
+ *   0  Linearisation 0 is eqf_observe_landmarks's, at the handle's estimate.  Each entry's verdict `used` is decided here and FROZEN:
+ *      later linearisations re-form the entries with verdict 1 only, and no entry is gated again, then or at the commit.
+ *   k  With M the landmark 3-blocks of the frozen-in entries: S_k = Ht_k Sigma_MM Ht_k^T + blockdiag(R_e), w = S_k^-1 r~_k,
+ *      g_{k+1} = Sigma_MM Ht_k^T w -- gamma = Sigma Ht^T S^-1 r~ on those rows; +0.0 on an entry whose landmark is considered.
+ *      last_step = max over entries and components |g_{k+1} - g_k|.  last_step <= tol (tol > 0): converged, the rows of linearisation k
+ *      are committed.  Otherwise Q_trial = Delta_i(g_{k+1,e}, p0_i) Q_i from the handle's UNCHANGED Q_i (eqf_apply_increment's plain
+ *      step on that landmark), the rows Ht_{k+1}, resid_{k+1} there, and r~_{k+1} = resid_{k+1} + Ht_{k+1} g_{k+1,e} (per row: the
+ *      residual, then one fused multiply-add per component of g in order).  Chart coordinates are truth minus estimate, so moving the
+ *      estimate by g leaves eps_0 = eps_k + g: r~ is the residual of the rows on the PRIOR's error, to the order to which the filter
+ *      itself treats Sigma as unchanged by a group step.  Intermediate points use the plain step whatever "innovation_lift" says.
+ *   K  The commit IS eqf_update_landmarks(local = 0) on the prior state with the committed rows (Ht_K, r~_K, Rb) and the frozen verdicts,
+ *      bit for bit and launch for launch from k_blk_gain on: gate, mask, "innovation_lift", the consider lists, gamma and report are
+ *      that call's, and a filter whose info is not 0 keeps every bit.  Ht_out / resid_out return the committed rows (resid_out is r~_K).
+ * iter_report[b] = {n_lin, status, last_step}: the linearisations taken, the last step seen (NaN with status 3), and status
+ *   0 converged; 1 ran out of linearisations (always so with max_lin = 1); 2 STALLED: an entry was not observable at a trial point (d
+ *   zero or not finite, a singular chart) -- the rows of the previous linearisation are committed; 3 an intermediate solve failed (S_k
+ *   not positive definite or a value not finite) -- the rows of linearisation k are committed and the commit's own info says what the
+ *   full factorisation makes of them; 4 masked out (n_lin = 0).
+ * g_trace [max_lin][batch][stride][3]: the increment on each entry's landmark block at which linearisation k was TAKEN; plane 0 is all
+ * zeros, and so are the planes of a filter behind its last linearisation (a trial point that stalled was not taken).
+ * All max_lin linearisations are enqueued without waiting; a per-filter flag on the device turns every later launch into a no-op for a
+ * filter that has stopped, so a filter's result has the same bits alone in a handle or anywhere in a batch, whatever its neighbours do.
+ * No atomics, every sum in one fixed order.  max_lin = 1 is eqf_observe_landmarks bit for bit and launch for launch; otherwise the call
+ * adds (max_lin - 1) (3 + the factorisation's 3 nb - 1) + 1 launches, nb = ceil(rows stride / 64) (iterate::extraLaunches).  With used,
+ * Ht_out, resid_out, gamma, report, g_trace and iter_report all NULL the call enqueues and returns.
+ * Workspace, per filter and beyond eqf_observe_landmarks's: (mp + 2 + 3 stride) mp + 6 stride + 5121 doubles, mp = rows stride rounded
+ * up to 64, a second rows array, and max_lin stride 3 doubles of trace.
+ * Not covered: the partitioned filter, fp32 handles (EQF_ERR_UNSUPPORTED), eqf_update_linear and eqf_process_vision, re-gating between
+ * linearisations, a line search, linearisation points taken with the innovation lift. */
+#define EQF_ITER_MAX_LIN 16
+typedef struct {
+    int n_lin;
+    int status;
+    double last_step;
+} eqf_iter_report;
+int eqf_observe_landmarks_iterated(eqf_filter* f, int kind, const double* cam /* NULL | [7] | [batch][7] */, int cam_per_filter,
+    const int* nk /* [batch] */, const int* ids /* [batch][stride] */, int stride, const double* meas /* [batch][stride][3] */,
+    const double* Rb /* [batch][stride][rows][rows], lower triangles */, double gate, double lm_gate,
+    const unsigned char* mask /* [batch] or NULL */, const int* n_consider /* [batch] or NULL */,
+    const int* consider_ids /* [batch][cstride] */, int cstride, int max_lin, double tol, unsigned char* used /* [batch][stride] or NULL */,
+    double* Ht_out /* [batch][stride][rows][3] or NULL */, double* resid_out /* [batch][stride][rows] or NULL */,
+    double* gamma /* [batch][ldg] or NULL */, int ldg, eqf_linear_report* report /* [batch] or NULL */,
+    double* g_trace /* [max_lin][batch][stride][3] or NULL */, eqf_iter_report* iter_report /* [batch] or NULL */);
 
 /* Moment matching over the filters of ONE handle, on the device (csrc/eqf_mixture.hpp): a weighted batch -- a Monte-Carlo study, a particle
  * set, a bank of hypotheses -- turned back into one mean and one covariance that includes the spread between its members, and several

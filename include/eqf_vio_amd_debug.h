@@ -63,6 +63,10 @@ int eqf_debug_sigma_local_all(eqf_filter* f);
 /* Test hook: the number of kernel launches the handle's most recent eqf_merge_filters or eqf_get_mixture_moments enqueued, counted
  * as they were made (it does not depend on the number of members); 0 before the first.  Does not touch the device or flush anything; EQF_ERR_INVALID for a NULL handle. */
 int eqf_debug_mixture_launches(eqf_filter* f);
+/* Test hook: the number of kernel launches the handle's most recent eqf_observe_landmarks_iterated ADDED to eqf_observe_landmarks's own,
+ * counted as they were made (csrc/eqf_iterate_host.hpp's extraLaunches states it); 0 before the first.  Does not touch the device or
+ * flush anything; EQF_ERR_INVALID for a NULL handle. */
+int eqf_debug_iterate_launches(eqf_filter* f);
 /* Test hook: the largest |entry| of the structural pad row and column (internal index 11, csrc/eqf_device.hpp) of filter b's covariance
  * (image = 0) or of slot b of the scratch image of eqf_get_sigma_local, where eqf_get_mixture_moments leaves P in slot ref (image = 1), over
  * the filter's own internal order 12 + 3 N; NaN if one is NaN.  Settles what the handle has deferred and synchronises.  EQF_ERR_INVALID
