@@ -139,6 +139,7 @@ class FrameScores:
 _lib = None
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
+_up = C.POINTER(C.c_ubyte)
 
 EXPORTED_SYMBOLS = [
     "eqf_settings_default", "eqf_create", "eqf_destroy", "eqf_reset", "eqf_process_imu", "eqf_process_vision",
@@ -374,6 +375,11 @@ def settings_from_dict(d):
 
 def _p(a):
     return a.ctypes.data_as(_dp)
+
+
+def _pn(a, ptr=_dp):
+    """an optional array (None: NULL) as a pointer"""
+    return None if a is None else a.ctypes.data_as(ptr)
 
 
 def _check(rc, what):
@@ -688,13 +694,10 @@ class FilterBatch:
         gamma[0:6], X <- VIOExp(liftInnovation(gamma[6:], xi0)) X, whatever the lift settings are; Sigma, the origin, the clock and the
         integrator stay (include/eqf_vio_amd.h: eqf_apply_increment).  gamma: array (B, n_max) or a list of per-filter vectors (n_b,);
         mask (B,): 0 leaves a filter alone, every bit.  Enqueues and returns."""
-        B = self.B
         G = self._rows(gamma, "apply_increment")
         if G.shape[1] != 1:
             raise ValueError("apply_increment: one increment per filter")
-        m = None if mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mask), (B,)) != 0, dtype=np.uint8)
-        _check(lib().eqf_apply_increment(self._h, _p(G), int(G.shape[2]), None if m is None else m.ctypes.data_as(C.POINTER(C.c_ubyte))),
-               "eqf_apply_increment")
+        _check(lib().eqf_apply_increment(self._h, _p(G), int(G.shape[2]), _pn(self._mask(mask), _up)), "eqf_apply_increment")
 
     def perturb(self, z, first=0, scale=None, stats=False):
         """sample_sigma(z, local=False, first, scale) with one z per filter and apply_increment of the result as one enqueued sequence on the
@@ -739,6 +742,28 @@ class FilterBatch:
             cid[b, :len(c)] = c
         return nc, cid, cstride
 
+    def _mask(self, mask):
+        """mask (B,), a scalar or None -> uint8 (B,) of zeros and ones, or None"""
+        return None if mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mask), (self.B,)) != 0, dtype=np.uint8)
+
+    def _padded_ids(self, idl, stride, what):
+        """the filters' id lists (int32 vectors) -> their lengths nk (B,), the ids padded with zeros to (B, stride) and stride (None: the
+        longest list, at least 1)"""
+        longest = max(1, max(len(i) for i in idl))
+        stride = longest if stride is None else int(stride)
+        if stride < longest:
+            raise ValueError(f"{what}: stride is shorter than the longest list")
+        idm = np.zeros((self.B, stride), dtype=np.int32)
+        for b, i in enumerate(idl):
+            idm[b, :len(i)] = i
+        return np.array([len(i) for i in idl], dtype=np.int32), idm, stride
+
+    @staticmethod
+    def _report(rep, **more):
+        """eqf_linear_report [B] as the dict the updates return: nis, logdet_S, loglik, dof, info (B,), then the call's further items"""
+        return dict(nis=np.array([s.nis for s in rep]), logdet_S=np.array([s.logdet_S for s in rep]), loglik=np.array([s.loglik for s in rep]),
+                    dof=np.array([s.dof for s in rep], dtype=np.int32), info=np.array([s.info for s in rep], dtype=np.int32), **more)
+
     def update_linear(self, H, resid, R, local=True, gate=float("inf"), mask=None, want_gamma=False, stats=True, consider=None):
         """A measurement update with m <= 16 linear rows for EVERY filter of the handle in one call (include/eqf_vio_amd.h:
         eqf_update_linear): resid = H eps + noise, noise ~ N(0, R), eps "truth minus estimate" in the coordinates of sigma_local() (local)
@@ -760,27 +785,19 @@ class FilterBatch:
         r = np.ascontiguousarray(np.broadcast_to(r, (B, m)))
         Rs = np.asarray(R, dtype=np.float64) if not isinstance(R, (list, tuple)) else np.stack([np.asarray(x, dtype=np.float64) for x in R])
         Rs = np.ascontiguousarray(np.broadcast_to(Rs, (B, m, m)))
-        mk = None if mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mask), (B,)) != 0, dtype=np.uint8)
+        mk = self._mask(mask)
         ldg = max(ldh, 11 + 3 * max(self.num_landmarks(b) for b in range(B))) if want_gamma else 0
         G = np.zeros((B, ldg)) if want_gamma else None
         rep = (LinearReport * B)() if (stats or want_gamma) else None
-        mkp = None if mk is None else mk.ctypes.data_as(C.POINTER(C.c_ubyte))
+        head = (self._h, int(bool(local)), m, _p(Hs), ldh, _p(r), _p(Rs), float(gate), _pn(mk, _up))
         if consider is None:
-            _check(lib().eqf_update_linear(self._h, int(bool(local)), m, _p(Hs), ldh, _p(r), _p(Rs), float(gate), mkp,
-                                           None if G is None else _p(G), ldg, rep),
-                   "eqf_update_linear")
+            _check(lib().eqf_update_linear(*head, _pn(G), ldg, rep), "eqf_update_linear")
         else:
             nc, cid, cstride = self._consider(consider, "update_linear")
-            _check(lib().eqf_update_linear_schmidt(self._h, int(bool(local)), m, _p(Hs), ldh, _p(r), _p(Rs), float(gate), mkp,
-                                                   nc.ctypes.data_as(_ip), cid.ctypes.data_as(_ip), cstride, None if G is None else _p(G), ldg, rep),
-                   "eqf_update_linear_schmidt")
+            _check(lib().eqf_update_linear_schmidt(*head, _pn(nc, _ip), _pn(cid, _ip), cstride, _pn(G), ldg, rep), "eqf_update_linear_schmidt")
         if rep is None:
             return None
-        out = dict(nis=np.array([s.nis for s in rep]), logdet_S=np.array([s.logdet_S for s in rep]), loglik=np.array([s.loglik for s in rep]),
-                   dof=np.array([s.dof for s in rep], dtype=np.int32), info=np.array([s.info for s in rep], dtype=np.int32))
-        if want_gamma:
-            out["gamma"] = G
-        return out
+        return self._report(rep, gamma=G) if want_gamma else self._report(rep)
 
     def update_landmarks(self, ids, H, resid, R, rows=None, local=True, gate=float("inf"), lm_gate=float("inf"), mask=None, wait=True,
                          stride=None, consider=None):
@@ -812,12 +829,7 @@ class FilterBatch:
                 raise ValueError("update_landmarks: rows cannot be taken from H")
             rows = shapes.pop()
         rows = int(rows)
-        longest = max(1, max(len(i) for i in idl))
-        stride = longest if stride is None else int(stride)
-        if stride < longest:
-            raise ValueError("update_landmarks: stride is shorter than the longest list")
-        nk = np.array([len(i) for i in idl], dtype=np.int32)
-        idm = np.zeros((B, stride), dtype=np.int32)
+        nk, idm, stride = self._padded_ids(idl, stride, "update_landmarks")
         Hs = np.zeros((B, stride, rows, 3))
         rs = np.zeros((B, stride, rows))
         Rs = np.zeros((B, stride, rows, rows))
@@ -825,33 +837,23 @@ class FilterBatch:
             k = int(nk[b])
             if k == 0:
                 continue
-            idm[b, :k] = idl[b]
             Hs[b, :k] = np.asarray(H[b], dtype=np.float64).reshape(k, rows, 3)
             rs[b, :k] = np.asarray(resid[b], dtype=np.float64).reshape(k, rows)
             Rs[b, :k] = np.broadcast_to(np.asarray(R[b], dtype=np.float64), (k, rows, rows))
-        mk = None if mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mask), (B,)) != 0, dtype=np.uint8)
-        up = C.POINTER(C.c_ubyte)
+        mk = self._mask(mask)
         ldg = 11 + 3 * max(self.num_landmarks(b) for b in range(B))
         G = np.zeros((B, ldg)) if wait else None
         used = np.zeros((B, stride), dtype=np.uint8) if wait else None
         rep = (LinearReport * B)() if wait else None
+        head = (self._h, int(bool(local)), rows, _pn(nk, _ip), _pn(idm, _ip), stride, _p(Hs), _p(rs), _p(Rs), float(gate), float(lm_gate),
+                _pn(mk, _up))
+        tail = (_pn(used, _up), _pn(G), ldg if wait else 0, rep)
         if consider is None:
-            _check(lib().eqf_update_landmarks(self._h, int(bool(local)), rows, nk.ctypes.data_as(_ip), idm.ctypes.data_as(_ip), stride, _p(Hs), _p(rs),
-                                              _p(Rs), float(gate), float(lm_gate), None if mk is None else mk.ctypes.data_as(up),
-                                              None if used is None else used.ctypes.data_as(up), None if G is None else _p(G), ldg if wait else 0, rep),
-                   "eqf_update_landmarks")
+            _check(lib().eqf_update_landmarks(*head, *tail), "eqf_update_landmarks")
         else:
             nc, cid, cstride = self._consider(consider, "update_landmarks")
-            _check(lib().eqf_update_landmarks_schmidt(self._h, int(bool(local)), rows, nk.ctypes.data_as(_ip), idm.ctypes.data_as(_ip), stride,
-                                                      _p(Hs), _p(rs), _p(Rs), float(gate), float(lm_gate),
-                                                      None if mk is None else mk.ctypes.data_as(up), nc.ctypes.data_as(_ip),
-                                                      cid.ctypes.data_as(_ip), cstride, None if used is None else used.ctypes.data_as(up),
-                                                      None if G is None else _p(G), ldg if wait else 0, rep),
-                   "eqf_update_landmarks_schmidt")
-        if not wait:
-            return None
-        return dict(nis=np.array([s.nis for s in rep]), logdet_S=np.array([s.logdet_S for s in rep]), loglik=np.array([s.loglik for s in rep]),
-                    dof=np.array([s.dof for s in rep], dtype=np.int32), info=np.array([s.info for s in rep], dtype=np.int32), used=used, gamma=G)
+            _check(lib().eqf_update_landmarks_schmidt(*head, _pn(nc, _ip), _pn(cid, _ip), cstride, *tail), "eqf_update_landmarks_schmidt")
+        return self._report(rep, used=used, gamma=G) if wait else None
 
     def observe_landmarks(self, kind, ids, meas, R, cam=None, gate=float("inf"), lm_gate=float("inf"), mask=None, consider=None, wait=True,
                           want_rows=False, stride=None, max_lin=1, tol=0.0, want_trace=False):
@@ -886,19 +888,13 @@ class FilterBatch:
         if not (len(ids) == len(meas) == len(R) == B):
             raise ValueError("observe_landmarks: one item per filter")
         idl = [np.asarray(x, dtype=np.int32).reshape(-1) for x in ids]
-        longest = max(1, max(len(i) for i in idl))
-        stride = longest if stride is None else int(stride)
-        if stride < longest:
-            raise ValueError("observe_landmarks: stride is shorter than the longest list")
-        nk = np.array([len(i) for i in idl], dtype=np.int32)
-        idm = np.zeros((B, stride), dtype=np.int32)
+        nk, idm, stride = self._padded_ids(idl, stride, "observe_landmarks")
         ms = np.zeros((B, stride, 3))
         Rs = np.zeros((B, stride, rows, rows))
         for b in range(B):
             k = int(nk[b])
             if k == 0:
                 continue
-            idm[b, :k] = idl[b]
             m = np.asarray(meas[b], dtype=np.float64).reshape(k, -1)
             ms[b, :k, :m.shape[1]] = m
             Rb = np.asarray(R[b], dtype=np.float64)
@@ -911,8 +907,7 @@ class FilterBatch:
                 raise ValueError("observe_landmarks: one camera offset, or one per filter")
             camp = np.ascontiguousarray([np.concatenate([np.asarray(q, dtype=np.float64).reshape(4), np.asarray(t, dtype=np.float64).reshape(3)])
                                          for q, t in pairs])
-        mk = None if mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mask), (B,)) != 0, dtype=np.uint8)
-        up = C.POINTER(C.c_ubyte)
+        mk = self._mask(mask)
         out = bool(wait or want_rows or want_trace)
         ldg = 11 + 3 * max(self.num_landmarks(b) for b in range(B))
         G = np.zeros((B, ldg)) if out else None
@@ -921,39 +916,27 @@ class FilterBatch:
         Ht = np.zeros((B, stride, rows, 3)) if want_rows else None
         rs = np.zeros((B, stride, rows)) if want_rows else None
         nc, cid, cstride = (None, None, 0) if consider is None else self._consider(consider, "observe_landmarks")
+        # both entry points take the same arguments: the iterated one max_lin and tol between them, the trace and its report behind them
+        head = (self._h, kind, _pn(camp), per, _pn(nk, _ip), _pn(idm, _ip), stride, _p(ms), _p(Rs), float(gate), float(lm_gate), _pn(mk, _up),
+                _pn(nc, _ip), _pn(cid, _ip), cstride)
+        tail = (_pn(used, _up), _pn(Ht), _pn(rs), _pn(G), ldg if out else 0, rep)
+        more = {}
         if iterated:
             irep = (IterReport * B)() if out else None
             trace = np.zeros((max(max_lin, 1), B, stride, 3)) if want_trace else None
-            _check(lib().eqf_observe_landmarks_iterated(
-                self._h, kind, None if camp is None else _p(camp), per, nk.ctypes.data_as(_ip), idm.ctypes.data_as(_ip), stride, _p(ms), _p(Rs),
-                float(gate), float(lm_gate), None if mk is None else mk.ctypes.data_as(up), None if nc is None else nc.ctypes.data_as(_ip),
-                None if cid is None else cid.ctypes.data_as(_ip), cstride, max_lin, float(tol), None if used is None else used.ctypes.data_as(up),
-                None if Ht is None else _p(Ht), None if rs is None else _p(rs), None if G is None else _p(G), ldg if out else 0, rep,
-                None if trace is None else _p(trace), irep), "eqf_observe_landmarks_iterated")
-            if not out:
-                return None
-            res = dict(nis=np.array([s.nis for s in rep]), logdet_S=np.array([s.logdet_S for s in rep]), loglik=np.array([s.loglik for s in rep]),
-                       dof=np.array([s.dof for s in rep], dtype=np.int32), info=np.array([s.info for s in rep], dtype=np.int32), used=used,
-                       gamma=G, n_lin=np.array([s.n_lin for s in irep], dtype=np.int32), status=np.array([s.status for s in irep], dtype=np.int32),
-                       last_step=np.array([s.last_step for s in irep]))
-            if want_rows:
-                res.update(Ht=Ht, resid=rs)
-            if want_trace:
-                res.update(g_trace=trace)
-            return res
-        _check(lib().eqf_observe_landmarks(self._h, kind, None if camp is None else _p(camp), per, nk.ctypes.data_as(_ip), idm.ctypes.data_as(_ip),
-                                           stride, _p(ms), _p(Rs), float(gate), float(lm_gate), None if mk is None else mk.ctypes.data_as(up),
-                                           None if nc is None else nc.ctypes.data_as(_ip), None if cid is None else cid.ctypes.data_as(_ip),
-                                           cstride, None if used is None else used.ctypes.data_as(up), None if Ht is None else _p(Ht),
-                                           None if rs is None else _p(rs), None if G is None else _p(G), ldg if out else 0, rep),
-               "eqf_observe_landmarks")
+            _check(lib().eqf_observe_landmarks_iterated(*head, max_lin, float(tol), *tail, _pn(trace), irep), "eqf_observe_landmarks_iterated")
+            if out:
+                more.update(n_lin=np.array([s.n_lin for s in irep], dtype=np.int32), status=np.array([s.status for s in irep], dtype=np.int32),
+                            last_step=np.array([s.last_step for s in irep]))
+        else:
+            _check(lib().eqf_observe_landmarks(*head, *tail), "eqf_observe_landmarks")
         if not out:
             return None
-        res = dict(nis=np.array([s.nis for s in rep]), logdet_S=np.array([s.logdet_S for s in rep]), loglik=np.array([s.loglik for s in rep]),
-                   dof=np.array([s.dof for s in rep], dtype=np.int32), info=np.array([s.info for s in rep], dtype=np.int32), used=used, gamma=G)
         if want_rows:
-            res.update(Ht=Ht, resid=rs)
-        return res
+            more.update(Ht=Ht, resid=rs)
+        if want_trace:
+            more.update(g_trace=trace)
+        return self._report(rep, used=used, gamma=G, **more)
 
     @staticmethod
     def _members(idx, w):

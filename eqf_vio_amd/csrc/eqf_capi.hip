@@ -132,7 +132,7 @@ struct BlkRoute {
     DevPtr<double> ws, out, obs;
     DevPtr<int> wi;
     size_t wsCap = 0, wiCap = 0, obsCap = 0;
-    bool ldsSet = false;
+    bool ldsSet = false, downLdsSet = false;  // (the factorisation's kernels; k_blk_downdate)
 };
 // the innovation lift of eqf_update_linear / eqf_update_landmarks / eqf_apply_increment / eqf_perturb_filters (eqf_lift.hpp;
 // eqf_set_option "innovation_lift"): the records [B][kLiftRec] of the last of these calls, and -- from the first call with the option on
@@ -1769,6 +1769,21 @@ int resolveGate(eqf_filter* f) {
     return visionCore(f, mids, f->gate.nb, f->gate.bearings, f->gate.bearStride, act, nullptr, &gated);
 }
 
+// Dynamic LDS beyond 64 KB for the kernels of an optional route (see allowUpdateLds): applied once per handle, under the flag `set`, which
+// is raised here and nowhere else -- one flag per list of kernels.
+struct LdsWant {
+    const void* fn;
+    int bytes;
+};
+template <class K>
+const void* ldsFn(K* kernel) { return reinterpret_cast<const void*>(kernel); }
+int allowRouteLds(bool& set, std::initializer_list<LdsWant> wants) {
+    if (set) return EQF_OK;
+    for (const LdsWant& w : wants) HIPC(hipFuncSetAttribute(w.fn, hipFuncAttributeMaxDynamicSharedMemorySize, w.bytes));
+    set = true;
+    return EQF_OK;
+}
+
 // ---- the blocked factorisation (eqf_factor.hpp): the one launch loop of every route that factors
 // Enqueues A = L L^T of `images` images (grid.y) of order at most mMax each (nb block columns: the one place on the host where an order
 // becomes a block-column count for a launch of these kernels), with rhsRows block rows of right-hand side carried along: diag(0) always (it clears the pivot word, also for an empty matrix), then per block column the diagonal block, the panel if a
@@ -1777,11 +1792,8 @@ int resolveGate(eqf_filter* f) {
 template <class Args>
 int enqueueFactor(hipStream_t stream, bool& ldsSet, const Args& a, int images, int mMax, int rhsRows, int* launches = nullptr) {
     const int nb = mMax <= 0 ? 0 : (mMax + kSB - 1) / kSB;
-    if (!ldsSet) {  // (dynamic LDS beyond 64 KB: see allowUpdateLds)
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_factor_panel<Args>), hipFuncAttributeMaxDynamicSharedMemorySize, kFactorPanelLdsBytes));
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_factor_trail<Args>), hipFuncAttributeMaxDynamicSharedMemorySize, kFactorTrailLdsBytes));
-        ldsSet = true;
-    }
+    const int rc = allowRouteLds(ldsSet, {{ldsFn(&k_factor_panel<Args>), kFactorPanelLdsBytes}, {ldsFn(&k_factor_trail<Args>), kFactorTrailLdsBytes}});
+    if (rc) return rc;
     int made = 1;
     hipLaunchKernelGGL(k_factor_diag<Args>, dim3(1, images), dim3(256), kLdsFactorBytes, stream, a, 0);
     for (int K = 0; K < nb; ++K) {
@@ -3170,11 +3182,13 @@ int eqf_get_nees(eqf_filter* f, int local, int first, int nrhs, const double* er
 // ---- the innovation lift of the calls that inform a filter outside a vision frame (eqf_lift.hpp; decisions and layout: eqf_lift_host.hpp)
 static_assert(lift::kRefBase == kBase && lift::kPadBase == kLm0 && lift::kOff == kLiftOff && lift::kRhs == kLiftRhs && lift::kRec == kLiftRec &&
               lift::kHead == kLiftHead && kLiftHead == kLinHead && lift::kWordFailed == kLiftWordFailed &&
-              lift::kWordFailed != blocks::kInfoIdle && lift::kPadPos == kBase - kLiftOff,
+              lift::kWordFailed != blocks::kInfoIdle && lift::kWordIdle == blocks::kInfoIdle && lift::kPadPos == kBase - kLiftOff,
     "eqf_lift_host.hpp repeats the layout constants");
 static_assert(border::kBlock == kSB && border::kStage == kQB && border::kRows == kBorderRows, "eqf_border_host.hpp repeats the layout constants");
 namespace {
 int liftCallKind(const eqf_filter* f) { return lift::callKind(f->lift.opt, f->prm.useInnovationLift, f->prm.useDiscreteInnovationLift); }
+// lift::updateReport's fields as the C ABI has them
+eqf_linear_report linearReport(const lift::UpdateReport& r) { return eqf_linear_report{r.nis, r.logdet_S, r.loglik, r.dof, r.info}; }
 // What a call needs before any effect: the records always, the factorisation's buffers where the call factors.
 int liftReserve(eqf_filter* f, bool factors) {
     const size_t B = size_t(f->B);
@@ -3208,6 +3222,96 @@ int liftEnqueue(eqf_filter* f, const double* gamma, long long strideG, int offG,
     ia.liftStride = kLiftRec;
     return EQF_OK;
 }
+
+// ---- the Schmidt (consider) variants (eqf_schmidt.hpp; the host's decisions: eqf_schmidt_host.hpp)
+static_assert(schmidt::kOk == EQF_OK && schmidt::kInvalid == EQF_ERR_INVALID && schmidt::kCapacity == EQF_ERR_CAPACITY &&
+                  schmidt::kUnsorted == EQF_ERR_UNSORTED && schmidt::kPadBase == kLm0 && schmidt::kTile == kSB,
+    "eqf_schmidt_host.hpp repeats the layout constants and the error codes");
+// the consider lists of a call as the C ABI has them
+struct SchCall {
+    const int* n;
+    const int* ids;
+    int cstride;
+};
+// the partition's image, from capacity and batch
+int schReserve(eqf_filter* f) {
+    const workspace::Want w[] = {WANT_STAGED(f->sch.img, (schmidt::Image{size_t(f->B), size_t(f->ld)}.bytes()))};
+    return reserveSlots(f, w);
+}
+// Builds every filter's partition from the handle's id mirror in the pinned image (schReserve has run, the lists are checked); the launch of
+// k_schmidt_gamma brings it to the device.  sa: the arguments both kernels share, but for the verdict records and gamma; gridX: the
+// gathered downdate's.
+int schUpload(eqf_filter* f, const SchCall& sc, const int* N, SchArgs& sa, int& gridX) {
+    const int B = f->B;
+    const schmidt::Image im{size_t(B), size_t(f->ld)};
+    HIPC(f->sch.img.wait());
+    std::vector<int> act;
+    std::vector<unsigned char> fl;
+    int nAmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int nc = sc.n ? sc.n[b] : 0;
+        schmidt::buildActive(N[b], f->ids[b].data(), nc, nc ? sc.ids + size_t(b) * sc.cstride : nullptr, act, fl);
+        schmidt::fillFilter(im, size_t(b), act, fl, f->sch.img.host);
+        nAmax = std::max(nAmax, int(act.size()));
+    }
+    const int nMax = schmidt::paddedOrder(maxN(f));
+    sa = SchArgs{};
+    sa.g = f->g[f->pG]; sa.Sigma = static_cast<double*>(f->Sigma[f->pS]); sa.ld = f->ld; sa.sigmaStride = f->sigmaStride;
+    sa.cnt = reinterpret_cast<const int*>(f->sch.img.dev + im.offCount()); sa.act = reinterpret_cast<const int*>(f->sch.img.dev + im.offActive());
+    sa.flag = reinterpret_cast<const unsigned char*>(f->sch.img.dev + im.offFlag()); sa.pitch = f->ld; sa.nJT = schmidt::colTiles(nMax);
+    sa.cntH = reinterpret_cast<const int*>(f->sch.img.host.dev + im.offCount()); sa.actH = reinterpret_cast<const int*>(f->sch.img.host.dev + im.offActive());
+    sa.flagH = reinterpret_cast<const unsigned char*>(f->sch.img.host.dev + im.offFlag());
+    sa.cntW = reinterpret_cast<int*>(f->sch.img.dev + im.offCount()); sa.actW = reinterpret_cast<int*>(f->sch.img.dev + im.offActive());
+    sa.flagW = reinterpret_cast<unsigned char*>(f->sch.img.dev + im.offFlag());
+    gridX = schmidt::gridX(nAmax, nMax);
+    return EQF_OK;
+}
+// (sch.img's event: the pinned image has been read)
+int schGammaLaunch(eqf_filter* f, const SchArgs& sa) {
+    hipLaunchKernelGGL(k_schmidt_gamma, dim3((f->ld + 255) / 256, f->B), dim3(256), 0, f->stream, sa);
+    HIPC(f->sch.img.record(f->stream));
+    return EQF_OK;
+}
+
+// ---- the closing stage of every call that leaves an increment on the device: eqf_update_linear, eqf_update_landmarks and their variants
+// behind the solve, eqf_apply_increment and eqf_perturb_filters behind their upload or draw
+struct IncCall {
+    double* gamma;              // filter b's increment: gamma[b * strideG + j] is internal index off + j
+    long long strideG;
+    int off;
+    const unsigned char* mask;  // device [B], 0 leaves a filter alone; nullptr: none
+    double* verdict;            // records [B][kLinHead] whose entry 3 the lift and the group step obey; nullptr: none
+    bool liftRefuses;           // ... an update's: a lift that fails writes its refusal there
+    const SchCall* sch;         // the Schmidt stage: nullptr, or the consider lists (checked; schReserve has run) ...
+    const int* N;               // ... and every filter's landmark count
+};
+// Enqueues: the Schmidt partition and k_schmidt_gamma where the call has consider lists (in front of the lift and the group step: they see
+// the masked gamma); the lift (it reads the Sigma the call started from and may still refuse a filter: in front of the downdate); the
+// route's downdate -- downdate(sa, gridX) -> rc, sa the Schmidt arguments and gridX the gathered downdate's grid, or nullptr and 0 --;
+// the group step, behind the verdict.  (liftReserve has run.)
+extern "C++" template <class Downdate>  // (this part of the file lies inside the C ABI's linkage block)
+int closeIncrement(eqf_filter* f, const IncCall& c, Downdate&& downdate) {
+    SchArgs sa{};
+    int schGrid = 0;
+    if (c.sch) {
+        int rc = schUpload(f, *c.sch, c.N, sa, schGrid);
+        if (rc) return rc;
+        sa.out = c.verdict; sa.gamma = c.gamma; sa.strideG = c.strideG;
+        rc = schGammaLaunch(f, sa);
+        if (rc) return rc;
+    }
+    IncArgs ia{};
+    ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = c.gamma; ia.strideG = c.strideG; ia.off = c.off;
+    ia.mask = c.mask; ia.info = c.verdict;
+    int rc = liftEnqueue(f, c.gamma, c.strideG, c.off, c.mask, c.verdict, c.liftRefuses, ia);
+    if (!rc) rc = downdate(c.sch ? &sa : nullptr, schGrid);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_apply_increment, dim3(f->B), dim3(256), 0, f->stream, ia);
+    HIPC(hipGetLastError());
+    f->csValid = false;  // (C Sigma / S left by an earlier burst describe the old Sigma and the landmarks as they were)
+    return EQF_OK;
+}
+constexpr auto noDowndate = [](const SchArgs*, int) { return int(EQF_OK); };  // (a call that leaves Sigma alone)
 }  // namespace
 
 int eqf_get_lift_report(eqf_filter* f, int b, eqf_lift_report* out) {
@@ -3326,14 +3430,7 @@ int eqf_apply_increment(eqf_filter* f, const double* gamma, int ldg, const unsig
         h.mask[b] = mask ? mask[b] : 1;
     }
     HIPC(f->samp.small.upload(sizeof(double) * size_t(B) * len + size_t(B), f->stream, sizeof(double) * size_t(B)));  // (the vectors; the mask lies behind)
-    IncArgs a{};
-    a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.cap = f->cap; a.gamma = d.vec; a.strideG = len; a.off = 0; a.mask = d.mask;
-    rc = liftEnqueue(f, d.vec, len, 0, d.mask, nullptr, false, a);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, a);
-    HIPC(hipGetLastError());
-    f->csValid = false;  // (C Sigma / S left by an earlier burst were built around the landmarks as they were)
-    return EQF_OK;
+    return closeIncrement(f, IncCall{d.vec, len, 0, d.mask, nullptr, false, nullptr, nullptr}, noDowndate);
 }
 
 int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, const double* scale, eqf_sigma_stats* stats) {
@@ -3363,15 +3460,9 @@ int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, cons
     HIPC(f->samp.small.record(f->stream));
     // (a submatrix of order 0 -- first = 11, no landmarks anywhere -- has no sample: k_apply_increment then reads no entry of the image)
     sampTrmm(f, off, 1, ldE, d.scale);
-    IncArgs a{};
-    a.g = f->g[f->pG]; a.p0 = f->p0; a.Q = f->Q[f->pG]; a.cap = f->cap; a.gamma = f->samp.E; a.strideG = ldE; a.off = off; a.mask = d.mask;
-    a.info = f->nees.out;
-    // (the lift factors Sigma[6:, 6:] in the scratch image: the draw's factor has been consumed by sampTrmm)
-    rc = liftEnqueue(f, f->samp.E, ldE, off, d.mask, f->nees.out, false, a);
+    // (the lift factors Sigma[6:, 6:] in the scratch image: the draw's factor has been consumed by sampTrmm; the draw's records are the verdict)
+    rc = closeIncrement(f, IncCall{f->samp.E, ldE, off, d.mask, f->nees.out, false, nullptr, nullptr}, noDowndate);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, a);
-    HIPC(hipGetLastError());
-    f->csValid = false;
     if (!stats) return EQF_OK;
     std::vector<double> hO(size_t(B) * (kNeesHead + kNeesRhs));
     HIPC(hipMemcpyAsync(hO.data(), f->nees.out, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
@@ -3391,56 +3482,6 @@ int linReserve(eqf_filter* f) {
     const workspace::Want w[] = {WANT_STAGED(f->lin.small, sl.bytes()), want(f->lin.ws, sizeof(double) * size_t(wl.stride()) * f->B),
         want(f->lin.out, sizeof(double) * size_t(kLinHead) * f->B)};
     return reserveSlots(f, w);
-}
-
-// ---- the Schmidt (consider) variants (eqf_schmidt.hpp; the host's decisions: eqf_schmidt_host.hpp)
-static_assert(schmidt::kOk == EQF_OK && schmidt::kInvalid == EQF_ERR_INVALID && schmidt::kCapacity == EQF_ERR_CAPACITY &&
-                  schmidt::kUnsorted == EQF_ERR_UNSORTED && schmidt::kPadBase == kLm0 && schmidt::kTile == kSB,
-    "eqf_schmidt_host.hpp repeats the layout constants and the error codes");
-// the consider lists of a call as the C ABI has them
-struct SchCall {
-    const int* n;
-    const int* ids;
-    int cstride;
-};
-// the partition's image, from capacity and batch
-int schReserve(eqf_filter* f) {
-    const workspace::Want w[] = {WANT_STAGED(f->sch.img, (schmidt::Image{size_t(f->B), size_t(f->ld)}.bytes()))};
-    return reserveSlots(f, w);
-}
-// Builds every filter's partition from the handle's id mirror in the pinned image (schReserve has run, the lists are checked); the launch of
-// k_schmidt_gamma brings it to the device.  sa: the arguments both kernels share, but for the verdict records and gamma; gridX: the
-// gathered downdate's.
-int schUpload(eqf_filter* f, const SchCall& sc, const int* N, SchArgs& sa, int& gridX) {
-    const int B = f->B;
-    const schmidt::Image im{size_t(B), size_t(f->ld)};
-    HIPC(f->sch.img.wait());
-    std::vector<int> act;
-    std::vector<unsigned char> fl;
-    int nAmax = 0;
-    for (int b = 0; b < B; ++b) {
-        const int nc = sc.n ? sc.n[b] : 0;
-        schmidt::buildActive(N[b], f->ids[b].data(), nc, nc ? sc.ids + size_t(b) * sc.cstride : nullptr, act, fl);
-        schmidt::fillFilter(im, size_t(b), act, fl, f->sch.img.host);
-        nAmax = std::max(nAmax, int(act.size()));
-    }
-    const int nMax = schmidt::paddedOrder(maxN(f));
-    sa = SchArgs{};
-    sa.g = f->g[f->pG]; sa.Sigma = static_cast<double*>(f->Sigma[f->pS]); sa.ld = f->ld; sa.sigmaStride = f->sigmaStride;
-    sa.cnt = reinterpret_cast<const int*>(f->sch.img.dev + im.offCount()); sa.act = reinterpret_cast<const int*>(f->sch.img.dev + im.offActive());
-    sa.flag = reinterpret_cast<const unsigned char*>(f->sch.img.dev + im.offFlag()); sa.pitch = f->ld; sa.nJT = schmidt::colTiles(nMax);
-    sa.cntH = reinterpret_cast<const int*>(f->sch.img.host.dev + im.offCount()); sa.actH = reinterpret_cast<const int*>(f->sch.img.host.dev + im.offActive());
-    sa.flagH = reinterpret_cast<const unsigned char*>(f->sch.img.host.dev + im.offFlag());
-    sa.cntW = reinterpret_cast<int*>(f->sch.img.dev + im.offCount()); sa.actW = reinterpret_cast<int*>(f->sch.img.dev + im.offActive());
-    sa.flagW = reinterpret_cast<unsigned char*>(f->sch.img.dev + im.offFlag());
-    gridX = schmidt::gridX(nAmax, nMax);
-    return EQF_OK;
-}
-// (sch.img's event: the pinned image has been read)
-int schGammaLaunch(eqf_filter* f, const SchArgs& sa) {
-    hipLaunchKernelGGL(k_schmidt_gamma, dim3((f->ld + 255) / 256, f->B), dim3(256), 0, f->stream, sa);
-    HIPC(f->sch.img.record(f->stream));
-    return EQF_OK;
 }
 
 // eqf_update_linear (sc == nullptr: the launches it has always enqueued) and eqf_update_linear_schmidt
@@ -3488,32 +3529,19 @@ int linUpdate(eqf_filter* f, int local, int m, const double* H, int ldh, const d
     rc = profiled(f, EQF_PROF_LIN_ROWS, [&] { hipLaunchKernelGGL(k_lin_rows, dim3(B), dim3(256), 0, f->stream, a); });
     if (!rc) rc = profiled(f, EQF_PROF_LIN_GAIN, [&] { hipLaunchKernelGGL(k_lin_gain, dim3(nt, B), dim3(256), kLinGainLdsBytes, f->stream, a); });
     if (!rc) rc = profiled(f, EQF_PROF_LIN_SOLVE, [&] { hipLaunchKernelGGL(k_lin_solve, dim3(B), dim3(256), 0, f->stream, a); });
-    SchArgs sa{};
-    int schGrid = 0;
-    if (!rc && sc) {
-        rc = schUpload(f, *sc, N.data(), sa, schGrid);
-        sa.out = f->lin.out; sa.gamma = f->lin.ws + wl.offGamma(); sa.strideG = wl.stride();
-        if (!rc) rc = schGammaLaunch(f, sa);  // (in front of the lift and the group step: they see the masked gamma)
-    }
-    // the group step, behind the solve's verdict (entry 3 of the record, where eqf_nees.hpp's info sits)
-    IncArgs ia{};
-    ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = f->lin.ws + wl.offGamma(); ia.strideG = wl.stride();
-    ia.off = 0; ia.mask = nullptr; ia.info = f->lin.out;
-    // the lift reads the Sigma the call started from and may still refuse the filter: in front of the downdate
-    if (!rc) rc = liftEnqueue(f, ia.gamma, ia.strideG, 0, nullptr, f->lin.out, true, ia);
-    if (!rc && sc) {
-        const SchLin lay{f->lin.ws + wl.offY(), wl.stride(), f->ld};
-        rc = profiled(f, EQF_PROF_LIN_DOWNDATE, [&] {
-            hipLaunchKernelGGL(k_schmidt_downdate<SchLin>, dim3(schGrid, B), dim3(256), schmidtLdsBytes<SchLin>(), f->stream, sa, lay);
-        });
-    } else if (!rc) {
-        rc = profiled(f, EQF_PROF_LIN_DOWNDATE,
-            [&] { hipLaunchKernelGGL(k_lin_downdate, dim3(linear::triTiles(nt), B), dim3(256), 0, f->stream, a); });
-    }
     if (rc) return rc;
-    hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, ia);
-    HIPC(hipGetLastError());
-    f->csValid = false;  // (C Sigma / S left by an earlier burst describe the old Sigma and the old landmarks)
+    // the group step obeys the solve's verdict (entry 3 of the record, where eqf_nees.hpp's info sits)
+    rc = closeIncrement(f, IncCall{f->lin.ws + wl.offGamma(), wl.stride(), 0, nullptr, f->lin.out, true, sc, N.data()},
+        [&](const SchArgs* sa, int schGrid) {
+            if (!sa)
+                return profiled(f, EQF_PROF_LIN_DOWNDATE,
+                    [&] { hipLaunchKernelGGL(k_lin_downdate, dim3(linear::triTiles(nt), B), dim3(256), 0, f->stream, a); });
+            const SchLin lay{f->lin.ws + wl.offY(), wl.stride(), f->ld};
+            return profiled(f, EQF_PROF_LIN_DOWNDATE, [&] {
+                hipLaunchKernelGGL(k_schmidt_downdate<SchLin>, dim3(schGrid, B), dim3(256), schmidtLdsBytes<SchLin>(), f->stream, *sa, lay);
+            });
+        });
+    if (rc) return rc;
     if (!gamma && !report) return EQF_OK;
     std::vector<double> hO(size_t(B) * kLinHead), hG;
     HIPC(hipMemcpyAsync(hO.data(), f->lin.out, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
@@ -3525,17 +3553,8 @@ int linUpdate(eqf_filter* f, int local, int m, const double* H, int ldh, const d
     HIPC(hipStreamSynchronize(f->stream));
     for (int b = 0; b < B; ++b) {
         const double* o = hO.data() + size_t(b) * kLinHead;
-        const int info = int(o[3]);
-        if (report) {
-            const bool solved = lift::updateSolved(info);
-            const double nan = std::nan("");
-            report[b].nis = solved ? o[0] : nan;
-            report[b].logdet_S = solved ? o[1] : nan;
-            report[b].loglik = solved ? o[2] : nan;
-            report[b].dof = m;
-            report[b].info = lift::mergeInfo(info);
-        }
-        if (gamma) linear::unpackGamma(hG.data() + size_t(b) * f->ld, N[b], gamma + size_t(b) * ldg, info != 0);
+        if (report) report[b] = linearReport(lift::updateReport(o, m, false));
+        if (gamma) linear::unpackGamma(hG.data() + size_t(b) * f->ld, N[b], gamma + size_t(b) * ldg, int(o[3]) != 0);
     }
     return EQF_OK;
 }
@@ -3557,15 +3576,7 @@ int eqf_update_linear_schmidt(eqf_filter* f, int local, int m, const double* H, 
 static_assert(blocks::kRefBase == kBase && blocks::kPadBase == kLm0 && blocks::kTile == kSB && blocks::kHead == kLinHead,
     "eqf_blocks_host.hpp repeats the layout constants");
 namespace {
-// The buffers of eqf_update_landmarks for this call's shape; what is there and large enough is kept.  obsBytes: the rows array of
-// eqf_observe_landmarks (0: not this call's).
-int blkReserve(eqf_filter* f, size_t smallBytes, const blocks::WorkLayout& wl, size_t obsBytes) {
-    const workspace::Want w[] = {WANT_STAGED(f->blk.small, smallBytes), want(f->blk.ws, sizeof(double) * size_t(wl.strideD()) * f->B, &f->blk.wsCap),
-        want(f->blk.wi, sizeof(int) * size_t(wl.strideI()) * f->B, &f->blk.wiCap), want(f->blk.out, sizeof(double) * size_t(kLinHead) * f->B),
-        want(f->blk.obs, obsBytes, &f->blk.obsCap)};
-    return reserveSlots(f, w);
-}
-// what eqf_observe_landmarks hands blkUpdate in place of rows
+// what eqf_observe_landmarks hands the call in place of rows
 struct ObsCall {
     int kind;
     const double* cam;
@@ -3581,243 +3592,297 @@ struct IterCall {
     double* gTrace;
     eqf_iter_report* rep;
 };
-// the buffers of the intermediate linearisations; what is there and large enough is kept
-int iterReserve(eqf_filter* f, const iterate::WorkLayout& il, int maxLin, int stride) {
-    const workspace::Want w[] = {want(f->iter.ws, sizeof(double) * size_t(il.strideD()) * f->B, &f->iter.wsCap),
-        want(f->iter.wi, sizeof(int) * size_t(iterate::WorkLayout::kInts) * f->B, &f->iter.wiCap),
-        want(f->iter.trace, sizeof(double) * iterate::traceDoubles(maxLin, f->B, stride), &f->iter.traceCap)};
-    return reserveSlots(f, w);
+// One call of the route as its four entry points fill it: eqf_update_landmarks (sch, obs, iter nullptr: the launches it has always
+// enqueued), eqf_update_landmarks_schmidt (sch), eqf_observe_landmarks (obs: local = 0, Hb and resid nullptr -- k_obs_rows forms the rows on
+// the device in k_blk_rows's place) and eqf_observe_landmarks_iterated (obs and iter: with more than one linearisation the kernels of
+// eqf_iterate.hpp run between k_obs_rows and k_blk_gain and leave the committed rows where k_obs_rows left its own)
+struct BlkCall {
+    int local, rows;
+    const int *nk, *ids;
+    int stride;
+    const double *Hb, *resid, *Rb;
+    double gate, lmGate;
+    const unsigned char* mask;
+    const SchCall* sch;
+    const ObsCall* obs;
+    const IterCall* iter;
+    unsigned char* used;
+    double* gamma;
+    int ldg;
+    eqf_linear_report* report;
+};
+// What the call's shape decides, once, behind the checks: the layouts; where the operands both kinds of image hold lie in this call's
+// (observe::SmallLayout with obs, blocks::SmallLayout without); whether intermediate linearisations run; the bytes of the image and of the
+// rows array (two of them when iterating, none without obs); the grids' tile counts
+struct BlkPlan {
+    blocks::SmallLayout sl;
+    observe::SmallLayout ol;
+    observe::RowsLayout orl;
+    blocks::WorkLayout wl;
+    iterate::WorkLayout il;
+    bool iterating;
+    size_t smallBytes, obsBytes, offR, offIdx, offNk, offMask;
+    int nMax, nt, nPT;
+};
+BlkPlan blkPlan(const eqf_filter* f, const BlkCall& c) {
+    BlkPlan p{{f->B, c.stride, c.rows}, {f->B, c.stride, c.rows}, {f->B, c.stride, c.rows}, {f->ld, c.stride, c.rows, kDRec},
+        {c.stride, c.rows, kDRec}};
+    p.iterating = c.iter && c.iter->maxLin > 1;
+    p.smallBytes = p.iterating ? iterate::smallBytes(p.ol) : (c.obs ? p.ol.bytes() : p.sl.bytes());
+    p.obsBytes = c.obs ? sizeof(double) * p.orl.doubles() * (p.iterating ? 2 : 1) : 0;
+    p.offR = c.obs ? p.ol.offR() : p.sl.offR(); p.offIdx = c.obs ? p.ol.offIdx() : p.sl.offIdx();
+    p.offNk = c.obs ? p.ol.offNk() : p.sl.offNk(); p.offMask = c.obs ? p.ol.offMask() : p.sl.offMask();
+    p.nMax = maxN(f); p.nt = blocks::rowTiles(p.nMax); p.nPT = blocks::pairTiles(c.stride);
+    return p;
 }
 
-// eqf_update_landmarks (sc == nullptr: the launches it has always enqueued), eqf_update_landmarks_schmidt and, with oc,
-// eqf_observe_landmarks: local = 0, Hb and resid nullptr -- k_obs_rows forms the rows on the device in k_blk_rows's place; with ic (and
-// more than one linearisation) the kernels of eqf_iterate.hpp run between k_obs_rows and k_blk_gain and leave the committed rows where
-// k_obs_rows left its own
-int blkUpdate(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb, const double* resid,
-    const double* Rb, double gate, double lm_gate, const unsigned char* mask, const SchCall* sc, const ObsCall* oc, unsigned char* used,
-    double* gamma, int ldg, eqf_linear_report* report, const IterCall* ic = nullptr) {
+// The argument checks.  Behind GATE (queued IMU calls and a pending gate first: the gate may still change the landmark lists) N holds the
+// landmark counts.
+int blkCheck(eqf_filter* f, const BlkCall& c, std::vector<int>& N) {
     if (!f) return EQF_ERR_INVALID;
-    if (ic && !iterate::argsOk(ic->maxLin, ic->tol)) return EQF_ERR_INVALID;
-    if (oc ? !observe::headArgsOk(oc->kind, oc->camPerFilter, nk, ids, stride, oc->meas, Rb, gate, lm_gate)
-           : !blocks::headArgsOk(local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate))
+    const ObsCall* oc = c.obs;
+    if (c.iter && !iterate::argsOk(c.iter->maxLin, c.iter->tol)) return EQF_ERR_INVALID;
+    if (oc ? !observe::headArgsOk(oc->kind, oc->camPerFilter, c.nk, c.ids, c.stride, oc->meas, c.Rb, c.gate, c.lmGate)
+           : !blocks::headArgsOk(c.local, c.rows, c.nk, c.ids, c.stride, c.Hb, c.resid, c.Rb, c.gate, c.lmGate))
         return EQF_ERR_INVALID;
     if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
-    GATE(f);  // (queued IMU calls and a pending gate first: the gate may still change the landmark lists)
+    GATE(f);
     const int B = f->B;
-    std::vector<int> N(B);
+    N.resize(B);
     for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
-    switch (oc ? observe::argsCheck(oc->kind, oc->cam, oc->camPerFilter, nk, ids, stride, oc->meas, Rb, mask, gamma, ldg, B, N.data(), f->cap)
-               : blocks::argsCheck(rows, nk, ids, stride, Hb, resid, Rb, mask, gamma, ldg, B, N.data(), f->cap)) {
-        case 1: return EQF_ERR_INVALID;
-        case 2: return EQF_ERR_UNSORTED;
-        case 3: return EQF_ERR_CAPACITY;
-        default: break;
+    const int bad = oc ? observe::argsCheck(oc->kind, oc->cam, oc->camPerFilter, c.nk, c.ids, c.stride, oc->meas, c.Rb, c.mask, c.gamma, c.ldg, B,
+                             N.data(), f->cap)
+                       : blocks::argsCheck(c.rows, c.nk, c.ids, c.stride, c.Hb, c.resid, c.Rb, c.mask, c.gamma, c.ldg, B, N.data(), f->cap);
+    if (bad) return bad == 1 ? EQF_ERR_INVALID : (bad == 2 ? EQF_ERR_UNSORTED : EQF_ERR_CAPACITY);
+    return c.sch ? schmidt::checkLists(B, f->cap, c.sch->n, c.sch->ids, c.sch->cstride) : int(EQF_OK);
+}
+
+// Every buffer of the call for its shape -- its own, the intermediate linearisations', the lift's, the Schmidt partition's; what is there
+// and large enough is kept -- and the dynamic LDS of its two downdates
+int blkReserve(eqf_filter* f, const BlkCall& c, const BlkPlan& p) {
+    const size_t B = size_t(f->B);
+    const workspace::Want w[] = {WANT_STAGED(f->blk.small, p.smallBytes), want(f->blk.ws, sizeof(double) * size_t(p.wl.strideD()) * B, &f->blk.wsCap),
+        want(f->blk.wi, sizeof(int) * size_t(p.wl.strideI()) * B, &f->blk.wiCap), want(f->blk.out, sizeof(double) * size_t(kLinHead) * B),
+        want(f->blk.obs, p.obsBytes, &f->blk.obsCap)};
+    int rc = reserveSlots(f, w);
+    if (!rc && p.iterating) {
+        const workspace::Want wi[] = {want(f->iter.ws, sizeof(double) * size_t(p.il.strideD()) * B, &f->iter.wsCap),
+            want(f->iter.wi, sizeof(int) * size_t(iterate::WorkLayout::kInts) * B, &f->iter.wiCap),
+            want(f->iter.trace, sizeof(double) * iterate::traceDoubles(c.iter->maxLin, f->B, c.stride), &f->iter.traceCap)};
+        rc = reserveSlots(f, wi);
     }
-    if (sc) {
-        const int bad = schmidt::checkLists(B, f->cap, sc->n, sc->ids, sc->cstride);
-        if (bad) return bad;
-    }
-    const blocks::SmallLayout sl{B, stride, rows};
-    const observe::SmallLayout ol{B, stride, rows};
-    const observe::RowsLayout orl{B, stride, rows};
-    const blocks::WorkLayout wl{f->ld, stride, rows, kDRec};
-    const iterate::WorkLayout il{stride, rows, kDRec};
-    const bool iterating = ic && ic->maxLin > 1;
-    const size_t smallBytes = iterating ? iterate::smallBytes(ol) : (oc ? ol.bytes() : sl.bytes()), offR = oc ? ol.offR() : sl.offR(), offIdx = oc ? ol.offIdx() : sl.offIdx(),
-                 offNk = oc ? ol.offNk() : sl.offNk(), offMask = oc ? ol.offMask() : sl.offMask();
-    int rc = blkReserve(f, smallBytes, wl, oc ? sizeof(double) * orl.doubles() * (iterating ? 2 : 1) : 0);
-    if (!rc && iterating) rc = iterReserve(f, il, ic->maxLin, stride);
-    if (!rc) rc = liftReserve(f, lift::callFactors(liftCallKind(f), maxN(f)));
-    if (!rc && sc) rc = schReserve(f);
-    if (rc) return rc;
-    if (sc && !f->sch.ldsSet) {  // (dynamic LDS beyond 64 KB, as k_blk_downdate's)
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schmidt_downdate<SchBlk>), hipFuncAttributeMaxDynamicSharedMemorySize,
-            schmidtLdsBytes<SchBlk>()));
-        f->sch.ldsSet = true;
-    }
-    if (!f->blk.ldsSet)  // (dynamic LDS beyond 64 KB: see allowUpdateLds; enqueueFactor sets its own kernels' and the flag)
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_blk_downdate), hipFuncAttributeMaxDynamicSharedMemorySize, kBlkDownLdsBytes));
-    if (local) {
-        rc = launchLocal(f, 0, B, false);  // (only writes the J records)
-        if (rc) return rc;
-    }
+    if (!rc) rc = liftReserve(f, lift::callFactors(liftCallKind(f), p.nMax));
+    if (!rc && c.sch) rc = schReserve(f);
+    if (!rc && c.sch) rc = allowRouteLds(f->sch.ldsSet, {{ldsFn(&k_schmidt_downdate<SchBlk>), int(schmidtLdsBytes<SchBlk>())}});
+    if (!rc) rc = allowRouteLds(f->blk.downLdsSet, {{ldsFn(&k_blk_downdate), kBlkDownLdsBytes}});
+    return rc;
+}
+
+// The call's operands into the pinned image and on their way to the device: the caller's arrays as they are, and per entry the landmark's
+// index in its filter's state (-1: the id is not there, the entry lies beyond nk or the filter is masked out); when iterating, one byte per
+// entry behind them: its landmark is a consider one
+int blkPack(eqf_filter* f, const BlkCall& c, const BlkPlan& p, const int* N) {
+    const int B = f->B, stride = c.stride, rows = c.rows;
+    const ObsCall* oc = c.obs;
+    const SchCall* sc = c.sch;
     HIPC(f->blk.small.wait());
     char* hs = f->blk.small.host;
-    const size_t ne = sl.entries();
+    const size_t ne = p.sl.entries();
     if (oc) {
-        double* hCam = reinterpret_cast<double*>(hs + ol.offCam());
+        double* hCam = reinterpret_cast<double*>(hs + p.ol.offCam());
         for (int b = 0; b < B; ++b) {
-            const bool read = oc->cam && (!oc->camPerFilter || !mask || mask[b]);  // (a masked filter's own offset is never read)
+            const bool read = oc->cam && (!oc->camPerFilter || !c.mask || c.mask[b]);  // (a masked filter's own offset is never read)
             observe::unitCam(read ? oc->cam + (oc->camPerFilter ? size_t(b) * observe::kCam : 0) : nullptr, hCam + size_t(b) * observe::kCam);
         }
-        std::memcpy(hs + ol.offMeas(), oc->meas, sizeof(double) * ne * 3);
+        std::memcpy(hs + p.ol.offMeas(), oc->meas, sizeof(double) * ne * 3);
     } else {
-        std::memcpy(hs + sl.offH(), Hb, sizeof(double) * ne * rows * 3);
-        std::memcpy(hs + sl.offResid(), resid, sizeof(double) * ne * rows);
+        std::memcpy(hs + p.sl.offH(), c.Hb, sizeof(double) * ne * rows * 3);
+        std::memcpy(hs + p.sl.offResid(), c.resid, sizeof(double) * ne * rows);
     }
-    std::memcpy(hs + offR, Rb, sizeof(double) * ne * rows * rows);
-    int* hIdx = reinterpret_cast<int*>(hs + offIdx);
-    int* hNk = reinterpret_cast<int*>(hs + offNk);
-    unsigned char* hm = reinterpret_cast<unsigned char*>(hs + offMask);
+    std::memcpy(hs + p.offR, c.Rb, sizeof(double) * ne * rows * rows);
+    int* hIdx = reinterpret_cast<int*>(hs + p.offIdx);
+    int* hNk = reinterpret_cast<int*>(hs + p.offNk);
+    unsigned char* hm = reinterpret_cast<unsigned char*>(hs + p.offMask);
     for (int b = 0; b < B; ++b) {
-        hNk[b] = nk[b];
-        hm[b] = mask ? (mask[b] ? 1 : 0) : 1;
+        hNk[b] = c.nk[b];
+        hm[b] = c.mask ? (c.mask[b] ? 1 : 0) : 1;
         for (int k = 0; k < stride; ++k)
-            hIdx[size_t(b) * stride + k] = (hm[b] && k < nk[b]) ? blocks::findId(f->ids[b].data(), N[b], ids[size_t(b) * stride + k]) : -1;
-        for (int k = 0; iterating && k < stride; ++k)
-            hs[iterate::offConsider(ol) + size_t(b) * stride + k] = (sc && sc->n && hm[b] && k < nk[b] &&
-                iterate::considered(sc->ids + size_t(b) * sc->cstride, sc->n[b], ids[size_t(b) * stride + k])) ? 1 : 0;
+            hIdx[size_t(b) * stride + k] = (hm[b] && k < c.nk[b]) ? blocks::findId(f->ids[b].data(), N[b], c.ids[size_t(b) * stride + k]) : -1;
+        for (int k = 0; p.iterating && k < stride; ++k)
+            hs[iterate::offConsider(p.ol) + size_t(b) * stride + k] = (sc && sc->n && hm[b] && k < c.nk[b] &&
+                iterate::considered(sc->ids + size_t(b) * sc->cstride, sc->n[b], c.ids[size_t(b) * stride + k])) ? 1 : 0;
     }
-    HIPC(f->blk.small.upload(smallBytes, f->stream));
-    const int nMax = maxN(f), nt = blocks::rowTiles(nMax);
-    const int nPT = blocks::pairTiles(stride);
+    HIPC(f->blk.small.upload(p.smallBytes, f->stream));
+    return EQF_OK;
+}
+
+// the arguments every kernel of the route takes: the rows where k_obs_rows forms them, or in the uploaded image
+BlkArgs blkArgs(eqf_filter* f, const BlkCall& c, const BlkPlan& p) {
+    const char* ds = f->blk.small.dev;
     BlkArgs a{};
     a.g = f->g[f->pG]; a.Sigma = static_cast<double*>(f->Sigma[f->pS]); a.ld = f->ld; a.sigmaStride = f->sigmaStride;
-    if (oc) {
-        a.Hb = f->blk.obs + orl.offHt(); a.resid = f->blk.obs + orl.offResid();
+    if (c.obs) {
+        a.Hb = f->blk.obs + p.orl.offHt(); a.resid = f->blk.obs + p.orl.offResid();
     } else {
-        a.Hb = reinterpret_cast<const double*>(f->blk.small.dev + sl.offH()); a.resid = reinterpret_cast<const double*>(f->blk.small.dev + sl.offResid());
+        a.Hb = reinterpret_cast<const double*>(ds + p.sl.offH()); a.resid = reinterpret_cast<const double*>(ds + p.sl.offResid());
     }
-    a.Rb = reinterpret_cast<const double*>(f->blk.small.dev + offR); a.idx = reinterpret_cast<const int*>(f->blk.small.dev + offIdx);
-    a.nk = reinterpret_cast<const int*>(f->blk.small.dev + offNk); a.mask = reinterpret_cast<const unsigned char*>(f->blk.small.dev + offMask);
-    a.jac = local ? f->dJac : nullptr; a.cap = f->cap; a.rows = rows; a.stride = stride; a.mp = wl.mp(); a.nb = wl.nb();
-    a.gate = gate; a.lmGate = lm_gate;
-    a.ws = f->blk.ws; a.wsStride = wl.strideD(); a.offHt = wl.offHt(); a.offGamma = wl.offGamma(); a.offD = wl.offD();
-    a.wi = f->blk.wi; a.wiStride = wl.strideI(); a.out = f->blk.out;
-    if (oc) {
-        ObsArgs o{};
-        o.a = a; o.kind = oc->kind; o.cam = reinterpret_cast<const double*>(f->blk.small.dev + ol.offCam());
-        o.meas = reinterpret_cast<const double*>(f->blk.small.dev + ol.offMeas()); o.p0 = f->p0; o.Q = f->Q[f->pG];
-        o.Ht = f->blk.obs + orl.offHt(); o.resid = f->blk.obs + orl.offResid();
-        hipLaunchKernelGGL(k_obs_rows, dim3(B), dim3(256), 0, f->stream, o);
-        if (ic) f->iter.launches = 0;
-        if (iterating) {
-            IterArgs t{};
-            t.a = a; t.kind = o.kind; t.cam = o.cam; t.meas = o.meas; t.p0 = o.p0; t.Q = o.Q;
-            t.consider = reinterpret_cast<const unsigned char*>(f->blk.small.dev + iterate::offConsider(ol));
-            t.rowsBuf = f->blk.obs; t.bufStride = (long long)orl.doubles(); t.offResid = (long long)orl.offResid();
-            t.ws = f->iter.ws; t.wsStride = il.strideD(); t.offT = il.offT(); t.offW = il.offW(); t.offG = il.offG(); t.offGn = il.offGn();
-            t.offD = il.offD(); t.offStep = il.offStep(); t.wi = f->iter.wi; t.trace = f->iter.trace; t.maxLin = ic->maxLin; t.B = B;
-            t.tol = ic->tol;
-            // the progress words, g, gNext and lastStep of every filter and the whole trace start as zeros
-            HIPC(hipMemsetAsync(f->iter.wi, 0, sizeof(int) * size_t(iterate::WorkLayout::kInts) * B, f->stream));
-            HIPC(hipMemset2DAsync(f->iter.ws + il.offG(), sizeof(double) * il.strideD(), 0, sizeof(double) * (il.strideD() - il.offG()), B,
-                f->stream));
-            HIPC(hipMemsetAsync(f->iter.trace, 0, sizeof(double) * iterate::traceDoubles(ic->maxLin, B, stride), f->stream));
-            for (int k = 0; k + 1 < ic->maxLin; ++k) {
-                hipLaunchKernelGGL(k_iter_form, dim3(nPT * nPT, B), dim3(256), 0, f->stream, t, nPT);
-                rc = enqueueFactor(f->stream, f->iter.ldsSet, t, B, il.mp(), 1, &f->iter.launches);
-                if (rc) return rc;
-                hipLaunchKernelGGL(k_iter_step, dim3(B), dim3(256), 0, f->stream, t, k);
-                hipLaunchKernelGGL(k_iter_rows, dim3(B), dim3(256), 0, f->stream, t, k);
-                f->iter.launches += 3;
-            }
-            hipLaunchKernelGGL(k_iter_commit, dim3(B), dim3(256), 0, f->stream, t);
-            ++f->iter.launches;
-        }
-    } else {
-        hipLaunchKernelGGL(k_blk_rows, dim3(B), dim3(256), 0, f->stream, a);
+    a.Rb = reinterpret_cast<const double*>(ds + p.offR); a.idx = reinterpret_cast<const int*>(ds + p.offIdx);
+    a.nk = reinterpret_cast<const int*>(ds + p.offNk); a.mask = reinterpret_cast<const unsigned char*>(ds + p.offMask);
+    a.jac = c.local ? f->dJac : nullptr; a.cap = f->cap; a.rows = c.rows; a.stride = c.stride; a.mp = p.wl.mp(); a.nb = p.wl.nb();
+    a.gate = c.gate; a.lmGate = c.lmGate;
+    a.ws = f->blk.ws; a.wsStride = p.wl.strideD(); a.offHt = p.wl.offHt(); a.offGamma = p.wl.offGamma(); a.offD = p.wl.offD();
+    a.wi = f->blk.wi; a.wiStride = p.wl.strideI(); a.out = f->blk.out;
+    return a;
+}
+
+// The intermediate linearisations behind k_obs_rows: per solve the form kernel, the factorisation, the step and the rows kernel; one commit
+// behind them.  Every launch is counted (eqf_debug_iterate_launches).
+int blkIterate(eqf_filter* f, const BlkCall& c, const BlkPlan& p, const ObsArgs& o) {
+    const int B = f->B, maxLin = c.iter->maxLin;
+    const iterate::WorkLayout& il = p.il;
+    IterArgs t{};
+    t.a = o.a; t.kind = o.kind; t.cam = o.cam; t.meas = o.meas; t.p0 = o.p0; t.Q = o.Q;
+    t.consider = reinterpret_cast<const unsigned char*>(f->blk.small.dev + iterate::offConsider(p.ol));
+    t.rowsBuf = f->blk.obs; t.bufStride = (long long)p.orl.doubles(); t.offResid = (long long)p.orl.offResid();
+    t.ws = f->iter.ws; t.wsStride = il.strideD(); t.offT = il.offT(); t.offW = il.offW(); t.offG = il.offG(); t.offGn = il.offGn();
+    t.offD = il.offD(); t.offStep = il.offStep(); t.wi = f->iter.wi; t.trace = f->iter.trace; t.maxLin = maxLin; t.B = B;
+    t.tol = c.iter->tol;
+    // the progress words, g, gNext and lastStep of every filter and the whole trace start as zeros
+    HIPC(hipMemsetAsync(f->iter.wi, 0, sizeof(int) * size_t(iterate::WorkLayout::kInts) * B, f->stream));
+    HIPC(hipMemset2DAsync(f->iter.ws + il.offG(), sizeof(double) * il.strideD(), 0, sizeof(double) * (il.strideD() - il.offG()), B, f->stream));
+    HIPC(hipMemsetAsync(f->iter.trace, 0, sizeof(double) * iterate::traceDoubles(maxLin, B, c.stride), f->stream));
+    for (int k = 0; k + 1 < maxLin; ++k) {
+        hipLaunchKernelGGL(k_iter_form, dim3(p.nPT * p.nPT, B), dim3(256), 0, f->stream, t, p.nPT);
+        const int rc = enqueueFactor(f->stream, f->iter.ldsSet, t, B, il.mp(), 1, &f->iter.launches);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_iter_step, dim3(B), dim3(256), 0, f->stream, t, k);
+        hipLaunchKernelGGL(k_iter_rows, dim3(B), dim3(256), 0, f->stream, t, k);
+        f->iter.launches += 3;
     }
-    hipLaunchKernelGGL(k_blk_gain, dim3(nt + nPT * nPT, B), dim3(256), 0, f->stream, a, nt, nPT);
-    rc = enqueueFactor(f->stream, f->blk.ldsSet, a, B, wl.mp(), blocks::rhsBlocks(blocks::paddedOrder(nMax)));
+    hipLaunchKernelGGL(k_iter_commit, dim3(B), dim3(256), 0, f->stream, t);
+    ++f->iter.launches;
+    return EQF_OK;
+}
+// The rows: the caller's through k_blk_rows, or formed at each filter's own estimate by k_obs_rows and, where the call iterates, re-formed
+int blkFormRows(eqf_filter* f, const BlkCall& c, const BlkPlan& p, const BlkArgs& a) {
+    if (!c.obs) {
+        hipLaunchKernelGGL(k_blk_rows, dim3(f->B), dim3(256), 0, f->stream, a);
+        return EQF_OK;
+    }
+    const char* ds = f->blk.small.dev;
+    ObsArgs o{};
+    o.a = a; o.kind = c.obs->kind; o.cam = reinterpret_cast<const double*>(ds + p.ol.offCam());
+    o.meas = reinterpret_cast<const double*>(ds + p.ol.offMeas()); o.p0 = f->p0; o.Q = f->Q[f->pG];
+    o.Ht = f->blk.obs + p.orl.offHt(); o.resid = f->blk.obs + p.orl.offResid();
+    hipLaunchKernelGGL(k_obs_rows, dim3(f->B), dim3(256), 0, f->stream, o);
+    if (c.iter) f->iter.launches = 0;
+    return p.iterating ? blkIterate(f, c, p, o) : int(EQF_OK);
+}
+// the solve: gain, factorisation, gamma and the tail, which leaves every filter's verdict
+int blkSolve(eqf_filter* f, const BlkPlan& p, const BlkArgs& a) {
+    const int B = f->B;
+    hipLaunchKernelGGL(k_blk_gain, dim3(p.nt + p.nPT * p.nPT, B), dim3(256), 0, f->stream, a, p.nt, p.nPT);
+    const int rc = enqueueFactor(f->stream, f->blk.ldsSet, a, B, p.wl.mp(), blocks::rhsBlocks(blocks::paddedOrder(p.nMax)));
     if (rc) return rc;
-    hipLaunchKernelGGL(k_blk_gamma, dim3(nt, B), dim3(64), 0, f->stream, a);
+    hipLaunchKernelGGL(k_blk_gamma, dim3(p.nt, B), dim3(64), 0, f->stream, a);
     hipLaunchKernelGGL(k_blk_tail, dim3(B), dim3(256), 0, f->stream, a);
-    SchArgs sa{};
-    int schGrid = 0;
-    if (sc) {
-        rc = schUpload(f, *sc, N.data(), sa, schGrid);
-        if (rc) return rc;
-        sa.out = f->blk.out; sa.gamma = f->blk.ws + wl.offGamma(); sa.strideG = wl.strideD();
-        rc = schGammaLaunch(f, sa);  // (in front of the lift and the group step: they see the masked gamma)
-        if (rc) return rc;
-    }
-    // the group step, behind the tail's verdict (entry 3 of the record, where eqf_nees.hpp's info sits)
-    IncArgs ia{};
-    ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = f->blk.ws + wl.offGamma(); ia.strideG = wl.strideD();
-    ia.off = 0; ia.mask = nullptr; ia.info = f->blk.out;
-    // the lift reads the Sigma the call started from and may still refuse the filter: in front of the downdate
-    rc = liftEnqueue(f, ia.gamma, ia.strideG, 0, nullptr, f->blk.out, true, ia);
-    if (rc) return rc;
-    if (sc) {
-        const SchBlk lay{f->blk.ws, wl.strideD(), wl.mp(), rows, f->blk.wi + wl.offCount(), wl.strideI()};
-        hipLaunchKernelGGL(k_schmidt_downdate<SchBlk>, dim3(schGrid, B), dim3(256), schmidtLdsBytes<SchBlk>(), f->stream, sa, lay);
-    } else {
-        hipLaunchKernelGGL(k_blk_downdate, dim3(blocks::triTiles(nt), B), dim3(256), kBlkDownLdsBytes, f->stream, a);
-    }
-    hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, f->stream, ia);
-    HIPC(hipGetLastError());
-    f->csValid = false;  // (C Sigma / S left by an earlier burst describe the old Sigma)
-    if (!used && !gamma && !report && !(oc && (oc->HtOut || oc->residOut)) && !(ic && (ic->gTrace || ic->rep))) return EQF_OK;
+    return EQF_OK;
+}
+
+// What the caller asked to see, behind the device: enqueues and returns where that is nothing
+int blkReadBack(eqf_filter* f, const BlkCall& c, const BlkPlan& p, const int* N) {
+    const ObsCall* oc = c.obs;
+    const IterCall* ic = c.iter;
+    const blocks::WorkLayout& wl = p.wl;
+    const int B = f->B, stride = c.stride, rows = c.rows;
+    if (!c.used && !c.gamma && !c.report && !(oc && (oc->HtOut || oc->residOut)) && !(ic && (ic->gTrace || ic->rep))) return EQF_OK;
     std::vector<double> hO(size_t(B) * kLinHead), hG, hRows, hStep;
     std::vector<int> hU(size_t(B) * wl.strideI()), hIt;
-    if (iterating && ic->rep) {
+    if (p.iterating && ic->rep) {
         hStep.resize(B);
         hIt.resize(size_t(B) * iterate::WorkLayout::kInts);
         HIPC(hipMemcpyAsync(hIt.data(), f->iter.wi, sizeof(int) * hIt.size(), hipMemcpyDeviceToHost, f->stream));
-        HIPC(hipMemcpy2DAsync(hStep.data(), sizeof(double), f->iter.ws + il.offStep(), sizeof(double) * il.strideD(), sizeof(double), B,
+        HIPC(hipMemcpy2DAsync(hStep.data(), sizeof(double), f->iter.ws + p.il.offStep(), sizeof(double) * p.il.strideD(), sizeof(double), B,
             hipMemcpyDeviceToHost, f->stream));
     }
-    if (iterating && ic->gTrace)
+    if (p.iterating && ic->gTrace)
         HIPC(hipMemcpyAsync(ic->gTrace, f->iter.trace, sizeof(double) * iterate::traceDoubles(ic->maxLin, B, stride), hipMemcpyDeviceToHost,
             f->stream));
     if (oc && (oc->HtOut || oc->residOut)) {
-        hRows.resize(orl.doubles());
+        hRows.resize(p.orl.doubles());
         HIPC(hipMemcpyAsync(hRows.data(), f->blk.obs, sizeof(double) * hRows.size(), hipMemcpyDeviceToHost, f->stream));
     }
     HIPC(hipMemcpyAsync(hO.data(), f->blk.out, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
     HIPC(hipMemcpyAsync(hU.data(), f->blk.wi, sizeof(int) * hU.size(), hipMemcpyDeviceToHost, f->stream));
-    if (gamma) {
+    if (c.gamma) {
         hG.resize(size_t(B) * f->ld);
         HIPC(hipMemcpy2DAsync(hG.data(), sizeof(double) * f->ld, f->blk.ws + wl.offGamma(), sizeof(double) * wl.strideD(),
             sizeof(double) * f->ld, B, hipMemcpyDeviceToHost, f->stream));
     }
     HIPC(hipStreamSynchronize(f->stream));
-    if (ic && ic->gTrace && !iterating) std::fill(ic->gTrace, ic->gTrace + iterate::traceDoubles(1, B, stride), 0.0);
+    if (ic && ic->gTrace && !p.iterating) std::fill(ic->gTrace, ic->gTrace + iterate::traceDoubles(1, B, stride), 0.0);
     for (int b = 0; b < B; ++b) {
         const double* o = hO.data() + size_t(b) * kLinHead;
         const int* u = hU.data() + size_t(b) * wl.strideI();
-        const int word = int(o[3]), info = word == blocks::kInfoIdle ? 0 : word, cnt = word == 3 ? 0 : u[wl.offCount()];
-        if (report) {
-            const bool solved = lift::updateSolved(word);
-            const double nan = std::nan("");
-            report[b].nis = solved ? o[0] : (word == blocks::kInfoIdle ? 0.0 : nan);
-            report[b].logdet_S = solved ? o[1] : (word == blocks::kInfoIdle ? 0.0 : nan);
-            report[b].loglik = solved ? o[2] : (word == blocks::kInfoIdle ? 0.0 : nan);
-            report[b].dof = rows * cnt;
-            report[b].info = lift::mergeInfo(info);
-        }
-        if (used)
-            for (int k = 0; k < stride; ++k) used[size_t(b) * stride + k] = (word != 3 && k < nk[b]) ? (unsigned char)u[wl.offUsed() + k] : 0;
-        if (gamma) blocks::unpackGamma(hG.data() + size_t(b) * f->ld, N[b], gamma + size_t(b) * ldg, word != 0);
+        const int word = int(o[3]), cnt = word == 3 ? 0 : u[wl.offCount()];
+        if (c.report) c.report[b] = linearReport(lift::updateReport(o, rows * cnt, true));
+        if (c.used)
+            for (int k = 0; k < stride; ++k) c.used[size_t(b) * stride + k] = (word != 3 && k < c.nk[b]) ? (unsigned char)u[wl.offUsed() + k] : 0;
+        if (c.gamma) blocks::unpackGamma(hG.data() + size_t(b) * f->ld, N[b], c.gamma + size_t(b) * c.ldg, word != 0);
         if (ic && ic->rep) {
-            const int* w = iterating ? hIt.data() + size_t(b) * iterate::WorkLayout::kInts : nullptr;
-            // (one linearisation: nothing was solved on the way)
-            ic->rep[b].n_lin = w ? w[iterate::WorkLayout::kNLin] : (word == 3 ? 0 : 1);
-            ic->rep[b].status = w ? w[iterate::WorkLayout::kStatus] : (word == 3 ? iterate::kMasked : iterate::kExhausted);
-            ic->rep[b].last_step = w ? hStep[b] : 0.0;
+            using W = iterate::WorkLayout;  // (the filter's progress words; none without an intermediate solve)
+            const iterate::Report r = p.iterating ? iterate::Report{hIt[size_t(b) * W::kInts + W::kNLin], hIt[size_t(b) * W::kInts + W::kStatus], hStep[b]}
+                                                  : iterate::singleReport(word);
+            ic->rep[b] = eqf_iter_report{r.n_lin, r.status, r.last_step};
         }
         for (int k = 0; oc && k < stride; ++k) {  // (the kernel stores zeros for an entry that is absent or not observable)
             const size_t e = size_t(b) * stride + k;
-            const bool formed = word != 3 && k < nk[b];
-            for (int q = 0; oc->HtOut && q < 3 * rows; ++q) oc->HtOut[e * rows * 3 + q] = formed ? hRows[orl.offHt() + e * rows * 3 + q] : 0.0;
-            for (int q = 0; oc->residOut && q < rows; ++q) oc->residOut[e * rows + q] = formed ? hRows[orl.offResid() + e * rows + q] : 0.0;
+            const bool formed = word != 3 && k < c.nk[b];
+            for (int q = 0; oc->HtOut && q < 3 * rows; ++q) oc->HtOut[e * rows * 3 + q] = formed ? hRows[p.orl.offHt() + e * rows * 3 + q] : 0.0;
+            for (int q = 0; oc->residOut && q < rows; ++q) oc->residOut[e * rows + q] = formed ? hRows[p.orl.offResid() + e * rows + q] : 0.0;
         }
     }
     return EQF_OK;
+}
+
+int blkUpdate(eqf_filter* f, const BlkCall& c) {
+    std::vector<int> N;
+    int rc = blkCheck(f, c, N);
+    if (rc) return rc;
+    const BlkPlan p = blkPlan(f, c);
+    rc = blkReserve(f, c, p);
+    if (!rc && c.local) rc = launchLocal(f, 0, f->B, false);  // (only writes the J records)
+    if (!rc) rc = blkPack(f, c, p, N.data());
+    if (rc) return rc;
+    const BlkArgs a = blkArgs(f, c, p);
+    rc = blkFormRows(f, c, p, a);
+    if (!rc) rc = blkSolve(f, p, a);
+    if (rc) return rc;
+    // the group step obeys the tail's verdict (entry 3 of the record, where eqf_nees.hpp's info sits)
+    rc = closeIncrement(f, IncCall{f->blk.ws + p.wl.offGamma(), p.wl.strideD(), 0, nullptr, f->blk.out, true, c.sch, N.data()},
+        [&](const SchArgs* sa, int schGrid) {
+            if (sa) {
+                const SchBlk lay{f->blk.ws, p.wl.strideD(), p.wl.mp(), c.rows, f->blk.wi + p.wl.offCount(), p.wl.strideI()};
+                hipLaunchKernelGGL(k_schmidt_downdate<SchBlk>, dim3(schGrid, f->B), dim3(256), schmidtLdsBytes<SchBlk>(), f->stream, *sa, lay);
+            } else {
+                hipLaunchKernelGGL(k_blk_downdate, dim3(blocks::triTiles(p.nt), f->B), dim3(256), kBlkDownLdsBytes, f->stream, a);
+            }
+            return int(EQF_OK);
+        });
+    return rc ? rc : blkReadBack(f, c, p, N.data());
 }
 }  // namespace
 
 int eqf_update_landmarks(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb, const double* resid,
     const double* Rb, double gate, double lm_gate, const unsigned char* mask, unsigned char* used, double* gamma, int ldg,
     eqf_linear_report* report) {
-    return blkUpdate(f, local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate, mask, nullptr, nullptr, used, gamma, ldg, report);
+    return blkUpdate(f, BlkCall{local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate, mask, nullptr, nullptr, nullptr, used, gamma, ldg, report});
 }
 int eqf_update_landmarks_schmidt(eqf_filter* f, int local, int rows, const int* nk, const int* ids, int stride, const double* Hb,
     const double* resid, const double* Rb, double gate, double lm_gate, const unsigned char* mask, const int* n_consider,
     const int* consider_ids, int cstride, unsigned char* used, double* gamma, int ldg, eqf_linear_report* report) {
     const SchCall sc{n_consider, consider_ids, cstride};
-    return blkUpdate(f, local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate, mask, &sc, nullptr, used, gamma, ldg, report);
+    return blkUpdate(f, BlkCall{local, rows, nk, ids, stride, Hb, resid, Rb, gate, lm_gate, mask, &sc, nullptr, nullptr, used, gamma, ldg, report});
 }
 // the rows formed on the device (eqf_observe.hpp; per-entry arithmetic, layouts and argument checks: eqf_observe_host.hpp)
 static_assert(observe::kBearing == EQF_OBS_BEARING && observe::kRange == EQF_OBS_RANGE && observe::kPosition == EQF_OBS_POSITION,
@@ -3828,8 +3893,8 @@ int eqf_observe_landmarks(eqf_filter* f, int kind, const double* cam, int cam_pe
     eqf_linear_report* report) {
     const ObsCall oc{kind, cam, cam_per_filter, meas, Ht_out, resid_out};
     const SchCall sc{n_consider, consider_ids, cstride};
-    return blkUpdate(f, 0, observe::rowsOf(kind), nk, ids, stride, nullptr, nullptr, Rb, gate, lm_gate, mask, n_consider ? &sc : nullptr, &oc,
-        used, gamma, ldg, report);
+    return blkUpdate(f, BlkCall{0, observe::rowsOf(kind), nk, ids, stride, nullptr, nullptr, Rb, gate, lm_gate, mask, n_consider ? &sc : nullptr, &oc,
+                            nullptr, used, gamma, ldg, report});
 }
 // ... and re-formed at the moved estimate until the increment settles (eqf_iterate.hpp; eqf_iterate_host.hpp)
 static_assert(iterate::kMaxLin == EQF_ITER_MAX_LIN, "eqf_iterate_host.hpp repeats the limit");
@@ -3840,8 +3905,8 @@ int eqf_observe_landmarks_iterated(eqf_filter* f, int kind, const double* cam, i
     const ObsCall oc{kind, cam, cam_per_filter, meas, Ht_out, resid_out};
     const SchCall sc{n_consider, consider_ids, cstride};
     const IterCall ic{max_lin, tol, g_trace, iter_report};
-    return blkUpdate(f, 0, observe::rowsOf(kind), nk, ids, stride, nullptr, nullptr, Rb, gate, lm_gate, mask, n_consider ? &sc : nullptr, &oc,
-        used, gamma, ldg, report, &ic);
+    return blkUpdate(f, BlkCall{0, observe::rowsOf(kind), nk, ids, stride, nullptr, nullptr, Rb, gate, lm_gate, mask, n_consider ? &sc : nullptr, &oc,
+                            &ic, used, gamma, ldg, report});
 }
 
 static_assert(mixture::kRefBase == kBase && mixture::kPadBase == kLm0 && mixture::kRows == kMixRows && mixture::kLanes == kMixLanes &&

@@ -59,6 +59,13 @@ inline size_t traceDoubles(int maxLin, int B, int stride) { return size_t(maxLin
 // the call's image is observe::SmallLayout's with one byte per entry behind it: 1 when the entry's landmark is considered
 inline size_t offConsider(const observe::SmallLayout& s) { return s.bytes(); }
 inline size_t smallBytes(const observe::SmallLayout& s) { return s.bytes() + s.entries(); }
+// eqf_iter_report of a filter when the call took one linearisation (nothing was solved on the way), from the update's verdict word: a
+// filter that is masked out (word 3) took no part, every other one used up its single linearisation
+struct Report {
+    int n_lin, status;
+    double last_step;
+};
+inline Report singleReport(int word) { return word == 3 ? Report{0, kMasked, 0.0} : Report{1, kExhausted, 0.0}; }
 // is id in the strictly ascending list?
 inline bool considered(const int* list, int n, int id) {
     int lo = 0, hi = n;

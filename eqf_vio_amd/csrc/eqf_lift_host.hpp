@@ -71,5 +71,20 @@ inline void unpackReport(const double* rec, Report* out) {
 inline int mergeInfo(int word) { return word == kWordFailed ? kInfoFailed : word; }
 // nis, logdet_S and loglik of an update are valid numbers where the update itself solved: applied, gated, or refused by the lift
 inline bool updateSolved(int word) { return word == 0 || word == 2 || word == kWordFailed; }
+// the block update's verdict word "no entry takes part" (eqf_blocks_host.hpp's kInfoIdle, which this header does not see)
+constexpr int kWordIdle = 4;
+// An update's result record -> the fields of eqf_linear_report (a mirror, as Report above).  rec: [kHead], entry 3 the verdict word; dof:
+// what the route counts for the filter.  hasIdle: the route has the idle word -- such a filter reads as an applied update of no rows
+// (zeros, info 0); on a route without it the word passes like any other that did not solve (NaNs).
+struct UpdateReport {
+    double nis, logdet_S, loglik;
+    int dof, info;
+};
+inline UpdateReport updateReport(const double* rec, int dof, bool hasIdle) {
+    const int word = int(rec[3]);
+    const bool solved = updateSolved(word), idle = hasIdle && word == kWordIdle;
+    const double none = idle ? 0.0 : std::nan("");
+    return UpdateReport{solved ? rec[0] : none, solved ? rec[1] : none, solved ? rec[2] : none, dof, mergeInfo(idle ? 0 : word)};
+}
 
 }  // namespace eqf::lift

@@ -9,6 +9,7 @@
 //   trial KIND P0[3] Q[4] A G[3] CAM[7] MEAS[3]    ->  Ht[3 rows] r~[rows] notObservable      (trialRows)
 //   run MAXLIN TOL MASKED then per solve: FAILED LASTSTEP STALLED   ->  n_lin status last_step cur   (start, afterSolve, afterRows, afterAll;
 //        solves beyond the listed ones fail; the list ends the line)
+//   single WORD                                    ->  n_lin status last_step   (singleReport: the call took one linearisation)
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -108,6 +109,11 @@ int main() {
             }
             it::afterAll(s, maxLin, masked);
             std::printf("%d %d %a %d\n", s.nLin, s.status, s.lastStep, s.cur);
+        } else if (cmd == "single") {
+            int word;
+            in >> word;
+            const it::Report r = it::singleReport(word);
+            std::printf("%d %d %a\n", r.n_lin, r.status, r.last_step);
         } else if (!cmd.empty()) {
             std::fprintf(stderr, "unknown command %s\n", cmd.c_str());
             return 2;

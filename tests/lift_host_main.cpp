@@ -7,6 +7,8 @@
 //                                              100 (3 i + r) + c + 1 and gl[j] = -(j + 1), row by row
 //   report kind info                        -> the record {kind, info, 1 .. 6, 7, 8} unpacked: kind info 1 2 3 4 5 6 7 8
 //   merge word                              -> mergeInfo(word) updateSolved(word)
+//   update word dof hasIdle                 -> updateReport of the record {10.5, -2.25, 3.125, word, -7 ...}: nis logdet_S loglik (hex floats)
+//                                              dof info
 #include <cstdio>
 #include <iostream>
 #include <sstream>
@@ -62,6 +64,16 @@ int main() {
             int word;
             in >> word;
             std::printf("%d %d\n", mergeInfo(word), int(updateSolved(word)));
+        } else if (cmd == "update") {
+            int word, dof, hasIdle;
+            in >> word >> dof >> hasIdle;
+            std::vector<double> rec(kHead, -7.0);  // (exactly one record: nis 10.5, logdet_S -2.25, loglik 3.125, the verdict word)
+            rec[0] = 10.5;
+            rec[1] = -2.25;
+            rec[2] = 3.125;
+            rec[3] = word;
+            const UpdateReport r = updateReport(rec.data(), dof, hasIdle != 0);
+            std::printf("%a %a %a %d %d\n", r.nis, r.logdet_S, r.loglik, r.dof, r.info);
         } else if (!cmd.empty()) {
             return 2;
         }

@@ -146,6 +146,18 @@ def test_a_zero_increment_gives_the_one_shot_rows_and_an_injected_one_stalls(ite
         assert int(o[-1]) == 1 and all(float.fromhex(t) == 0.0 for t in o[:-1])
 
 
+def test_one_linearisation_report_for_every_verdict_word(iterate_host):
+    """eqf_iter_report when nothing was iterated (max_lin = 1), from the update's verdict word: only a masked filter (3) took no part; the
+    others -- applied, failed, gated, idle (blocks::kInfoIdle = 4), refused by the lift (lift::kWordFailed = 5), singular chart -- used their
+    single linearisation, which is all there were (1 = ran out).  Written out, one line per word."""
+    want = {0: (1, 1, 0.0), 1: (1, 1, 0.0), 2: (1, 1, 0.0), 3: (0, 4, 0.0), 4: (1, 1, 0.0), 5: (1, 1, 0.0), -1: (1, 1, 0.0)}
+    out = iterate_host("\n".join(f"single {w}" for w in want))
+    assert len(out) == len(want)
+    for (w, (n_lin, status, last)), o in zip(want.items(), out):
+        got = (int(o[0]), int(o[1]), float.fromhex(o[2]))
+        assert got == (n_lin, status, last) and np.copysign(1.0, got[2]) == 1.0, (w, o)
+
+
 def test_the_stop_rule_and_all_five_statuses(iterate_host):
     h = lambda v: float(v).hex()  # noqa: E731
     nan = float("nan")

@@ -3,6 +3,7 @@ is created) and the decisions and layouts of eqf_vio_amd/csrc/eqf_lift_host.hpp 
 tests/lift_host_main.cpp is compiled with g++ under the address and undefined-behaviour sanitizers and run as a child process, cases on
 stdin, results on stdout.  Every expected value is computed here."""
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -31,10 +32,10 @@ def lift_host(tmp_path_factory):
     subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I",
                     os.path.join(ROOT, "eqf_vio_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "lift_host_main.cpp")], check=True)
 
-    def run(text):
+    def run(text, conv=int):
         r = subprocess.run([exe], input=text, capture_output=True, text=True)
         assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-        return [[int(t) for t in ln.split()] for ln in r.stdout.split("\n")[:-1]]
+        return [[conv(t) for t in ln.split()] for ln in r.stdout.split("\n")[:-1]]
 
     return run
 
@@ -85,3 +86,34 @@ def test_report_and_info_merge(lift_host):
     out = lift_host("\n".join(f"merge {w}" for w in words))
     # 5, the word a failed lift leaves, reads as info = 4; 4 is the block update's idle word and passes as it is (its caller maps it)
     assert out == [[-1, 0], [0, 1], [1, 0], [2, 1], [3, 0], [4, 0], [4, 1]]
+
+
+def test_update_report_for_every_verdict_word(lift_host):
+    """What eqf_linear_report says for each verdict word of an update's record {nis 10.5, logdet_S -2.25, loglik 3.125, word}: written out
+    here, for the block route (it has the idle word; dof is rows times the entries that took part, which its caller hands in) and for the
+    linear route (no idle word; dof = m)."""
+    nan, val = float("nan"), (10.5, -2.25, 3.125)
+    cases = [
+        # (word, dof handed in, route has the idle word) -> nis, logdet_S, loglik, dof, info
+        ((0, 6, 1), (*val, 6, 0)),            # applied
+        ((1, 6, 1), (nan, nan, nan, 6, 1)),   # S not positive definite / a non-finite value: untouched
+        ((2, 6, 1), (*val, 6, 2)),            # gated: the statistics are what was compared
+        ((3, 0, 1), (nan, nan, nan, 0, 3)),   # masked out
+        ((4, 0, 1), (0.0, 0.0, 0.0, 0, 0)),   # blocks::kInfoIdle: no entry takes part -- an applied update of no rows
+        ((5, 6, 1), (*val, 6, 4)),            # lift::kWordFailed: the update solved, the lift refused the filter
+        ((-1, 6, 1), (nan, nan, nan, 6, -1)),  # local = 1 and a singular gravity chart
+        ((0, 3, 0), (*val, 3, 0)),
+        ((1, 3, 0), (nan, nan, nan, 3, 1)),
+        ((2, 3, 0), (*val, 3, 2)),
+        ((3, 3, 0), (nan, nan, nan, 3, 3)),
+        ((4, 3, 0), (nan, nan, nan, 3, 4)),   # the linear route has no idle word: 4 passes like any word that did not solve
+        ((5, 3, 0), (*val, 3, 4)),
+        ((-1, 3, 0), (nan, nan, nan, 3, -1)),
+    ]
+    out = lift_host("\n".join("update %d %d %d" % c for c, _ in cases), conv=str)
+    assert len(out) == len(cases)
+    for (c, want), o in zip(cases, out):
+        got = [float.fromhex(t) for t in o[:3]]
+        for g, w in zip(got, want[:3]):
+            assert (math.isnan(g) and math.isnan(w)) or (g == w and math.copysign(1.0, g) == math.copysign(1.0, w)), (c, o)
+        assert (int(o[3]), int(o[4])) == want[3:], (c, o)
