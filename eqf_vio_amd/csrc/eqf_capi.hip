@@ -27,6 +27,7 @@
 #include "eqf_factor.hpp"
 #include "eqf_nees.hpp"
 #include "eqf_clone.hpp"
+#include "eqf_clone_host.hpp"
 #include "eqf_frame.hpp"
 #include "eqf_sample.hpp"
 #include "eqf_sample_host.hpp"
@@ -243,7 +244,7 @@ struct eqf_filter {
     std::vector<std::vector<int>> permOnDevice;  // what dPerm holds (uploadPerm): the same landmark set in the same order needs no new copy
     DevPtr<double> dChord, dDepth2, dScratch, dMeas, dOut;
     IntStage stMap, stPerm;  // pinned rings: [B*cap + B] (map + new counts), [B*cap]
-    IntStage stEdit;         // pinned ring [2*B*cap + 4*B]: keep map | permutation | counts of a k_edit launch (one upload per frame)
+    IntStage stEdit;         // pinned ring [frame::ImageLayout::editInts()]: keep map | permutation | counts of a k_edit launch (one upload per frame)
     DevPtr<int> dEdit;       // its device image
     std::vector<int> editOnDevice;  // ... as last uploaded
     DevPtr<int> dEditBar;    // [B][4] k_edit's counters
@@ -605,6 +606,39 @@ int maxN(const eqf_filter* f) {
     size_t m = 0;
     for (auto& v : f->ids) m = std::max(m, v.size());
     return int(m);
+}
+// the layouts that follow from batch and capacity alone: the frame's pinned image, the small state (its arrays and their staging image)
+frame::ImageLayout frameImage(const eqf_filter* f) { return {size_t(f->B), size_t(f->cap)}; }
+clone::SmallLayout cloneSmall(const eqf_filter* f) { return {size_t(f->B), size_t(f->cap), sizeof(Glob), size_t(kInnovHead)}; }
+std::vector<int> landmarkCounts(const eqf_filter* f) {
+    std::vector<int> N(f->ids.size());
+    for (size_t b = 0; b < N.size(); ++b) N[b] = int(f->ids[b].size());
+    return N;
+}
+
+// ---- the host's mirror of a filter (ids, clock, the two initialisation flags, the gate report) where a call makes filter d a copy of s
+struct Mirror {
+    std::vector<int> ids;
+    double curTime;
+    char init, devInit;
+};
+Mirror mirrorOf(const eqf_filter* f, int s) { return Mirror{f->ids[s], f->curTime[s], f->init[s], f->devInit[s]}; }
+// dst's filter d takes over a mirror (of src's filter s); its gate report starts over (the gate and its threshold are settings: they stay)
+void adoptMirror(eqf_filter* dst, int d, Mirror m) {
+    dst->ids[d] = std::move(m.ids); dst->curTime[d] = m.curTime; dst->init[d] = m.init; dst->devInit[d] = m.devInit;
+    dst->report[d] = {};
+}
+void adoptMirror(eqf_filter* dst, int d, const eqf_filter* src, int s) { adoptMirror(dst, d, mirrorOf(src, s)); }
+// Would adoptMirror(f, d, f, s) change nothing?  (Then a call need not wait for the device's verdict to know the mirror of d.)
+bool mirrorsAgree(const eqf_filter* f, int d, int s) {
+    return f->ids[d] == f->ids[s] && f->curTime[d] == f->curTime[s] && f->init[d] == f->init[s] && f->devInit[d] == f->devInit[s] &&
+           f->report[d].ids.empty();
+}
+// what the host caches about the device's Sigma and landmark sets starts over
+void forgetDeviceCaches(eqf_filter* f) {
+    f->csValid = false;
+    f->permOnDevice.clear();
+    f->editOnDevice.clear();
 }
 
 // Can the handle's gate remove anything?  A chord between unit vectors never exceeds 2; a Mahalanobis distance is finite.
@@ -1432,7 +1466,7 @@ int probe(eqf_filter* f, const double* bearings, long long bearStride, bool with
 int flushMeas(eqf_filter* f, size_t extra = 0) {
     if (!f->measPending) return EQF_OK;
     f->measPending = false;
-    HIPC(hipMemcpyAsync(f->dMeas, f->hMeas, sizeof(double) * 3 * f->cap * f->B + extra, hipMemcpyHostToDevice, f->stream));
+    HIPC(hipMemcpyAsync(f->dMeas, f->hMeas, sizeof(double) * frameImage(f).bearingDoubles() + extra, hipMemcpyHostToDevice, f->stream));
     HIPC(hipEventRecord(f->evMeas, f->stream));
     return EQF_OK;
 }
@@ -1498,7 +1532,8 @@ int visionOneLaunch(eqf_filter* f, const frame::Meas& m, const double* bearings,
     const int B = f->B, cap = f->cap;
     // (per-call API: the image rides behind the bearings, one copy for both; stream API: a staging ring of its own)
     const bool withMeas = f->measPending;
-    int* h = withMeas ? reinterpret_cast<int*>(f->hMeas + (size_t)3 * cap * B) : nullptr;
+    const frame::ImageLayout fi = frameImage(f);
+    int* h = withMeas ? reinterpret_cast<int*>(f->hMeas + fi.offEdit()) : nullptr;
     int slot = 0;
     int rc = withMeas ? EQF_OK : stageAcquire(f->stEdit, &h, &slot);
     if (rc) return rc;
@@ -1507,12 +1542,12 @@ int visionOneLaunch(eqf_filter* f, const frame::Meas& m, const double* bearings,
     frame::EditPlan plan;
     if (!frame::editImage(f->ids, keep, m, gateArmed, cap, h, plan)) return EQF_ERR_CAPACITY;  // (cannot happen: every entry point checks nb <= capacity)
     // (a fixed set behind an armed gate: the same image every frame, nothing to upload)
-    const size_t nInts = (size_t)2 * B * cap + 4 * B;
+    const size_t nInts = fi.editInts();
     const int* devImage = f->dEdit;
     if (withMeas) {
         rc = flushMeas(f, sizeof(int) * nInts);
         if (rc) return rc;
-        devImage = reinterpret_cast<const int*>(f->dMeas + (size_t)3 * cap * B);
+        devImage = reinterpret_cast<const int*>(f->dMeas + fi.offEdit());
     } else if (f->editOnDevice.size() != nInts || !std::equal(h, h + nInts, f->editOnDevice.begin())) {
         f->editOnDevice.clear();
         HIPC(hipMemcpyAsync(f->dEdit, h, sizeof(int) * nInts, hipMemcpyHostToDevice, f->stream));
@@ -1946,15 +1981,17 @@ int eqf_create(const eqf_settings* settings, int capacity_landmarks, int batch, 
     f->ldS = mpC; f->ldY = ycC; f->ldE = nepC; f->ldZ = kSB;
     f->strideS = (long long)mpC * mpC; f->strideY = (long long)mpC * ycC;
     f->strideE = (long long)nepC * nepC; f->strideZ = (long long)nepC * kSB;
+    const clone::SmallLayout sm = cloneSmall(f);  // (doubles per filter of the small state's arrays)
+    const frame::ImageLayout fi = frameImage(f);
     int rc = EQF_OK;
     auto chk = [&](int r) { if (r && !rc) rc = r; };
     if (hipStreamCreateWithFlags(f->stream.put(), hipStreamNonBlocking) != hipSuccess) rc = EQF_ERR_HIP;
     for (int q = 0; q < 2 && !rc; ++q) {
         chk(dmalloc(f->Sigma[q], (size_t)f->sigmaStride * B, f->esz));
         chk(dmalloc(f->g[q], B));
-        chk(dmalloc(f->Q[q], (size_t)5 * cap * B));
+        chk(dmalloc(f->Q[q], sm.qCount() * B));
     }
-    chk(dmalloc(f->p0, (size_t)3 * cap * B));
+    chk(dmalloc(f->p0, sm.p0Count() * B));
     chk(dmalloc(f->lmc, (size_t)15 * cap * B));
     f->strideDS = std::max<long long>(f->strideS, (long long)(mpC / kSB) * kDRec);
     f->strideDE = std::max<long long>(f->strideE, (long long)(nepC / kSB) * kDRec);
@@ -1962,14 +1999,14 @@ int eqf_create(const eqf_settings* settings, int capacity_landmarks, int batch, 
     chk(dmalloc(f->YW, f->strideY * B)); chk(dmalloc(f->YO, f->strideY * B));
     chk(dmalloc(f->EA, f->strideE * B)); chk(dmalloc(f->EL, f->strideDE * B));
     chk(dmalloc(f->ZW, f->strideZ * B)); chk(dmalloc(f->ZO, f->strideZ * B));
-    chk(dmalloc(f->dbgDelta, (size_t)2 * cap * B));
-    chk(dmalloc(f->dbgGamma, (size_t)(kLm0 + 3 * cap) * B));
-    chk(dmalloc(f->dbgGammaTot, (size_t)(9 + 3 * cap) * B));
+    chk(dmalloc(f->dbgDelta, sm.deltaCount() * B));
+    chk(dmalloc(f->dbgGamma, sm.gammaCount() * B));
+    chk(dmalloc(f->dbgGammaTot, sm.gammaTotCount() * B));
     chk(dmalloc(f->red, (size_t)256 * B));
     chk(dmalloc(f->errflag, 1));
     chk(dmalloc(f->dMap, (size_t)cap * B + B)); if (!rc) f->dNewN = f->dMap + (size_t)cap * B;  /* (one copy brings both) */ chk(dmalloc(f->dPerm, (size_t)cap * B));
     chk(dmalloc(f->dChord, (size_t)cap * B)); chk(dmalloc(f->dDepth2, (size_t)cap * B));
-    chk(dmalloc(f->dScratch, (size_t)kLmRec * cap * B)); chk(dmalloc(f->dMeas, (size_t)3 * cap * B + ((size_t)2 * cap * B + 4 * B + 1) / 2));  /* (+ k_edit's image behind the bearings: one copy brings both) */
+    chk(dmalloc(f->dScratch, (size_t)kLmRec * cap * B)); chk(dmalloc(f->dMeas, fi.doubles()));  /* (k_edit's image behind the bearings: one copy brings both) */
     chk(dmalloc(f->dOut, (size_t)f->nTot * f->nTot + 16));
     chk(dmalloc(f->dRing, (size_t)kRing * B));
     chk(dmalloc(f->dBlk, (size_t)kBlkRec * cap * B, f->esz));
@@ -2020,12 +2057,12 @@ int eqf_create(const eqf_settings* settings, int capacity_landmarks, int batch, 
     if (!rc && hipMemset(f->dFlags, 0, sizeof(int) * 2 * f->flagStride * B) != hipSuccess) rc = EQF_ERR_HIP;
     if (const char* e = std::getenv("EQF_GATE_SPECULATIVE")) f->gateSpeculative = std::atoi(e);
     chk(stageInit(f, f->stMap, (size_t)cap * B + B)); chk(stageInit(f, f->stPerm, (size_t)cap * B));
-    chk(stageInit(f, f->stEdit, (size_t)2 * cap * B + 4 * B)); chk(dmalloc(f->dEdit, (size_t)2 * cap * B + 4 * B)); chk(dmalloc(f->dEditBar, (size_t)4 * B));
+    chk(stageInit(f, f->stEdit, fi.editInts())); chk(dmalloc(f->dEdit, fi.editInts())); chk(dmalloc(f->dEditBar, (size_t)4 * B));
     if (!rc && hipMemset(f->dEditBar, 0, sizeof(int) * 4 * B) != hipSuccess) rc = EQF_ERR_HIP;
     chk(hmalloc(f->hChord, (size_t)cap * B)); chk(dmalloc(f->dDepthSel, B));
     chk(hmalloc(f->hGate, B)); chk(dmalloc(f->dMask, B));
     chk(eventInit(f, f->evGate)); chk(eventInit(f, f->evMask)); chk(eventInit(f, f->evMeas));
-    chk(hmalloc(f->hMeas, (size_t)3 * cap * B + ((size_t)2 * cap * B + 4 * B + 1) / 2)); chk(hmalloc(f->hOut, (size_t)f->nTot * f->nTot + 16));
+    chk(hmalloc(f->hMeas, fi.doubles())); chk(hmalloc(f->hOut, (size_t)f->nTot * f->nTot + 16));
     chk(hmalloc(f->hRing, (size_t)kRing * B));
     for (auto& e : f->evRing) chk(eventInit(f, e));
     if (!rc) rc = initState(f);
@@ -2146,13 +2183,14 @@ int eqf_process_vision(eqf_filter* f, const double* stamps, const int* nb, const
     std::vector<const int*> mids(B);
     std::vector<int> nbv(nb, nb + B);
     std::vector<char> active(B);
+    const size_t bearStride = frameImage(f).bearingStride();
     for (int b = 0; b < B; ++b) {
-        std::memcpy(f->hMeas + (size_t)b * 3 * cap, bearings + (size_t)b * stride * 3, sizeof(double) * 3 * nb[b]);
+        std::memcpy(f->hMeas + (size_t)b * bearStride, bearings + (size_t)b * stride * 3, sizeof(double) * 3 * nb[b]);
         mids[b] = ids + (size_t)b * stride;
         active[b] = st[b] == EQF_OK;
     }
     f->measPending = true;
-    rc = visionCore(f, mids, nbv, f->dMeas, (long long)3 * cap, active, st.data());
+    rc = visionCore(f, mids, nbv, f->dMeas, (long long)bearStride, active, st.data());
     if (flushMeas(f)) return EQF_ERR_HIP;  // (visionCore left before it needed them)
     if (status) std::copy(st.begin(), st.end(), status);
     return rc;
@@ -2454,8 +2492,7 @@ int eqf_forecast(eqf_filter* f, int K, const double* imu, const double* t1, int 
     const int B = f->B, cap = f->cap;
     if (!fc::stampsOk(K, imu, t1, B)) return EQF_ERR_INVALID;
     GATE(f);
-    std::vector<int> N(B);
-    for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
+    const std::vector<int> N = landmarkCounts(f);
     const fc::Wants wants{out->p != nullptr, out->bearing != nullptr, out->lm != nullptr, out->S != nullptr, out->ycov != nullptr};
     if (!fc::strideOk(wants, stride, B, N.data())) return EQF_ERR_INVALID;
     int rc = forecastWorkspace(f);
@@ -2664,22 +2701,21 @@ static CloneSide cloneSide(eqf_filter* f) {
     s.cap = f->cap;
     return s;
 }
-// ... and of the staging image of the in-place case: one allocation, carved in the handle's own layout
-static size_t cloneSmallBytes(const eqf_filter* f) {
-    const size_t cap = f->cap;
-    return (sizeof(Glob) + sizeof(double) * (3 * cap + 5 * cap + 2 * cap + (kLm0 + 3 * cap) + (9 + 3 * cap) + (kInnovHead + cap))) * f->B;
-}
+// ... and of the staging image of the in-place case: one allocation in the handle's own layout (clone::SmallLayout)
+static_assert(clone::kPadBase == kLm0 && clone::kOk == EQF_OK && clone::kInvalid == EQF_ERR_INVALID && clone::kCapacity == EQF_ERR_CAPACITY &&
+                  sizeof(clone::Pair) == sizeof(ClonePair) && offsetof(clone::Pair, dst) == offsetof(ClonePair, dst) &&
+                  offsetof(clone::Pair, src) == offsetof(ClonePair, src) && offsetof(clone::Pair, N) == offsetof(ClonePair, N) &&
+                  offsetof(clone::Pair, fromStage) == offsetof(ClonePair, fromStage) && sizeof(Glob) % sizeof(double) == 0,
+    "eqf_clone_host.hpp repeats the layout constants, the pair table and the error codes");
 static CloneSide cloneStageSide(eqf_filter* f) {
-    const size_t cap = f->cap, B = f->B;
-    CloneSide s{};
+    const clone::SmallLayout sl = cloneSmall(f);
     char* p = f->clone.small;
-    s.g = reinterpret_cast<Glob*>(p); p += sizeof(Glob) * B;
-    s.p0 = reinterpret_cast<double*>(p); p += sizeof(double) * 3 * cap * B;
-    s.Q = reinterpret_cast<double*>(p); p += sizeof(double) * 5 * cap * B;
-    s.delta = reinterpret_cast<double*>(p); p += sizeof(double) * 2 * cap * B;
-    s.gamma = reinterpret_cast<double*>(p); p += sizeof(double) * (kLm0 + 3 * cap) * B;
-    s.gammaTot = reinterpret_cast<double*>(p); p += sizeof(double) * (9 + 3 * cap) * B;
-    s.innov = (f->innovStats && f->dInnov) ? reinterpret_cast<double*>(p) : nullptr;
+    auto doubles = [p](size_t off) { return reinterpret_cast<double*>(p + off); };
+    CloneSide s{};
+    s.g = reinterpret_cast<Glob*>(p + sl.offGlob());
+    s.p0 = doubles(sl.offP0()); s.Q = doubles(sl.offQ()); s.delta = doubles(sl.offDelta()); s.gamma = doubles(sl.offGamma());
+    s.gammaTot = doubles(sl.offGammaTot());
+    s.innov = (f->innovStats && f->dInnov) ? doubles(sl.offInnov()) : nullptr;
     s.cap = f->cap;
     return s;
 }
@@ -2698,39 +2734,18 @@ static void launchClone(eqf_filter* dst, hipStream_t st, const CloneSigmaArgs& s
 
 int eqf_copy_filters(eqf_filter* dst, eqf_filter* src, int n, const int* dst_idx, const int* src_idx) {
     if (!dst || !src || !dst_idx || !src_idx || n < 0) return EQF_ERR_INVALID;
-    {
-        std::vector<char> named(dst->B, 0);
-        for (int k = 0; k < n; ++k) {
-            if (dst_idx[k] < 0 || dst_idx[k] >= dst->B || src_idx[k] < 0 || src_idx[k] >= src->B) return EQF_ERR_INVALID;
-            if (named[dst_idx[k]]) return EQF_ERR_INVALID;
-            named[dst_idx[k]] = 1;
-        }
-    }
+    int rc = clone::headCheck(dst->B, src->B, n, dst_idx, src_idx);
+    if (rc) return rc;
     if (dst->precision != src->precision || dst->device != src->device) return EQF_ERR_UNSUPPORTED;
     if (n == 0) return EQF_OK;
     GATE(dst);
     if (src != dst) GATE(src);
     const bool inPlace = dst == src;
-    // the pairs that move something; in place, a source that is also somebody's destination is read from the staging image
-    std::vector<ClonePair> pairs, stagePairs;
-    std::vector<char> isDst(inPlace ? dst->B : 0, 0);
-    for (int k = 0; k < n; ++k) {
-        if (inPlace && dst_idx[k] == src_idx[k]) continue;
-        if (int(src->ids[src_idx[k]].size()) > dst->cap) return EQF_ERR_CAPACITY;
-        if (inPlace) isDst[dst_idx[k]] = 1;
-    }
+    // the pairs that move something, and those that bring a source to the staging image first (the landmark counts are settled now)
+    std::vector<clone::Pair> pairs, stagePairs;
     int nMaxN = 0;
-    for (int k = 0; k < n; ++k) {
-        if (inPlace && dst_idx[k] == src_idx[k]) continue;
-        const int s = src_idx[k], N = int(src->ids[s].size());
-        const int staged = inPlace && isDst[s] ? 1 : 0;
-        if (staged == 1 && isDst[s] == 1) {
-            stagePairs.push_back(ClonePair{s, s, N, 0});
-            isDst[s] = 2;  // (staged once, however many pairs read it)
-        }
-        pairs.push_back(ClonePair{dst_idx[k], s, N, staged});
-        nMaxN = std::max(nMaxN, N);
-    }
+    rc = clone::plan(dst->B, src->B, dst->cap, inPlace, n, dst_idx, src_idx, landmarkCounts(src).data(), pairs, stagePairs, nMaxN);
+    if (rc) return rc;
     if (pairs.empty()) return EQF_OK;
     // everything that can fail is had before anything is written
     const int nTab = int(pairs.size() + stagePairs.size());
@@ -2738,9 +2753,9 @@ int eqf_copy_filters(eqf_filter* dst, eqf_filter* src, int n, const int* dst_idx
         const bool stages = !stagePairs.empty();
         const workspace::Want wd[] = {want(dst->clone.evDone), want(dst->clone.hPairs, sizeof(ClonePair) * nTab, &dst->clone.pairsCap),
             want(dst->clone.dPairs, sizeof(ClonePair) * nTab, &dst->clone.pairsCap), sigmaLocWant(dst, stages),
-            want(dst->clone.small, stages ? cloneSmallBytes(dst) : 0)};
+            want(dst->clone.small, stages ? cloneSmall(dst).bytes() : 0)};
         const workspace::Want ws[] = {want(src->clone.evSrc)};
-        int rc = reserveSlots(dst, wd);
+        rc = reserveSlots(dst, wd);
         if (!rc) rc = reserveSlots(src, ws);
         if (rc) return rc;
     }
@@ -2750,8 +2765,8 @@ int eqf_copy_filters(eqf_filter* dst, eqf_filter* src, int n, const int* dst_idx
         HIPC(hipEventRecord(src->clone.evSrc, src->stream));
         HIPC(hipStreamWaitEvent(st, src->clone.evSrc, 0));
     }
-    std::copy(pairs.begin(), pairs.end(), dst->clone.hPairs.get());
-    std::copy(stagePairs.begin(), stagePairs.end(), dst->clone.hPairs + pairs.size());
+    std::memcpy(dst->clone.hPairs.get(), pairs.data(), sizeof(ClonePair) * pairs.size());
+    if (!stagePairs.empty()) std::memcpy(dst->clone.hPairs + pairs.size(), stagePairs.data(), sizeof(ClonePair) * stagePairs.size());
     HIPC(hipMemcpyAsync(dst->clone.dPairs, dst->clone.hPairs, sizeof(ClonePair) * nTab, hipMemcpyHostToDevice, st));
     CloneSigmaArgs sa{};
     sa.src = src->Sigma[src->pS]; sa.stage = dst->dSigmaLoc; sa.dst = dst->Sigma[dst->pS];
@@ -2777,21 +2792,11 @@ int eqf_copy_filters(eqf_filter* dst, eqf_filter* src, int n, const int* dst_idx
     HIPC(hipEventRecord(dst->clone.evDone, st));
     if (!inPlace) HIPC(hipStreamWaitEvent(src->stream, dst->clone.evDone, 0));  // (the source's later work flips its buffers: not before the copy has read them)
     // host mirrors (read first: in place a destination may be a source); the caches that describe the device's landmark sets start over
-    std::vector<std::vector<int>> ids(pairs.size());
-    std::vector<double> t(pairs.size());
-    std::vector<char> ini(pairs.size()), dini(pairs.size());
-    for (size_t k = 0; k < pairs.size(); ++k) {
-        const int s = pairs[k].src;
-        ids[k] = src->ids[s]; t[k] = src->curTime[s]; ini[k] = src->init[s]; dini[k] = src->devInit[s];
-    }
-    for (size_t k = 0; k < pairs.size(); ++k) {
-        const int d = pairs[k].dst;
-        dst->ids[d] = std::move(ids[k]); dst->curTime[d] = t[k]; dst->init[d] = ini[k]; dst->devInit[d] = dini[k];
-        dst->report[d] = {};  // (the gate and its threshold are settings: they stay dst's)
-    }
-    dst->csValid = false;
-    dst->permOnDevice.clear();
-    dst->editOnDevice.clear();
+    std::vector<Mirror> mirrors;
+    mirrors.reserve(pairs.size());
+    for (const auto& p : pairs) mirrors.push_back(mirrorOf(src, p.src));
+    for (size_t k = 0; k < pairs.size(); ++k) adoptMirror(dst, pairs[k].dst, std::move(mirrors[k]));
+    forgetDeviceCaches(dst);
     return EQF_OK;
 }
 
@@ -2855,10 +2860,7 @@ int eqf_edit_landmarks(eqf_filter* f, const int* n_remove, const int* remove_ids
     HIPC(hipGetLastError());
     if (pl.anyRemoved) f->pS ^= 1;
     f->ids = std::move(pl.newIds);
-    // what the host caches per landmark set starts over
-    f->csValid = false;
-    f->permOnDevice.clear();
-    f->editOnDevice.clear();
+    forgetDeviceCaches(f);
     return EQF_OK;
 }
 
@@ -3027,7 +3029,7 @@ int eqf_set_option(eqf_filter* f, const char* name, int value) {
         if (value && f->precision == EQF_PRECISION_F32) return EQF_ERR_UNSUPPORTED;
         GATE(f);
         if (value && !f->dInnov) {
-            const workspace::Want w[] = {want(f->dInnov, sizeof(double) * (size_t)(kInnovHead + f->cap) * f->B)};
+            const workspace::Want w[] = {want(f->dInnov, sizeof(double) * cloneSmall(f).innovCount() * f->B)};
             const int rc = reserveSlots(f, w);
             if (rc) return rc;
         }
@@ -3104,10 +3106,11 @@ int eqf_get_innovation_stats(eqf_filter* f, int b, eqf_innovation_stats* out, do
 }
 
 // the buffers of eqf_get_nees and of the draws' factorisation, from capacity and batch
+static_assert(sample::kRecHead == kNeesHead && sample::kTileRows == kNeesRhs, "eqf_sample_host.hpp repeats the layout constants");
 static int neesReserve(eqf_filter* f) {
     const size_t B = size_t(f->B);
     const workspace::Want w[] = {want(f->nees.E, sizeof(double) * size_t(kNeesRhs) * f->ld * B), want(f->nees.D, sizeof(double) * size_t(kDRec) * B),
-        want(f->nees.out, sizeof(double) * size_t(kNeesHead + kNeesRhs) * B), want(f->nees.bad, sizeof(int) * B), sigmaLocWant(f)};
+        want(f->nees.out, sample::RecordsLayout{B}.bytes()), want(f->nees.bad, sizeof(int) * B), sigmaLocWant(f)};
     return reserveSlots(f, w);
 }
 
@@ -3132,10 +3135,18 @@ static int neesFactor(eqf_filter* f, int local, int off, int nrhs) {
     HIPC(hipGetLastError());
     return EQF_OK;
 }
-// k_nees_tail's records [B][kNeesHead + kNeesRhs] -> the caller's
+// k_nees_tail's records (sample::RecordsLayout) brought to the host; returns once they are there
+static int readNeesRecords(eqf_filter* f, std::vector<double>& hO) {
+    hO.resize(sample::RecordsLayout{size_t(f->B)}.doubles());
+    HIPC(hipMemcpyAsync(hO.data(), f->nees.out, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
+    HIPC(hipStreamSynchronize(f->stream));
+    return EQF_OK;
+}
+// ... -> the caller's
 static void neesStats(const double* hO, int B, eqf_sigma_stats* stats) {
+    const sample::RecordsLayout rl{size_t(B)};
     for (int b = 0; b < B; ++b) {
-        const double* o = hO + size_t(b) * (kNeesHead + kNeesRhs);
+        const double* o = hO + rl.offRecord(b);
         stats[b].logdet = o[0];
         stats[b].min_pivot = o[1];
         stats[b].dof = int(o[2]);
@@ -3170,12 +3181,13 @@ int eqf_get_nees(eqf_filter* f, int local, int first, int nrhs, const double* er
     }
     rc = neesFactor(f, local, off, nrhs);
     if (rc) return rc;
-    std::vector<double> hO(size_t(B) * (kNeesHead + kNeesRhs));
-    HIPC(hipMemcpyAsync(hO.data(), f->nees.out, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
-    HIPC(hipStreamSynchronize(f->stream));
+    std::vector<double> hO;
+    rc = readNeesRecords(f, hO);
+    if (rc) return rc;
     neesStats(hO.data(), B, stats);
+    const sample::RecordsLayout rl{size_t(B)};
     for (int b = 0; b < B; ++b)
-        for (int k = 0; k < nrhs; ++k) nees[size_t(b) * nrhs + k] = hO[size_t(b) * (kNeesHead + kNeesRhs) + kNeesHead + k];
+        for (int k = 0; k < nrhs; ++k) nees[size_t(b) * nrhs + k] = hO[rl.offNees(b, k)];
     return EQF_OK;
 }
 
@@ -3331,19 +3343,20 @@ int eqf_get_lift_report(eqf_filter* f, int b, eqf_lift_report* out) {
 
 // ---- draws from the covariance and the group step (eqf_sample.hpp; index arithmetic and argument checks: eqf_sample_host.hpp)
 namespace {
-size_t sampVecLen(const eqf_filter* f) { return size_t(kLm0) + 3 * size_t(f->cap); }
-size_t sampSmallBytes(const eqf_filter* f) { return sizeof(double) * f->B * (1 + sampVecLen(f)) + size_t(f->B); }
+sample::SmallLayout sampSmall(const eqf_filter* f) { return {size_t(f->B), size_t(f->cap)}; }
+// one side of the staged image (sample::SmallLayout)
 struct SampSmall {
     double *scale, *vec;
     unsigned char* mask;
 };
-SampSmall sampCarve(const eqf_filter* f, char* p) {
+SampSmall sampSide(const eqf_filter* f, char* p) {
+    const sample::SmallLayout sl = sampSmall(f);
     double* d = reinterpret_cast<double*>(p);
-    return SampSmall{d, d + f->B, reinterpret_cast<unsigned char*>(d + f->B * (1 + sampVecLen(f)))};
+    return SampSmall{d + sl.offScale(), d + sl.offVec(), reinterpret_cast<unsigned char*>(d + sl.offMask())};
 }
 // the small operands as a staged image
 int sampSmallReserve(eqf_filter* f) {
-    const workspace::Want w[] = {WANT_STAGED(f->samp.small, sampSmallBytes(f))};
+    const workspace::Want w[] = {WANT_STAGED(f->samp.small, sampSmall(f).bytes())};
     return reserveSlots(f, w);
 }
 // room for `rows` samples per filter
@@ -3389,22 +3402,24 @@ int eqf_sample_sigma(eqf_filter* f, int local, int first, int nsamp, const doubl
         const double* dScale = nullptr;
         if (scale) {
             HIPC(f->samp.small.wait());
-            SampSmall h = sampCarve(f, f->samp.small.host), d = sampCarve(f, f->samp.small.dev);
+            SampSmall h = sampSide(f, f->samp.small.host), d = sampSide(f, f->samp.small.dev);
             std::copy(scale, scale + B, h.scale);
-            HIPC(f->samp.small.upload(sizeof(double) * B, f->stream));  // (the scales lie in front)
+            const sample::Range r = sampSmall(f).scaleRange();
+            HIPC(f->samp.small.upload(r.bytes, f->stream, r.offset));
             dScale = d.scale;
         }
         sampTrmm(f, off, nsamp, ldE, dScale);
         HIPC(hipGetLastError());
         HIPC(hipMemcpyAsync(hZ.data(), f->samp.E, sizeof(double) * hZ.size(), hipMemcpyDeviceToHost, f->stream));
     }
-    std::vector<double> hO(size_t(B) * (kNeesHead + kNeesRhs));
-    HIPC(hipMemcpyAsync(hO.data(), f->nees.out, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
-    HIPC(hipStreamSynchronize(f->stream));
+    std::vector<double> hO;
+    rc = readNeesRecords(f, hO);
+    if (rc) return rc;
     if (stats) neesStats(hO.data(), B, stats);
     const double nan = std::nan("");
+    const sample::RecordsLayout rl{size_t(B)};
     for (int b = 0; b < B; ++b) {
-        const bool bad = hO[size_t(b) * (kNeesHead + kNeesRhs) + 3] != 0.0;
+        const bool bad = hO[rl.offInfo(b)] != 0.0;
         for (int k = 0; k < nsamp; ++k)
             sample::unpackRow(hZ.data() + (size_t(b) * nsamp + k) * ldE, first, int(f->ids[b].size()), eps + (size_t(b) * nsamp + k) * lde,
                 bad ? &nan : nullptr);
@@ -3416,20 +3431,20 @@ int eqf_apply_increment(eqf_filter* f, const double* gamma, int ldg, const unsig
     if (!f || !gamma) return EQF_ERR_INVALID;
     GATE(f);
     const int B = f->B;
-    std::vector<int> N(B);
-    for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
+    const std::vector<int> N = landmarkCounts(f);
     if (!sample::incrementArgsOk(gamma, ldg, mask, B, N.data())) return EQF_ERR_INVALID;
     int rc = sampSmallReserve(f);
     if (!rc) rc = liftReserve(f, lift::callFactors(liftCallKind(f), maxN(f)));
     if (rc) return rc;
     HIPC(f->samp.small.wait());
-    SampSmall h = sampCarve(f, f->samp.small.host), d = sampCarve(f, f->samp.small.dev);
-    const int len = int(sampVecLen(f));
+    SampSmall h = sampSide(f, f->samp.small.host), d = sampSide(f, f->samp.small.dev);
+    const int len = int(sampSmall(f).vecLen());
     for (int b = 0; b < B; ++b) {
         sample::packRow(gamma + size_t(b) * ldg, 0, N[b], h.vec + size_t(b) * len, kLm0 + 3 * N[b]);
         h.mask[b] = mask ? mask[b] : 1;
     }
-    HIPC(f->samp.small.upload(sizeof(double) * size_t(B) * len + size_t(B), f->stream, sizeof(double) * size_t(B)));  // (the vectors; the mask lies behind)
+    const sample::Range r = sampSmall(f).vecMaskRange();
+    HIPC(f->samp.small.upload(r.bytes, f->stream, r.offset));
     return closeIncrement(f, IncCall{d.vec, len, 0, d.mask, nullptr, false, nullptr, nullptr}, noDowndate);
 }
 
@@ -3448,7 +3463,7 @@ int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, cons
     rc = neesFactor(f, 0, off, 0);
     if (rc) return rc;
     HIPC(f->samp.small.wait());
-    SampSmall h = sampCarve(f, f->samp.small.host), d = sampCarve(f, f->samp.small.dev);
+    SampSmall h = sampSide(f, f->samp.small.host), d = sampSide(f, f->samp.small.dev);
     for (int b = 0; b < B; ++b) {
         h.scale[b] = scale ? scale[b] : 1.0;
         h.mask[b] = h.scale[b] != 0.0;
@@ -3464,9 +3479,9 @@ int eqf_perturb_filters(eqf_filter* f, int first, const double* z, int ldz, cons
     rc = closeIncrement(f, IncCall{f->samp.E, ldE, off, d.mask, f->nees.out, false, nullptr, nullptr}, noDowndate);
     if (rc) return rc;
     if (!stats) return EQF_OK;
-    std::vector<double> hO(size_t(B) * (kNeesHead + kNeesRhs));
-    HIPC(hipMemcpyAsync(hO.data(), f->nees.out, sizeof(double) * hO.size(), hipMemcpyDeviceToHost, f->stream));
-    HIPC(hipStreamSynchronize(f->stream));
+    std::vector<double> hO;
+    rc = readNeesRecords(f, hO);
+    if (rc) return rc;
     neesStats(hO.data(), B, stats);
     return EQF_OK;
 }
@@ -3491,8 +3506,7 @@ int linUpdate(eqf_filter* f, int local, int m, const double* H, int ldh, const d
     if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
     GATE(f);  // (queued IMU calls and a pending gate first: the gate may still change the landmark counts)
     const int B = f->B;
-    std::vector<int> N(B);
-    for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
+    const std::vector<int> N = landmarkCounts(f);
     if (!linear::argsOk(m, H, ldh, resid, R, mask, gamma, ldg, B, N.data())) return EQF_ERR_INVALID;
     if (sc) {
         const int bad = schmidt::checkLists(B, f->cap, sc->n, sc->ids, sc->cstride);
@@ -3648,8 +3662,7 @@ int blkCheck(eqf_filter* f, const BlkCall& c, std::vector<int>& N) {
     if (f->precision != EQF_PRECISION_F64) return EQF_ERR_UNSUPPORTED;
     GATE(f);
     const int B = f->B;
-    N.resize(B);
-    for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
+    N = landmarkCounts(f);
     const int bad = oc ? observe::argsCheck(oc->kind, oc->cam, oc->camPerFilter, c.nk, c.ids, c.stride, oc->meas, c.Rb, c.mask, c.gamma, c.ldg, B,
                              N.data(), f->cap)
                        : blocks::argsCheck(c.rows, c.nk, c.ids, c.stride, c.Hb, c.resid, c.Rb, c.mask, c.gamma, c.ldg, B, N.data(), f->cap);
@@ -4064,8 +4077,7 @@ int eqf_merge_filters(eqf_filter* f, int n, const int* idx, const double* w, int
     HIPC(hipGetLastError());
     // The host's bookkeeping of dst follows eqf_copy_filters(ref -> dst) -- if the device wrote.  Where that bookkeeping would not change
     // (dst shares the reference's ids, clock and flags and has no gate report: a member, as a rule) the verdict is not waited for.
-    const bool same = f->ids[dst] == f->ids[ref] && f->curTime[dst] == f->curTime[ref] && f->init[dst] == f->init[ref] &&
-                      f->devInit[dst] == f->devInit[ref] && f->report[dst].ids.empty();
+    const bool same = mirrorsAgree(f, dst, ref);
     int info = 0;
     if (report || !same) {
         double out[4];
@@ -4077,13 +4089,8 @@ int eqf_merge_filters(eqf_filter* f, int n, const int* idx, const double* w, int
         if (report) mixFillReport(report, c, n, out, info);
     }
     if (info == 0) {
-        if (dst != ref) {
-            f->ids[dst] = f->ids[ref]; f->curTime[dst] = f->curTime[ref]; f->init[dst] = f->init[ref]; f->devInit[dst] = f->devInit[ref];
-        }
-        f->report[dst] = {};  // (the gate and its threshold are settings: they stay)
-        f->csValid = false;
-        f->permOnDevice.clear();
-        f->editOnDevice.clear();
+        adoptMirror(f, dst, f, ref);  // (dst == ref: only the gate report starts over)
+        forgetDeviceCaches(f);
     }
     return EQF_OK;
 }
@@ -4104,8 +4111,7 @@ int eqf_split_filters(eqf_filter* f, int local, const double* a, int lda, int n,
     if (n == 0) return EQF_OK;
     GATE(f);  // (queued IMU calls and a pending gate first: the gate may still change the landmark counts)
     const int B = f->B;
-    std::vector<int> N(B);
-    for (int b = 0; b < B; ++b) N[b] = int(f->ids[b].size());
+    const std::vector<int> N = landmarkCounts(f);
     rc = split::rowCheck(a, lda, n, src_idx, gamma ? ldg : -1, N.data());
     if (rc) return rc;
     split::Plan pl;
@@ -4157,17 +4163,13 @@ int eqf_split_filters(eqf_filter* f, int local, const double* a, int lda, int n,
     ia.g = f->g[f->pG]; ia.p0 = f->p0; ia.Q = f->Q[f->pG]; ia.cap = f->cap; ia.gamma = sa.G; ia.strideG = f->ld; ia.off = 0; ia.mask = sa.mask;
     hipLaunchKernelGGL(k_apply_increment, dim3(B), dim3(256), 0, st, ia);  // (always the plain lift: ia.lift stays NULL)
     HIPC(hipGetLastError());
-    f->csValid = false;  // (the caches that describe the device's Sigma and landmark sets start over, as behind eqf_copy_filters)
-    f->permOnDevice.clear();
-    f->editOnDevice.clear();
+    forgetDeviceCaches(f);  // (as behind eqf_copy_filters)
     // The host's bookkeeping of a dst follows eqf_copy_filters(src -> dst) -- if the device wrote.  Where no dst's bookkeeping would change
     // (eqf_merge_filters' rule) the verdicts are not waited for.
     bool same = true;
     for (const auto& c : pl.children) {
         const int d = c.dst, s = pl.sources[c.source].src;
-        if (d != s && !(f->ids[d] == f->ids[s] && f->curTime[d] == f->curTime[s] && f->init[d] == f->init[s] && f->devInit[d] == f->devInit[s] &&
-                          f->report[d].ids.empty()))
-            same = false;
+        if (d != s && !mirrorsAgree(f, d, s)) same = false;
     }
     if (!gamma && !report && same) return EQF_OK;
     std::vector<double> hRec(size_t(2) * ns), hG;
@@ -4185,42 +4187,24 @@ int eqf_split_filters(eqf_filter* f, int local, const double* a, int lda, int n,
             report[c.call].info = info;
         }
         if (gamma) linear::unpackGamma(hG.data() + size_t(d) * f->ld, N[s], gamma + size_t(c.call) * ldg, info != 0);
-        if (info == 0 && d != s) {
-            f->ids[d] = f->ids[s]; f->curTime[d] = f->curTime[s]; f->init[d] = f->init[s]; f->devInit[d] = f->devInit[s];
-            f->report[d] = {};  // (the gate and its threshold are settings: they stay)
-        }
+        if (info == 0 && d != s) adoptMirror(f, d, f, s);
     }
     return EQF_OK;
 }
 
 // ---- pairwise merge costs (eqf_mergecost.hpp; argument checks, items, chunk plan and cost formulas: eqf_mergecost_host.hpp)
 static_assert(mergecost::kRefBase == kBase && mergecost::kPadBase == kLm0 && mergecost::kBlock == kSB &&
-              sizeof(mergecost::Item) == sizeof(PairItem) && sizeof(Glob) % 8 == 0,
+              sizeof(mergecost::Item) == sizeof(PairItem) && mergecost::kRec == kPairRec && sizeof(Glob) % 8 == 0,
     "eqf_mergecost_host.hpp repeats the layout constants");
 namespace {
-struct McWs {
-    double *W, *E, *D, *out;
-    Glob* g;
-    int* bad;
-};
-size_t mcWsDoubles(const eqf_filter* f, int C) {
-    return size_t(C) * (size_t(f->sigmaStride) + size_t(f->nTot) + size_t(kDRec) + size_t(kNeesHead + kNeesRhs) + sizeof(Glob) / 8) + size_t(C + 1) / 2;
-}
-McWs mcCarve(const eqf_filter* f, char* p, int C) {
-    McWs w;
-    w.W = reinterpret_cast<double*>(p);
-    w.E = w.W + size_t(C) * size_t(f->sigmaStride);
-    w.D = w.E + size_t(C) * size_t(f->nTot);
-    w.out = w.D + size_t(C) * size_t(kDRec);
-    w.g = reinterpret_cast<Glob*>(w.out + size_t(C) * size_t(kNeesHead + kNeesRhs));
-    w.bad = reinterpret_cast<int*>(w.g + C);
-    return w;
+mergecost::WorkLayout mcWork(const eqf_filter* f, int C) {
+    return {size_t(C), size_t(f->sigmaStride), size_t(f->nTot), size_t(kDRec), size_t(kNeesHead + kNeesRhs), sizeof(Glob) / 8};
 }
 // both blocks of a call; a block this call installed is zero-filled where its unused parts are read
 int mcReserve(eqf_filter* f, int chunk, size_t nItems) {
-    const size_t wsBytes = sizeof(double) * mcWsDoubles(f, chunk);
+    const size_t wsBytes = sizeof(double) * mcWork(f, chunk).doubles();
     const workspace::Want w[] = {want(f->mc.ws, wsBytes, &f->mc.wsBytes),
-        want(f->mc.items, nItems * (sizeof(PairItem) + sizeof(double) * kPairRec), &f->mc.itemBytes)};
+        want(f->mc.items, mergecost::ItemsLayout{nItems}.bytes(), &f->mc.itemBytes)};
     workspace::Result got;
     const int rc = reserveSlots(f, w, &got);
     if (rc) return rc;
@@ -4265,16 +4249,21 @@ int eqf_get_merge_costs(eqf_filter* f, int n, const int* idx, const double* w, i
     }
     HIPC(hipGetLastError());
     const int off = mergecost::offsetOf(first), m = mergecost::paddedOrder(N, off);
-    const McWs ws = mcCarve(f, f->mc.ws, f->mc.chunkCap);
-    PairItem* dItems = reinterpret_cast<PairItem*>(f->mc.items.get());
-    double* dRec = reinterpret_cast<double*>(f->mc.items + sizeof(PairItem) * f->mc.itemCap);
+    const mergecost::WorkLayout wl = mcWork(f, f->mc.chunkCap);
+    const mergecost::ItemsLayout il{f->mc.itemCap};
+    double* ws = reinterpret_cast<double*>(f->mc.ws.get());
+    double *wsW = ws + wl.offW(), *wsE = ws + wl.offE(), *wsD = ws + wl.offD(), *wsOut = ws + wl.offOut();
+    Glob* wsG = reinterpret_cast<Glob*>(ws + wl.offGlob());
+    PairItem* dItems = reinterpret_cast<PairItem*>(f->mc.items + il.offItems());
+    double* dRec = reinterpret_cast<double*>(f->mc.items + il.offRecords());
     HIPC(hipMemcpyAsync(dItems, items.data(), sizeof(PairItem) * items.size(), hipMemcpyHostToDevice, f->stream));
     PairArgs pa{};
     pa.items = dItems; pa.S = f->dSigmaLoc; pa.ld = f->ld; pa.strideS = f->sigmaStride; pa.err = a.err; pa.jacT = a.jacT; pa.cap = f->cap;
-    pa.N = N; pa.off = off; pa.kind = kind; pa.W = ws.W; pa.E = ws.E; pa.ldE = std::max(m, 1); pa.wg = ws.g; pa.neesOut = ws.out; pa.rec = dRec;
+    pa.N = N; pa.off = off; pa.kind = kind; pa.W = wsW; pa.E = wsE; pa.ldE = std::max(m, 1); pa.wg = wsG; pa.neesOut = wsOut; pa.rec = dRec;
     NeesArgs na{};
-    na.g = ws.g; na.A = ws.W; na.ld = f->ld; na.strideA = f->sigmaStride; na.E = ws.E; na.ldE = pa.ldE; na.D = ws.D; na.bad = ws.bad;
-    na.jac = nullptr; na.cap = f->cap; na.off = off; na.nrhs = 1; na.out = ws.out;
+    na.g = wsG; na.A = wsW; na.ld = f->ld; na.strideA = f->sigmaStride; na.E = wsE; na.ldE = pa.ldE; na.D = wsD;
+    na.bad = reinterpret_cast<int*>(ws + wl.offBad());
+    na.jac = nullptr; na.cap = f->cap; na.off = off; na.nrhs = 1; na.out = wsOut;
     // the members, then the pairs: chunks of at most `chunk` images, never both kinds in one
     const long long seg0[2] = {0, n}, segLen[2] = {n, npairs};
     for (int s = 0; s < 2; ++s)
@@ -4316,40 +4305,10 @@ static_assert(score::kBlock == kSB && sizeof(score::Item) == sizeof(ScoreItem) &
               score::kCapacity == EQF_ERR_CAPACITY && score::kUnsorted == EQF_ERR_UNSORTED,
     "eqf_score_host.hpp repeats the layout constants and the error codes");
 namespace {
-struct ScWs {
-    double *W, *E, *D;
-    int* bad;
-};
-size_t scWsDoubles(const eqf_filter* f, int C) {
-    const size_t ldW = size_t(score::paddedOrder(f->cap));
-    return size_t(C) * (ldW * ldW + ldW + size_t(kDRec)) + size_t(C + 1) / 2;
-}
-ScWs scCarve(const eqf_filter* f, char* p, int C) {
-    const size_t ldW = size_t(score::paddedOrder(f->cap));
-    ScWs w;
-    w.W = reinterpret_cast<double*>(p);
-    w.E = w.W + size_t(C) * ldW * ldW;
-    w.D = w.E + size_t(C) * ldW;
-    w.bad = reinterpret_cast<int*>(w.D + size_t(C) * size_t(kDRec));
-    return w;
-}
-// the tables of a call in one block: records | per-landmark statistics | bearings | items | slots
-struct ScTab {
-    size_t rec, nisLm, y, items, slots, bytes;
-};
-ScTab scTabLayout(size_t nItems, size_t nMatched) {
-    ScTab t;
-    t.rec = 0;
-    t.nisLm = t.rec + sizeof(double) * score::kRec * nItems;
-    t.y = t.nisLm + sizeof(double) * nMatched;
-    t.items = t.y + sizeof(double) * 3 * nMatched;
-    t.slots = t.items + sizeof(ScoreItem) * nItems;
-    t.bytes = t.slots + sizeof(int) * nMatched;
-    return t;
-}
+score::WorkLayout scWork(const eqf_filter* f, int C) { return {size_t(C), size_t(score::paddedOrder(f->cap)), size_t(kDRec)}; }
 // both blocks of a call; a workspace this call installed is zero-filled
 int scReserve(eqf_filter* f, int chunk, size_t tabBytes) {
-    const size_t wsBytes = sizeof(double) * scWsDoubles(f, chunk);
+    const size_t wsBytes = sizeof(double) * scWork(f, chunk).doubles();
     const workspace::Want w[] = {want(f->sc.ws, wsBytes, &f->sc.wsBytes), want(f->sc.tab, tabBytes, &f->sc.tabBytes)};
     workspace::Result got;
     const int rc = reserveSlots(f, w, &got);
@@ -4396,22 +4355,24 @@ int eqf_score_vision(eqf_filter* f, int ncand, const int* nb, const int* ids, co
     std::vector<double> hRec(nItems * score::kRec, 0.0), hLm(nMatched, 0.0);
     if (nMatched > 0) {
         const int chunk = score::chunkSize(f->sc.chunkOpt, B);
-        const ScTab tab = scTabLayout(nItems, nMatched);
-        int rc = scReserve(f, chunk, tab.bytes);
+        const score::TabLayout tab{nItems, nMatched};
+        int rc = scReserve(f, chunk, tab.bytes());
         if (rc) return rc;
-        const ScWs ws = scCarve(f, f->sc.ws, f->sc.chunkCap);
+        const score::WorkLayout wl = scWork(f, f->sc.chunkCap);
+        double* ws = reinterpret_cast<double*>(f->sc.ws.get());
         ScoreArgs a{};
-        a.items = reinterpret_cast<const ScoreItem*>(f->sc.tab + tab.items);
-        a.slots = reinterpret_cast<const int*>(f->sc.tab + tab.slots);
-        a.y = reinterpret_cast<const double*>(f->sc.tab + tab.y);
-        a.nisLm = reinterpret_cast<double*>(f->sc.tab + tab.nisLm);
-        a.rec = reinterpret_cast<double*>(f->sc.tab + tab.rec);
+        a.items = reinterpret_cast<const ScoreItem*>(f->sc.tab + tab.offItems());
+        a.slots = reinterpret_cast<const int*>(f->sc.tab + tab.offSlots());
+        a.y = reinterpret_cast<const double*>(f->sc.tab + tab.offY());
+        a.nisLm = reinterpret_cast<double*>(f->sc.tab + tab.offNisLm());
+        a.rec = reinterpret_cast<double*>(f->sc.tab + tab.offRec());
         a.Q = f->Q[f->pG]; a.lmc = f->lmc; a.S = static_cast<const double*>(f->Sigma[f->pS]); a.sigmaStride = f->sigmaStride; a.ld = f->ld;
         a.cap = cap; a.measVar = f->set.measurementVariance;
-        a.ldW = score::paddedOrder(cap); a.strideW = (long long)a.ldW * a.ldW; a.W = ws.W; a.E = ws.E; a.D = ws.D; a.bad = ws.bad;
-        HIPC(hipMemcpyAsync(f->sc.tab + tab.items, items.data(), sizeof(ScoreItem) * nItems, hipMemcpyHostToDevice, f->stream));
-        HIPC(hipMemcpyAsync(f->sc.tab + tab.slots, slots.data(), sizeof(int) * nMatched, hipMemcpyHostToDevice, f->stream));
-        HIPC(hipMemcpyAsync(f->sc.tab + tab.y, y.data(), sizeof(double) * 3 * nMatched, hipMemcpyHostToDevice, f->stream));
+        a.ldW = score::paddedOrder(cap); a.strideW = (long long)a.ldW * a.ldW; a.W = ws + wl.offW(); a.E = ws + wl.offE(); a.D = ws + wl.offD();
+        a.bad = reinterpret_cast<int*>(ws + wl.offBad());
+        HIPC(hipMemcpyAsync(f->sc.tab + tab.offItems(), items.data(), sizeof(ScoreItem) * nItems, hipMemcpyHostToDevice, f->stream));
+        HIPC(hipMemcpyAsync(f->sc.tab + tab.offSlots(), slots.data(), sizeof(int) * nMatched, hipMemcpyHostToDevice, f->stream));
+        HIPC(hipMemcpyAsync(f->sc.tab + tab.offY(), y.data(), sizeof(double) * 3 * nMatched, hipMemcpyHostToDevice, f->stream));
         for (int ch = 0; ch < score::numChunks((long long)nItems, chunk); ++ch) {
             const int cnt = score::chunkCount((long long)nItems, chunk, ch);
             a.item0 = ch * chunk;
@@ -4422,8 +4383,8 @@ int eqf_score_vision(eqf_filter* f, int ncand, const int* nb, const int* ids, co
             hipLaunchKernelGGL(k_score_tail, dim3(cnt), dim3(256), 0, f->stream, a);
         }
         HIPC(hipGetLastError());
-        HIPC(hipMemcpyAsync(hRec.data(), f->sc.tab + tab.rec, sizeof(double) * hRec.size(), hipMemcpyDeviceToHost, f->stream));
-        HIPC(hipMemcpyAsync(hLm.data(), f->sc.tab + tab.nisLm, sizeof(double) * nMatched, hipMemcpyDeviceToHost, f->stream));
+        HIPC(hipMemcpyAsync(hRec.data(), f->sc.tab + tab.offRec(), sizeof(double) * hRec.size(), hipMemcpyDeviceToHost, f->stream));
+        HIPC(hipMemcpyAsync(hLm.data(), f->sc.tab + tab.offNisLm(), sizeof(double) * nMatched, hipMemcpyDeviceToHost, f->stream));
     }
     HIPC(hipStreamSynchronize(f->stream));
     if (nis_lm) std::fill(nis_lm, nis_lm + nItems * stride, 0.0);

@@ -98,15 +98,30 @@ struct EditPlan {
     bool anyWork = false;
     int Nmax = 0;
 };
-// k_edit's upload image into h: [B][cap] keep map | [B][cap] permutation (kept landmarks, then the new ones), both padded with -1 |
-// [B][4] {nK, nNew, gate, 0}.  False if a measurement exceeds cap (h is then half written).
+// The pinned image of a frame: the bearings [B][3][cap] in doubles, and behind them k_edit's image in ints -- [B][cap] keep map | [B][cap]
+// permutation | [B][4] counts --, so that one copy brings both; the whole rounded up to doubles.  The edit image alone is what the stream
+// API's staging ring and its device copy hold.
+struct ImageLayout {
+    size_t B, cap;
+    size_t bearingStride() const { return 3 * cap; }
+    size_t bearingDoubles() const { return bearingStride() * B; }
+    size_t offKeep() const { return 0; }
+    size_t offPerm() const { return B * cap; }
+    size_t offCounts() const { return 2 * B * cap; }
+    size_t editInts() const { return offCounts() + 4 * B; }
+    size_t offEdit() const { return bearingDoubles(); }  // (in doubles; the ints start there)
+    size_t doubles() const { return offEdit() + (editInts() + 1) / 2; }
+};
+// k_edit's upload image into h (ImageLayout's ints): the keep map and the permutation (kept landmarks, then the new ones), both padded
+// with -1, and {nK, nNew, gate, 0} per filter.  False if a measurement exceeds cap (h is then half written).
 inline bool editImage(const Lists& ids, const Lists& keep, const Meas& m, bool gateArmed, int cap, int* h, EditPlan& p) {
     const size_t B = ids.size();
+    const ImageLayout il{B, size_t(cap)};
     p = EditPlan{};
     p.newIds.resize(B);
     p.nKept.assign(B, 0);
     for (size_t b = 0; b < B; ++b) {
-        int *hm = h + b * cap, *hp = h + (B + b) * cap, *hc = h + 2 * B * cap + 4 * b;
+        int *hm = h + il.offKeep() + b * cap, *hp = h + il.offPerm() + b * cap, *hc = h + il.offCounts() + 4 * b;
         const int nK = p.nKept[b] = int(keep[b].size());
         std::copy(keep[b].begin(), keep[b].end(), hm);
         std::fill(hm + nK, hm + cap, -1);

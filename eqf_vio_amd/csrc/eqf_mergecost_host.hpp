@@ -1,4 +1,5 @@
-// Argument checks, pair canonicalisation and enumeration, the chunk plan and the two cost formulas of eqf_get_merge_costs.  Host only,
+// Argument checks, pair canonicalisation and enumeration, the chunk plan, the layouts of the two device blocks and the two cost formulas of
+// eqf_get_merge_costs.  Host only,
 // standard library only (no HIP, no other eqf_*.hpp; the constants repeated here are static_assert-ed against eqf_device.hpp /
 // eqf_mergecost.hpp where both are seen): tests/mergecost_host_main.cpp runs it under the sanitizers without a GPU.  The cost formulas are
 // __host__ __device__ where a HIP compiler sees them: k_pair_tail evaluates the same text.
@@ -21,6 +22,7 @@ constexpr int kRefBase = 11;       // reference base coordinates (kBase)
 constexpr int kPadBase = 12;       // ... padded (kLm0)
 constexpr int kBlock = 64;         // block column of the factorisation (kSB)
 constexpr int kChunkMax = 4096;    // upper end of the option "merge_cost_chunk"
+constexpr int kRec = 8;            // doubles of an item's record on the device (kPairRec)
 
 // One image that is factored: a member by itself (self = 1, i == j: a plain copy) or SigmaBar of the pair of POSITIONS i < j.
 struct Item {
@@ -120,6 +122,27 @@ inline int launchesPerChunk(int m) {
     }
     return l;
 }
+
+// The workspace of a chunk of C images, in doubles: W [C][sigmaStride] the images | E [C][nTot] their right-hand sides | D [C][dRec] the
+// records of the current diagonal block | out [C][headDoubles] k_nees_tail's records | Glob [C] of globDoubles doubles each | bad [C] ints
+// behind them, rounded up to whole doubles.
+struct WorkLayout {
+    size_t C, sigmaStride, nTot, dRec, headDoubles, globDoubles;
+    size_t offW() const { return 0; }
+    size_t offE() const { return C * sigmaStride; }
+    size_t offD() const { return offE() + C * nTot; }
+    size_t offOut() const { return offD() + C * dRec; }
+    size_t offGlob() const { return offOut() + C * headDoubles; }
+    size_t offBad() const { return offGlob() + C * globDoubles; }  // (in doubles; the ints start there)
+    size_t doubles() const { return offBad() + (C + 1) / 2; }
+};
+// The items of a call and their records [kRec] behind them, in bytes, for a block that holds itemCap of them
+struct ItemsLayout {
+    size_t itemCap;
+    size_t offItems() const { return 0; }
+    size_t offRecords() const { return sizeof(Item) * itemCap; }
+    size_t bytes() const { return offRecords() + sizeof(double) * kRec * itemCap; }
+};
 
 // ---- the costs from (ld_i, ld_j, ld_ij, maha, w~_i, w~_j)
 EQF_MC_HD inline double runnalls(double ldi, double ldj, double ldij, double maha, double wi, double wj, double alpha) {

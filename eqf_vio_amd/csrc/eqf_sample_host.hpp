@@ -1,6 +1,6 @@
 // Index arithmetic and argument checks of the covariance draws (eqf_sample_sigma, eqf_apply_increment, eqf_perturb_filters): the reference <->
 // padded index map of a trailing submatrix, the tile counts of k_sample_trmm's grid, the packing of the caller's vectors into the device's
-// rows and back, and what makes a call EQF_ERR_INVALID.  Host only, standard library only (no HIP, no other eqf_*.hpp; the layout constants
+// rows and back, the layouts of the staged small operands and of the factorisation's records, and what makes a call EQF_ERR_INVALID.  Host only, standard library only (no HIP, no other eqf_*.hpp; the layout constants
 // arrive as arguments where eqf_device.hpp defines them): tests/sample_host_main.cpp runs it under the sanitizers without a GPU.
 #pragma once
 #include <cmath>
@@ -27,6 +27,35 @@ inline int paddedOrder(int N, int off) { return kPadBase + 3 * N - off; }
 inline int blockColumns(int m) { return m <= 0 ? 0 : (m + kBlock - 1) / kBlock; }
 inline int rowTiles(int nsamp) { return nsamp <= 0 ? 0 : (nsamp + kTileRows - 1) / kTileRows; }
 inline int paddedRows(int nsamp) { return kTileRows * rowTiles(nsamp); }
+
+// The small operands of a call as one staged image, in doubles: scale [B] | vectors [B][vecLen()] (z of a perturbation or the increments,
+// padded index map) | the mask, one byte per filter, behind them.  eqf_sample_sigma uploads the scales alone, eqf_apply_increment the
+// vectors with the mask.
+struct Range {
+    size_t offset, bytes;
+};
+struct SmallLayout {
+    size_t B, cap;
+    size_t vecLen() const { return size_t(kPadBase) + 3 * cap; }
+    size_t offScale() const { return 0; }
+    size_t offVec() const { return B; }
+    size_t offMask() const { return B * (1 + vecLen()); }  // (in doubles; the bytes start there)
+    size_t bytes() const { return sizeof(double) * offMask() + B; }
+    Range scaleRange() const { return {0, sizeof(double) * B}; }
+    Range vecMaskRange() const { return {sizeof(double) * offVec(), bytes() - sizeof(double) * offVec()}; }
+};
+// k_nees_tail's records, in doubles: per filter logdet, min_pivot, dof, info | nees [kTileRows]
+constexpr int kRecHead = 4;  // (kNeesHead)
+constexpr int kRecInfo = 3;
+struct RecordsLayout {
+    size_t B;
+    static constexpr size_t record() { return size_t(kRecHead + kTileRows); }
+    size_t offRecord(size_t b) const { return b * record(); }
+    size_t offInfo(size_t b) const { return offRecord(b) + kRecInfo; }
+    size_t offNees(size_t b, size_t k) const { return offRecord(b) + kRecHead + k; }
+    size_t doubles() const { return B * record(); }
+    size_t bytes() const { return sizeof(double) * doubles(); }
+};
 
 // eqf_sample_sigma's arguments (nMax: the most landmarks any filter of the handle holds).  True: the call may go on.
 inline bool drawArgsOk(int local, int first, int nsamp, const double* z, int ldz, const double* eps, int lde, const void* stats, int nMax) {

@@ -1,4 +1,5 @@
-// Argument checks, id matching, the chunk plan and the record arithmetic of eqf_score_vision.  Host only, standard library only (no HIP, no
+// Argument checks, id matching, the chunk plan, the layouts of the two device blocks and the record arithmetic of eqf_score_vision.  Host
+// only, standard library only (no HIP, no
 // other eqf_*.hpp; the constants repeated here are static_assert-ed against eqf_device.hpp / the C header where both are seen):
 // tests/score_host_main.cpp runs it under the sanitizers without a GPU.  The record arithmetic is __host__ __device__ where a HIP compiler
 // sees it: k_score_tail evaluates the same text.
@@ -96,6 +97,28 @@ inline int launchesPerChunk(int m) {
     }
     return l;
 }
+
+// The workspace of a chunk of C images of leading dimension ldW = paddedOrder(capacity), in doubles: W [C][ldW][ldW] the images | E [C][ldW]
+// their right-hand-side rows | D [C][dRec] the records of the current diagonal block | bad [C] ints behind them, rounded up to whole doubles
+struct WorkLayout {
+    size_t C, ldW, dRec;
+    size_t offW() const { return 0; }
+    size_t offE() const { return C * ldW * ldW; }
+    size_t offD() const { return offE() + C * ldW; }
+    size_t offBad() const { return offD() + C * dRec; }  // (in doubles; the ints start there)
+    size_t doubles() const { return offBad() + (C + 1) / 2; }
+};
+// The tables of a call in one block, in bytes: rec [nItems][kRec] doubles | nisLm [nMatched] doubles | y [nMatched][3] doubles | items
+// [nItems] Item | slots [nMatched] ints
+struct TabLayout {
+    size_t nItems, nMatched;
+    size_t offRec() const { return 0; }
+    size_t offNisLm() const { return sizeof(double) * kRec * nItems; }
+    size_t offY() const { return offNisLm() + sizeof(double) * nMatched; }
+    size_t offItems() const { return offY() + sizeof(double) * 3 * nMatched; }
+    size_t offSlots() const { return offItems() + sizeof(Item) * nItems; }
+    size_t bytes() const { return offSlots() + sizeof(int) * nMatched; }
+};
 
 // ---- the record from (nis, logdet_S, dof)
 EQF_SC_HD inline double logLikelihood(double nis, double logdet, int dof) {

@@ -2,6 +2,7 @@
 // Cases arrive on stdin as whitespace-separated tokens, results leave on stdout as lines of integers; the expected values are computed in
 // Python, never by this header.  A scene is `B cap` and per filter `active nIds id.. nMeas measId..`.  The three `history` routes replay
 // frames the way eqf_capi.hip drives the header: the chords a kernel would have written are made from the frame's list of outlier ids.
+// `layout B cap` prints frame::ImageLayout: bearingStride bearingDoubles offKeep offPerm offCounts editInts offEdit doubles.
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -99,7 +100,7 @@ int historyFrame(Scene& s, int route, double thr, int editMax, int editSafeN, co
     if (route == 2) {
         const EditChoice e = editEligible(s.ids, keep, m, true, gateArmed, editMax, editSafeN);
         if (e.ok && (anyLost || e.anyFresh || gateArmed)) {
-            std::vector<int> image((size_t)2 * s.B * s.cap + 4 * s.B);
+            std::vector<int> image(ImageLayout{size_t(s.B), size_t(s.cap)}.editInts());
             EditPlan plan;
             if (!editImage(s.ids, keep, m, gateArmed, s.cap, image.data(), plan)) std::exit(4);
             s.ids = plan.newIds;
@@ -173,6 +174,13 @@ int main() {
             }
             continue;
         }
+        if (cmd == "layout") {
+            const size_t B = size_t(readInt()), cap = size_t(readInt());
+            const ImageLayout l{B, cap};
+            std::printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", l.bearingStride(), l.bearingDoubles(), l.offKeep(), l.offPerm(), l.offCounts(),
+                l.editInts(), l.offEdit(), l.doubles());
+            continue;
+        }
         Scene s;
         s.read();
         const Meas m = s.m();
@@ -202,9 +210,14 @@ int main() {
             const int editMax = readInt(), editSafeN = readInt();
             const bool anyLost = keepPresent(s.ids, m, keep);
             const EditChoice e = editEligible(s.ids, keep, m, handleOk, gateArmed, editMax, editSafeN);
-            std::vector<int> image((size_t)2 * s.B * s.cap + 4 * s.B, 12345);
+            // (exactly editInts() ints are the image: every one of them is written, and the canary behind them is not)
+            const size_t nInts = ImageLayout{size_t(s.B), size_t(s.cap)}.editInts(), nCanary = 4;
+            std::vector<int> image(nInts + nCanary, 12345);
             EditPlan plan;
             const bool ok = editImage(s.ids, keep, m, gateArmed, s.cap, image.data(), plan);
+            for (size_t k = nInts; k < image.size(); ++k)
+                if (image[k] != 12345) std::exit(6);
+            image.resize(nInts);
             std::printf("%d %d %d %d\n", int(e.ok), int(e.anyFresh), int(anyLost), int(ok));
             if (!ok) continue;
             std::printf("%d %d\n", int(plan.anyWork), plan.Nmax);

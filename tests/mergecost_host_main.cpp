@@ -9,6 +9,8 @@
 //   order N first                                   -> offset, padded order, block columns, launches per chunk
 //   cost kind ldi ldj ldij maha wi wj               -> alpha, cost
 //   option value                                    -> 0 | 1
+//   work C sigmaStride nTot dRec head glob          -> offW offE offD offOut offGlob offBad doubles   (all in doubles)
+//   itemblock itemCap                               -> offItems offRecords bytes sizeof(Item)
 #include <cstdio>
 #include <iostream>
 #include <sstream>
@@ -88,6 +90,16 @@ int main() {
             for (double& x : v) x = readDouble(in);
             const double a = alphaOf(kind, v[4], v[5]);
             std::printf("%a %a\n", a, cost(kind, v[0], v[1], v[2], v[3], v[4], v[5], a));
+        } else if (cmd == "work") {
+            size_t v[6];
+            for (size_t& x : v) in >> x;
+            const WorkLayout w{v[0], v[1], v[2], v[3], v[4], v[5]};
+            std::printf("%zu %zu %zu %zu %zu %zu %zu\n", w.offW(), w.offE(), w.offD(), w.offOut(), w.offGlob(), w.offBad(), w.doubles());
+        } else if (cmd == "itemblock") {
+            size_t cap;
+            in >> cap;
+            const ItemsLayout l{cap};
+            std::printf("%zu %zu %zu %zu\n", l.offItems(), l.offRecords(), l.bytes(), sizeof(Item));
         } else if (cmd == "option") {
             int value;
             in >> value;

@@ -5,6 +5,8 @@
 //   grid nsamp m                     -> rowTiles paddedRows blockColumns
 //   pack first N width               -> the packed row of src[i] = i + 1, then the row unpacked into a buffer of -7 (two entries beyond n)
 //   fill first N                     -> the unpack with a fill value of 9
+//   small B cap                      -> vecLen offScale offVec offMask (doubles) bytes, then offset and bytes of the two upload ranges
+//   records B                        -> record doubles bytes, then per filter offRecord offInfo offNees(0) offNees(15)
 //   draw local first nsamp z ldz eps lde stats nMax                 (z / eps / stats: 1 = given, 0 = NULL) -> 0 | 1
 //   inc B ldg mask? N[B] mask[B] (bad_b bad_i kind)                 kind 0 none | 1 NaN | 2 Inf                -> 0 | 1
 //   perturb first z ldz nMax B scale? (scale_b kind)                                                         -> 0 | 1
@@ -56,6 +58,20 @@ int main() {
                 unpackRow(row.data(), first, N, out.data(), &nine);
             }
             for (double v : out) std::printf("%d ", int(v));
+            std::printf("\n");
+        } else if (cmd == "small") {
+            size_t B, cap;
+            in >> B >> cap;
+            const SmallLayout s{B, cap};
+            const Range a = s.scaleRange(), v = s.vecMaskRange();
+            std::printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\n", s.vecLen(), s.offScale(), s.offVec(), s.offMask(), s.bytes(), a.offset, a.bytes,
+                v.offset, v.bytes);
+        } else if (cmd == "records") {
+            size_t B;
+            in >> B;
+            const RecordsLayout r{B};
+            std::printf("%zu %zu %zu", RecordsLayout::record(), r.doubles(), r.bytes());
+            for (size_t b = 0; b < B; ++b) std::printf(" %zu %zu %zu %zu", r.offRecord(b), r.offInfo(b), r.offNees(b, 0), r.offNees(b, kTileRows - 1));
             std::printf("\n");
         } else if (cmd == "draw") {
             int local, first, nsamp, hz, ldz, he, lde, hs, nMax;

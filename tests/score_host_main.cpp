@@ -5,7 +5,9 @@
 //   option v                                                                                                            -> 0 | 1
 //   plan items option B                                                                                                 -> chunk chunks counts..
 //   order cap m                                                                                                         -> padded order, block columns, launches
-//   rec nis logdet dof bad                                                                                              -> nis logdet loglik dof info
+//   work C ldW dRec                                                  -> offW offE offD offBad doubles   (all in doubles)
+//   tab nItems nMatched                                              -> offRec offNisLm offY offItems offSlots bytes sizeof(Item)
+//   rec nis logdet dof bad                                                                                            -> nis logdet loglik dof info
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -80,6 +82,16 @@ int main() {
             int cap, m;
             in >> cap >> m;
             std::printf("%d %d %d\n", sc::paddedOrder(cap), sc::blockColumns(m), sc::launchesPerChunk(m));
+        } else if (cmd == "work") {
+            size_t C, ldW, dRec;
+            in >> C >> ldW >> dRec;
+            const sc::WorkLayout w{C, ldW, dRec};
+            std::printf("%zu %zu %zu %zu %zu\n", w.offW(), w.offE(), w.offD(), w.offBad(), w.doubles());
+        } else if (cmd == "tab") {
+            size_t nItems, nMatched;
+            in >> nItems >> nMatched;
+            const sc::TabLayout t{nItems, nMatched};
+            std::printf("%zu %zu %zu %zu %zu %zu %zu\n", t.offRec(), t.offNisLm(), t.offY(), t.offItems(), t.offSlots(), t.bytes(), sizeof(sc::Item));
         } else if (cmd == "rec") {
             const double nis = rd(in), logdet = rd(in);
             int dof, bad;

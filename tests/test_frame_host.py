@@ -159,6 +159,20 @@ def test_k_edit_eligibility_and_upload_image(frame_host):
     assert not verdicts["kEditMax and kEditMax + 1 side by side", 1, 0] and not verdicts["60 measurement entries", 0, 0]
 
 
+def test_pinned_image_layout(frame_host):
+    """The frame's pinned image against the formula written out: 3 cap B doubles of bearings, then 2 B cap + 4 B ints (keep | perm |
+    counts) rounded up to doubles -- what eqf_create has always allocated.  That editImage writes exactly editInts() ints and nothing behind
+    them is the canary of the `edit` command (test_k_edit_eligibility_and_upload_image) and the sanitizer."""
+    cases = [(B, cap) for B in (1, 3, 8) for cap in (1, 5, 21, 200)]
+    for (B, cap), got in zip(cases, frame_host("\n".join(f"layout {B} {cap}" for B, cap in cases))):
+        ints = 2 * B * cap + 4 * B
+        total = 3 * cap * B + (ints + 1) // 2
+        assert got == [3 * cap, 3 * cap * B, 0, B * cap, 2 * B * cap, ints, 3 * cap * B, total], (B, cap)
+        keep, perm, counts = got[2:5]
+        assert keep + B * cap <= perm and perm + B * cap <= counts and counts + 4 * B == ints  # ascending, no overlap, no gap
+        assert (8 * got[6]) % 4 == 0 and 8 * (total - got[6]) >= 4 * ints  # (the ints fit behind the bearings)
+
+
 # ---- the gate: (scene after the lost landmarks are gone, chords per filter and landmark)
 NAN = float("nan")
 GATES = {

@@ -115,6 +115,44 @@ def test_chunk_plan_and_launch_count(mergecost_host):
         assert [int(x) for x in mergecost_host(f"order {N} {first}")[0]] == [off, m, nb, launches]
 
 
+def _parts_ascend_without_overlap(offs, sizes, total):
+    """Parts [off, off + size) in the order given: ascending, none overlapping the next, the last within the total."""
+    ends = [o + s for o, s in zip(offs, sizes)]
+    return offs[0] == 0 and all(e <= o for e, o in zip(ends, offs[1:])) and all(a < b or s == 0 for a, b, s in zip(offs, offs[1:], sizes)) \
+        and ends[-1] <= total
+
+
+def test_workspace_and_item_block_layouts(mergecost_host):
+    """W | E | D | out | Glob | bad, in doubles, against the formula written out; the total is what the call has always allocated:
+    C (sigmaStride + nTot + dRec + head + glob) + (C + 1) // 2 doubles."""
+    head, dRec = 20, 5120
+    cases = [(C, cap, glob) for C in (1, 2, 3, 8) for cap in (1, 5, 21, 200) for glob in (30, 41)]
+    lines = []
+    for C, cap, glob in cases:
+        nTot = 12 + 3 * cap
+        lines.append(f"work {C} {nTot * (-(-nTot // 16) * 16)} {nTot} {dRec} {head} {glob}")
+    for (C, cap, glob), got in zip(cases, mergecost_host("\n".join(lines))):
+        got = [int(x) for x in got]
+        nTot = 12 + 3 * cap
+        stride = nTot * (-(-nTot // 16) * 16)
+        sizes = [C * stride, C * nTot, C * dRec, C * head, C * glob]
+        want, at = [], 0
+        for s in sizes:
+            want.append(at)
+            at += s
+        want.append(at)  # (the int tail starts behind the Globs)
+        total = C * (stride + nTot + dRec + head + glob) + (C + 1) // 2
+        assert got == want + [total], (C, cap, glob)
+        offs, tail_bytes = got[:6], 4 * C
+        assert _parts_ascend_without_overlap([8 * o for o in offs], [8 * s for s in sizes] + [tail_bytes], 8 * total)
+        assert (8 * offs[4]) % 8 == 0 and (8 * offs[5]) % 4 == 0
+        assert 8 * (total - offs[5]) >= tail_bytes  # (C ints fit, C odd or even)
+    for cap in (0, 1, 7, 2016):
+        offI, offR, nbytes, item = [int(x) for x in mergecost_host(f"itemblock {cap}")[0]]
+        assert item == 6 * 4 + 3 * 8  # (six ints and three doubles: the device's PairItem)
+        assert [offI, offR, nbytes] == [0, item * cap, cap * (item + 8 * 8)] and offR % 8 == 0
+
+
 def test_cost_formulas(mergecost_host):
     rng = np.random.default_rng(5)
     lines, want = [], []

@@ -147,6 +147,25 @@ def test_pack_and_unpack_rows(sample_host):
         assert next(out) == [0] * first + [9] * (n - first) + [-7, -7], (first, N)
 
 
+def test_small_image_and_record_layouts(sample_host):
+    """scale | vectors | mask against the formula written out -- 8 B (1 + 12 + 3 cap) + B bytes, as the calls have always allocated --, the
+    two upload ranges (the scales in front; the vectors with the mask behind them), and the records [B][4 + 16]."""
+    cases = [(B, cap) for B in (1, 3, 8) for cap in (1, 5, 21, 200)]
+    for (B, cap), got in zip(cases, sample_host("\n".join(f"small {B} {cap}" for B, cap in cases))):
+        n = 12 + 3 * cap
+        total = 8 * B * (1 + n) + B
+        assert got == [n, 0, B, B * (1 + n), total, 0, 8 * B, 8 * B, 8 * B * n + B], (B, cap)
+        offs, sizes = [8 * got[1], 8 * got[2], 8 * got[3]], [8 * B, 8 * B * n, B]
+        assert offs == sorted(offs) and all(o + s <= nxt for o, s, nxt in zip(offs, sizes, offs[1:] + [total]))
+        # the ranges: exactly the scales; exactly the vectors and the mask, to the end of the image
+        assert got[5] + got[6] == offs[1] and got[7] == offs[1] and got[7] + got[8] == total
+    for B in (1, 3, 8):
+        got = sample_host(f"records {B}")[0]
+        assert got[:3] == [20, 20 * B, 160 * B]
+        assert got[3:] == [v for b in range(B) for v in (20 * b, 20 * b + 3, 20 * b + 4, 20 * b + 19)]
+        assert max(got[3:]) < got[1]
+
+
 def test_argument_checks(sample_host):
     n = 11 + 3 * 5
     ok = dict(local=1, first=0, nsamp=1, z=1, ldz=n, eps=1, lde=n, stats=1, nMax=5)

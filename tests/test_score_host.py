@@ -124,6 +124,40 @@ def test_chunk_plan_and_launch_count(score_host):
         assert 64 * -(-2 * cap // 64) >= 2 * cap
 
 
+def _ascending_parts(offs, sizes, total):
+    """Parts [off, off + size) in the order given start at 0, do not overlap and end within the total."""
+    ends = [o + s for o, s in zip(offs, sizes)]
+    return offs[0] == 0 and all(e <= o for e, o in zip(ends, offs[1:])) and ends[-1] <= total
+
+
+def test_workspace_and_table_layouts(score_host):
+    """W | E | D | bad in doubles and rec | nisLm | y | items | slots in bytes, against the formulas written out; the totals are what the
+    call has always allocated: C (ldW^2 + ldW + dRec) + (C + 1) // 2 doubles, and the sum of the five tables."""
+    dRec = 5120
+    works = [(C, cap) for C in (1, 2, 3, 8) for cap in (1, 5, 21, 200)]
+    for (C, cap), got in zip(works, score_host("\n".join(f"work {C} {64 * -(-2 * cap // 64)} {dRec}" for C, cap in works))):
+        got = [int(x) for x in got]
+        ldW = 64 * -(-2 * cap // 64)
+        sizes = [C * ldW * ldW, C * ldW, C * dRec]
+        total = C * (ldW * ldW + ldW + dRec) + (C + 1) // 2
+        assert got == [0, sizes[0], sizes[0] + sizes[1], sum(sizes), total], (C, cap)
+        assert _ascending_parts([8 * o for o in got[:4]], [8 * s for s in sizes] + [4 * C], 8 * total)
+        assert (8 * got[3]) % 4 == 0 and 8 * (total - got[3]) >= 4 * C  # (C ints fit, C odd or even)
+    tabs = [(i, m) for i in (0, 1, 7) for m in (0, 1, 7)]
+    for (nItems, nMatched), got in zip(tabs, score_host("\n".join(f"tab {i} {m}" for i, m in tabs))):
+        got = [int(x) for x in got]
+        item = got[6]
+        assert item == 16  # (four ints: the device's ScoreItem)
+        sizes = [8 * 8 * nItems, 8 * nMatched, 8 * 3 * nMatched, item * nItems, 4 * nMatched]
+        want, at = [], 0
+        for s in sizes:
+            want.append(at)
+            at += s
+        assert got[:6] == want + [at], (nItems, nMatched)
+        assert _ascending_parts(got[:5], sizes, got[5])
+        assert all(o % 8 == 0 for o in got[:4]) and got[4] % 4 == 0  # (doubles and items on 8 bytes, the int slots on 4)
+
+
 def test_record_arithmetic(score_host):
     rng = np.random.default_rng(11)
     lines, want = [], []
