@@ -18,6 +18,9 @@ SIZES = (1, 15, 16, 17, 33, 49, 70)   # 16: kTileLm; 15 / 17 / 33 / 49: one off 
 BIG = 130                             # four rows per wavefront with more than two ring columns
 RAGGED = (5, 17, 33)                  # one handle, three filters
 TILED = ((37, 8), (50, 16))           # (N, landmarks per block) of the partitioned filter
+# The same at block sizes that reach its production paths (whole 128 x 128 product tiles, the blocked potrf, the split solve); GPU tests
+# and one CPU test only -- kept out of ALL_SIZES / CPU_SIZES, whose parametrised tests keep their cost
+TILED_BIG = ((200, 64), (230, 108))
 KSTEP = (17, 70)
 F32 = (17, 70)
 ALL_SIZES = tuple(sorted(set(SIZES + (BIG,) + RAGGED + tuple(n for n, _ in TILED))))

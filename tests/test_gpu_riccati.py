@@ -233,9 +233,10 @@ def test_fp32_handles(hip, monkeypatch, route):
     assert not bad, bad[:10]
 
 
-@pytest.mark.parametrize("N,bl", rc.TILED)
+@pytest.mark.parametrize("N,bl", rc.TILED + rc.TILED_BIG[:1])
 def test_partitioned_filter(hip, N, bl):
-    """tiled.TiledFilter on a 1 x 1 grid through initialise_from(snapshot), stateCovariance() against the same reference.  The filter queues IMU
+    """(200, 64 -- rc.TILED_BIG: four block rows, the last one ragged, 13 landmark tiles of 16 per row -- as well as rc.TILED.)
+    tiled.TiledFilter on a 1 x 1 grid through initialise_from(snapshot), stateCovariance() against the same reference.  The filter queues IMU
     calls by default (TiledFilter.burst) and a getter flushes them through k_tl_build / k_tl_base / k_tl_riccati_burst, also when one call is
     queued; k_tl_riccati runs only with burst = False.  So: one processIMUData with burst off (k_tl_riccati) and with burst on
     (k_tl_riccati_burst, one step) on all four families, and one burst of four (the second call on the first's stamp) on families a, b, c."""

@@ -19,7 +19,11 @@
 (f) eleven injected faults, each leaving its bound; the table the test prints says for each whether today's gates (rel_fro <= 2e-9 on Sigma+,
     1e-9 max(1, |.|) on gamma and Gamma) would have passed it.
 (g) the propagate's part of the bound against what it bounds: Sigma' moved by +-E_ric moves the reference by 0.9 (Sigma+), 0.7 (gamma) and
-    0.4 (Gamma[0:6]) of it, never more."""
+    0.4 (Gamma[0:6]) of it, never more.
+(h) the partitioned filter's block-row schedule (csrc/eqf_tiledf.hip; tests/tiled_reference.py over a numpy backend: diagonal blocks of 2 bl /
+    3 bl rows, trailing updates per block row, the split solve, the downdate per block row) on update_cases.TILED_BIG stays at ratio <= 1
+    against the bound with the schedule's counted terms -- Sigma+ 0.005 / 0.004 / 0.05 / 0.005 on a / b / c / e at (200, 64), within 1 % of
+    its ratio to the single-GPU bound -- and three schedule faults leave it by eight to eleven orders."""
 import numpy as np
 import pytest
 import scipy.linalg as sl
@@ -343,3 +347,120 @@ def test_a_perturbation_inside_e_ric_moves_the_reference_by_less_than_the_bound(
     print(f"N = {N}: Sigma' moved by E_ric, worst change over the bound  " + "  ".join(f"{k} {v:.3f}" for k, v in worst.items()))
     assert all(v <= 1.0 for v in worst.values()), worst
     assert worst["Sp"] > 0.3 and worst["Gamma6"] > 0.02, worst
+
+
+# ---- (h) the partitioned filter's block-row schedule ------------------------------------------------------------------------------------------
+SCHEDULE_FAULTS = {  # name: the quantities of which at least one must leave its bound
+    "trailing_tile": ("Sp", "gamma"), "split_product": ("Sp", "gamma", "Gamma6"), "share_twice": ("Sp",)}
+
+
+def _schedule_backend(d, capacity, bl, fault=None):
+    """tests/tiled_double.py's NumpyBackend (the numpy oracle's prep and finish, LAPACK on the diagonal blocks) with the dense operations the way
+    csrc/eqf_tiledf.hip schedules them, fp64 throughout: a block row's solve split once ([L11 0; L21 L22]: X1, B2 -= L21 X1, X2) wherever it has
+    two 64-row blocks and 256 columns -- what "trsm_leaf" = 1 does at 128 rows; the default splits from six blocks on --, the downdate one
+    product per block row of Y ("downdate_early"), and set_state, so that the schedule starts from a snapshot.  fault: one of SCHEDULE_FAULTS."""
+    from tiled_double import NumpyBackend
+
+    class ScheduleBackend(NumpyBackend):
+        def set_state(self, st):
+            self.f = ec.numpy_filter(en, st, d)
+            S = np.asarray(st["sigma"], dtype=float)
+            self.Sbb, self.Sb = S[:11, :11].copy(), S[:11, 11:].copy()
+            self.active = np.ones(len(st["ids"]), dtype=bool)
+            self.trailing_launches = self.s_solves = 0
+
+        def trsm_left(self, L, drec, Bm):
+            Ln, B = np.tril(L.numpy()), Bm.numpy()
+            n = len(Ln)
+            nb = -(-n // 64)
+            if nb < 2 or B.shape[1] < 256:
+                B[...] = sl.solve_triangular(Ln, B, lower=True)
+                return
+            h = 64 * (nb // 2)
+            B[:h] = sl.solve_triangular(Ln[:h, :h], B[:h], lower=True)
+            self.s_solves += n == 2 * bl
+            if not (fault == "split_product" and n == 2 * bl and self.s_solves == 3):   # (the S-chain's third block row)
+                B[h:] -= Ln[h:, :h] @ B[:h]
+            B[h:] = sl.solve_triangular(Ln[h:, h:], B[h:], lower=True)
+
+        def gemm_tn(self, Cm, A, B, alpha, mask=None):
+            N = self.num_landmarks()
+            if mask is not None and alpha == -1.0 and mask[0] == 3 * bl and A.shape[0] == 2 * N:
+                # the downdate: one share per block row of Y, each added to Sigma by itself
+                for k, r0 in enumerate(range(0, 2 * N, 2 * bl)):
+                    for _ in range(2 if fault == "share_twice" and k == 1 else 1):
+                        NumpyBackend.gemm_tn(self, Cm, A[r0:r0 + 2 * bl], B[r0:r0 + 2 * bl], alpha, mask)
+                return
+            if fault == "trailing_tile" and mask is not None and alpha == -1.0 and mask[0] == 2 * bl and A.shape[0] == 2 * bl:
+                self.trailing_launches += 1
+                if self.trailing_launches == 1:   # block row 0 of the S-chain: the 128 x 128 tile of block (1, 2) keeps its old value
+                    keep = Cm[0:128, 128:256].clone()
+                    NumpyBackend.gemm_tn(self, Cm, A, B, alpha, mask)
+                    Cm[0:128, 128:256] = keep
+                    return
+            NumpyBackend.gemm_tn(self, Cm, A, B, alpha, mask)
+
+    return ScheduleBackend(d, capacity)
+
+
+def schedule_form(oracle_lib, N, bl, fam, fault=None):
+    """One vision call through tests/tiled_reference.py's TiledFilter (the exchange schedule the C++ loop is the twin of) on a 1 x 1 grid over
+    the backend above: diagonal blocks of 2 bl / 3 bl rows, trailing updates per block row, the look-ahead factor from a copy."""
+    import tiled_reference as tr
+
+    S0, (stamp, ids, y), _, _, _ = reference(oracle_lib, N, fam)
+    tf = tr.TiledFilter(tr.ProcessGrid(None, 1, 1), _schedule_backend(uc.settings(), N + 5, bl, fault), bl)
+    tf.burst = False
+    tf.check_every = 0 if fault else 1   # (a fault may cost a later diagonal block its positive pivots: the run goes on, as the device's would)
+    tf.initialise_from(dict(snapshot(oracle_lib, N), sigma=S0))
+    assert tf.processVisionData(stamp, ids, y) == 0
+    lu = tf.lastUpdate()
+    return dict(Sp=tf.stateCovariance(), gamma=lu["gamma"], delta=lu["delta"], Gamma6=lu["Gamma"][0:6])
+
+
+def schedule_bounds(oracle_lib, N, bl, fam):
+    """the bound with the schedule's counted terms: one addition per block row, one level of the split solve"""
+    _, _, _, ref, bd = reference(oracle_lib, N, fam)
+    return ref, ux.update_bounds(ref, bd["parts"]["E_ric"], block_rows=-(-N // bl), split_levels=1)
+
+
+@pytest.mark.parametrize("N,bl", uc.TILED_BIG)
+def test_block_row_schedule_stays_inside_the_bound(oracle_lib, N, bl):
+    """update_cases.TILED_BIG, all four families: the fp64 restatement of the partitioned filter's schedule at ratio <= 1 for Sigma+, gamma,
+    delta and (families a, c, e) Gamma[0:6] -- with the counted terms of the schedule, and printed beside it against the bound as it stands
+    for the single-GPU routes."""
+    worst, plain, bad = {}, {}, []
+    for fam in uc.FAMILIES:
+        ref, bd = schedule_bounds(oracle_lib, N, bl, fam)
+        got = schedule_form(oracle_lib, N, bl, fam)
+        r, r0 = ratios(got, ref, bd), ratios(got, ref, reference(oracle_lib, N, fam)[4])
+        r["symmetry"] = ux.symmetry_ratio(got["Sp"], bd["Sp"])
+        if not uc.gamma6_asserted(N, fam):
+            r.pop("Gamma6"), r0.pop("Gamma6")
+        _collect(worst, fam, r), _collect(plain, fam, r0)
+        if not all(v <= 1.0 for v in r.values()):
+            bad.append((N, bl, fam, r))
+    print(f"N = {N}, blocks of {bl}, block-row schedule: worst ratio to the bound  {_fmt(worst)}")
+    print(f"N = {N}, blocks of {bl}, the same against the single-GPU bound          {_fmt(plain)}")
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("fam", ["a", "e"])
+def test_injected_schedule_faults_leave_the_bound(oracle_lib, fam):
+    """(200, 64): one 128 x 128 trailing tile not updated in one block row (block (1, 2) of S under block row 0), the split solve's L21 X1
+    product left out in the S-chain's third block row, block row 1's share of the downdate applied twice -- each leaves the bound of a quantity it touches.  Beside it what
+    the normwise gates of tests/test_gpu_tiled.py (rel_fro 1e-9 on Sigma+) make of it."""
+    N, bl = uc.TILED_BIG[0]
+    ref, bd = schedule_bounds(oracle_lib, N, bl, fam)
+    ok = schedule_form(oracle_lib, N, bl, fam)
+    assert all(v <= 1.0 for v in ratios(ok, ref, bd).values())
+    missed = []
+    for name, touched in SCHEDULE_FAULTS.items():
+        got = schedule_form(oracle_lib, N, bl, fam, fault=name)
+        r = ratios(got, ref, bd)
+        fro = rel_fro(got["Sp"], ok["Sp"])
+        print(f"family {fam} schedule fault {name:14s} ratio Sp {r['Sp']:.3g} gamma {r['gamma']:.3g} Gamma6 {r['Gamma6']:.3g} | Sigma+ rel_fro {fro:.2e} -> "
+              f"{'PASSES rel_fro 1e-9' if fro <= 1e-9 else 'caught by rel_fro 1e-9'}")
+        if not any(r[k] > 1.0 for k in touched):
+            missed.append((name, r))
+    assert not missed, missed

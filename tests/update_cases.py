@@ -27,6 +27,7 @@ BURST = (33, 70)
 RAGGED = (5, 21, 33)
 BATCH_N = 200
 TILED = rc.TILED
+TILED_BIG = rc.TILED_BIG
 CPU_SIZES = tuple(sorted(set(SIZES + F32 + RAGGED)))
 ROTATION = 0.05
 FRAME = 4
@@ -34,6 +35,25 @@ FRAME = 4
 
 def settings():
     return rc.settings()
+
+
+TRSM_SPLIT = 6   # csrc/eqf_tiledf.hip kTrsmSplit: 64-row blocks of a diagonal factor from which a block row's solve is split once
+
+
+def tiled_schedule(N, bl, solve_inverse=False, trsm_leaf=0):
+    """The keyword arguments of update_exact.update_bounds for the partitioned filter on (N, bl), counted from the schedule of
+    csrc/eqf_tiledf.hip (update_exact's docstring, "The partitioned filter"): one addition per block row, one per level of the split solve of
+    the larger chain's largest diagonal block (none under solve_inverse, which does not solve), and the whole-block inverse."""
+    def levels(nb):
+        if trsm_leaf > 0:
+            return 0 if nb <= trsm_leaf else 1 + levels(nb - nb // 2)
+        return 1 if nb >= TRSM_SPLIT else 0
+
+    b = min(bl, N)
+    out = dict(block_rows=-(-N // bl), split_levels=0 if solve_inverse else max(levels(-(-unit * b // 64)) for unit in (2, 3)))
+    if solve_inverse:
+        out["inverse_blocks"] = (2 * bl, 3 * bl)
+    return out
 
 
 def gamma6_asserted(N, fam):

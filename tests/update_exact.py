@@ -69,7 +69,33 @@ i8_emulator.bound(m, e, e, S), the rigorous bound of that construction from the 
 2^(e_i + e_j)), plus gamma_2 |Y|^T |Y| for the recombination's last addition and the subtraction.
 fp32 handles (Sigma stored as float, the downdate on Y rounded to float, the factorisations and solves fp64): E3 = (gamma_{m+2}(2^-24) +
 2 x 2^-24) |Y|^T |Y| and the storage term 2^-24 (|Sigma'| + |Sigma+|); E_ric is riccati_exact's fp32 bound, which already holds the rounding
-of Sigma'."""
+of Sigma'.
+
+The partitioned filter (csrc/eqf_tiledf.hip, Chain::step and enqueueUpdate; update_bounds(block_rows=, split_levels=, inverse_blocks=), all
+defaulting to the single-GPU bound; update_cases.tiled_schedule counts them from (N, bl) and the options).  Its two factorisations are
+right-looking by block ROWS of 2 bl (S) and 3 bl (Sigma_e's landmark part) rows; re-read against the counts above:
+    trailing updates    X_ij -= U_ki^T U_kj is ONE LAUNCH per block row k < i: the bk products of an entry are summed from zero on the
+                        matrix cores and the sum is added to X_ij by one atomic addition.  Over nbr block rows an entry's m products still
+                        meet m additions in all, and no term passes more than bk + nbr - 1 <= m of them, so "m products in any order"
+                        (E1, E3) holds as it stands; the addition per block row is counted on top all the same -- block_rows = nbr more
+                        roundings in EVERY count (m + 1, m + 16, m + 2 and the E-chain's n_e + 1, n_e + 16, n_e + 2) -- because the
+                        right-hand sides [C Sigma' | delta | V] ride through the same launches and chol_bounds' m + 16 was counted for one
+                        strip kernel, not for a solve whose rows arrive in nbr instalments.  nbr / m < 2 % at the committed sizes.
+    reductions          the base panel's downdate, gamma and hV are Yn_k^T [Y_k | Yn_k] added into an accumulator once per block row
+                        (S.hook), the downdate of the landmark blocks one product over all m rows -- or, with "downdate_early", one product
+                        per block row for the first shares: the same count, one addition per block row, covered by block_rows.
+    the split solve     trsmLeft: [L11 0; L21 L22], X1 = L11^-1 B1, B2 -= L21 X1 as one product, X2 = L22^-1 B2; once from six 64-row
+                        blocks and 256 columns on, recursively with "trsm_leaf".  A leaf is the strip kernel with its own (rows + 16) u;
+                        each level adds the one rounding of B2 - (L21 X1): split_levels more in the same counts.
+    "solve_inverse"     R <- (L_kk^-T)^T R with the explicit inverse of the WHOLE diagonal factor, itself the strip kernel's right solve of
+                        the identity: |Wh L_kk^T - I| <= (bk + 16) u (|Wh||L_kk^T| + I) T^T (chol_bounds, right solve) and the product's
+                        gamma_bk |Wh^T||R| give, with |R| <= |L_kk||Y_k| and T_b = blockdiag(|L_kk||L_kk^-1|) over whole diagonal blocks,
+                            |L_kk Yh_k - R| <= (bk + 16) u (T (T_b + I) + T_b) |L_kk||Y_k|,
+                        chol_bounds' T = |L_jj||L_jj^-1| argument taken over the whole block: inverse_blocks = (2 bl, 3 bl) puts
+                        T (T_b + I) + T_b in T's place in E1, E2 and their E-chain twins (the factor's off-diagonal blocks ARE solved
+                        block rows).  The five base coordinates of Sigma_e, which k_tl_eprep eliminates on their own, are a block of T_b.
+  No term is fitted to a device result; tests/test_update_exact.py holds a numpy restatement of the schedule to these bounds and sees three
+  injected schedule faults leave them."""
 import numpy as np
 import scipy.linalg
 from mpmath import mp, mpf
@@ -281,14 +307,28 @@ def _mirror_lower(E):
     return np.tril(E) + np.tril(E, -1).T
 
 
-def update_bounds(ref, E_ric, fp32=False, tau=None, k_delta=None, slices=0):
+def whole_block_T(L, starts):
+    """blockdiag(|L_kk| |L_kk^-1|) over the diagonal blocks that begin at `starts` (ascending, the first 0), fp64: chol_bounds.block_T with the
+    kernels' 16 x 16 blocks replaced by whole diagonal blocks of a block-row schedule"""
+    n = len(L)
+    T = np.zeros((n, n))
+    edges = list(starts) + [n]
+    for a, e in zip(edges[:-1], edges[1:]):
+        if e > a:
+            T[a:e, a:e] = (np.abs(cb._ld(L[a:e, a:e])) @ np.abs(cb.inv_lower(L[a:e, a:e]))).astype(np.float64)
+    return T
+
+
+def update_bounds(ref, E_ric, fp32=False, tau=None, k_delta=None, slices=0, block_rows=0, split_levels=0, inverse_blocks=None):
     """{"Sp", "gamma", "delta", "Gamma6"}: the entrywise bounds of the module docstring (float64) from update_reference's longdouble result and
-    the propagate's bound E_ric."""
+    the propagate's bound E_ric.  block_rows, split_levels, inverse_blocks: the counted terms of the partitioned filter's block-row schedule
+    (module docstring, "The partitioned filter"); their defaults give the bound of the single-GPU routes."""
     tau = rx.TAU_BLK if tau is None else tau
     k_delta = K_DELTA if k_delta is None else k_delta
     u = U64
     N = ref["N"]
     m, ne = 2 * N, 5 + 3 * N
+    extra = int(block_rows) + int(split_levels)   # rounded additions per entry on top of the counts m + 1, m + 16, m + 2 (and n_e + ...)
     a = lambda k: np.abs(f64(ref[k]))  # noqa: E731
     aS1, aB, aS, aL, aY, az, aSp, agam, adelta = a("S1"), a("B"), a("S"), a("L"), a("Y"), a("z"), a("Sp"), a("gamma"), a("delta")
     aC0, aZP, aPd, aKp = a("C0"), a("ZP"), a("Pd"), a("Kpar")
@@ -299,16 +339,19 @@ def update_bounds(ref, E_ric, fp32=False, tau=None, k_delta=None, slices=0):
     aK, aw = np.abs(f64(Kt)).T, np.abs(f64(w))
     dC0 = np.stack([np.full((2, 3), tau * u * aC0[i].max()) for i in range(N)]) if N else aC0
     T = cb.block_T(f64(L))
+    if inverse_blocks:  # a block row solved as ONE product with the explicit inverse of its whole diagonal factor
+        Tb = whole_block_T(f64(L), range(0, m, int(inverse_blocks[0])))
+        T = T @ (Tb + np.eye(m)) + Tb
     ddelta = k_delta * u * (1 + adelta)
 
     dB = gamma(OPS_C) * c_times(aC0, aS1, N) + c_times(dC0, aS1, N)
     dS = times_ct(dB, aC0, N) + gamma(OPS_S) * times_ct(aB, aC0, N) + times_ct(aB, dC0, N) + u * aS
     dS = np.maximum(dS, dS.T)
-    E1 = _mirror_lower(((m + 1) * u + cb.P) * ((aL @ aL.T) @ T.T))
-    E2 = (m + 16) * u * (T @ (aL @ aY + aB))
-    E2z = (m + 16) * u * (T @ (aL @ az + adelta))
+    E1 = _mirror_lower(((m + 1 + extra) * u + cb.P) * ((aL @ aL.T) @ T.T))
+    E2 = (m + 16 + extra) * u * (T @ (aL @ aY + aB))
+    E2z = (m + 16 + extra) * u * (T @ (aL @ az + adelta))
     u3 = U32 if fp32 else U64
-    E3 = (gamma(m + 2, u3) + (2 * U32 if fp32 else 0.0)) * (aY.T @ aY)
+    E3 = (gamma(m + 2 + extra, u3) + (2 * U32 if fp32 else 0.0)) * (aY.T @ aY)
     if slices:  # the rigorous bound of tests/i8_emulator.py from the exponent words of Y's columns, and the subtraction
         words = i8.exponent_words(f64(ref["Y"]) * (1 + 2.0 ** -30))   # (the device's Y is not the reference's to the last bit)
         live = i8.bound(m, np.maximum(words, 1), np.maximum(words, 1), slices) * ((words > 0)[:, None] & (words > 0)[None, :])
@@ -320,7 +363,7 @@ def update_bounds(ref, E_ric, fp32=False, tau=None, k_delta=None, slices=0):
     out = {"delta": ddelta}
     out["Sp"] = Gm + Gm.T + aK @ dSE @ aK.T + E3 + u3 * (aS1 + aSp) + aJ @ E_ric @ aJ.T
     aCtw = _ct_vec(aC0, aw, N)
-    dgam = aK @ (E2z + ddelta) + (dB + E2).T @ aw + aK @ (dSE @ aw) + gamma(m + 2) * (aY.T @ az) + aJ @ (E_ric @ aCtw)
+    dgam = aK @ (E2z + ddelta) + (dB + E2).T @ aw + aK @ (dSE @ aw) + gamma(m + 2 + extra) * (aY.T @ az) + aJ @ (E_ric @ aCtw)
     out["gamma"] = dgam
 
     # ---- Gamma[0:6]
@@ -332,13 +375,16 @@ def update_bounds(ref, E_ric, fp32=False, tau=None, k_delta=None, slices=0):
     aGt, aVe, aA, aLe = np.abs(f64(Gt)), np.abs(f64(Ve)), np.abs(f64(A)), np.abs(f64(Le))
     G11 = f64(Gt.T @ Gt)
     Te = cb.block_T(f64(Le))
-    E1e = _mirror_lower(((ne + 1) * u + cb.P) * ((aLe @ aLe.T) @ Te.T))
-    E2e = (ne + 16) * u * (Te @ (aLe @ aGt + aA))
+    if inverse_blocks:  # (the E-chain's blocks start behind the five base coordinates, which k_tl_eprep eliminates on their own)
+        Tbe = whole_block_T(f64(Le), [0] + list(range(5, ne, int(inverse_blocks[1]))))
+        Te = Te @ (Tbe + np.eye(ne)) + Tbe
+    E1e = _mirror_lower(((ne + 1 + extra) * u + cb.P) * ((aLe @ aLe.T) @ Te.T))
+    E2e = (ne + 16 + extra) * u * (Te @ (aLe @ aGt + aA))
     dZ = np.zeros((ne, 11))
     for i in range(N):
         dZ[5 + 3 * i:8 + 3 * i, 0:6] = tau * u * aZP[5 + 3 * i:8 + 3 * i].max()
     X = aVe.T @ (E2e + dZ)
-    dG11 = X + X.T + gamma(ne + 2) * (aGt.T @ aGt)
+    dG11 = X + X.T + gamma(ne + 2 + extra) * (aGt.T @ aGt)
     # the symmetric perturbations of Sigma_e (its factorisation's backward error and the propagate's error) reach M and b together
     Esym = E1e + E_ric[6:, 6:]
     sol_ld = ref["sol"]
@@ -358,9 +404,9 @@ def update_bounds(ref, E_ric, fp32=False, tau=None, k_delta=None, slices=0):
     Kv = solve_upper_t(L, Yv)
     aYv, aKv = np.abs(f64(Yv)), np.abs(f64(Kv))
     hV = f64(Yv.T @ ref["z"])
-    E2v = (m + 16) * u * (T @ (aL @ aYv + np.abs(f64(Vm))))
+    E2v = (m + 16 + extra) * u * (T @ (aL @ aYv + np.abs(f64(Vm))))
     CEC = times_ct(c_times(aC0, E_ric, N), aC0, N)
-    dhV = (dV + E2v).T @ aw + aKv.T @ (E2z + ddelta) + aKv.T @ ((dSE + CEC) @ aw) + gamma(m + 2) * (aYv.T @ az)
+    dhV = (dV + E2v).T @ aw + aKv.T @ (E2z + ddelta) + aKv.T @ ((dSE + CEC) @ aw) + gamma(m + 2 + extra) * (aYv.T @ az)
     g5, dg5 = f64(ref["gamma"])[6:11], dgam[6:11]
     dUw = f64(ref["dU"])
     ddU = np.zeros(6)
@@ -384,7 +430,7 @@ def update_bounds(ref, E_ric, fp32=False, tau=None, k_delta=None, slices=0):
             + aMinv @ (dM @ np.abs(sol) + gamma(OPS_B) * (aKp.T @ np.abs(b6)) + dsym + gamma(OPS_SOLVE4) * (Pm @ (np.abs(Lm) @ np.abs(Um)) @ np.abs(sol))))
     out["Gamma6"] = ddU + aKp @ dsol + 2 * u * np.abs(f64(ref["Gamma6"]))
     # (dS .. T: what the bounds of the innovation statistics, tests/consistency_exact.py part C, are made of)
-    out["parts"] = dict(cond_M=float(np.linalg.cond(M)), hV=hV, G6=G6, T65=T65, dS=dS, E1=E1, E2z=E2z, ddelta=ddelta, aw=aw, CEC=CEC, T=T)
+    out["parts"] = dict(cond_M=float(np.linalg.cond(M)), hV=hV, G6=G6, T65=T65, dS=dS, E1=E1, E2z=E2z, ddelta=ddelta, aw=aw, CEC=CEC, T=T, E_ric=E_ric)
     return out
 
 
